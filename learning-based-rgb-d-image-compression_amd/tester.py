@@ -205,7 +205,7 @@ class TesterUnited:
             pool = [self.net]
         from .sched import check_hw_queues
 
-        check_hw_queues()  # refuses GPU_MAX_HW_QUEUES > 48: launches on other streams were seen to fail there
+        check_hw_queues()  # refuses a queue count above sched.MAX_SAFE_HW_QUEUES: launches on other streams were seen to fail there
         while len(pool) < W:
             pool.append(self.net.clone_shared())
         self._pool_nets = pool

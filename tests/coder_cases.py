@@ -36,3 +36,69 @@ def lane_edge_symbols(rng, n, sizes, offsets, rows=None):
     far = (2.0 ** rng.uniform(0, 20, n)).astype(np.int64)
     sym = np.where(esc, np.where(rng.rand(n) < 0.5, offsets[idx] - far, offsets[idx] + sizes[idx] - 2 + far), sym)
     return idx, sym.astype(np.int32)
+
+
+def seeded_case(seed, scale_table):
+    """test_oracle_coder.py::test_against_reference_cpp[seed]: n (symbol, index) pairs over the Gaussian table (2 % of them
+    with four times the scale, 1 % far escapes) and 20 random pmfs of 2 ... 39 entries.  Returns (sym, idx, pmfs)."""
+    rng = np.random.RandomState(seed)
+    n = [17, 4096, 20000][seed]
+    idx = rng.randint(0, 64, n).astype(np.int32)
+    sym = np.rint(rng.standard_normal(n) * scale_table[idx] * (1 + 3 * (rng.rand(n) < 0.02))).astype(np.int32)
+    sym[rng.rand(n) < 0.01] = rng.randint(-100000, 100000)
+    pmfs = []
+    for _ in range(20):
+        m = rng.randint(2, 40)
+        p = rng.rand(m).astype(np.float32) ** 4
+        p /= p.sum()
+        pmfs.append(p)
+    return sym, idx, pmfs
+
+
+def reference_cpp_vectors(ref, scale_table, gc_tables):
+    """What the reference's own C++ coder (`oracle.coder.load_reference_coder()`) returns on every input of the
+    *_against_reference_cpp tests: streams, decoded symbols and quantised CDFs, keyed by case.  Stored as
+    tests/golden/coder_ref_cpp.npz (tests/golden/make_coder_ref.py), so that those tests run without the reference."""
+    out = {}
+
+    def encode(sym, idx, cdf_l, sz_l, off_l):
+        return ref["ans"].RansEncoder().encode_with_indexes(sym.tolist(), idx.tolist(), cdf_l, sz_l, off_l)
+
+    def decode(stream, parts, cdf_l, sz_l, off_l):
+        d = ref["ans"].RansDecoder()
+        d.set_stream(stream)
+        return [np.array(d.decode_stream(p.tolist(), cdf_l, sz_l, off_l), np.int32) for p in parts]
+
+    cdf_l, sz_l, off_l = gc_tables.cdf.tolist(), gc_tables.sizes.tolist(), gc_tables.offsets.tolist()
+    for seed in range(3):
+        sym, idx, pmfs = seeded_case(seed, scale_table)
+        s = encode(sym, idx, cdf_l, sz_l, off_l)
+        out[f"seeded{seed}_stream"] = np.frombuffer(s, np.uint8)
+        cut = len(idx) // 3
+        out[f"seeded{seed}_dec0"], out[f"seeded{seed}_dec1"] = decode(s, [idx[:cut], idx[cut:]], cdf_l, sz_l, off_l)
+        for t, p in enumerate(pmfs):
+            out[f"seeded{seed}_pmf{t}"] = np.array(ref["_CXX"].pmf_to_quantized_cdf([float(v) for v in p], 16), np.uint32)
+    for seed in range(2):
+        cdf, sizes, offsets, rng = lane_edge_tables(seed)
+        tl = cdf.tolist(), sizes.tolist(), offsets.tolist()
+        for n in (1, 63, 64, 65, 4000):
+            idx, sym = lane_edge_symbols(rng, n, sizes, offsets)
+            if n < 2:  # (the reference's flush() under-allocates its output for fewer than two symbols)
+                continue
+            s = encode(sym, idx, *tl)
+            out[f"lane{seed}_n{n}_stream"] = np.frombuffer(s, np.uint8)
+            out[f"lane{seed}_n{n}_dec"] = decode(s, [idx], *tl)[0]
+    cdf, sizes, offsets, rng = lane_edge_tables(0, COARSE_EDGE_SLOTS)
+    tl = cdf.tolist(), sizes.tolist(), offsets.tolist()
+    for k, (n, rows) in enumerate(coarse_edge_cases()):
+        idx, sym = lane_edge_symbols(rng, n, sizes, offsets, rows=rows)
+        s = encode(sym, idx, *tl)
+        out[f"coarse{k}_stream"] = np.frombuffer(s, np.uint8)
+        out[f"coarse{k}_dec"] = decode(s, [idx], *tl)[0]
+    return out
+
+
+def coarse_edge_cases():
+    """(n, rows) of test_oracle_coder.py::test_coarse_edge_tables_against_reference_cpp, in draw order."""
+    coarse = [r for r, n in enumerate(COARSE_EDGE_SLOTS) if 128 < n <= 4032]
+    return [(65, None), (3000, coarse), (3000, None)]

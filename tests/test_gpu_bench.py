@@ -66,3 +66,37 @@ def test_two_ranks_spawned_by_bench_itself():
     r = _run("--gpus", "2", "--steps", "3", "--warmup", "2", "--workers", "2", env={"RGBD_DIST_BACKEND": "gloo"})
     assert r["n_gpus"] == 2 and r["steps"] == 3 and r["config"]["images_per_gpu"] == 4
     assert r["value"] > 0.5 and "latency" not in r and "cpu_baseline" not in r
+
+
+@pytest.mark.timeout(900)
+def test_dump_outputs_are_what_the_timed_path_returned(tmp_path):
+    """--dump-outputs: the last timed step's reconstructions and streams (4 pairs of 480x640, padded to 512x640), within
+    64 MB; decoding the dumped streams with a fresh engine instance gives the dumped reconstructions bit for bit."""
+    require_gpu()
+    import numpy as np
+    import torch
+
+    import rgbd_amd
+    from rgbd_amd import ELIC_united, synth
+
+    d = tmp_path / "dump"
+    r = _run("--steps", "4", "--warmup", "1", "--workers", "1", "--no-extras", "--no-cpu-baseline", "--dump-outputs", str(d))
+    assert r["steps"] == 4 and r["config"]["calls"] == 1 and r["config"]["images_per_call"] == 16
+    ld = {f[:-4]: np.load(d / f) for f in os.listdir(d) if f.endswith(".npy")}
+    assert sum(a.nbytes for a in ld.values()) <= 64 << 20
+    assert ld["x_hat_r"].shape == (4, 3, 512, 640) and ld["x_hat_d"].shape == (4, 1, 512, 640)
+    assert ld["x_hat_r"].dtype == np.float32 and np.isfinite(ld["x_hat_r"]).all()
+
+    def streams(m, k):
+        raw, lens = bytes(ld[f"{m}_{k}_strings"].astype(np.uint8)), ld[f"{m}_{k}_lengths"].astype(np.int64)
+        assert len(lens) == 4 and lens.sum() == len(raw)
+        return [raw[a:b] for a, b in zip(np.concatenate([[0], np.cumsum(lens)[:-1]]), np.cumsum(lens))]
+
+    net = ELIC_united(config=rgbd_amd.model_config(), channel=4).eval()
+    net.load_state_dict(synth.synthetic_state_dict(0, model="ELIC_united"))
+    net.update(force=True)
+    net = net.to("cuda:0")
+    net.per_image_streams = True
+    rec = net.decompress([streams("r", "y"), streams("r", "z")], [streams("d", "y"), streams("d", "z")], torch.Size((8, 10)))
+    assert np.array_equal(rec["x_hat"]["r"].cpu().numpy(), ld["x_hat_r"])
+    assert np.array_equal(rec["x_hat"]["d"].cpu().numpy(), ld["x_hat_d"])

@@ -1,10 +1,15 @@
-"""The plain-C oracle coder against (a) known answers produced by the reference's own C++ (tests/golden/coder_kat.npz)
-and (b) the reference C++ itself where oracle/_ref has been built.  All integer work: bit-exact."""
+"""The plain-C oracle coder against known answers produced by the reference's own C++ (tests/golden/coder_kat.npz,
+tests/golden/coder_ref_cpp.npz), and against the reference C++ itself where oracle/_ref has been built.  All integer work:
+bit-exact."""
 import hashlib
+import os
 
 import numpy as np
 import pytest
 
+from coder_cases import (COARSE_EDGE_SLOTS, coarse_edge_cases, lane_edge_symbols, lane_edge_tables, reference_cpp_vectors,
+                         seeded_case)
+from conftest import GOLDEN
 from oracle import coder
 
 
@@ -88,76 +93,61 @@ def test_table_construction_matches_reference(kat):
     assert np.array_equal(eo.scale_table().numpy(), kat["scale_table"])
 
 
-@pytest.mark.parametrize("seed", [0, 1, 2])
-def test_against_reference_cpp(seed, kat, gc_tables):
+@pytest.fixture(scope="module")
+def ref_cpp(kat, gc_tables):
+    """The reference C++ coder's answers on the inputs below (tests/golden/coder_ref_cpp.npz, tests/golden/make_coder_ref.py).
+    Where oracle/_ref has been built, the stored answers are first recomputed with the reference itself and must be equal."""
+    stored = dict(np.load(os.path.join(GOLDEN, "coder_ref_cpp.npz")))
     ref = coder.load_reference_coder()
-    if ref is None:
-        pytest.skip("oracle/_ref not built (make -C oracle ref needs /root/reference)")
-    rng = np.random.RandomState(seed)
-    n = [17, 4096, 20000][seed]
-    idx = rng.randint(0, 64, n).astype(np.int32)
-    sym = np.rint(rng.standard_normal(n) * kat["scale_table"][idx] * (1 + 3 * (rng.rand(n) < 0.02))).astype(np.int32)
-    sym[rng.rand(n) < 0.01] = rng.randint(-100000, 100000)
-    cdf_l, sz_l, off_l = gc_tables.cdf.tolist(), gc_tables.sizes.tolist(), gc_tables.offsets.tolist()
-    want = ref["ans"].RansEncoder().encode_with_indexes(sym.tolist(), idx.tolist(), cdf_l, sz_l, off_l)
+    if ref is not None:
+        live = reference_cpp_vectors(ref, kat["scale_table"], gc_tables)
+        assert sorted(live) == sorted(stored)
+        for k in live:
+            assert np.array_equal(live[k], stored[k]), k
+    return stored
+
+
+@pytest.mark.parametrize("seed", [0, 1, 2])
+def test_against_reference_cpp(seed, kat, gc_tables, ref_cpp):
+    sym, idx, pmfs = seeded_case(seed, kat["scale_table"])
+    n = len(idx)
+    want = ref_cpp[f"seeded{seed}_stream"].tobytes()
     assert coder.rans_encode(sym, idx, gc_tables) == want
-    d_ref = ref["ans"].RansDecoder()
-    d_ref.set_stream(want)
     d = coder.RansDecoder()
     d.set_stream(want)
     cut = n // 3
-    for a, b in ((0, cut), (cut, n)):
-        assert d.decode_stream(idx[a:b], gc_tables).tolist() == d_ref.decode_stream(idx[a:b].tolist(), cdf_l, sz_l, off_l)
-    for trial in range(20):
-        m = rng.randint(2, 40)
-        p = rng.rand(m).astype(np.float32) ** 4
-        p /= p.sum()
-        assert coder.pmf_to_quantized_cdf(p).tolist() == ref["_CXX"].pmf_to_quantized_cdf([float(v) for v in p], 16)
+    for h, (a, b) in enumerate(((0, cut), (cut, n))):
+        assert d.decode_stream(idx[a:b], gc_tables).tolist() == ref_cpp[f"seeded{seed}_dec{h}"].tolist()
+    for t, p in enumerate(pmfs):
+        assert coder.pmf_to_quantized_cdf(p).tolist() == ref_cpp[f"seeded{seed}_pmf{t}"].tolist()
 
 
 @pytest.mark.parametrize("seed", [0, 1])
-def test_lane_edge_tables_against_reference_cpp(seed):
+def test_lane_edge_tables_against_reference_cpp(seed, ref_cpp):
     """The table family of tests/test_gpu_coder.py::test_rows_around_the_lane_count (rows of 2 ... 70 slots, frequency-1
     symbols, escapes on both sides) through the reference's own C++ coder: pins the oracle on exactly the inputs the GPU
     decoder's lane-count edges are tested with."""
-    from coder_cases import lane_edge_symbols, lane_edge_tables
-
-    ref = coder.load_reference_coder()
-    if ref is None:
-        pytest.skip("oracle/_ref not built (make -C oracle ref needs /root/reference)")
     cdf, sizes, offsets, rng = lane_edge_tables(seed)
     ot = coder.Tables(cdf, sizes, offsets)
-    cdf_l, sz_l, off_l = cdf.tolist(), sizes.tolist(), offsets.tolist()
     for n in (1, 63, 64, 65, 4000):
         idx, sym = lane_edge_symbols(rng, n, sizes, offsets)
         if n < 2:  # (the reference's flush() under-allocates its output for fewer than two symbols: rans_interface.cpp:171)
             continue
-        want = ref["ans"].RansEncoder().encode_with_indexes(sym.tolist(), idx.tolist(), cdf_l, sz_l, off_l)
+        want = ref_cpp[f"lane{seed}_n{n}_stream"].tobytes()
         assert coder.rans_encode(sym, idx, ot) == want
-        d_ref = ref["ans"].RansDecoder()
-        d_ref.set_stream(want)
-        assert d_ref.decode_stream(idx.tolist(), cdf_l, sz_l, off_l) == sym.tolist()
+        assert ref_cpp[f"lane{seed}_n{n}_dec"].tolist() == sym.tolist()
         assert coder.rans_decode(want, idx, ot).tolist() == sym.tolist()
 
 
-def test_coarse_edge_tables_against_reference_cpp():
+def test_coarse_edge_tables_against_reference_cpp(ref_cpp):
     """The table family of tests/test_gpu_coder.py::test_rows_around_the_coarse_level (rows of 128 ... 4033 slots next to narrow
     ones, every slot, escapes on both sides) through the reference's own C++ coder: the oracle is pinned on exactly the inputs
     the GPU decoder's coarse first level is tested with."""
-    from coder_cases import COARSE_EDGE_SLOTS, lane_edge_symbols, lane_edge_tables
-
-    ref = coder.load_reference_coder()
-    if ref is None:
-        pytest.skip("oracle/_ref not built (make -C oracle ref needs /root/reference)")
     cdf, sizes, offsets, rng = lane_edge_tables(0, COARSE_EDGE_SLOTS)
     ot = coder.Tables(cdf, sizes, offsets)
-    cdf_l, sz_l, off_l = cdf.tolist(), sizes.tolist(), offsets.tolist()
-    coarse = [r for r, n in enumerate(COARSE_EDGE_SLOTS) if 128 < n <= 4032]
-    for n, rows in ((65, None), (3000, coarse), (3000, None)):
+    for k, (n, rows) in enumerate(coarse_edge_cases()):
         idx, sym = lane_edge_symbols(rng, n, sizes, offsets, rows=rows)
-        want = ref["ans"].RansEncoder().encode_with_indexes(sym.tolist(), idx.tolist(), cdf_l, sz_l, off_l)
+        want = ref_cpp[f"coarse{k}_stream"].tobytes()
         assert coder.rans_encode(sym, idx, ot) == want
-        d_ref = ref["ans"].RansDecoder()
-        d_ref.set_stream(want)
-        assert d_ref.decode_stream(idx.tolist(), cdf_l, sz_l, off_l) == sym.tolist()
+        assert ref_cpp[f"coarse{k}_dec"].tolist() == sym.tolist()
         assert coder.rans_decode(want, idx, ot).tolist() == sym.tolist()

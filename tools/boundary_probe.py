@@ -14,7 +14,6 @@ import threading
 import time
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "24")
 import torch  # noqa: E402
 
 import rgbd_amd  # noqa: E402,F401

@@ -1,5 +1,6 @@
-import sys, numpy as np
-sys.path.insert(0, '/root/repo'); sys.path.insert(0, '/root/repo/tests')
+import os, sys, numpy as np
+_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, _ROOT); sys.path.insert(0, os.path.join(_ROOT, 'tests'))
 import rgbd_amd
 from rgbd_amd import ans
 from rgbd_amd.entropy_models import GaussianConditional, get_scale_table

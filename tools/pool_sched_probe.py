@@ -6,7 +6,6 @@ import sys
 import time
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "32")  # one hardware queue per engine instance, as bench.py sets it
 import torch  # noqa: E402
 
 import rgbd_amd  # noqa: E402

@@ -5,7 +5,6 @@ Usage: soak.py [rounds] [workers]"""
 import os
 import sys
 
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "24")
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 

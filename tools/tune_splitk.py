@@ -40,8 +40,6 @@ def opt(name, default, cast=int):
 MAX_PX = opt("--max-px", 2048)
 STREAMS = opt("--streams", 1)
 MODEL = opt("--model", "ELIC_united", str)
-if STREAMS > 1:
-    os.environ.setdefault("GPU_MAX_HW_QUEUES", str(STREAMS + 4))
 WORKLOADS = [tuple(int(v) for v in a.split(",")) for a in argv if not a.startswith("--")] or [(4, 512, 640)]
 L = lib()
 L.rgbd_debug_bench_streams(STREAMS)

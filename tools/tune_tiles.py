@@ -28,7 +28,6 @@ STREAMS = 1  # --streams S: time every variant with S copies of the launch in fl
 if "--streams" in argv:
     STREAMS = int(argv[argv.index("--streams") + 1])
     del argv[argv.index("--streams"):argv.index("--streams") + 2]
-    os.environ.setdefault("GPU_MAX_HW_QUEUES", str(STREAMS + 4))
 args = [a for a in argv if not a.startswith("--")]
 WRITE = "--write" in sys.argv
 ONLY_CKBD = "--only-ckbd" in sys.argv  # only the checkerboard-output launches (key field nphase >= 10)
