@@ -325,9 +325,7 @@ void rgbd_tables_destroy(rgbd_tables* t)
     delete t;
 }
 
-static int64_t enc_cap_words(int64_t n) { return rgbd_enc_cap_words(n); }
-
-int64_t rgbd_rans_max_bytes(int64_t n) { return 4 * enc_cap_words(n); }
+int64_t rgbd_rans_max_bytes(int64_t n) { return 4 * rgbd_enc_cap_words(n); }
 
 int rgbd_rans_encode(const rgbd_tables* t, const int32_t* symbols, const int32_t* indexes, int64_t n, uint8_t* out,
                      int64_t cap, int64_t* out_len)
@@ -336,7 +334,7 @@ int rgbd_rans_encode(const rgbd_tables* t, const int32_t* symbols, const int32_t
     if (!t || !t->ts.ready || n < 0 || !out || !out_len || (n && (!symbols || !indexes))) return RGBD_EINVAL;
     for (int64_t i = 0; i < n; ++i)
         if (indexes[i] < 0 || indexes[i] >= t->ts.d.nrows) return RGBD_EINVAL;
-    const int64_t capw = enc_cap_words(n);
+    const int64_t capw = rgbd_enc_cap_words(n);
     int32_t *dsym = nullptr, *didx = nullptr;
     uint32_t* dout = nullptr;
     int64_t* dmeta = nullptr;

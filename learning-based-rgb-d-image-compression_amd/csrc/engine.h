@@ -1272,12 +1272,18 @@ struct rgbd_elic {
         }
     }
 
-    // The same layer kind for both modalities (names n[0] / n[1]: RGB / depth branch): one grouped launch when the two
-    // plans agree in every shape, otherwise (first / last image-facing layers: 3 vs 1 channels) two launches.
-    void conv2(const std::string n[2], const Act x[2], int stride, int pad, const Epi ep[2], const Act* const dst[2], Act out[2],
-               const std::string* const fuse1x1[2] = nullptr, const std::string* const lead1x1[2] = nullptr,
+    // The same layer kind for nm modalities (names n[0] / n[1]: RGB / depth branch).  nm == 2: one grouped launch when the
+    // two plans agree in every shape, otherwise (first / last image-facing layers: 3 vs 1 channels) two launches.
+    // nm == 1: conv() of entry 0.  Every array argument is read at [0, nm) only.
+    void conv2(int nm, const std::string n[2], const Act x[2], int stride, int pad, const Epi ep[2], const Act* const dst[2],
+               Act out[2], const std::string* const fuse1x1[2] = nullptr, const std::string* const lead1x1[2] = nullptr,
                const Act* const lead_dst[2] = nullptr)
     {
+        if (nm == 1) {
+            out[0] = conv(n[0], x[0], stride, pad, ep[0], dst ? dst[0] : nullptr, fuse1x1 ? fuse1x1[0] : nullptr,
+                          lead1x1 ? lead1x1[0] : nullptr, lead_dst ? lead_dst[0] : nullptr);
+            return;
+        }
         if (!fuse1x1 && (gate_needs_own_pass(n[0], x[0], stride, pad, ep[0]) || gate_needs_own_pass(n[1], x[1], stride, pad, ep[1]))) {
             for (int m = 0; m < 2; ++m) out[m] = conv(n[m], x[m], stride, pad, ep[m], dst ? dst[m] : nullptr);
             return;
@@ -1368,208 +1374,117 @@ struct rgbd_elic {
     }
     // outputs of leading layers that a previous block's launch has already produced, by layer name
     std::map<std::string, Act> pre_leads;
-    Act take_lead(const std::string& name, const Act& x)
-    {
-        auto it = pre_leads.find(name);
-        if (it != pre_leads.end()) {
-            Act t = it->second;
-            pre_leads.erase(it);
-            return t;
-        }
-        Epi relu;
-        relu.act = ACT_RELU;
-        return conv(name, x, 1, 0, relu);
-    }
 
-    // modules/layers/res_blk.py:7-27.  next_lead: the leading layer of the block that consumes this block's output ("" = none)
-    Act bottleneck(const std::string& p, const Act& x, const Act* dst = nullptr, const std::string& next_lead = std::string())
+    // ---- blocks of nm modalities (p[0] / p[1]: the RGB / depth branch's layer names; arrays are read at [0, nm)) --------
+    // With nm == 2 every layer pair is one grouped launch (conv2) and the fusion decisions are taken for the pair: a grouped
+    // launch tiles like the layer at twice the batch.  nm == 1 is the block of one branch.
+    void take_lead2(int nm, const std::string n[2], const Act x[2], Act t[2])
     {
-        const PackedConv* last = conv_of(p + ".branch.4.weight");
-        if (!last) return Act();
-        Act out = dst ? *dst : alloc(x.n, x.h, x.w, last->cout);
-        const std::string last_name = p + ".branch.4";
-        const bool fuse = fusable(p + ".branch.2", last_name, x);
-        const bool lead = fuse && lead_fusable(last_name, next_lead, x);
-        Act lead_out;
-        if (lead) lead_out = alloc(x.n, x.h, x.w, convs.find(next_lead + ".weight")->second.cout);  // outlives this block
-        const size_t mark = arena.top;
-        Epi relu;
-        relu.act = ACT_RELU;
-        Act t1 = take_lead(p + ".branch.0", x);
-        Epi e;
-        Act idn = x;
-        if (convs.count(p + ".skip.weight")) idn = conv(p + ".skip", x, 1, 0, Epi(), &out);  // (in place: see bottleneck2)
-        e.res1 = &idn;
-        if (lead) {
-            conv(p + ".branch.2", t1, 1, 1, e, &out, &last_name, &next_lead, &lead_out);
-            pre_leads[next_lead] = lead_out;
-        } else if (fuse) {
-            conv(p + ".branch.2", t1, 1, 1, e, &out, &last_name);
-        } else {
-            Act t2 = conv(p + ".branch.2", t1, 1, 1, relu);
-            conv(last_name, t2, 1, 0, e, &out);
-        }
-        arena.top = mark;
-        return out;
-    }
-
-    // CompressAI/compressai/layers/layers.py:177-196
-    Act res_unit(const std::string& p, const Act& x, const std::string& next_lead = std::string())
-    {
-        Act out = alloc(x.n, x.h, x.w, x.c);
-        const std::string last_name = p + ".conv.4";
-        const bool fuse = fusable(p + ".conv.2", last_name, x);
-        const bool lead = fuse && lead_fusable(last_name, next_lead, x);
-        Act lead_out;
-        if (lead) lead_out = alloc(x.n, x.h, x.w, convs.find(next_lead + ".weight")->second.cout);
-        const size_t mark = arena.top;
-        Epi relu;
-        relu.act = ACT_RELU;
-        Act t1 = take_lead(p + ".conv.0", x);
-        Epi e;
-        e.act = ACT_RELU;
-        e.res1 = &x;
-        if (lead) {
-            conv(p + ".conv.2", t1, 1, 1, e, &out, &last_name, &next_lead, &lead_out);
-            pre_leads[next_lead] = lead_out;
-        } else if (fuse) {
-            conv(p + ".conv.2", t1, 1, 1, e, &out, &last_name);
-        } else {
-            Act t2 = conv(p + ".conv.2", t1, 1, 1, relu);
-            conv(last_name, t2, 1, 0, e, &out);
-        }
-        arena.top = mark;
-        return out;
-    }
-
-    // layers.py:198-213
-    Act attention(const std::string& p, const Act& x, const Act* dst = nullptr)
-    {
-        Act out = dst ? *dst : alloc(x.n, x.h, x.w, x.c);
-        const size_t mark = arena.top;
-        Act a = x;
-        for (int u = 0; u < 3; ++u)
-            a = res_unit(p + ".conv_a." + std::to_string(u), a,
-                         u < 2 ? p + ".conv_a." + std::to_string(u + 1) + ".conv.0" : std::string());
-        Act b = x;
-        for (int u = 0; u < 3; ++u)
-            b = res_unit(p + ".conv_b." + std::to_string(u), b,
-                         u < 2 ? p + ".conv_b." + std::to_string(u + 1) + ".conv.0" : std::string());
-        Epi e;
-        e.act = ACT_SIGMOID;
-        e.mul = &a;
-        e.res2 = &x;
-        conv(p + ".conv_b.3", b, 1, 0, e, &out);
-        arena.top = mark;
-        return out;
-    }
-
-    // ---- the same blocks for both modalities at once (p[0] / p[1]: the RGB / depth branch's layer names) ----------------
-    // Every layer pair is one grouped launch (conv2).  The fusion decisions are taken for the pair: a grouped launch tiles
-    // like the layer at twice the batch.
-    void take_lead2(const std::string n[2], const Act x[2], Act t[2])
-    {
-        auto i0 = pre_leads.find(n[0]), i1 = pre_leads.find(n[1]);
-        if (i0 != pre_leads.end() && i1 != pre_leads.end()) {
-            t[0] = i0->second;
-            t[1] = i1->second;
-            pre_leads.erase(n[0]);
-            pre_leads.erase(n[1]);
+        int found = 0;
+        for (int m = 0; m < nm; ++m) found += (int)pre_leads.count(n[m]);
+        if (found == nm) {
+            for (int m = 0; m < nm; ++m) {
+                t[m] = pre_leads[n[m]];
+                pre_leads.erase(n[m]);
+            }
             return;
         }
-        if (i0 != pre_leads.end() || i1 != pre_leads.end()) {  // (never planned that way; stay correct)
-            t[0] = take_lead(n[0], x[0]);
-            t[1] = take_lead(n[1], x[1]);
+        if (found) {  // (never planned that way; stay correct)
+            for (int m = 0; m < nm; ++m) take_lead2(1, n + m, x + m, t + m);
             return;
         }
         Epi relu[2];
         relu[0].act = relu[1].act = ACT_RELU;
-        conv2(n, x, 1, 0, relu, nullptr, t);
+        conv2(nm, n, x, 1, 0, relu, nullptr, t);
     }
 
-    // res_blk.py:7-27 for both modalities
-    void bottleneck2(const std::string p[2], const Act x[2], const Act* const dst[2], const std::string next_lead[2], Act out[2])
+    // modules/layers/res_blk.py:7-27.  next_lead[m]: the leading layer of the block that consumes this block's output
+    // ("" = none)
+    void bottleneck2(int nm, const std::string p[2], const Act x[2], const Act* const dst[2], const std::string next_lead[2],
+                     Act out[2])
     {
-        const PackedConv* last[2] = {conv_of(p[0] + ".branch.4.weight"), conv_of(p[1] + ".branch.4.weight")};
-        if (!last[0] || !last[1]) return;
-        const int G = g_pair ? 2 : 1;
+        const PackedConv* last[2] = {};
+        for (int m = 0; m < nm; ++m) last[m] = conv_of(p[m] + ".branch.4.weight");
+        if (!last[0] || !last[nm - 1]) return;
+        const int G = (g_pair && nm == 2) ? 2 : 1;
         std::string last_name[2], mid[2], lead0[2];
         bool fuse = true, lead = true;
-        const bool skip = convs.count(p[0] + ".skip.weight") && convs.count(p[1] + ".skip.weight");
-        for (int m = 0; m < 2; ++m) {
+        int skips = 0;
+        for (int m = 0; m < nm; ++m) {
             out[m] = (dst && dst[m]) ? *dst[m] : alloc(x[m].n, x[m].h, x[m].w, last[m]->cout);
             last_name[m] = p[m] + ".branch.4";
             mid[m] = p[m] + ".branch.2";
             lead0[m] = p[m] + ".branch.0";
+            skips += (int)convs.count(p[m] + ".skip.weight");
             // the pair is planned at 2N; should the two plans not share a launch after all (conv2 falls back to two launches
             // when pairable() fails), each of them is re-planned at N -- so fusing has to be possible at both sizes
-            fuse = fuse && fusable(mid[m], last_name[m], x[m], G) && fusable(mid[m], last_name[m], x[m], 1);
+            fuse = fuse && fusable(mid[m], last_name[m], x[m], G) && (nm == 1 || fusable(mid[m], last_name[m], x[m], 1));
         }
-        for (int m = 0; m < 2; ++m) lead = lead && fuse && lead_fusable(last_name[m], next_lead[m], x[m]);
+        for (int m = 0; m < nm; ++m) lead = lead && fuse && lead_fusable(last_name[m], next_lead[m], x[m]);
         Act lead_out[2];
         if (lead)
-            for (int m = 0; m < 2; ++m)
+            for (int m = 0; m < nm; ++m)
                 lead_out[m] = alloc(x[m].n, x[m].h, x[m].w, convs.find(next_lead[m] + ".weight")->second.cout);  // outlives this block
         const size_t mark = arena.top;
-        Act t1[2];
-        take_lead2(lead0, x, t1);
-        Act idn[2] = {x[0], x[1]};
-        if (skip) {
+        Act t1[2], idn[2];
+        take_lead2(nm, lead0, x, t1);
+        for (int m = 0; m < nm; ++m) idn[m] = x[m];
+        if (skips == nm) {
             // the skip path lands in the block's output buffer and the last layer adds to it in place (each element is read
             // and written by the one thread that owns it): no 2 x 252 MB identity tensor at the workspace's peak stage
-            const std::string sk[2] = {p[0] + ".skip", p[1] + ".skip"};
+            std::string sk[2];
+            for (int m = 0; m < nm; ++m) sk[m] = p[m] + ".skip";
             const Epi none[2];
             const Act* sdst[2] = {&out[0], &out[1]};
-            conv2(sk, x, 1, 0, none, sdst, idn);
-        } else if (convs.count(p[0] + ".skip.weight") || convs.count(p[1] + ".skip.weight")) {
+            conv2(nm, sk, x, 1, 0, none, sdst, idn);
+        } else if (skips) {
             fail(RGBD_EINVAL);  // (the two branches are built alike)
             return;
         }
         Epi e[2];
-        e[0].res1 = &idn[0];
-        e[1].res1 = &idn[1];
+        for (int m = 0; m < nm; ++m) e[m].res1 = &idn[m];
         const Act* odst[2] = {&out[0], &out[1]};
         Act o[2];
         if (fuse) {
             const std::string* f1[2] = {&last_name[0], &last_name[1]};
             const std::string* l1[2] = {&next_lead[0], &next_lead[1]};
             const Act* ld[2] = {&lead_out[0], &lead_out[1]};
-            conv2(mid, t1, 1, 1, e, odst, o, f1, lead ? l1 : nullptr, lead ? ld : nullptr);
+            conv2(nm, mid, t1, 1, 1, e, odst, o, f1, lead ? l1 : nullptr, lead ? ld : nullptr);
             if (lead)
-                for (int m = 0; m < 2; ++m) pre_leads[next_lead[m]] = lead_out[m];
+                for (int m = 0; m < nm; ++m) pre_leads[next_lead[m]] = lead_out[m];
         } else {
             Epi relu[2];
             relu[0].act = relu[1].act = ACT_RELU;
             Act t2[2];
-            conv2(mid, t1, 1, 1, relu, nullptr, t2);
-            conv2(last_name, t2, 1, 0, e, odst, o);
+            conv2(nm, mid, t1, 1, 1, relu, nullptr, t2);
+            conv2(nm, last_name, t2, 1, 0, e, odst, o);
         }
         arena.top = mark;
     }
 
-    // layers.py:177-196 for both modalities
-    void res_unit2(const std::string p[2], const Act x[2], const std::string next_lead[2], Act out[2])
+    // CompressAI/compressai/layers/layers.py:177-196
+    void res_unit2(int nm, const std::string p[2], const Act x[2], const std::string next_lead[2], Act out[2])
     {
-        const int G = g_pair ? 2 : 1;
+        const int G = (g_pair && nm == 2) ? 2 : 1;
         std::string last_name[2], mid[2], lead0[2];
         bool fuse = true, lead = true;
-        for (int m = 0; m < 2; ++m) {
+        for (int m = 0; m < nm; ++m) {
             out[m] = alloc(x[m].n, x[m].h, x[m].w, x[m].c);
             last_name[m] = p[m] + ".conv.4";
             mid[m] = p[m] + ".conv.2";
             lead0[m] = p[m] + ".conv.0";
-            fuse = fuse && fusable(mid[m], last_name[m], x[m], G) && fusable(mid[m], last_name[m], x[m], 1);  // (see bottleneck2)
+            fuse = fuse && fusable(mid[m], last_name[m], x[m], G) && (nm == 1 || fusable(mid[m], last_name[m], x[m], 1));  // (see bottleneck2)
         }
-        for (int m = 0; m < 2; ++m) lead = lead && fuse && lead_fusable(last_name[m], next_lead[m], x[m]);
+        for (int m = 0; m < nm; ++m) lead = lead && fuse && lead_fusable(last_name[m], next_lead[m], x[m]);
         Act lead_out[2];
         if (lead)
-            for (int m = 0; m < 2; ++m)
+            for (int m = 0; m < nm; ++m)
                 lead_out[m] = alloc(x[m].n, x[m].h, x[m].w, convs.find(next_lead[m] + ".weight")->second.cout);
         const size_t mark = arena.top;
         Act t1[2];
-        take_lead2(lead0, x, t1);
+        take_lead2(nm, lead0, x, t1);
         Epi e[2];
-        for (int m = 0; m < 2; ++m) {
+        for (int m = 0; m < nm; ++m) {
             e[m].act = ACT_RELU;
             e[m].res1 = &x[m];
         }
@@ -1579,152 +1494,116 @@ struct rgbd_elic {
             const std::string* f1[2] = {&last_name[0], &last_name[1]};
             const std::string* l1[2] = {&next_lead[0], &next_lead[1]};
             const Act* ld[2] = {&lead_out[0], &lead_out[1]};
-            conv2(mid, t1, 1, 1, e, odst, o, f1, lead ? l1 : nullptr, lead ? ld : nullptr);
+            conv2(nm, mid, t1, 1, 1, e, odst, o, f1, lead ? l1 : nullptr, lead ? ld : nullptr);
             if (lead)
-                for (int m = 0; m < 2; ++m) pre_leads[next_lead[m]] = lead_out[m];
+                for (int m = 0; m < nm; ++m) pre_leads[next_lead[m]] = lead_out[m];
         } else {
             Epi relu[2];
             relu[0].act = relu[1].act = ACT_RELU;
             Act t2[2];
-            conv2(mid, t1, 1, 1, relu, nullptr, t2);
-            conv2(last_name, t2, 1, 0, e, odst, o);
+            conv2(nm, mid, t1, 1, 1, relu, nullptr, t2);
+            conv2(nm, last_name, t2, 1, 0, e, odst, o);
         }
         arena.top = mark;
     }
 
-    // layers.py:198-213 for both modalities
-    void attention2(const std::string p[2], const Act x[2], const Act* const dst[2], Act out[2])
+    // layers.py:198-213
+    void attention2(int nm, const std::string p[2], const Act x[2], const Act* const dst[2], Act out[2])
     {
-        for (int m = 0; m < 2; ++m) out[m] = (dst && dst[m]) ? *dst[m] : alloc(x[m].n, x[m].h, x[m].w, x[m].c);
+        for (int m = 0; m < nm; ++m) out[m] = (dst && dst[m]) ? *dst[m] : alloc(x[m].n, x[m].h, x[m].w, x[m].c);
         const size_t mark = arena.top;
-        Act a[2] = {x[0], x[1]}, b[2] = {x[0], x[1]};
+        Act a[2], b[2];
+        for (int m = 0; m < nm; ++m) a[m] = b[m] = x[m];
         for (int br = 0; br < 2; ++br) {
             const char* tag = br ? ".conv_b." : ".conv_a.";
             Act* cur = br ? b : a;
             for (int u = 0; u < 3; ++u) {
                 std::string n[2], nl[2];
-                for (int m = 0; m < 2; ++m) {
+                for (int m = 0; m < nm; ++m) {
                     n[m] = p[m] + tag + std::to_string(u);
                     nl[m] = u < 2 ? p[m] + tag + std::to_string(u + 1) + ".conv.0" : std::string();
                 }
                 Act o[2];
-                res_unit2(n, cur, nl, o);
+                res_unit2(nm, n, cur, nl, o);
                 cur[0] = o[0];
                 cur[1] = o[1];
             }
         }
         Epi e[2];
-        for (int m = 0; m < 2; ++m) {
+        std::string n[2];
+        for (int m = 0; m < nm; ++m) {
             e[m].act = ACT_SIGMOID;
             e[m].mul = &a[m];
             e[m].res2 = &x[m];
+            n[m] = p[m] + ".conv_b.3";
         }
-        const std::string n[2] = {p[0] + ".conv_b.3", p[1] + ".conv_b.3"};
         const Act* odst[2] = {&out[0], &out[1]};
         Act o[2];
-        conv2(n, b, 1, 0, e, odst, o);
+        conv2(nm, n, b, 1, 0, e, odst, o);
         arena.top = mark;
     }
 
-    // attention.py:84-97 for both modalities: x[m] -> dst[m] = x[m] * sigmoid(...) (+ add[m])
-    void esa2(const std::string p[2], const Act x[2], const Act dst[2], const Act* const add[2])
+    // modules/transform/attention.py:84-97: x[m] -> dst[m] = x[m] * sigmoid(...) (+ add[m]: STF_united adds the gated
+    // features to the stream instead of concatenating them; add may be nullptr)
+    void esa2(int nm, const std::string p[2], const Act x[2], const Act dst[2], const Act* const add[2])
     {
         const size_t mark = arena.top;
         const Epi none[2];
         Epi relu[2];
         relu[0].act = relu[1].act = ACT_RELU;
         auto names = [&](const char* suf, std::string n[2]) {
-            n[0] = p[0] + suf;
-            n[1] = p[1] + suf;
+            for (int m = 0; m < nm; ++m) n[m] = p[m] + suf;
         };
         std::string n[2];
         Act c1_[2], c1[2];
         names(".conv1", n);
-        conv2(n, x, 1, 0, none, nullptr, c1_);
+        conv2(nm, n, x, 1, 0, none, nullptr, c1_);
         names(".conv2", n);
-        conv2(n, c1_, 2, 0, none, nullptr, c1);
+        conv2(nm, n, c1_, 2, 0, none, nullptr, c1);
         if (c1[0].h < 7 || c1[0].w < 7) {
             fail(RGBD_EINVAL);
             return;
         }
         const int ph = (c1[0].h - 7) / 3 + 1, pw = (c1[0].w - 7) / 3 + 1;
         Act v[2];
-        for (int m = 0; m < 2; ++m) v[m] = alloc(x[m].n, ph, pw, c1[m].c);
-        const bool same = g_pair && c1[0].n == c1[1].n && c1[0].h == c1[1].h && c1[0].w == c1[1].w && c1[0].cs == c1[1].cs;
+        for (int m = 0; m < nm; ++m) v[m] = alloc(x[m].n, ph, pw, c1[m].c);
+        const bool same = nm == 2 && g_pair && c1[0].n == c1[1].n && c1[0].h == c1[1].h && c1[0].w == c1[1].w &&
+                          c1[0].cs == c1[1].cs;
         if (!dry() && !rc) {  // both modalities' pooled branches in one launch when they have the same shape (they do)
             int r = launch_maxpool7s3(c1[0].p, c1[0].n, c1[0].h, c1[0].w, c1[0].cs, v[0].p, ph, pw, s, same ? c1[1].p : nullptr,
                                       same ? v[1].p : nullptr);
-            if (!r && !same) r = launch_maxpool7s3(c1[1].p, c1[1].n, c1[1].h, c1[1].w, c1[1].cs, v[1].p, ph, pw, s);
+            if (!r && nm == 2 && !same) r = launch_maxpool7s3(c1[1].p, c1[1].n, c1[1].h, c1[1].w, c1[1].cs, v[1].p, ph, pw, s);
             if (r) fail(r);
         }
         Act vr[2], c3[2], c3b[2], up[2], sum[2], o[2];
         names(".conv_max", n);
-        conv2(n, v, 1, 1, relu, nullptr, vr);
+        conv2(nm, n, v, 1, 1, relu, nullptr, vr);
         names(".conv3", n);
-        conv2(n, vr, 1, 1, relu, nullptr, c3);
+        conv2(nm, n, vr, 1, 1, relu, nullptr, c3);
         names(".conv3_", n);
-        conv2(n, c3, 1, 1, none, nullptr, c3b);
-        for (int m = 0; m < 2; ++m) up[m] = alloc(x[m].n, x[m].h, x[m].w, c3b[m].c);
+        conv2(nm, n, c3, 1, 1, none, nullptr, c3b);
+        for (int m = 0; m < nm; ++m) up[m] = alloc(x[m].n, x[m].h, x[m].w, c3b[m].c);
         if (!dry() && !rc) {
             const bool same2 = same && x[0].h == x[1].h && x[0].w == x[1].w && c3b[0].cs == c3b[1].cs && up[0].cs == up[1].cs;
             const int rc0 = refnum ? c3b[0].c : 0, rc1 = refnum ? c3b[1].c : 0;
             int r = launch_bilinear(c3b[0].p, c3b[0].n, c3b[0].h, c3b[0].w, c3b[0].cs, up[0].p, x[0].h, x[0].w, s,
                                     same2 ? c3b[1].p : nullptr, same2 ? up[1].p : nullptr, rc0);
-            if (!r && !same2)
+            if (!r && nm == 2 && !same2)
                 r = launch_bilinear(c3b[1].p, c3b[1].n, c3b[1].h, c3b[1].w, c3b[1].cs, up[1].p, x[1].h, x[1].w, s, nullptr, nullptr, rc1);
             if (r) fail(r);
         }
-        Epi addup[2];
-        addup[0].res1 = &up[0];
-        addup[1].res1 = &up[1];
-        names(".conv_f", n);
-        conv2(n, c1_, 1, 0, addup, nullptr, sum);
-        Epi gate[2];
-        for (int m = 0; m < 2; ++m) {
+        Epi addup[2], gate[2];
+        for (int m = 0; m < nm; ++m) {
+            addup[m].res1 = &up[m];
             gate[m].act = ACT_SIGMOID;
             gate[m].mul = &x[m];
             gate[m].res2 = add ? add[m] : nullptr;
         }
+        names(".conv_f", n);
+        conv2(nm, n, c1_, 1, 0, addup, nullptr, sum);
         const Act* odst[2] = {&dst[0], &dst[1]};
         names(".conv4", n);
-        conv2(n, sum, 1, 0, gate, odst, o);
-        arena.top = mark;
-    }
-
-    // modules/transform/attention.py:84-97; x: [.., n_feats]; writes x * sigmoid(...) into dst
-    void esa(const std::string& p, const Act& x, const Act& dst, const Act* add = nullptr)
-    {
-        const size_t mark = arena.top;
-        Act c1_ = conv(p + ".conv1", x, 1, 0);
-        Act c1 = conv(p + ".conv2", c1_, 2, 0);
-        const int ph = (c1.h - 7) / 3 + 1, pw = (c1.w - 7) / 3 + 1;
-        if (c1.h < 7 || c1.w < 7) {
-            fail(RGBD_EINVAL);
-            return;
-        }
-        Act v = alloc(x.n, ph, pw, c1.c);
-        if (!dry() && !rc) {
-            const int r = launch_maxpool7s3(c1.p, c1.n, c1.h, c1.w, c1.cs, v.p, ph, pw, s);
-            if (r) fail(r);
-        }
-        Epi relu;
-        relu.act = ACT_RELU;
-        Act vr = conv(p + ".conv_max", v, 1, 1, relu);
-        Act c3 = conv(p + ".conv3", vr, 1, 1, relu);
-        c3 = conv(p + ".conv3_", c3, 1, 1);
-        Act up = alloc(x.n, x.h, x.w, c3.c);
-        if (!dry() && !rc) {
-            const int r = launch_bilinear(c3.p, c3.n, c3.h, c3.w, c3.cs, up.p, x.h, x.w, s, nullptr, nullptr, refnum ? c3.c : 0);
-            if (r) fail(r);
-        }
-        Epi addup;
-        addup.res1 = &up;
-        Act sum = conv(p + ".conv_f", c1_, 1, 0, addup);
-        Epi gate;
-        gate.act = ACT_SIGMOID;
-        gate.mul = &x;
-        gate.res2 = add;  // STF_united adds the gated features to the stream instead of concatenating them
-        conv(p + ".conv4", sum, 1, 0, gate, &dst);
+        conv2(nm, n, sum, 1, 0, gate, odst, o);
         arena.top = mark;
     }
 
@@ -1751,14 +1630,14 @@ struct rgbd_elic {
             const Epi ep[2] = {er, ed};
             const Act* dst[2] = {&rf, &df};
             Act o[2];
-            conv2(n, x, 1, 1, ep, dst, o);
+            conv2(2, n, x, 1, 1, ep, dst, o);
         }
         {
             const std::string n[2] = {p + ".r_esa", p + ".d_esa"};
             const Act x[2] = {rd, dr};
             const Act dst[2] = {r_dst, d_dst};
             const Act* add[2] = {residual ? &rgb : nullptr, residual ? &depth : nullptr};
-            esa2(n, x, dst, add);
+            esa2(2, n, x, dst, add);
         }
         arena.top = mark;
     }
@@ -1837,20 +1716,20 @@ struct rgbd_elic {
                 pr_dst = &rdst;
                 pd_dst = &ddst;
             }
-            const std::string nm[2] = {pr + si, pd + si};
+            const std::string names[2] = {pr + si, pd + si};
             const Act xin[2] = {r, d};
             const Act* dsts[2] = {pr_dst, pd_dst};
             Act o[2];
             if (k == "conv") {
                 const Epi none[2];
-                conv2(nm, xin, 2, 2, none, nullptr, o);
+                conv2(2, names, xin, 2, 2, none, nullptr, o);
                 r = o[0];
                 d = o[1];
             } else if (k == "rb") {
                 const bool next_rb = (i + 1 < 18) && std::string(kinds[i + 1]) == "rb";
                 const std::string sn = std::to_string(i + 1) + ".branch.0";
                 const std::string nl[2] = {next_rb ? pr + sn : std::string(), next_rb ? pd + sn : std::string()};
-                bottleneck2(nm, xin, dsts, nl, o);
+                bottleneck2(2, names, xin, dsts, nl, o);
                 r = o[0];
                 d = o[1];
                 if (next_spf) {
@@ -1858,7 +1737,7 @@ struct rgbd_elic {
                     d = dcat;
                 }
             } else if (k == "attn") {
-                attention2(nm, xin, dsts, o);
+                attention2(2, names, xin, dsts, o);
                 r = o[0];
                 d = o[1];
                 if (next_spf) {
@@ -1901,20 +1780,20 @@ struct rgbd_elic {
                 pr_dst = &rdst;
                 pd_dst = &ddst;
             }
-            const std::string nm[2] = {pr + si, pd + si};
+            const std::string names[2] = {pr + si, pd + si};
             const Act xin[2] = {r, d};
             const Act* dsts[2] = {pr_dst, pd_dst};
             Act o[2];
             if (k == "deconv") {
                 const Epi none[2];
-                conv2(nm, xin, 2, 2, none, next_spf ? dsts : nullptr, o);
+                conv2(2, names, xin, 2, 2, none, next_spf ? dsts : nullptr, o);
             } else if (k == "rb") {
                 const bool next_rb = (i + 1 < 18) && std::string(kinds[i + 1]) == "rb";
                 const std::string sn = std::to_string(i + 1) + ".branch.0";
                 const std::string nl[2] = {next_rb ? pr + sn : std::string(), next_rb ? pd + sn : std::string()};
-                bottleneck2(nm, xin, dsts, nl, o);
+                bottleneck2(2, names, xin, dsts, nl, o);
             } else {
-                attention2(nm, xin, dsts, o);
+                attention2(2, names, xin, dsts, o);
             }
             r = o[0];
             d = o[1];
@@ -1941,9 +1820,9 @@ struct rgbd_elic {
         const Act x0[2] = {*in[0], *in[1]};
         Act t0[2], t1[2], t2[2];
         const std::string n0[2] = {p[0] + "0", p[1] + "0"}, n2[2] = {p[0] + "2", p[1] + "2"}, n4[2] = {p[0] + "4", p[1] + "4"};
-        conv2(n0, x0, 1, 1, relu2, nullptr, t0);
-        conv2(n2, t0, 2, 2, relu2, nullptr, t1);
-        conv2(n4, t1, 2, 2, none, nullptr, t2);
+        conv2(2, n0, x0, 1, 1, relu2, nullptr, t0);
+        conv2(2, n2, t0, 2, 2, relu2, nullptr, t1);
+        conv2(2, n4, t1, 2, 2, none, nullptr, t2);
         *out[0] = t2[0];
         *out[1] = t2[1];
     }
@@ -2062,38 +1941,30 @@ struct rgbd_elic {
 
     // synthesis.py:345-362.  cat(own, other) -> SE -> deconv without materialising the unscaled concatenation: the channel
     // means of the two inputs land side by side (what the mean of the concatenation would be, channel by channel), the
-    // gate is computed from them, and each input is scaled straight into its half of the deconv's input buffer
-    Act hs_block(const std::string& p, const Act& own, const Act& other, bool last)
-    {
-        Act f = alloc(own.n, own.h, own.w, own.c + other.c);
-        se_cat_to(p + ".se", own, other, f);
-        Epi e;
-        e.act = last ? ACT_NONE : ACT_LEAKY;
-        Act o;
-        if (!last && deconv_s2_ref(p + ".deconv", f, ACT_LEAKY, &o)) return o;
-        return conv(p + ".deconv", f, last ? 1 : 2, last ? 1 : 2, e);
-    }
-
-    // one stage of both modalities: the SE gates stay per modality, the two (transposed) convs are one grouped launch
-    void hs_block2(const std::string p[2], const Act own[2], const Act other[2], bool last, Act out[2])
+    // gate is computed from them, and each input is scaled straight into its half of the deconv's input buffer.  The SE
+    // gates stay per modality; with nm == 2 the two (transposed) convs are one grouped launch.
+    void hs_block2(int nm, const std::string p[2], const Act own[2], const Act other[2], bool last, Act out[2])
     {
         Act f[2];
-        for (int m = 0; m < 2; ++m) {
+        std::string n[2];
+        for (int m = 0; m < nm; ++m) {
             f[m] = alloc(own[m].n, own[m].h, own[m].w, own[m].c + other[m].c);
             se_cat_to(p[m] + ".se", own[m], other[m], f[m]);
             if (rc) return;
+            n[m] = p[m] + ".deconv";
         }
         Epi e[2];
         e[0].act = e[1].act = last ? ACT_NONE : ACT_LEAKY;
-        const std::string n[2] = {p[0] + ".deconv", p[1] + ".deconv"};
+        // a stride-2 layer with a measured recipe runs deconv_s2_ref per modality: the pair refuses to go without it, the
+        // single branch's conv() takes that route itself and falls back to the sub-pixel kernel
         const PackedConv* pc0 = conv_of(n[0] + ".weight");
-        if (!last && refnum && pc0 && ref_blocks(3, pc0->cin, pc0->cout, f[0].h, f[0].w)) {
+        if (nm == 2 && !last && refnum && pc0 && ref_blocks(3, pc0->cin, pc0->cout, f[0].h, f[0].w)) {
             bool ok = true;
             for (int m = 0; m < 2; ++m) ok = deconv_s2_ref(n[m], f[m], ACT_LEAKY, &out[m]) && ok;
             if (!ok) fail(RGBD_ESTATE);
             return;
         }
-        conv2(n, f, last ? 1 : 2, last ? 1 : 2, e, nullptr, out);
+        conv2(nm, n, f, last ? 1 : 2, last ? 1 : 2, e, nullptr, out);
     }
 
     // synthesis.py:316-323
@@ -2104,7 +1975,7 @@ struct rgbd_elic {
             const std::string p[2] = {"h_s.r_h_s" + std::to_string(st), "h_s.d_h_s" + std::to_string(st)};
             const Act other[2] = {cur[1], cur[0]};
             Act o[2];
-            hs_block2(p, cur, other, st == 3, o);
+            hs_block2(2, p, cur, other, st == 3, o);
             cur[0] = o[0];
             cur[1] = o[1];
         }
@@ -2138,36 +2009,24 @@ struct rgbd_elic {
         return out;
     }
 
-    // context.py:10-30
-    Act channel_context(const std::string& p, const Act& x, const Act* dst = nullptr)
-    {
-        const PackedConv* last = conv_of(p + ".fushion.4.weight");
-        if (!last) return Act();
-        Act out = dst ? *dst : alloc(x.n, x.h, x.w, last->cout);
-        const size_t mark = arena.top;
-        Epi relu;
-        relu.act = ACT_RELU;
-        Act t = conv(p + ".fushion.0", x, 1, 2, relu);
-        t = conv(p + ".fushion.2", t, 1, 2, relu);
-        conv(p + ".fushion.4", t, 1, 2, Epi(), &out);
-        arena.top = mark;
-        return out;
-    }
-
-    // context.py:10-30 for both modalities (slice i's two nets read only what earlier slices decoded: independent)
-    void channel_context2(const std::string p[2], const Act x[2], const Act dst[2])
+    // context.py:10-30 (slice i's two nets read only what earlier slices decoded: independent)
+    void channel_context2(int nm, const std::string p[2], const Act x[2], const Act dst[2])
     {
         const size_t mark = arena.top;
         Epi relu[2];
         relu[0].act = relu[1].act = ACT_RELU;
         const Epi none[2];
-        const std::string n0[2] = {p[0] + ".fushion.0", p[1] + ".fushion.0"}, n2[2] = {p[0] + ".fushion.2", p[1] + ".fushion.2"},
-                          n4[2] = {p[0] + ".fushion.4", p[1] + ".fushion.4"};
+        std::string n0[2], n2[2], n4[2];
+        for (int m = 0; m < nm; ++m) {
+            n0[m] = p[m] + ".fushion.0";
+            n2[m] = p[m] + ".fushion.2";
+            n4[m] = p[m] + ".fushion.4";
+        }
         Act t0[2], t1[2], o[2];
-        conv2(n0, x, 1, 2, relu, nullptr, t0);
-        conv2(n2, t0, 1, 2, relu, nullptr, t1);
+        conv2(nm, n0, x, 1, 2, relu, nullptr, t0);
+        conv2(nm, n2, t0, 1, 2, relu, nullptr, t1);
         const Act* odst[2] = {&dst[0], &dst[1]};
-        conv2(n4, t1, 1, 2, none, odst, o);
+        conv2(nm, n4, t1, 1, 2, none, odst, o);
         arena.top = mark;
     }
 
@@ -2280,7 +2139,7 @@ struct rgbd_elic {
                 const std::string cn[2] = {"rgb_channel_context." + si, "depth_channel_context." + si};
                 const Act cx[2] = {view(yhat_r, 0, c0), view(yhat_d, 0, c0)};
                 const Act cdst[2] = {cr, cdv};
-                channel_context2(cn, cx, cdst);
+                channel_context2(2, cn, cx, cdst);
                 means_of(view(ctx, 4 * C + 2 * HC, 4 * C), sm + 4 * C + 2 * HC, wide);  // both channel contexts: adjacent
             }
             const float* smc = mean_cache ? sm : nullptr;
@@ -2376,7 +2235,7 @@ struct rgbd_elic {
         names(".norm1", n);
         layernorm2(n, x, t);
         names(".attn.qkv", n);
-        conv2(n, t, 1, 0, none, nullptr, qkv);
+        conv2(2, n, t, 1, 0, none, nullptr, qkv);
         float* rpb[2];
         for (int m = 0; m < 2; ++m) {
             a[m] = alloc(x[m].n, x[m].h, x[m].w, x[m].c);
@@ -2396,19 +2255,19 @@ struct rgbd_elic {
         e1[0].res1 = &x[0];
         e1[1].res1 = &x[1];
         names(".attn.proj", n);
-        conv2(n, a, 1, 0, e1, nullptr, x1);
+        conv2(2, n, a, 1, 0, e1, nullptr, x1);
         names(".norm2", n);
         layernorm2(n, x1, t2);
         Epi g[2];
         g[0].act = g[1].act = ACT_GELU;
         names(".mlp.fc1", n);
-        conv2(n, t2, 1, 0, g, nullptr, hdn);
+        conv2(2, n, t2, 1, 0, g, nullptr, hdn);
         Epi e2[2];
         e2[0].res1 = &x1[0];
         e2[1].res1 = &x1[1];
         const Act* odst[2] = {&out[0], &out[1]};
         names(".mlp.fc2", n);
-        conv2(n, hdn, 1, 0, e2, odst, o);
+        conv2(2, n, hdn, 1, 0, e2, odst, o);
         arena.top = mark;
     }
     // stf_united.py:270-366 for both modalities; down: 0 none, 1 PatchMerging (:217-249), 2 PatchSplit (:252-267)
@@ -2435,13 +2294,13 @@ struct rgbd_elic {
                 }
             }
             layernorm2(pn, g4, t);
-            conv2(prd, t, 1, 0, none, nullptr, out);
+            conv2(2, prd, t, 1, 0, none, nullptr, out);
             return;
         }
         if (down == 2) {
             Act t[2], r2[2];
             layernorm2(pn, x, t);
-            conv2(prd, t, 1, 0, none, nullptr, r2);
+            conv2(2, prd, t, 1, 0, none, nullptr, r2);
             for (int m = 0; m < 2; ++m) {
                 out[m] = alloc(x[m].n, 2 * x[m].h, 2 * x[m].w, x[m].c / 2);
                 if (!dry() && !rc) {
@@ -2497,7 +2356,7 @@ struct rgbd_elic {
         const Act in[2] = {r, d};
         const Epi none[2];
         Act t[2];
-        conv2(n0, in, 1, 2, none, nullptr, t);
+        conv2(2, n0, in, 1, 2, none, nullptr, t);
         const char* mods[2] = {"rgb", "depth"};
         Act* out[2] = {xr, xd};
         for (int m = 0; m < 2; ++m) {
@@ -2522,7 +2381,8 @@ struct rgbd_elic {
         Act df = view(dr, 0, half), rf = view(dr, half, half);
         conv(p + ".d_ext", depth, 1, 1, relu, &df);
         conv(p + ".r_ext", rgb, 1, 1, relu, &rf);
-        esa(p + ".d_esa", dr, d_dst);
+        const std::string n = p + ".d_esa";
+        esa2(1, &n, &dr, &d_dst, nullptr);
         arena.top = mark;
     }
     // analysis.py:56-112 / synthesis.py:186-242: the same 18 stages as ELIC_united; the fusion stage only widens depth
@@ -2539,23 +2399,22 @@ struct rgbd_elic {
                 continue;
             }
             Act dcat, ddst;
-            const Act* pd_dst = nullptr;
+            const Act* dsts[2] = {nullptr, nullptr};
             if (next_spf) {
                 const int oh = (k == "deconv") ? d.h * 2 : (k == "conv" ? d.h / 2 : d.h);
                 const int ow = (k == "deconv") ? d.w * 2 : (k == "conv" ? d.w / 2 : d.w);
                 dcat = alloc(d.n, oh, ow, 2 * N);
                 ddst = view(dcat, 0, N);
-                pd_dst = &ddst;
+                dsts[1] = &ddst;
             }
-            if (k == "conv" || k == "deconv") {
-                r = conv(pr + si, r, 2, 2);
-                d = conv(pd + si, d, 2, 2, Epi(), pd_dst);
-            } else if (k == "rb") {
-                r = bottleneck(pr + si, r);
-                d = bottleneck(pd + si, d, pd_dst);
-            } else {
-                r = attention(pr + si, r);
-                d = attention(pd + si, d, pd_dst);
+            const std::string names[2] = {pr + si, pd + si}, no_lead;
+            Act* cur[2] = {&r, &d};
+            for (int m = 0; m < 2; ++m) {  // one branch after the other
+                Act o;
+                if (k == "conv" || k == "deconv") o = conv(names[m], *cur[m], 2, 2, Epi(), dsts[m]);
+                else if (k == "rb") bottleneck2(1, &names[m], cur[m], &dsts[m], &no_lead, &o);
+                else attention2(1, &names[m], cur[m], &dsts[m], &o);
+                *cur[m] = o;
             }
             if (next_spf) d = dcat;
         }
@@ -2588,12 +2447,17 @@ struct rgbd_elic {
     // synthesis.py:336-343
     void h_s_r2d(const Act& zr, const Act& zd, Act* hr, Act* hd)
     {
-        Act r1 = hs_block_single("h_s.r_h_s1", zr, false);
-        Act d1 = hs_block("h_s.d_h_s1", zd, zr, false);
-        Act r2 = hs_block_single("h_s.r_h_s2", r1, false);
-        Act d2 = hs_block("h_s.d_h_s2", d1, r1, false);
-        *hr = hs_block_single("h_s.r_h_s3", r2, true);
-        *hd = hs_block("h_s.d_h_s3", d2, r2, true);
+        Act r = zr, d = zd;
+        for (int st = 1; st <= 3; ++st) {
+            const std::string pd = "h_s.d_h_s" + std::to_string(st);
+            const Act r_next = hs_block_single("h_s.r_h_s" + std::to_string(st), r, st == 3);
+            Act d_next;
+            hs_block2(1, &pd, &d, &r, st == 3, &d_next);
+            r = r_next;
+            d = d_next;
+        }
+        *hr = r;
+        *hd = d;
     }
     // elic_united_R2D.py:149-326.  RGB context buffer [r_loc 2C | hyper_r 2M | ch_r 2C]: anchor reads the suffix, non-anchor
     // the whole.  Depth context buffer as in ELIC_united: [r_loc 2C | d_loc 2C | hyper_r | hyper_d | ch_r | ch_d].
@@ -2617,8 +2481,10 @@ struct rgbd_elic {
             copy_ch(hyp_d, view(cdx, 4 * C + HC, HC));
             if (i) {
                 const Act chr_ = view(cdx, 4 * C + 2 * HC, 2 * C), chd = view(cdx, 6 * C + 2 * HC, 2 * C);
-                channel_context("rgb_channel_context." + si, view(yhat_r, 0, c0), &chr_);
-                channel_context("depth_channel_context." + si, view(yhat_d, 0, c0), &chd);
+                const std::string cn[2] = {"rgb_channel_context." + si, "depth_channel_context." + si};
+                const Act cx[2] = {view(yhat_r, 0, c0), view(yhat_d, 0, c0)};
+                const Act cdst[2] = {chr_, chd};
+                for (int m = 0; m < 2; ++m) channel_context2(1, cn + m, cx + m, cdst + m);
                 copy_ch(chr_, view(cr, 2 * C + HC, 2 * C));
             }
             const Act yr = y_r ? view(*y_r, c0, C) : Act();
@@ -2660,11 +2526,14 @@ struct rgbd_elic {
     Act stack1(const std::string& prefix, const char* const* kinds, int n, const Act& x_in)
     {
         Act x = x_in;
+        const std::string no_lead;
         for (int i = 0; i < n; ++i) {
             const std::string k = kinds[i], name = prefix + std::to_string(i);
-            if (k == "conv" || k == "deconv") x = conv(name, x, 2, 2);
-            else if (k == "rb") x = bottleneck(name, x);
-            else x = attention(name, x);
+            Act o;
+            if (k == "conv" || k == "deconv") o = conv(name, x, 2, 2);
+            else if (k == "rb") bottleneck2(1, &name, &x, nullptr, &no_lead, &o);
+            else attention2(1, &name, &x, nullptr, &o);
+            x = o;
         }
         return x;
     }
@@ -2731,8 +2600,9 @@ struct rgbd_elic {
             Act ctx = alloc(hyper.n, h, w, wide);
             copy_ch(hyper, view(ctx, wide - HC, HC));
             if (i) {
-                const Act cc = view(ctx, 2 * C, 2 * C);
-                channel_context("channel_context." + si, view(yhat, 0, c0), &cc);
+                const std::string cn = "channel_context." + si;
+                const Act cx = view(yhat, 0, c0), cc = view(ctx, 2 * C, 2 * C);
+                channel_context2(1, &cn, &cx, &cc);
             }
             const Act ys = y ? view(*y, c0, C) : Act();
             const Act hs = view(yhat, c0, C);
@@ -2748,6 +2618,35 @@ struct rgbd_elic {
             arena.top = mark;
         }
     }
+    // ---- stream I/O of the call paths (engine.hip), for nm = 1 (single-modal ELIC) or 2 modalities ----------------------
+    // workspace of a compress call: symbols, indexes and stream slots of every modality, and the stream geometry
+    struct EncBufs {
+        // meta: [0,B) y stream base inside a modality region (checkerboard kernels); [2B,3B) z bases; [3B,4B) z counts;
+        //   [6B,6B+nm*B) z out_words; from 8B: y encoder bases [nm*ny] (absolute), counts [nm*ny], out_words [nm*ny]
+        int64_t* meta = nullptr;
+        int32_t *sym = nullptr, *idx = nullptr;    // [nm][B*T]
+        int32_t *zsym = nullptr, *zidx = nullptr;  // [nm][B*Tz]
+        uint32_t* ywords = nullptr;                // [nm][ny] slots of ycap words
+        uint32_t* zwords = nullptr;                // [nm][B] slots of zcap words
+        int* err = nullptr;
+        int ny = 0;  // y streams per modality
+        int64_t ycap = 0, zcap = 0;
+    };
+    int enc_streams(int nm, int B, int64_t T, int64_t Tz, int per_image, EncBufs* e);
+    int fetch_streams(int nm, int B, bool with_z, const EncBufs& e);
+    // workspace of a decompress call with its streams uploaded
+    struct DecBufs {
+        uint32_t* words = nullptr;  // [y rgb | y depth | z rgb | z depth] slots of the size the encoder may produce
+        uint64_t *state = nullptr, *zstate = nullptr;      // rANS states [nm][ns_y][2] / [nm][ns_z][2]
+        int32_t *sym = nullptr, *idx = nullptr;            // [nm][B*T]
+        int32_t *zsym = nullptr, *zidx = nullptr;          // [nm][B*Tz]
+        const int64_t *yoff = nullptr, *ylen = nullptr;    // [nm][ns_y], in words
+        const int64_t *zoff = nullptr, *zlen = nullptr;    // [nm][ns_z]
+        const int64_t *ybase = nullptr, *zbase = nullptr;  // [B] symbol base of every image
+    };
+    int dec_streams(int nm, const uint8_t* const* ys[2], const int64_t* ylen[2], int ns_y, const uint8_t* const* zs[2],
+                    const int64_t* zlen[2], int ns_z, int B, int64_t T, int64_t Tz, int per_image, DecBufs* d);
+
     int run_compress1(const float* x_dev, int B, int H, int W, int per_image);
     int run_forward1(const float* x_dev, int B, int H, int W, float* xhat_dev, float* ly, float* lz);
     int run_decompress1(const uint8_t* const* ys, const int64_t* ylen, int n_y, const uint8_t* const* zs, const int64_t* zlen,

@@ -30,6 +30,166 @@ int rgbd_elic::ensure_arena(size_t bytes)
     return RGBD_OK;
 }
 
+// ---- stream I/O, for nm = 1 or 2 modalities ------------------------------------------------------------------------------
+// workspace of a compress call (symbols, indexes, stream slots, error flag, debug copies) and the upload of its stream
+// geometry (EncBufs::meta)
+int rgbd_elic::enc_streams(int nm, int B, int64_t T, int64_t Tz, int per_image, EncBufs* e)
+{
+    const int ny = per_image ? B : 1;
+    const int64_t ycount = per_image ? T : T * B;
+    const size_t nmeta = (size_t)(8 + 3 * nm) * B + 64;
+    e->ny = ny;
+    e->ycap = rgbd_enc_cap_words(ycount);
+    e->zcap = rgbd_enc_cap_words(Tz);
+    e->meta = (int64_t*)arena.take(sizeof(int64_t) * nmeta);
+    e->sym = (int32_t*)arena.take(sizeof(int32_t) * (size_t)(nm * B * T));
+    e->idx = (int32_t*)arena.take(sizeof(int32_t) * (size_t)(nm * B * T));
+    e->zsym = (int32_t*)arena.take(sizeof(int32_t) * (size_t)(nm * B * Tz));
+    e->zidx = (int32_t*)arena.take(sizeof(int32_t) * (size_t)(nm * B * Tz));
+    e->ywords = (uint32_t*)arena.take(sizeof(uint32_t) * (size_t)(nm * ny * e->ycap));
+    e->zwords = (uint32_t*)arena.take(sizeof(uint32_t) * (size_t)(nm * B * e->zcap));
+    e->err = (int*)arena.take(256);
+    dbg_sym = e->sym;
+    dbg_idx = e->idx;
+    dbg_per_mod = (int64_t)B * T;
+    dbg_x = dbg_s = nullptr;
+    if (debug_floats) {
+        dbg_x = (float*)arena.take(sizeof(float) * (size_t)(nm * B * T));
+        dbg_s = (float*)arena.take(sizeof(float) * (size_t)(nm * B * T));
+    }
+    if (dry()) return RGBD_OK;
+    void* pv = nullptr;
+    if (const int r = pin_take(nmeta * sizeof(int64_t), &pv)) return r;
+    int64_t* hmeta = (int64_t*)pv;
+    memset(hmeta, 0, nmeta * sizeof(int64_t));
+    for (int b = 0; b < B; ++b) {
+        hmeta[b] = per_image ? (int64_t)b * T : 0;
+        hmeta[2 * B + b] = (int64_t)b * Tz;
+        hmeta[3 * B + b] = Tz;
+    }
+    for (int m = 0; m < nm; ++m)
+        for (int i = 0; i < ny; ++i) {
+            hmeta[(size_t)8 * B + (size_t)m * ny + i] = (int64_t)m * B * T + (per_image ? (int64_t)i * T : 0);
+            hmeta[(size_t)8 * B + (size_t)nm * ny + (size_t)m * ny + i] = ycount;
+        }
+    HIP_TRY(hipMemcpyAsync(e->meta, hmeta, sizeof(int64_t) * nmeta, hipMemcpyHostToDevice, s));
+    return pin_release();
+}
+
+// epilogue of a compress call: the finished streams into streams[m][0] (y) and streams[m][1] (z; with_z)
+int rgbd_elic::fetch_streams(int nm, int B, bool with_z, const EncBufs& e)
+{
+    // stream sizes come back through a small pinned buffer: a device-to-host copy into pageable memory is synchronous in
+    // HIP, i.e. the host thread would spin inside it for the whole call; with pinned memory the thread sleeps on an event
+    if (!res_pin) HIP_TRY(hipHostMalloc((void**)&res_pin, kResPinBytes, hipHostMallocDefault));
+    if ((size_t)(4 * B + 2) * sizeof(int64_t) > kResPinBytes) return RGBD_EINVAL;
+    const int ny = e.ny;
+    int64_t* ow = res_pin;  // [y rgb | y depth | z rgb | z depth], B slots each, then the error flag
+    memset(ow, 0, (size_t)(4 * B + 2) * sizeof(int64_t));
+    for (int m = 0; m < nm; ++m)
+        HIP_TRY(hipMemcpyAsync(ow + (size_t)m * B, e.meta + 8 * B + (2 * nm + m) * ny, sizeof(int64_t) * ny, hipMemcpyDeviceToHost, s));
+    if (with_z) HIP_TRY(hipMemcpyAsync(ow + 2 * B, e.meta + 6 * B, sizeof(int64_t) * nm * B, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(ow + 4 * B, e.err, sizeof(int), hipMemcpyDeviceToHost, s));
+    if (const int r = wait_stream()) return r;
+    if ((int)ow[4 * B]) return RGBD_ENOSPC;
+    for (int m = 0; m < 2; ++m) {
+        const int ns_y = m < nm ? ny : 0, ns_z = m < nm && with_z ? B : 0;
+        streams[m][0].assign(ns_y, {});
+        streams[m][1].assign(ns_z, {});
+        for (int i = 0; i < ns_y; ++i) {
+            const int64_t nw = ow[(size_t)m * B + i];
+            if (nw < 0 || nw > e.ycap) return RGBD_EHIP;
+            streams[m][0][i].resize((size_t)nw * 4);
+            const uint32_t* src = e.ywords + ((size_t)m * ny + i) * e.ycap + (e.ycap - nw);
+            HIP_TRY(hipMemcpyAsync(streams[m][0][i].data(), src, (size_t)nw * 4, hipMemcpyDeviceToHost, s));
+        }
+        for (int i = 0; i < ns_z; ++i) {
+            const int64_t nw = ow[(size_t)2 * B + (size_t)m * B + i];
+            if (nw < 0 || nw > e.zcap) return RGBD_EHIP;
+            streams[m][1][i].resize((size_t)nw * 4);
+            const uint32_t* src = e.zwords + ((size_t)m * B + i) * e.zcap + (e.zcap - nw);
+            HIP_TRY(hipMemcpyAsync(streams[m][1][i].data(), src, (size_t)nw * 4, hipMemcpyDeviceToHost, s));
+        }
+    }
+    return wait_stream();
+}
+
+// workspace of a decompress call and the upload of its streams: ns_y y streams and ns_z z streams per modality, every
+// stream in a slot of the size the encoder may produce for this shape, so that the workspace layout (and with it a cached
+// graph) does not depend on the stream lengths
+int rgbd_elic::dec_streams(int nm, const uint8_t* const* ys[2], const int64_t* ylen[2], int ns_y, const uint8_t* const* zs[2],
+                           const int64_t* zlen[2], int ns_z, int B, int64_t T, int64_t Tz, int per_image, DecBufs* d)
+{
+    const int64_t ycap = rgbd_enc_cap_words(per_image ? T : T * B), zcap = rgbd_enc_cap_words(Tz);
+    // meta64: y off[nm][ns_y], y len[nm][ns_y], z off[nm][ns_z], z len[nm][ns_z], y base[B], z base[B]
+    const size_t o_ylen = (size_t)nm * ns_y, o_zoff = 2 * o_ylen, o_zlen = o_zoff + (size_t)nm * ns_z;
+    const size_t o_ybase = o_zlen + (size_t)nm * ns_z, nmeta = o_ybase + (size_t)2 * B;
+    int64_t* meta64 = (int64_t*)arena.take(sizeof(int64_t) * nmeta);
+    const size_t nwords_cap = (size_t)nm * ns_y * ycap + (size_t)nm * ns_z * zcap;
+    d->words = (uint32_t*)arena.take(sizeof(uint32_t) * (nwords_cap + 4));
+    d->state = (uint64_t*)arena.take(sizeof(uint64_t) * (size_t)(2 * nm * (ns_y + ns_z)));
+    d->zstate = d->state + (size_t)2 * nm * ns_y;
+    d->sym = (int32_t*)arena.take(sizeof(int32_t) * (size_t)(nm * B * T));
+    d->idx = (int32_t*)arena.take(sizeof(int32_t) * (size_t)(nm * B * T));
+    d->zsym = (int32_t*)arena.take(sizeof(int32_t) * (size_t)(nm * B * Tz));
+    d->zidx = (int32_t*)arena.take(sizeof(int32_t) * (size_t)(nm * B * Tz));
+    d->yoff = meta64;
+    d->ylen = meta64 + o_ylen;
+    d->zoff = meta64 + o_zoff;
+    d->zlen = meta64 + o_zlen;
+    d->ybase = meta64 + o_ybase;
+    d->zbase = d->ybase + B;
+    dbg_sym = d->sym;
+    dbg_idx = d->idx;
+    dbg_per_mod = (int64_t)B * T;
+    dbg_x = dbg_s = nullptr;
+    if (debug_floats) {
+        dbg_x = (float*)arena.take(sizeof(float) * (size_t)(nm * B * T));
+        dbg_s = (float*)arena.take(sizeof(float) * (size_t)(nm * B * T));
+    }
+    for (int m = 0; m < nm; ++m) {
+        for (int i = 0; i < ns_y; ++i)
+            if (!ys[m] || !ys[m][i] || ylen[m][i] < 8 || (ylen[m][i] & 3) || ylen[m][i] / 4 > ycap) return RGBD_EINVAL;
+        for (int i = 0; i < ns_z; ++i)
+            if (!zs[m] || !zs[m][i] || zlen[m][i] < 8 || (zlen[m][i] & 3) || zlen[m][i] / 4 > zcap) return RGBD_EINVAL;
+    }
+    if (dry()) return RGBD_OK;
+    size_t total_words = 0;
+    for (int m = 0; m < nm; ++m) {
+        for (int i = 0; i < ns_y; ++i) total_words += (size_t)ylen[m][i] / 4;
+        for (int i = 0; i < ns_z; ++i) total_words += (size_t)zlen[m][i] / 4;
+    }
+    void* pv = nullptr;
+    if (const int r = pin_take(nmeta * sizeof(int64_t) + total_words * 4, &pv)) return r;
+    int64_t* hmeta = (int64_t*)pv;
+    uint32_t* hw = (uint32_t*)(hmeta + nmeta);
+    size_t used = 0;
+    auto put = [&](const uint8_t* src, int64_t len, size_t slot_off, size_t meta_off, size_t meta_len) -> int {
+        memcpy(hw + used, src, (size_t)len);
+        hmeta[meta_off] = (int64_t)slot_off;
+        hmeta[meta_len] = len / 4;
+        HIP_TRY(hipMemcpyAsync(d->words + slot_off, hw + used, (size_t)len, hipMemcpyHostToDevice, s));
+        used += (size_t)len / 4;
+        return RGBD_OK;
+    };
+    for (int m = 0; m < nm; ++m)
+        for (int i = 0; i < ns_y; ++i) {
+            const size_t k = (size_t)m * ns_y + i;
+            if (const int r = put(ys[m][i], ylen[m][i], k * (size_t)ycap, k, o_ylen + k)) return r;
+        }
+    for (int m = 0; m < nm; ++m)
+        for (int i = 0; i < ns_z; ++i) {
+            const size_t k = (size_t)m * ns_z + i;
+            if (const int r = put(zs[m][i], zlen[m][i], (size_t)nm * ns_y * ycap + k * (size_t)zcap, o_zoff + k, o_zlen + k)) return r;
+        }
+    for (int b = 0; b < B; ++b) {
+        hmeta[o_ybase + b] = per_image ? (int64_t)b * T : 0;
+        hmeta[o_ybase + B + b] = (int64_t)b * Tz;
+    }
+    HIP_TRY(hipMemcpyAsync(meta64, hmeta, sizeof(int64_t) * nmeta, hipMemcpyHostToDevice, s));
+    return pin_release();
+}
+
 int rgbd_elic::run_compress(const float* rgb_dev, const float* depth_dev, int B, int H, int W, int per_image,
                             const Latents* lat)
 {
@@ -37,7 +197,6 @@ int rgbd_elic::run_compress(const float* rgb_dev, const float* depth_dev, int B,
     const int Ctot = M;
     const int64_t T = (int64_t)Ctot * h * w;  // y symbols per image per modality
     const int64_t Tz = (int64_t)N * zh * zw;
-    const int ny = per_image ? B : 1;
     ref_batch = per_image ? 1 : B;  // per-image streams stand for the reference called image by image
     named.clear();
     pre_leads.clear();
@@ -45,24 +204,8 @@ int rgbd_elic::run_compress(const float* rgb_dev, const float* depth_dev, int B,
     rc = 0;
 
     // ==== prologue (never captured): workspace of the call, upload of the stream geometry, input layout conversion ====
-    int64_t* meta64 = (int64_t*)arena.take(sizeof(int64_t) * (size_t)(14 * B + 64));
-    int32_t* sym = (int32_t*)arena.take(sizeof(int32_t) * (size_t)(2 * B * T));
-    int32_t* idx = (int32_t*)arena.take(sizeof(int32_t) * (size_t)(2 * B * T));
-    int32_t* zsym = (int32_t*)arena.take(sizeof(int32_t) * (size_t)(2 * B * Tz));
-    int32_t* zidx = (int32_t*)arena.take(sizeof(int32_t) * (size_t)(2 * B * Tz));
-    const int64_t ycount = per_image ? T : T * B;
-    const int64_t ycap = ((5 * ycount + 32 + 704) + 63) & ~(int64_t)63, zcap = ((5 * Tz + 32 + 704) + 63) & ~(int64_t)63;
-    uint32_t* ywords = (uint32_t*)arena.take(sizeof(uint32_t) * (size_t)(2 * ny * ycap));
-    uint32_t* zwords = (uint32_t*)arena.take(sizeof(uint32_t) * (size_t)(2 * B * zcap));
-    int* err = (int*)arena.take(256);
-    dbg_sym = sym;
-    dbg_idx = idx;
-    dbg_per_mod = (int64_t)B * T;
-    dbg_x = dbg_s = nullptr;
-    if (debug_floats) {
-        dbg_x = (float*)arena.take(sizeof(float) * (size_t)(2 * B * T));
-        dbg_s = (float*)arena.take(sizeof(float) * (size_t)(2 * B * T));
-    }
+    EncBufs e;
+    if (const int r = enc_streams(2, B, T, Tz, per_image, &e)) return r;
     int32_t *fy = nullptr, *fz = nullptr;  // teacher forcing (rgbd_elic_set_forced_symbols)
     if (!force_y[0].empty() || !force_y[1].empty()) {
         if (force_y[0].size() != (size_t)(B * T) || force_y[1].size() != (size_t)(B * T)) return RGBD_EINVAL;
@@ -77,28 +220,6 @@ int rgbd_elic::run_compress(const float* rgb_dev, const float* depth_dev, int B,
         if (!dry())
             for (int m = 0; m < 2; ++m)
                 HIP_TRY(hipMemcpyAsync(fz + (size_t)m * B * Tz, force_z[m].data(), sizeof(int32_t) * (size_t)(B * Tz), hipMemcpyHostToDevice, s));
-    }
-
-    // meta64 layout: [0,B) y stream_base inside a modality region (checkerboard kernels) ; [2B,3B) z base ;
-    //   [3B,4B) z counts ; [6B,8B) z out_words ; from 8B: y encoder bases [2ny] (absolute), counts [2ny], out_words [2ny]
-    if (!dry()) {
-        const size_t nmeta = (size_t)14 * B + 64;
-        void* pv = nullptr;
-        if (const int r = pin_take(nmeta * sizeof(int64_t), &pv)) return r;
-        int64_t* hmeta = (int64_t*)pv;
-        memset(hmeta, 0, nmeta * sizeof(int64_t));
-        for (int b = 0; b < B; ++b) {
-            hmeta[b] = per_image ? (int64_t)b * T : 0;
-            hmeta[2 * B + b] = (int64_t)b * Tz;
-            hmeta[3 * B + b] = Tz;
-        }
-        for (int m = 0; m < 2; ++m)
-            for (int i = 0; i < ny; ++i) {
-                hmeta[(size_t)8 * B + (size_t)m * ny + i] = (int64_t)m * B * T + (per_image ? (int64_t)i * T : 0);
-                hmeta[(size_t)8 * B + 2 * ny + (size_t)m * ny + i] = ycount;
-            }
-        HIP_TRY(hipMemcpyAsync(meta64, hmeta, sizeof(int64_t) * nmeta, hipMemcpyHostToDevice, s));
-        if (const int r = pin_release()) return r;
     }
 
     Act y_r = alloc(B, h, w, M), y_d = alloc(B, h, w, M);
@@ -126,7 +247,7 @@ int rgbd_elic::run_compress(const float* rgb_dev, const float* depth_dev, int B,
     // ==== body: every kernel of the call, in stream order; captured into / replayed from a HIP graph per call shape ====
     if (body_begin()) {
         if (!dry()) {
-            const int zr = launch_fill_zero((float*)err, 64, s);  // (a kernel, not a memset node: see launch_fill_zero)
+            const int zr = launch_fill_zero((float*)e.err, 64, s);  // (a kernel, not a memset node: see launch_fill_zero)
             if (zr) fail(zr);
         }
         named["y_r"] = y_r;
@@ -158,12 +279,12 @@ int rgbd_elic::run_compress(const float* rgb_dev, const float* depth_dev, int B,
                 for (int m = 0; m < 2 && !rc; ++m) {
                     float* md = dense_of(med[m]);
                     if (!md) break;
-                    int32_t* zs = zsym + (size_t)m * B * Tz;
-                    int32_t* zi = zidx + (size_t)m * B * Tz;
+                    int32_t* zs = e.zsym + (size_t)m * B * Tz;
+                    int32_t* zi = e.zidx + (size_t)m * B * Tz;
                     int r = launch_z_quant(zz[m]->p, zz[m]->cs, B, zh, zw, N, md, zs, zi, s, perm());
                     if (!r)
-                        r = launch_rans_encode(zs, zi, meta64 + 2 * B, meta64 + 3 * B, B, B, tables[2 + m].d, tables[2 + m].d,
-                                               zwords + (size_t)m * B * zcap, zcap, meta64 + 6 * B + (size_t)m * B, err, s);
+                        r = launch_rans_encode(zs, zi, e.meta + 2 * B, e.meta + 3 * B, B, B, tables[2 + m].d, tables[2 + m].d,
+                                               e.zwords + (size_t)m * B * e.zcap, e.zcap, e.meta + 6 * B + (size_t)m * B, e.err, s);
                     if (!r) r = launch_z_dequant(fz ? fz + (size_t)m * B * Tz : zs, B, zh, zw, N, md, zo[m]->p, zo[m]->cs, s, perm());
                     if (r) fail(r);
                 }
@@ -189,17 +310,18 @@ int rgbd_elic::run_compress(const float* rgb_dev, const float* depth_dev, int B,
         cd.encode = true;
         cd.per_image = per_image;
         cd.per_image_total = T;
-        cd.sym = sym;
-        cd.idx = idx;
-        cd.stream_base = meta64;
+        cd.sym = e.sym;
+        cd.idx = e.idx;
+        cd.stream_base = e.meta;
         cd.force = fy;
         if (variant == 3) bicee_r2d(cd, &y_r, &y_d, hyp_r, hyp_d, yhat_r, yhat_d);
         else bicee(cd, &y_r, &y_d, hyp_r, hyp_d, yhat_r, yhat_d);
 
         if (!dry() && !rc) {
             // both modalities in one launch: streams [0, ny) are rgb, [ny, 2ny) depth; bases are relative to `sym`
-            const int r = launch_rans_encode(sym, idx, meta64 + 8 * B, meta64 + 8 * B + 2 * ny, 2 * ny, ny, tables[0].d,
-                                             tables[1].d, ywords, ycap, meta64 + 8 * B + 4 * ny, err, s);
+            const int ny = e.ny;
+            const int r = launch_rans_encode(e.sym, e.idx, e.meta + 8 * B, e.meta + 8 * B + 2 * ny, 2 * ny, ny, tables[0].d,
+                                             tables[1].d, e.ywords, e.ycap, e.meta + 8 * B + 4 * ny, e.err, s);
             if (r) fail(r);
         }
     }
@@ -211,37 +333,7 @@ int rgbd_elic::run_compress(const float* rgb_dev, const float* depth_dev, int B,
     if (dry()) return RGBD_OK;
 
     // ==== epilogue (never captured): fetch the streams ================================================================
-    // stream sizes come back through a small pinned buffer: a device-to-host copy into pageable memory is synchronous in
-    // HIP, i.e. the host thread would spin inside it for the whole call; with pinned memory the thread sleeps on an event
-    if (!res_pin) HIP_TRY(hipHostMalloc((void**)&res_pin, kResPinBytes, hipHostMallocDefault));
-    if ((size_t)(4 * B + 2) * sizeof(int64_t) > kResPinBytes) return RGBD_EINVAL;
-    int64_t* ow = res_pin;  // [y rgb | y depth | z rgb | z depth], B slots each, then the error flag
-    memset(ow, 0, (size_t)(4 * B + 2) * sizeof(int64_t));
-    HIP_TRY(hipMemcpyAsync(ow, meta64 + 8 * B + 4 * ny, sizeof(int64_t) * ny, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(ow + B, meta64 + 8 * B + 5 * ny, sizeof(int64_t) * ny, hipMemcpyDeviceToHost, s));
-    if (!lat) HIP_TRY(hipMemcpyAsync(ow + 2 * B, meta64 + 6 * B, sizeof(int64_t) * 2 * B, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(ow + 4 * B, err, sizeof(int), hipMemcpyDeviceToHost, s));
-    if (const int r = wait_stream()) return r;
-    if ((int)ow[4 * B]) return RGBD_ENOSPC;
-    for (int m = 0; m < 2; ++m) {
-        streams[m][0].assign(ny, {});
-        streams[m][1].assign(lat ? 0 : B, {});
-        for (int i = 0; i < ny; ++i) {
-            const int64_t nw = ow[(size_t)m * B + i];
-            if (nw < 0 || nw > ycap) return RGBD_EHIP;
-            streams[m][0][i].resize((size_t)nw * 4);
-            const uint32_t* src = ywords + ((size_t)m * ny + i) * ycap + (ycap - nw);
-            HIP_TRY(hipMemcpyAsync(streams[m][0][i].data(), src, (size_t)nw * 4, hipMemcpyDeviceToHost, s));
-        }
-        for (int i = 0; i < B && !lat; ++i) {
-            const int64_t nw = ow[(size_t)2 * B + (size_t)m * B + i];
-            if (nw < 0 || nw > zcap) return RGBD_EHIP;
-            streams[m][1][i].resize((size_t)nw * 4);
-            const uint32_t* src = zwords + ((size_t)m * B + i) * zcap + (zcap - nw);
-            HIP_TRY(hipMemcpyAsync(streams[m][1][i].data(), src, (size_t)nw * 4, hipMemcpyDeviceToHost, s));
-        }
-    }
-    return wait_stream();
+    return fetch_streams(2, B, !lat, e);
 }
 
 // eval-mode forward(): models/elic_united.py:234-263 with quant == "ste" (round in eval), likelihoods as in
@@ -371,79 +463,9 @@ int rgbd_elic::run_decompress_impl(const uint8_t* const* ys[2], const int64_t* y
     rc = 0;
 
     // ==== prologue (never captured): upload the streams ================================================================
-    // words region = [y rgb | y depth | z rgb | z depth], every stream in a slot of the size the encoder may produce for
-    // this shape, so that the workspace layout (and with it a cached graph) does not depend on the stream lengths
     const int ns_y = n_y, ns_z = lat ? 0 : B;
-    const int64_t ycount = per_image ? T : T * B;
-    const int64_t ycap = ((5 * ycount + 32 + 704) + 63) & ~(int64_t)63, zcap = ((5 * Tz + 32 + 704) + 63) & ~(int64_t)63;
-    // meta64: y off[2][ns_y], y len[2][ns_y], z off[2][ns_z], z len[2][ns_z], y base[B], z base[B]
-    const size_t nmeta = (size_t)4 * ns_y + (size_t)4 * ns_z + (size_t)2 * B;
-    int64_t* meta64 = (int64_t*)arena.take(sizeof(int64_t) * nmeta);
-    const size_t nwords_cap = (size_t)2 * ns_y * ycap + (size_t)2 * ns_z * zcap;
-    uint32_t* words = (uint32_t*)arena.take(sizeof(uint32_t) * (nwords_cap + 4));
-    uint64_t* state = (uint64_t*)arena.take(sizeof(uint64_t) * (size_t)(4 * (ns_y + ns_z)));
-    int32_t* sym = (int32_t*)arena.take(sizeof(int32_t) * (size_t)(2 * B * T));
-    int32_t* idx = (int32_t*)arena.take(sizeof(int32_t) * (size_t)(2 * B * T));
-    int32_t* zsym = (int32_t*)arena.take(sizeof(int32_t) * (size_t)(2 * B * Tz));
-    int32_t* zidx = (int32_t*)arena.take(sizeof(int32_t) * (size_t)(2 * B * Tz));
-    dbg_sym = sym;
-    dbg_idx = idx;
-    dbg_per_mod = (int64_t)B * T;
-    dbg_x = dbg_s = nullptr;
-    if (debug_floats) {
-        dbg_x = (float*)arena.take(sizeof(float) * (size_t)(2 * B * T));
-        dbg_s = (float*)arena.take(sizeof(float) * (size_t)(2 * B * T));
-    }
-    for (int m = 0; m < 2; ++m) {
-        for (int i = 0; i < ns_y; ++i)
-            if (!ys[m] || !ys[m][i] || ylen[m][i] < 8 || (ylen[m][i] & 3) || ylen[m][i] / 4 > ycap) return RGBD_EINVAL;
-        for (int i = 0; i < ns_z; ++i)
-            if (!zs[m] || !zs[m][i] || zlen[m][i] < 8 || (zlen[m][i] & 3) || zlen[m][i] / 4 > zcap) return RGBD_EINVAL;
-    }
-    if (!dry()) {
-        size_t total_words = 0;
-        for (int m = 0; m < 2; ++m) {
-            for (int i = 0; i < ns_y; ++i) total_words += (size_t)ylen[m][i] / 4;
-            for (int i = 0; i < ns_z; ++i) total_words += (size_t)zlen[m][i] / 4;
-        }
-        void* pv = nullptr;
-        if (const int r = pin_take(nmeta * sizeof(int64_t) + total_words * 4, &pv)) return r;
-        int64_t* hmeta = (int64_t*)pv;
-        uint32_t* hw = (uint32_t*)(hmeta + nmeta);
-        size_t used = 0;
-        auto put = [&](const uint8_t* src, int64_t len, size_t slot_off, size_t meta_off, size_t meta_len) -> int {
-            memcpy(hw + used, src, (size_t)len);
-            hmeta[meta_off] = (int64_t)slot_off;
-            hmeta[meta_len] = len / 4;
-            HIP_TRY(hipMemcpyAsync(words + slot_off, hw + used, (size_t)len, hipMemcpyHostToDevice, s));
-            used += (size_t)len / 4;
-            return RGBD_OK;
-        };
-        for (int m = 0; m < 2; ++m)
-            for (int i = 0; i < ns_y; ++i) {
-                const size_t k = (size_t)m * ns_y + i;
-                if (const int r = put(ys[m][i], ylen[m][i], k * (size_t)ycap, k, (size_t)2 * ns_y + k)) return r;
-            }
-        for (int m = 0; m < 2; ++m)
-            for (int i = 0; i < ns_z; ++i) {
-                const size_t k = (size_t)m * ns_z + i;
-                if (const int r = put(zs[m][i], zlen[m][i], (size_t)2 * ns_y * ycap + k * (size_t)zcap, (size_t)4 * ns_y + k,
-                                      (size_t)4 * ns_y + 2 * ns_z + k))
-                    return r;
-            }
-        for (int b = 0; b < B; ++b) {
-            hmeta[(size_t)4 * ns_y + 4 * ns_z + b] = per_image ? (int64_t)b * T : 0;
-            hmeta[(size_t)4 * ns_y + 4 * ns_z + B + b] = (int64_t)b * Tz;
-        }
-        HIP_TRY(hipMemcpyAsync(meta64, hmeta, sizeof(int64_t) * nmeta, hipMemcpyHostToDevice, s));
-        if (const int r = pin_release()) return r;
-    }
-    const int64_t* d_yoff = meta64;
-    const int64_t* d_ylen = meta64 + 2 * ns_y;
-    const int64_t* d_zoff = meta64 + 4 * ns_y;
-    const int64_t* d_zlen = meta64 + 4 * ns_y + 2 * ns_z;
-    const int64_t* d_ybase = meta64 + 4 * ns_y + 4 * ns_z;
-    const int64_t* d_zbase = d_ybase + B;
+    DecBufs d;
+    if (const int r = dec_streams(2, ys, ylen, ns_y, zs, zlen, ns_z, B, T, Tz, per_image, &d)) return r;
 
     Act hyp_r, hyp_d;
     if (lat) {
@@ -468,15 +490,14 @@ int rgbd_elic::run_decompress_impl(const uint8_t* const* ys[2], const int64_t* y
                 for (int m = 0; m < 2 && !rc; ++m) {
                     float* md = dense_of(med[m]);
                     if (!md) break;
-                    int32_t* zs_ = zsym + (size_t)m * B * Tz;
-                    int32_t* zi_ = zidx + (size_t)m * B * Tz;
+                    int32_t* zs_ = d.zsym + (size_t)m * B * Tz;
+                    int32_t* zi_ = d.zidx + (size_t)m * B * Tz;
                     // indexes = channel id in (c, row, col) order: the quantiser's index writer on a zeroed tensor
                     int r = launch_fill_zero(zo[m]->p, zo[m]->elems(), s);
                     if (!r) r = launch_z_quant(zo[m]->p, zo[m]->cs, B, zh, zw, N, md, zs_, zi_, s, perm());
                     if (!r)
-                        r = launch_rans_decode(words, d_zoff + (size_t)m * ns_z, d_zlen + (size_t)m * ns_z, ns_z,
-                                               state + (size_t)4 * ns_y + (size_t)m * ns_z * 2, 1, zi_, zs_, d_zbase, 0, Tz,
-                                               tables[2 + m].d, s);
+                        r = launch_rans_decode(d.words, d.zoff + (size_t)m * ns_z, d.zlen + (size_t)m * ns_z, ns_z,
+                                               d.zstate + (size_t)m * ns_z * 2, 1, zi_, zs_, d.zbase, 0, Tz, tables[2 + m].d, s);
                     if (!r) r = launch_z_dequant(zs_, B, zh, zw, N, md, zo[m]->p, zo[m]->cs, s, perm());
                     if (r) fail(r);
                 }
@@ -501,13 +522,13 @@ int rgbd_elic::run_decompress_impl(const uint8_t* const* ys[2], const int64_t* y
         cd.encode = false;
         cd.per_image = per_image;
         cd.per_image_total = T;
-        cd.sym = sym;
-        cd.idx = idx;
-        cd.stream_base = d_ybase;
-        cd.words = words;
-        cd.stream_off = d_yoff;
-        cd.stream_len = d_ylen;
-        cd.state = state;
+        cd.sym = d.sym;
+        cd.idx = d.idx;
+        cd.stream_base = d.ybase;
+        cd.words = d.words;
+        cd.stream_off = d.yoff;
+        cd.stream_len = d.ylen;
+        cd.state = d.state;
         cd.nstreams = ns_y;
         if (variant == 3) bicee_r2d(cd, nullptr, nullptr, hyp_r, hyp_d, yhat_r, yhat_d);
         else bicee(cd, nullptr, nullptr, hyp_r, hyp_d, yhat_r, yhat_d);
@@ -622,46 +643,13 @@ int rgbd_elic::run_compress1(const float* x_dev, int B, int H, int W, int per_im
 {
     const int h = H / 16, w = W / 16, zh = H / 64, zw = W / 64;
     const int64_t T = (int64_t)M * h * w, Tz = (int64_t)N * zh * zw;
-    const int ny = per_image ? B : 1;
     ref_batch = per_image ? 1 : B;
     named.clear();
     pre_leads.clear();
     arena.reset();
     rc = 0;
-    int64_t* meta64 = (int64_t*)arena.take(sizeof(int64_t) * (size_t)(8 * B + 64));
-    int32_t* sym = (int32_t*)arena.take(sizeof(int32_t) * (size_t)(B * T));
-    int32_t* idx = (int32_t*)arena.take(sizeof(int32_t) * (size_t)(B * T));
-    int32_t* zsym = (int32_t*)arena.take(sizeof(int32_t) * (size_t)(B * Tz));
-    int32_t* zidx = (int32_t*)arena.take(sizeof(int32_t) * (size_t)(B * Tz));
-    const int64_t ycount = per_image ? T : T * B;
-    const int64_t ycap = ((5 * ycount + 32 + 704) + 63) & ~(int64_t)63, zcap = ((5 * Tz + 32 + 704) + 63) & ~(int64_t)63;
-    uint32_t* ywords = (uint32_t*)arena.take(sizeof(uint32_t) * (size_t)(ny * ycap));
-    uint32_t* zwords = (uint32_t*)arena.take(sizeof(uint32_t) * (size_t)(B * zcap));
-    int* err = (int*)arena.take(256);
-    dbg_sym = sym;
-    dbg_idx = idx;
-    dbg_per_mod = (int64_t)B * T;
-    dbg_x = dbg_s = nullptr;
-    if (debug_floats) {
-        dbg_x = (float*)arena.take(sizeof(float) * (size_t)(B * T));
-        dbg_s = (float*)arena.take(sizeof(float) * (size_t)(B * T));
-    }
-    // meta64: [0,B) y stream base (checkerboard kernels); [B,2B) z base; [2B,3B) z counts; [3B,4B) z out_words;
-    //         [4B,4B+ny) y encoder bases; [5B,5B+ny) y counts; [6B,6B+ny) y out_words
-    std::vector<int64_t> hmeta((size_t)8 * B + 64, 0);
-    for (int b = 0; b < B; ++b) {
-        hmeta[b] = per_image ? (int64_t)b * T : 0;
-        hmeta[B + b] = (int64_t)b * Tz;
-        hmeta[2 * B + b] = Tz;
-    }
-    for (int i = 0; i < ny; ++i) {
-        hmeta[(size_t)4 * B + i] = per_image ? (int64_t)i * T : 0;
-        hmeta[(size_t)5 * B + i] = ycount;
-    }
-    if (!dry()) {
-        // (pageable source: the copy has left the host buffer when the call returns, so the vector may go out of scope)
-        HIP_TRY(hipMemcpyAsync(meta64, hmeta.data(), sizeof(int64_t) * hmeta.size(), hipMemcpyHostToDevice, s));
-    }
+    EncBufs e;
+    if (const int r = enc_streams(1, B, T, Tz, per_image, &e)) return r;
     Act x = alloc(B, H, W, in_ch);
     if (!dry()) {
         const int r = launch_nchw_to_nhwc16(x_dev, B, in_ch, H, W, x.p, x.cs, s);
@@ -670,7 +658,7 @@ int rgbd_elic::run_compress1(const float* x_dev, int B, int H, int W, int per_im
     // ==== body: captured into / replayed from a HIP graph per call shape ================================================
     if (body_begin()) {
         if (!dry()) {
-            const int zr = launch_fill_zero((float*)err, 64, s);  // (a kernel, not a memset node: DESIGN 3.5)
+            const int zr = launch_fill_zero((float*)e.err, 64, s);  // (a kernel, not a memset node: DESIGN 3.5)
             if (zr) fail(zr);
         }
         Act y = alloc(B, h, w, M);
@@ -685,11 +673,11 @@ int rgbd_elic::run_compress1(const float* x_dev, int B, int H, int W, int per_im
         Act zhat = alloc(B, zh, zw, N);
         float* md = dense_of("entropy_bottleneck.medians");
         if (!dry() && !rc && md) {
-            int r = launch_z_quant(z.p, z.cs, B, zh, zw, N, md, zsym, zidx, s, perm());
+            int r = launch_z_quant(z.p, z.cs, B, zh, zw, N, md, e.zsym, e.zidx, s, perm());
             if (!r)
-                r = launch_rans_encode(zsym, zidx, meta64 + B, meta64 + 2 * B, B, B, tables[2].d, tables[2].d, zwords, zcap,
-                                       meta64 + 3 * B, err, s);
-            if (!r) r = launch_z_dequant(zsym, B, zh, zw, N, md, zhat.p, zhat.cs, s, perm());
+                r = launch_rans_encode(e.zsym, e.zidx, e.meta + 2 * B, e.meta + 3 * B, B, B, tables[2].d, tables[2].d, e.zwords,
+                                       e.zcap, e.meta + 6 * B, e.err, s);
+            if (!r) r = launch_z_dequant(e.zsym, B, zh, zw, N, md, zhat.p, zhat.cs, s, perm());
             if (r) fail(r);
         }
         named["zhat"] = zhat;
@@ -701,13 +689,14 @@ int rgbd_elic::run_compress1(const float* x_dev, int B, int H, int W, int per_im
         cd.encode = true;
         cd.per_image = per_image;
         cd.per_image_total = T;
-        cd.sym = sym;
-        cd.idx = idx;
-        cd.stream_base = meta64;
+        cd.sym = e.sym;
+        cd.idx = e.idx;
+        cd.stream_base = e.meta;
         bicee1(cd, &y, hyper, yhat);
         if (!dry() && !rc) {
-            const int r = launch_rans_encode(sym, idx, meta64 + 4 * B, meta64 + 5 * B, ny, ny, tables[0].d, tables[0].d, ywords,
-                                             ycap, meta64 + 6 * B, err, s);
+            const int ny = e.ny;
+            const int r = launch_rans_encode(e.sym, e.idx, e.meta + 8 * B, e.meta + 8 * B + ny, ny, ny, tables[0].d, tables[0].d,
+                                             e.ywords, e.ycap, e.meta + 8 * B + 2 * ny, e.err, s);
             if (r) fail(r);
         }
     }  // body
@@ -716,33 +705,8 @@ int rgbd_elic::run_compress1(const float* x_dev, int B, int H, int W, int per_im
         if (rc) return rc;
         if (r) return r;
     }
-    if (rc) return rc;
     if (dry()) return RGBD_OK;
-    std::vector<int64_t> ow((size_t)2 * B, 0);
-    int herr = 0;
-    HIP_TRY(hipMemcpyAsync(ow.data(), meta64 + 6 * B, sizeof(int64_t) * ny, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(ow.data() + B, meta64 + 3 * B, sizeof(int64_t) * B, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(&herr, err, sizeof(int), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    if (herr) return RGBD_ENOSPC;
-    streams[0][0].assign(ny, {});
-    streams[0][1].assign(B, {});
-    streams[1][0].clear();
-    streams[1][1].clear();
-    for (int i = 0; i < ny; ++i) {
-        const int64_t nw = ow[i];
-        streams[0][0][i].resize((size_t)nw * 4);
-        HIP_TRY(hipMemcpyAsync(streams[0][0][i].data(), ywords + (size_t)i * ycap + (ycap - nw), (size_t)nw * 4,
-                               hipMemcpyDeviceToHost, s));
-    }
-    for (int i = 0; i < B; ++i) {
-        const int64_t nw = ow[(size_t)B + i];
-        streams[0][1][i].resize((size_t)nw * 4);
-        HIP_TRY(hipMemcpyAsync(streams[0][1][i].data(), zwords + (size_t)i * zcap + (zcap - nw), (size_t)nw * 4,
-                               hipMemcpyDeviceToHost, s));
-    }
-    HIP_TRY(hipStreamSynchronize(s));
-    return RGBD_OK;
+    return fetch_streams(1, B, true, e);
 }
 
 int rgbd_elic::run_decompress1(const uint8_t* const* ys, const int64_t* ylen, int n_y, const uint8_t* const* zs,
@@ -757,61 +721,9 @@ int rgbd_elic::run_decompress1(const uint8_t* const* ys, const int64_t* ylen, in
     arena.reset();
     rc = 0;
 
-    // ==== prologue (never captured): upload the streams, every stream into a slot of the size the encoder may produce for
-    // this shape, so that the workspace layout (and with it a cached graph) does not depend on the stream lengths
-    const int64_t ycount = per_image ? T : T * B;
-    const int64_t ycap = ((5 * ycount + 32 + 704) + 63) & ~(int64_t)63, zcap = ((5 * Tz + 32 + 704) + 63) & ~(int64_t)63;
-    // meta64: y off[n_y], y len[n_y], z off[B], z len[B], y base[B], z base[B]
-    const size_t nmeta = (size_t)2 * n_y + (size_t)4 * B;
-    const size_t o_zoff = (size_t)2 * n_y, o_ybase = (size_t)2 * n_y + 2 * B, o_zbase = o_ybase + B;
-    int64_t* meta64 = (int64_t*)arena.take(sizeof(int64_t) * nmeta);
-    uint32_t* words = (uint32_t*)arena.take(sizeof(uint32_t) * ((size_t)n_y * ycap + (size_t)B * zcap + 4));
-    uint64_t* state = (uint64_t*)arena.take(sizeof(uint64_t) * (size_t)(2 * (n_y + B)));
-    int32_t* sym = (int32_t*)arena.take(sizeof(int32_t) * (size_t)(B * T));
-    int32_t* idx = (int32_t*)arena.take(sizeof(int32_t) * (size_t)(B * T));
-    int32_t* zsym = (int32_t*)arena.take(sizeof(int32_t) * (size_t)(B * Tz));
-    int32_t* zidx = (int32_t*)arena.take(sizeof(int32_t) * (size_t)(B * Tz));
-    dbg_sym = sym;
-    dbg_idx = idx;
-    dbg_per_mod = (int64_t)B * T;
-    dbg_x = dbg_s = nullptr;
-    if (debug_floats) {
-        dbg_x = (float*)arena.take(sizeof(float) * (size_t)(B * T));
-        dbg_s = (float*)arena.take(sizeof(float) * (size_t)(B * T));
-    }
-    for (int i = 0; i < n_y; ++i)
-        if (!ys[i] || ylen[i] < 8 || (ylen[i] & 3) || ylen[i] / 4 > ycap) return RGBD_EINVAL;
-    for (int i = 0; i < B; ++i)
-        if (!zs[i] || zlen[i] < 8 || (zlen[i] & 3) || zlen[i] / 4 > zcap) return RGBD_EINVAL;
-    if (!dry()) {
-        size_t total_words = 0;
-        for (int i = 0; i < n_y; ++i) total_words += (size_t)ylen[i] / 4;
-        for (int i = 0; i < B; ++i) total_words += (size_t)zlen[i] / 4;
-        void* pv = nullptr;
-        if (const int r = pin_take(nmeta * sizeof(int64_t) + total_words * 4, &pv)) return r;
-        int64_t* hmeta = (int64_t*)pv;
-        uint32_t* hw = (uint32_t*)(hmeta + nmeta);
-        size_t used = 0;
-        auto put = [&](const uint8_t* src, int64_t len, size_t slot_off, size_t meta_off, size_t meta_len) -> int {
-            memcpy(hw + used, src, (size_t)len);
-            hmeta[meta_off] = (int64_t)slot_off;
-            hmeta[meta_len] = len / 4;
-            HIP_TRY(hipMemcpyAsync(words + slot_off, hw + used, (size_t)len, hipMemcpyHostToDevice, s));
-            used += (size_t)len / 4;
-            return RGBD_OK;
-        };
-        for (int i = 0; i < n_y; ++i)
-            if (const int r = put(ys[i], ylen[i], (size_t)i * (size_t)ycap, (size_t)i, (size_t)n_y + i)) return r;
-        for (int i = 0; i < B; ++i)
-            if (const int r = put(zs[i], zlen[i], (size_t)n_y * ycap + (size_t)i * (size_t)zcap, o_zoff + i, o_zoff + B + i))
-                return r;
-        for (int b = 0; b < B; ++b) {
-            hmeta[o_ybase + b] = per_image ? (int64_t)b * T : 0;
-            hmeta[o_zbase + b] = (int64_t)b * Tz;
-        }
-        HIP_TRY(hipMemcpyAsync(meta64, hmeta, sizeof(int64_t) * nmeta, hipMemcpyHostToDevice, s));
-        if (const int r = pin_release()) return r;
-    }
+    // ==== prologue (never captured): upload the streams
+    DecBufs d;
+    if (const int r = dec_streams(1, &ys, &ylen, n_y, &zs, &zlen, B, B, T, Tz, per_image, &d)) return r;
 
     // ==== body: captured into / replayed from a HIP graph per call shape ================================================
     Act xh;
@@ -820,11 +732,9 @@ int rgbd_elic::run_decompress1(const uint8_t* const* ys, const int64_t* ylen, in
         float* md = dense_of("entropy_bottleneck.medians");
         if (!dry() && md) {
             int q = launch_fill_zero(zhat.p, zhat.elems(), s);
-            if (!q) q = launch_z_quant(zhat.p, zhat.cs, B, zh, zw, N, md, zsym, zidx, s, perm());  // indexes = channel id
-            if (!q)
-                q = launch_rans_decode(words, meta64 + o_zoff, meta64 + o_zoff + B, B, state + (size_t)2 * n_y, 1, zidx, zsym,
-                                       meta64 + o_zbase, 0, Tz, tables[2].d, s);
-            if (!q) q = launch_z_dequant(zsym, B, zh, zw, N, md, zhat.p, zhat.cs, s, perm());
+            if (!q) q = launch_z_quant(zhat.p, zhat.cs, B, zh, zw, N, md, d.zsym, d.zidx, s, perm());  // indexes = channel id
+            if (!q) q = launch_rans_decode(d.words, d.zoff, d.zlen, B, d.zstate, 1, d.zidx, d.zsym, d.zbase, 0, Tz, tables[2].d, s);
+            if (!q) q = launch_z_dequant(d.zsym, B, zh, zw, N, md, zhat.p, zhat.cs, s, perm());
             if (q) fail(q);
         }
         named["zhat"] = zhat;
@@ -836,13 +746,13 @@ int rgbd_elic::run_decompress1(const uint8_t* const* ys, const int64_t* ylen, in
         cd.encode = false;
         cd.per_image = per_image;
         cd.per_image_total = T;
-        cd.sym = sym;
-        cd.idx = idx;
-        cd.stream_base = meta64 + o_ybase;
-        cd.words = words;
-        cd.stream_off = meta64;
-        cd.stream_len = meta64 + n_y;
-        cd.state = state;
+        cd.sym = d.sym;
+        cd.idx = d.idx;
+        cd.stream_base = d.ybase;
+        cd.words = d.words;
+        cd.stream_off = d.yoff;
+        cd.stream_len = d.ylen;
+        cd.state = d.state;
         cd.nstreams = n_y;
         bicee1(cd, nullptr, hyper, yhat);
         xh = g_s1(yhat);
