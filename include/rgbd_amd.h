@@ -332,6 +332,36 @@ int rgbd_msssim_stats(const float* x, const float* y, int32_t P, int32_t H, int3
 int rgbd_layernorm(const float* x, int64_t ntok, int32_t C, int32_t xcs, const float* w, const float* b, float* y, int32_t ycs,
                    void* stream);
 void rgbd_debug_force_layernorm_form(int32_t form);
+/* The same LayerNorm over two operand sets in one launch (the engine's RGB / depth pair): set 1 is x1 / w1 / b1 / y1, of the
+ * same ntok / C / xcs / ycs.  Pad channels C .. ycs - 1 of both outputs are zeroed. */
+int rgbd_layernorm2(const float* x, int64_t ntok, int32_t C, int32_t xcs, const float* w, const float* b, float* y, int32_t ycs,
+                    const float* x1, const float* w1, const float* b1, float* y1, void* stream);
+
+/* STF_united test hooks: the Swin kernels the engine launches, each behind its own operator boundary.  All tensors are NHWC
+ * fp32 on the device with a channel stride (xcs / ycs / qcs / ocs floats per pixel).  Each returns RGBD_EINVAL (-22) without
+ * launching when an argument breaks what its kernel assumes.
+ *
+ * rgbd_window_attention: WindowAttention of a 4x4 window with head_dim 16 and the cyclic shift around it
+ * (models/stf_united.py:48-114, 162-203).  qkv: [B][H][W][qcs], channel which * C + head * 16 + d (which = q, k, v);
+ * rpb: [49][heads] relative position bias table; out: [B][H][W][ocs].  Requires H % 4 == 0, W % 4 == 0, C == 16 * heads,
+ * 0 <= shift < 4 (shift > 0: roll by -shift, the -100 mask between the regions of the rolled frame, roll back),
+ * qcs >= 3 C, qcs % 4 == 0, ocs >= C, qkv 16-byte aligned.  qkv1 / rpb1 / out1: NULL, or a second operand set of the same
+ * shape run in the same launch.  Pad channels C .. ocs - 1 of out are not written.
+ *
+ * rgbd_patch_merge_gather: PatchMerging's 2x2 gather (stf_united.py:240-245), y[b][h][w] = cat(x[2h][2w], x[2h+1][2w],
+ * x[2h][2w+1], x[2h+1][2w+1]) over the first C channels; x: [B][H][W][xcs], y: [B][H/2][W/2][ycs].  H, W even, C % 4 == 0,
+ * xcs % 4 == 0, ycs >= 4 C, ycs % 4 == 0, both 16-byte aligned.  Pad channels 4C .. ycs - 1 of y are not written.
+ *
+ * rgbd_pixel_shuffle2: nn.PixelShuffle(2) on NHWC, y[b][2h+i][2w+j][c] = x[b][h][w][4c + 2i + j]; x: [B][H][W][xcs] with
+ * xcs >= 4 Co, y: [B][2H][2W][ycs] with ycs >= Co.  Pad channels Co .. ycs - 1 of y are zeroed.
+ * ------------------------------------------------------------------------------------------------------------- */
+int rgbd_window_attention(const float* qkv, int32_t B, int32_t H, int32_t W, int32_t C, int32_t qcs, int32_t heads, int32_t shift,
+                          const float* rpb, float* out, int32_t ocs, const float* qkv1, const float* rpb1, float* out1,
+                          void* stream);
+int rgbd_patch_merge_gather(const float* x, int32_t B, int32_t H, int32_t W, int32_t C, int32_t xcs, float* y, int32_t ycs,
+                            void* stream);
+int rgbd_pixel_shuffle2(const float* x, int32_t B, int32_t H, int32_t W, int32_t Co, int32_t xcs, float* y, int32_t ycs,
+                        void* stream);
 
 /* Bytes of HBM workspace this engine instance holds (grows with the largest call shape seen, never shrinks); the packed
  * weights, shared by all instances of a pool, are not included.  bench.py reports it as config.hbm_workspace_gib. */

@@ -378,3 +378,47 @@ int launch_pixel_shuffle2(const float* x, int B, int H, int W, int Co, int xcs, 
     HIP_TRY(hipGetLastError());
     return RGBD_OK;
 }
+
+// ---------------------------------------------------------------------------------------------
+// Operator boundaries of the kernels above for the tests (include/rgbd_amd.h).  The engine calls the launch_* functions
+// directly; these only check what the kernels assume before launching them.
+static bool wa_set_ok(const float* qkv, const float* rpb, const float* out)
+{
+    return qkv && rpb && out && ((uintptr_t)qkv & 15) == 0;
+}
+
+extern "C" int rgbd_window_attention(const float* qkv, int32_t B, int32_t H, int32_t W, int32_t C, int32_t qcs, int32_t heads,
+                                     int32_t shift, const float* rpb, float* out, int32_t ocs, const float* qkv1,
+                                     const float* rpb1, float* out1, void* stream)
+{
+    if (B <= 0 || H <= 0 || W <= 0 || heads <= 0 || H % 4 || W % 4 || C != 16 * heads || shift < 0 || shift >= 4 ||
+        qcs < 3 * C || qcs % 4 || ocs < C || !wa_set_ok(qkv, rpb, out))
+        return RGBD_EINVAL;
+    const bool pair = qkv1 || rpb1 || out1;
+    if (pair && !wa_set_ok(qkv1, rpb1, out1)) return RGBD_EINVAL;
+    return launch_window_attention(qkv, B, H, W, C, qcs, heads, shift, rpb, out, ocs, (hipStream_t)stream, pair ? qkv1 : nullptr,
+                                   pair ? rpb1 : nullptr, pair ? out1 : nullptr);
+}
+
+extern "C" int rgbd_patch_merge_gather(const float* x, int32_t B, int32_t H, int32_t W, int32_t C, int32_t xcs, float* y,
+                                       int32_t ycs, void* stream)
+{
+    const auto al16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
+    if (!x || !y || B <= 0 || H <= 0 || W <= 0 || C <= 0 || xcs < C || xcs % 4 || ycs < 4 * C || ycs % 4 || !al16(x) || !al16(y))
+        return RGBD_EINVAL;
+    return launch_patch_merge_gather(x, B, H, W, C, xcs, y, ycs, (hipStream_t)stream);
+}
+
+extern "C" int rgbd_pixel_shuffle2(const float* x, int32_t B, int32_t H, int32_t W, int32_t Co, int32_t xcs, float* y, int32_t ycs,
+                                   void* stream)
+{
+    if (!x || !y || B <= 0 || H <= 0 || W <= 0 || Co <= 0 || xcs < 4 * Co || ycs < Co) return RGBD_EINVAL;
+    return launch_pixel_shuffle2(x, B, H, W, Co, xcs, y, ycs, (hipStream_t)stream);
+}
+
+extern "C" int rgbd_layernorm2(const float* x, int64_t ntok, int32_t C, int32_t xcs, const float* w, const float* b, float* y,
+                               int32_t ycs, const float* x1, const float* w1, const float* b1, float* y1, void* stream)
+{
+    if (!x || !w || !b || !y || !x1 || !w1 || !b1 || !y1 || ntok <= 0 || xcs < C || ycs < C) return RGBD_EINVAL;
+    return launch_layernorm(x, (size_t)ntok, C, xcs, w, b, y, ycs, (hipStream_t)stream, x1, w1, b1, y1);
+}

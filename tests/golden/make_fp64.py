@@ -33,6 +33,9 @@ sys.path.insert(0, ROOT)
 
 from oracle import elic_oracle as eo  # noqa: E402
 
+sys.path.insert(0, HERE)
+from make_golden import STF_HELDOUT  # noqa: E402
+
 SCALE_BOUND = 0.11
 
 
@@ -226,6 +229,9 @@ def main():
         single_case("c1_256x256", 256, 256, 1)
     if on("stf_c5_256x256"):
         united_case("stf_c5_256x256", 1, 256, 256, 5, model="STF_united")
+    for name, (B, H, W, cid, seed) in STF_HELDOUT.items():  # held-out STF goldens: only when named
+        if "stf_" + name in want:
+            united_case("stf_" + name, B, H, W, cid, seed=seed, model="STF_united")
     if on("e_480x640_tl"):
         united_case("e_480x640_tl", 1, 480, 640, 3, recipe="trained_like")
     if on("f_480x640_stress"):

@@ -11,7 +11,8 @@ Outputs (data only -- inputs are regenerated from rgbd_amd.synth, never stored):
                                     weights, `--only-hr`)
     tests/golden/bicee_*.npz        Bi-CEE stage alone (BASELINE config 4): compress_united / decompress_united outputs
     tests/golden/elic_*.npz         single-modal ELIC (BASELINE config 1): streams, latents, reconstruction
-    tests/golden/stf_*.npz          STF_united (Swin transforms; BASELINE config 5 at reduced size)
+    tests/golden/stf_*.npz          STF_united (Swin transforms; BASELINE config 5 at reduced size; held-out off-square
+                                    cases: `--only-stf NAME`, NAME in STF_HELDOUT)
     tests/golden/r2d_*.npz          ELIC_united_R2D (one-directional variant)
     tests/golden/harness.json       pad / container / bpp / PSNR tuples (TesterUnited arithmetic)
 
@@ -38,6 +39,17 @@ import _reference_loader as rl  # noqa: E402
 
 def sha(b: bytes) -> str:
     return hashlib.sha256(b).hexdigest()[:16]
+
+
+def sha_f32(t) -> str:
+    """sha of a float32 tensor's bits (C order): what the held-out STF goldens keep of their whole latents / x_hat."""
+    return sha(np.ascontiguousarray(np.asarray(t, np.float32)).tobytes())
+
+
+def STF_Y_SUB(y):
+    """What the held-out STF goldens keep of the latents as values: channels 0, 24, ..., 360 (every slice of the 384) at
+    every other row and column."""
+    return y[:, ::24, ::2, ::2]
 
 
 def coder_kats(net, ext):
@@ -209,12 +221,15 @@ def elic_single_case(ext, model_config, synth, name, B, H, W, config_id, seed=0)
     return g
 
 
-def stf_case(model_config, synth, name, B, H, W, config_id):
-    """BASELINE config 5 (reduced size): the reference's STF_united (models/stf_united.py) compress()/decompress()."""
+def stf_case(model_config, synth, name, B, H, W, config_id, seed=0, full=True):
+    """BASELINE config 5 (reduced size): the reference's STF_united (models/stf_united.py) compress()/decompress().
+    seed: the synthetic weights.  full=False (the held-out cases): only what the tests read, kept small (the y streams
+    alone are ~0.3 MB per modality and image): streams, PSNR, a subsample of the latents (STF_Y_SUB) with the sha of the
+    whole latents, and the sha of the whole x_hat, without the forward() and Bi-CEE-alone keys."""
     from models.stf_united import SymmetricalTransFormerUnited as STF
 
     net = STF(config=model_config(), channel=4).eval()
-    net.load_state_dict(synth.synthetic_state_dict(0, model="STF_united"))
+    net.load_state_dict(synth.synthetic_state_dict(seed, model="STF_united"))
     assert net.update(force=True)
     r, d = synth.synthetic_batch(B, H, W, config_id=config_id)
     r, d = torch.from_numpy(r), torch.from_numpy(d)
@@ -222,26 +237,43 @@ def stf_case(model_config, synth, name, B, H, W, config_id):
         y_r, y_d = net.g_a(r, d)
         out = net.compress(r, d)
         dec = net.decompress(out["r_strings"], out["d_strings"], out["shape"])
-        fw = net(r, d)  # eval-mode forward (inherited models/elic_united.py:234-263 over the R2D slice coder)
-        # the Bi-CEE stage alone (inherited compress_united / decompress_united, elic_united.py:350-401,543-578)
-        lat = [torch.from_numpy(a) for a in synth.synthetic_latents(1, 8, 12, 320, 6)]
-        cu = net.compress_united(lat[0], lat[1], lat[2], lat[3])
-        du = net.decompress_united(cu[0][0], lat[1], cu[1][0], lat[3])
-    g = {"B": B, "H": H, "W": W, "config_id": config_id, "shape": np.array(tuple(out["shape"]), np.int32),
+    # the reference codes the whole batch into ONE y stream per modality (one z stream per image)
+    assert len(out["r_strings"][0]) == 1 and len(out["d_strings"][0]) == 1, (len(out["r_strings"][0]), len(out["d_strings"][0]))
+    assert len(out["r_strings"][1]) == B and len(out["d_strings"][1]) == B
+    g = {"B": B, "H": H, "W": W, "config_id": config_id, "seed": seed, "shape": np.array(tuple(out["shape"]), np.int32),
          "r_y": np.frombuffer(out["r_strings"][0][0], np.uint8), "d_y": np.frombuffer(out["d_strings"][0][0], np.uint8),
-         "r_z0": np.frombuffer(out["r_strings"][1][0], np.uint8), "d_z0": np.frombuffer(out["d_strings"][1][0], np.uint8),
-         "y_r": y_r.numpy(), "y_d": y_d.numpy(),
-         "fw_xhat_r_sub": fw["x_hat"]["r"][:, :, ::4, ::4].numpy(), "fw_xhat_d_sub": fw["x_hat"]["d"][:, :, ::4, ::4].numpy(),
-         "lik_y_r": fw["r_likelihoods"]["y"].numpy(), "lik_y_d": fw["d_likelihoods"]["y"].numpy(),
-         "lik_z_r": fw["r_likelihoods"]["z"].numpy(), "lik_z_d": fw["d_likelihoods"]["z"].numpy(),
-         "cu_seed": 6, "cu_r_y": np.frombuffer(cu[0][0], np.uint8), "cu_d_y": np.frombuffer(cu[1][0], np.uint8),
-         "cu_yhat_r": du[0].numpy(), "cu_yhat_d": du[1].numpy(),
-         "xhat_r_sub": dec["x_hat"]["r"][:, :, ::4, ::4].numpy(), "xhat_d_sub": dec["x_hat"]["d"][:, :, ::4, ::4].numpy(),
          "psnr": np.array([-10 * np.log10(torch.mean((dec["x_hat"]["r"] - r) ** 2).item()),
                            -10 * np.log10(torch.mean((dec["x_hat"]["d"] - d) ** 2).item())], np.float64)}
+    if full:
+        g.update({"y_r": y_r.numpy(), "y_d": y_d.numpy(), "xhat_r_sub": dec["x_hat"]["r"][:, :, ::4, ::4].numpy(),
+                  "xhat_d_sub": dec["x_hat"]["d"][:, :, ::4, ::4].numpy()})
+    else:
+        g.update({"y_r_sub": STF_Y_SUB(y_r).numpy(), "y_d_sub": STF_Y_SUB(y_d).numpy(), "y_r_sha": sha_f32(y_r),
+                  "y_d_sha": sha_f32(y_d), "xhat_r_sha": sha_f32(dec["x_hat"]["r"]), "xhat_d_sha": sha_f32(dec["x_hat"]["d"])})
+    for i in range(B):
+        g[f"r_z{i}"] = np.frombuffer(out["r_strings"][1][i], np.uint8)
+        g[f"d_z{i}"] = np.frombuffer(out["d_strings"][1][i], np.uint8)
+    if full:
+        with torch.no_grad():
+            fw = net(r, d)  # eval-mode forward (inherited models/elic_united.py:234-263 over the R2D slice coder)
+            # the Bi-CEE stage alone (inherited compress_united / decompress_united, elic_united.py:350-401,543-578) on
+            # latents of STF's M = 384 channels
+            lat = [torch.from_numpy(a) for a in synth.synthetic_latents(1, 8, 12, 384, 6)]
+            cu = net.compress_united(lat[0], lat[1], lat[2], lat[3])
+            du = net.decompress_united(cu[0][0], lat[1], cu[1][0], lat[3])
+        g.update({"fw_xhat_r_sub": fw["x_hat"]["r"][:, :, ::4, ::4].numpy(), "fw_xhat_d_sub": fw["x_hat"]["d"][:, :, ::4, ::4].numpy(),
+                  "lik_y_r": fw["r_likelihoods"]["y"].numpy(), "lik_y_d": fw["d_likelihoods"]["y"].numpy(),
+                  "lik_z_r": fw["r_likelihoods"]["z"].numpy(), "lik_z_d": fw["d_likelihoods"]["z"].numpy(),
+                  "cu_seed": 6, "cu_r_y": np.frombuffer(cu[0][0], np.uint8), "cu_d_y": np.frombuffer(cu[1][0], np.uint8),
+                  "cu_yhat_r": du[0].numpy(), "cu_yhat_d": du[1].numpy()})
     np.savez_compressed(os.path.join(HERE, f"stf_{name}.npz"), **g)
     print("stf", name, len(out["r_strings"][0][0]), len(out["d_strings"][0][0]), g["psnr"])
     return g
+
+
+# Held-out STF_united goldens (off the square; image seeds no other fixture uses; the second one with other weights):
+# name -> (B, H, W, image config_id, weight seed).  256 x 320 is the smallest non-square size STF's ESA pooling allows.
+STF_HELDOUT = {"q_b2_256x320": (2, 256, 320, 19, 0), "r_320x256_s11": (1, 320, 256, 20, 11)}
 
 
 def r2d_case(model_config, synth, name, B, H, W, config_id, seed=0):
@@ -295,6 +327,11 @@ def main():
              "lik_y": fw["likelihoods"]["y_likelihoods"].numpy(), "lik_z": fw["likelihoods"]["z_likelihoods"].numpy()}
         np.savez_compressed(os.path.join(HERE, "elic_fw_b2_128x192.npz"), **g)
         print("elic forward", g["x_hat"].shape, float(g["lik_y"].mean()), float(g["lik_z"].mean()))
+        return
+    if "--only-stf" in sys.argv:  # one held-out STF_united golden (STF_HELDOUT), no other fixture touched
+        name = sys.argv[sys.argv.index("--only-stf") + 1]
+        B, H, W, cid, seed = STF_HELDOUT[name]
+        stf_case(model_config, synth, name, B, H, W, cid, seed=seed, full=False)
         return
     if "--only-r2d" in sys.argv:  # refresh one fixture without touching the others
         r2d_case(model_config, synth, "128x192", 1, 128, 192, 4)

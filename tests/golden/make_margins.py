@@ -170,14 +170,14 @@ def single_case(ext, model_config, synth, name, H, W, cid):
     save("elic_" + name, obs)
 
 
-def stf_case(model_config, synth, name, H, W, cid):
+def stf_case(model_config, synth, name, H, W, cid, B=1, seed=0):
     from models.stf_united import SymmetricalTransFormerUnited as STF
 
     net = STF(config=model_config(), channel=4).eval()
-    net.load_state_dict(synth.synthetic_state_dict(0, model="STF_united"))
+    net.load_state_dict(synth.synthetic_state_dict(seed, model="STF_united"))
     assert net.update(force=True)
     obs = observe(net, {"r": "rgb_", "d": "depth_"})
-    r, d = synth.synthetic_batch(1, H, W, config_id=cid)
+    r, d = synth.synthetic_batch(B, H, W, config_id=cid)
     out = run(obs, lambda: net.compress(torch.from_numpy(r), torch.from_numpy(d)))
     same_streams(os.path.join(HERE, f"stf_{name}.npz"), [("r_y", out["r_strings"][0][0]), ("d_y", out["d_strings"][0][0]),
                                                         ("r_z0", out["r_strings"][1][0]), ("d_z0", out["d_strings"][1][0])])
@@ -226,6 +226,9 @@ def main():
         single_case(ext, model_config, synth, "c1_256x256", 256, 256, 1)
     if on("stf_c5_256x256"):
         stf_case(model_config, synth, "c5_256x256", 256, 256, 5)
+    for name, (B, H, W, cid, seed) in mg.STF_HELDOUT.items():  # held-out STF goldens: only when named
+        if "stf_" + name in want:
+            stf_case(model_config, synth, name, H, W, cid, B=B, seed=seed)
 
 
 if __name__ == "__main__":

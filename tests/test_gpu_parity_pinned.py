@@ -428,23 +428,36 @@ def test_elic_single_vs_reference_golden(gc, case, seed):
 
 
 def test_stf_vs_reference_golden(kat):
+    _stf_vs_golden(kat, "c5_256x256")
+
+
+@pytest.mark.parametrize("case", ["q_b2_256x320", "r_320x256_s11"])
+def test_stf_heldout_vs_reference_golden(kat, case):
+    """STF_united off the square (make_golden.py --only-stf): B=2 at 256x320, the batch coded into one y stream per modality,
+    and 320x256 with weight seed 11, both on images no other fixture uses."""
+    _stf_vs_golden(kat, case)
+
+
+def _stf_vs_golden(kat, case):
     from rgbd_amd import synth
 
     require_gpu()
-    sd = synth.synthetic_state_dict(0, model="STF_united")
+    g = np.load(os.path.join(GOLDEN, f"stf_{case}.npz"))
+    B, H, W = int(g["B"]), int(g["H"]), int(g["W"])
+    sd = synth.synthetic_state_dict(int(g["seed"]) if "seed" in g.files else 0, model="STF_united")
     m = _model("STF_united", sd)
-    g = np.load(os.path.join(GOLDEN, "stf_c5_256x256.npz"))
-    r, d = synth.synthetic_batch(1, 256, 256, config_id=int(g["config_id"]))
+    r, d = synth.synthetic_batch(B, H, W, config_id=int(g["config_id"]))
     m.set_debug_floats(True)
     out = m.compress(torch.from_numpy(r).cuda(), torch.from_numpy(d).cuda())
     m.set_debug_floats(False)
     gsym, gidx = _symbols(m)
     gc5 = coder.Tables(kat["gc_cdf"], kat["gc_sizes"], kat["gc_offsets"])  # the Gaussian table does not depend on the model
     clean, total = golden_parts_identical(gsym, gidx, {0: g["r_y"].tobytes(), 1: g["d_y"].tobytes()}, gc5,
-                                          part_sizes(m.slice_ch, 16, 16))
+                                          part_sizes(m.slice_ch, H // 16, W // 16, B))
     same = out["r_strings"][0][0] == g["r_y"].tobytes() and out["d_strings"][0][0] == g["d_y"].tobytes()
-    z_same = out["r_strings"][1][0] == g["r_z0"].tobytes() and out["d_strings"][1][0] == g["d_z0"].tobytes()
-    flip = {} if (same and z_same) else _first_flip(m, "stf_c5_256x256", gsym, gidx, medians=m.eb_medians_numpy())
+    z_same = all(out[key][1][i] == g[f"{t}_z{i}"].tobytes() for t, key in (("r", "r_strings"), ("d", "d_strings"))
+                 for i in range(B))
+    flip = {} if (same and z_same) else _first_flip(m, "stf_" + case, gsym, gidx, medians=m.eb_medians_numpy())
     rec = m.decompress(out["r_strings"], out["d_strings"], out["shape"])
     xr, xd = rec["x_hat"]["r"].cpu(), rec["x_hat"]["d"].cpu()
     vals = {"clean_parts_vs_golden": clean, "identical_streams": same, "identical_z": z_same,
@@ -452,8 +465,8 @@ def test_stf_vs_reference_golden(kat):
             "dpsnr_d": abs(eo.psnr(xd, torch.from_numpy(d)) - g["psnr"][1]),
             "dlen_r": abs(len(out["r_strings"][0][0]) - g["r_y"].shape[0])}
     vals.update(flip)
-    print("stf", vals)
-    _check("stf_c5_256x256", **vals)
+    print("stf", case, vals)
+    _check("stf_" + case, **vals)
 
 
 # ---- teacher forcing: every part of the goldens that are NOT identical, under the reference's context ------------------------

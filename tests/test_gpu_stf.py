@@ -94,6 +94,101 @@ def test_config5_256(net5, orc5):
     assert abs(eo.psnr(xr, r) - eo.psnr(oxr, r)) < 1e-4 and abs(eo.psnr(xd, d) - eo.psnr(oxd, d)) < 1e-4
 
 
+_NETS = {}
+
+
+def _stf_net(seed, sd5, net5):
+    """The GPU model and the oracle for synthetic weight seed `seed` (seed 0: the module's own)."""
+    if seed == 0:
+        return net5
+    if seed not in _NETS:
+        import rgbd_amd
+        from rgbd_amd import synth
+
+        m = rgbd_amd.modelZoo["STF_united"](config=rgbd_amd.model_config(), channel=4).eval()
+        m.load_state_dict(synth.synthetic_state_dict(seed, model="STF_united"), strict=True)
+        assert m.update(force=True)
+        _NETS[seed] = m.to("cuda")
+    return _NETS[seed]
+
+
+@pytest.mark.parametrize("golden", ["c5_256x256", "q_b2_256x320", "r_320x256_s11"])
+def test_stages_vs_oracle_off_square(golden, sd5, net5, orc5):
+    """The layered contract of test_config5_256 at (B, H, W) = (1, 256, 256), (2, 256, 320) and (1, 320, 256), on the images
+    and weights of the reference goldens of those shapes (tests/golden/stf_*.npz): a non-square map in both orientations and
+    a batch coded into one y stream per modality.  A Swin kernel with H and W (or the window indexes) swapped stays
+    self-consistent -- batch invariance, forward == decompress, replay == eager all hold -- but leaves the oracle here."""
+    from rgbd_amd import synth
+
+    g = np.load(os.path.join(os.path.dirname(__file__), "golden", f"stf_{golden}.npz"))
+    B, H, W, seed = int(g["B"]), int(g["H"]), int(g["W"]), int(g["seed"]) if "seed" in g.files else 0
+    net = _stf_net(seed, sd5, net5)
+    if seed == 0:
+        orc = orc5
+    else:
+        orc = eo.oracle_stf(synth.synthetic_state_dict(seed, model="STF_united"))
+        orc.update()
+    r, d = synth.synthetic_batch(B, H, W, config_id=int(g["config_id"]))
+    r, d = torch.from_numpy(r), torch.from_numpy(d)
+    out = net.compress(r.cuda(), d.cuda())
+    assert tuple(out["shape"]) == (H // 64, W // 64) == tuple(g["shape"])
+    assert len(out["r_strings"][0]) == 1 and len(out["r_strings"][1]) == B
+    orc.trace = {}
+    orc.compress(r, d)
+    tr, orc.trace = orc.trace, None
+    # float stage: y and z against the oracle, y also against the reference's own latents
+    for name in ("y_r", "y_d", "z_r", "z_d"):
+        got = net.debug_tensor(name)
+        assert got.shape == tuple(tr[name].shape), (name, got.shape, tr[name].shape)
+        assert _rel(got, tr[name].numpy()) < 5e-5, (name, _rel(got, tr[name].numpy()))
+    for tag in ("r", "d"):  # (the held-out goldens keep y[:, ::24, ::2, ::2] of the reference's latents: make_golden.stf_case)
+        got = net.debug_tensor(f"y_{tag}")[:, ::24, ::2, ::2]
+        ref = g[f"y_{tag}"][:, ::24, ::2, ::2] if f"y_{tag}" in g.files else g[f"y_{tag}_sub"]
+        assert _rel(got, ref) < 5e-5, (tag, _rel(got, ref))
+    # z streams from the GPU's own z; hyper synthesis on the GPU's own z_hat
+    for mod, key, zname in (("rgb", "r_strings", "z_r"), ("depth", "d_strings", "z_d")):
+        strings, _ = orc._z_compress(mod, torch.from_numpy(net.debug_tensor(zname)))
+        assert strings == out[key][1]
+    zh = [torch.from_numpy(net.debug_tensor(n)) for n in ("zhat_r", "zhat_d")]
+    ohr, ohd = eo.h_s(orc.sd, zh[0], zh[1])
+    assert _rel(net.debug_tensor("hyper_r"), ohr.numpy()) < 2e-5 and _rel(net.debug_tensor("hyper_d"), ohd.numpy()) < 2e-5
+    # y streams from the GPU's own symbols / indexes (the whole batch in one stream)
+    for mod, key in ((0, "r_strings"), (1, "d_strings")):
+        gsym, gidx = net.debug_symbols(mod)
+        assert gsym.shape[0] == B * 384 * (H // 16) * (W // 16)
+        assert coder.rans_encode(gsym, gidx, orc.gc) == out[key][0][0]
+    yhat_enc = [net.debug_tensor("yhat_r").copy(), net.debug_tensor("yhat_d").copy()]
+    rec = net.decompress(out["r_strings"], out["d_strings"], out["shape"])
+    assert np.array_equal(net.debug_tensor("yhat_r"), yhat_enc[0]) and np.array_equal(net.debug_tensor("yhat_d"), yhat_enc[1])
+    xr, xd = rec["x_hat"]["r"].cpu(), rec["x_hat"]["d"].cpu()
+    assert xr.shape == (B, 3, H, W) and xd.shape == (B, 1, H, W)
+    oxr, oxd = eo.g_s_stf(orc.sd, torch.from_numpy(yhat_enc[0]), torch.from_numpy(yhat_enc[1]))
+    oxr, oxd = oxr.clamp(0, 1), oxd.clamp(0, 1)
+    assert (xr - oxr).abs().max() < 2e-4 and (xd - oxd).abs().max() < 2e-4
+
+
+def test_grouped_pairs_same_bits(net5):
+    """rgbd_debug_force_pair for STF_united (tests/test_gpu_pairs.py for ELIC_united): the RGB and depth Swin blocks as one
+    paired launch per kernel (LayerNorm, window attention: blockIdx.y == 1) or as two launches -- same streams and x_hat, bit
+    for bit, at B=2 256x320."""
+    from rgbd_amd import synth
+    from rgbd_amd._lib import check, lib
+
+    r, d = synth.synthetic_batch(2, 256, 320, config_id=23)
+    rgb, depth = torch.from_numpy(r).cuda(), torch.from_numpy(d).cuda()
+    res = {}
+    try:
+        for pair in (0, 1):
+            check(lib().rgbd_debug_force_pair(pair), "force_pair")
+            out = net5.compress(rgb, depth)
+            rec = net5.decompress(out["r_strings"], out["d_strings"], out["shape"])
+            res[pair] = (out, rec["x_hat"]["r"].clone(), rec["x_hat"]["d"].clone())
+    finally:
+        check(lib().rgbd_debug_force_pair(1), "force_pair")
+    assert res[0][0]["r_strings"] == res[1][0]["r_strings"] and res[0][0]["d_strings"] == res[1][0]["d_strings"]
+    assert torch.equal(res[0][1], res[1][1]) and torch.equal(res[0][2], res[1][2])
+
+
 def test_batch_invariance_and_forward(net5):
     from rgbd_amd import synth
 
