@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Headline benchmark: RGB-D Mpixels/s, encode+decode, ELIC_united q=2_2 on MI355X (BASELINE.json).
 
-    python bench.py                                   # 1 GPU, c3 (4 x 480x640 per step) + c2 + B=1 latency + CPU baseline
+    python bench.py                                   # 1 GPU, c3 (4 x 480x640 per step): the headline figure only
+    python bench.py --full                            # ... + c2 + c5 + B=1 latency + roofline + CPU baseline
     python bench.py --gpus N --steps K --warmup W     # N>1: starts N ranks itself (one process per GPU, RCCL)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W         # ... or is started as one of N ranks (RANK/WORLD_SIZE in the env)
@@ -12,9 +13,14 @@ config 3's per-GPU share: 4 pairs of 480x640 (replicate-padded to 512x640) per G
 all-gather of the finished streams).  An engine call codes `--steps-per-call` steps together (default 4 for c3 and c2: the
 driver's 20 steps are 5 calls of 16 images on 5 engine instances -- same images in flight as 20 instances of 4, faster
 kernels; streams are per image and the kernels batch-invariant, so no output bit depends on it).  Inputs are resident in
-HBM before the timed region; conv profiling (HIP events) runs in a separate pass after it.  Rank 0 prints ONE JSON line:
+HBM before the timed region.  A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the line
+down to `parity`; the rest of the line is measured only with --full, in passes of its own after the timed region (conv
+profiling with HIP events, B=1 latency, child processes for c2 / c5, the CPU oracle).  Rank 0 prints ONE JSON line:
 
   value / ms_per_step   wall-clock job throughput with W engine instances in flight per GPU (`engine_instances`)
+  config.hbm_workspace_gib / pairs_in_flight   what the throughput costs in HBM and in images held at once
+  parity                the parity state the numbers were measured under (tests/golden/parity_floors.json: how many reference
+                        goldens are bit-identical, the largest dbpp / dPSNR, the state at the bench's own operating point)
   latency               the reference tester's calling pattern (testing/tester_united.py:142-147,180-186): B=1, one engine
                         instance, device-synchronised windows around compress() and decompress(), Mpx/s = sum(px) /
                         (sum(enc) + sum(dec))  -- SURVEY.md 8(d)'s metric definition
@@ -24,9 +30,7 @@ HBM before the timed region; conv profiling (HIP events) runs in a separate pass
                         = what the launches compute), `isolated` = one engine instance alone, `hbm` = PMC bytes of the conv launches,
                         `entropy` = the entropy stage (rANS ns per symbol on the model's own symbols, checkerboard pass GB/s)
   sustained             three more rounds on the same engine instances right after the headline (60 steps at --steps 20)
-  parity                the parity state the numbers were measured under (tests/golden/parity_floors.json: how many reference
-                        goldens are bit-identical, the largest dbpp / dPSNR, the state at the bench's own operating point)
-  config.hbm_workspace_gib / pairs_in_flight   what the throughput costs in HBM and in images held at once
+With --full and N > 1 ranks, every rank also checks after the timed region that the all-gather returned its streams.
 """
 import argparse
 import json
@@ -283,10 +287,16 @@ def main():
     ap.add_argument("--steps", type=int, default=48)
     ap.add_argument("--warmup", type=int, default=16)
     ap.add_argument("--workload", default="c3_4x480x640", choices=sorted(WORKLOADS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure what else the line can carry: sustained rounds, the conv "
+                         "profile passes (roofline), the B=1 latency and entropy-stage passes, the secondary workloads "
+                         "(c2, c5: child processes) and the CPU baseline; with N > 1 ranks, the stream all-gather check")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-budget", type=float, default=25.0, help="seconds of CPU-oracle work for cpu_baseline (the B = 8 leg "
                     "runs only with >= 20)")
-    ap.add_argument("--no-extras", action="store_true", help="skip the secondary workload and the B=1 latency pass")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="with --full: skip the sustained rounds, the B=1 latency and entropy-stage passes and the secondary "
+                         "workloads")
     ap.add_argument("--workers", type=int, default=0,
                     help="engine instances (HIP streams) per GPU; 1 = no overlap; 0 = as few full rounds of at most 20 "
                          "instances as --steps allows (20 steps -> 20 instances, 48 -> 16)")
@@ -457,20 +467,20 @@ def main():
     host_cores = host.get("cores_busy")
     # sustained: three more rounds of --steps steps on the same instances, timed as one region (what a long job settles at)
     sustained = None
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         sus = timed(net, rgb, depth, calls, 0, rounds=3, per_call=G)
         t_sus = sum(e for e, _ in sus)
         sustained = {"steps": 3 * args.steps, "ms_per_step": round(t_sus / (3 * args.steps) * 1e3, 3),
                      "value": round(world * B * H * W * 3 * args.steps / t_sus / 1e6, 4), "unit": "Mpx/s",
                      "ms_per_step_by_round": [round(e / args.steps * 1e3, 3) for e, _ in sus]}
     workspace_gib = round(sum(n_.workspace_bytes() for n_ in net.nets) / 2 ** 30, 2)
-    if world > 1:  # outside the timed region: what every rank received from this rank is what this rank sent
+    if args.full and world > 1:  # outside the timed region: what every rank received from this rank is what this rank sent
         mine = [s for s in last["r_strings"][0] + last["d_strings"][0]]
         got = distributed.gather_streams(mine)
         assert len(got) == world and list(got[rank]) == mine, "stream gather returned different bytes"
 
-    # ---- conv profile, separate passes (not in the timed region): one engine instance, nothing else on the chip.  Twice:
-    # with the tiles the timed region ran (throughput tiles when the chip is shared) and with the latency tiles, which
+    # ---- conv profile (--full), separate passes (not in the timed region): one engine instance, nothing else on the chip.
+    # Twice: with the tiles the timed region ran (throughput tiles when the chip is shared) and with the latency tiles, which
     # is what a lone engine instance runs by default (tile choice never changes a result bit, only the speed).
     solo = net.nets[0]
 
@@ -485,16 +495,17 @@ def main():
         one.set_profile(False)
         return p
 
-    prof1 = conv_pass(tile_mode)
-    prof_lat = prof1 if tile_mode == "latency" else conv_pass("latency")
-    if os.environ.get("RGBD_BENCH_DEBUG"):
-        print("[bench] conv passes:", tile_mode, prof1, "| latency", prof_lat, file=sys.stderr)
-    solo.set_tile_mode(tile_mode)
-    flops_step = prof1["flops"] / 2.0 / G        # (the pass runs two calls of G steps each)
-    launches_call = prof1["launches"] // 2
-    launches_step = launches_call / G
+    if args.full:
+        prof1 = conv_pass(tile_mode)
+        prof_lat = prof1 if tile_mode == "latency" else conv_pass("latency")
+        if os.environ.get("RGBD_BENCH_DEBUG"):
+            print("[bench] conv passes:", tile_mode, prof1, "| latency", prof_lat, file=sys.stderr)
+        solo.set_tile_mode(tile_mode)
+        flops_step = prof1["flops"] / 2.0 / G        # (the pass runs two calls of G steps each)
+        launches_call = prof1["launches"] // 2
+        launches_step = launches_call / G
 
-    extras = world == 1 and not args.no_extras
+    extras = args.full and world == 1 and not args.no_extras
     latency = latency_tl = latency_hr = None
 
     def tester_latency(one, n_img=8):
@@ -655,7 +666,7 @@ def main():
         try:
             env = dict(os.environ)
             cmd = [sys.executable, os.path.abspath(__file__), "--workload", "c2_8x256x256", "--steps", str(args.steps), "--warmup",
-                   str(args.warmup), "--no-extras", "--no-cpu-baseline"]
+                   str(args.warmup), "--full", "--no-extras", "--no-cpu-baseline"]
             cp = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
             line = [ln for ln in cp.stdout.splitlines() if ln.startswith("{")]
             if cp.returncode != 0 or not line:
@@ -671,7 +682,7 @@ def main():
         for name5 in ("c5_stf_1x512x512", "c5_stf_4x512x512"):
             env = dict(os.environ)
             cmd = [sys.executable, os.path.abspath(__file__), "--workload", name5, "--steps", "16", "--warmup", "16", "--workers", "16",
-                   "--no-extras", "--cpu-budget", "10"] + (["--no-cpu-baseline"] if (args.no_cpu_baseline or cpu5 is not None) else [])
+                   "--full", "--no-extras", "--cpu-budget", "10"] + (["--no-cpu-baseline"] if (args.no_cpu_baseline or cpu5 is not None) else [])
             try:
                 cp = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
                 line = [ln for ln in cp.stdout.splitlines() if ln.startswith("{")]
@@ -700,21 +711,9 @@ def main():
                 w["vs_cpu"] = round(w["value"] / cpu5["value"], 2)
             others.append(w)
 
-    traffic = None
-    for rnd in ("r05",):  # (the call shape of rounds 1-4 was one step per call: their per-launch bytes do not apply)  # HBM bytes per conv launch from the PMC passes (FETCH_SIZE x2 on gfx950 + WRITE_SIZE)
-        try:
-            name = {"c2_8x256x256": f"{rnd}_pmc_traffic.json", "c3_4x480x640": f"{rnd}_c3_pmc_traffic.json"}[args.workload]
-            with open(os.path.join(ROOT, "profiles", name)) as f:
-                traffic = round(json.load(f)["hbm_bytes_per_launch"])
-            break
-        except (OSError, KeyError, ValueError):
-            pass
     if rank == 0:
         px = world * B * H * W * args.steps
         bytes_y = sum(len(s) for s in last["r_strings"][0] + last["d_strings"][0])
-        job_tflops = flops_step * args.steps / elapsed / 1e12
-        iso_tflops = prof_lat["flops"] / (prof_lat["conv_ms"] / 1e3) / 1e12
-        iso_tp_tflops = prof1["flops"] / (prof1["conv_ms"] / 1e3) / 1e12
         res = {
             "metric": "RGB-D Mpixels/s encode+decode",
             "value": round(px / elapsed / 1e6, 4),
@@ -741,40 +740,53 @@ def main():
                        "pairs_in_flight": pairs_in_flight, "hbm_workspace_gib": workspace_gib,
                        "hbm_workspace_gib_per_instance": round(workspace_gib / max(args.workers, 1), 3)},
             "parity": parity_state(),
+        }
+        if args.full:
+            traffic = None
+            for rnd in ("r05",):  # (the call shape of rounds 1-4 was one step per call: their per-launch bytes do not apply)  # HBM bytes per conv launch from the PMC passes (FETCH_SIZE x2 on gfx950 + WRITE_SIZE)
+                try:
+                    name = {"c2_8x256x256": f"{rnd}_pmc_traffic.json", "c3_4x480x640": f"{rnd}_c3_pmc_traffic.json"}[args.workload]
+                    with open(os.path.join(ROOT, "profiles", name)) as f:
+                        traffic = round(json.load(f)["hbm_bytes_per_launch"])
+                    break
+                except (OSError, KeyError, ValueError):
+                    pass
+            job_tflops = flops_step * args.steps / elapsed / 1e12
+            iso_tflops = prof_lat["flops"] / (prof_lat["conv_ms"] / 1e3) / 1e12
+            iso_tp_tflops = prof1["flops"] / (prof1["conv_ms"] / 1e3) / 1e12
             # `achieved`: algorithmic conv FLOPs of the timed steps / wall time of the timed region (job level, a lower
             # bound on MFMA utilisation: the wall clock also holds every other kernel).  With several engine instances
             # sharing the chip a per-launch event bracket would also contain CU time-sharing, so the per-launch figure is
             # measured for one instance alone in a separate pass (`isolated`; agrees with `rocprofv3 --stats` of
             # `--workers 1`, committed under profiles/).
-            "roofline": {"bound": "mfma", "kernel": "conv_mfma_kernel (all conv/deconv layers)",
-                         "achieved": round(job_tflops, 3), "peak": PEAK_FP32_MFMA_TFLOPS, "unit": "TFLOP/s",
-                         "frac": round(job_tflops / PEAK_FP32_MFMA_TFLOPS, 4), "traffic": traffic,
-                         "traffic_note": "HBM bytes per conv launch, rocprofv3 PMC passes committed under profiles/ "
-                                         "(not collectable from inside this process)",
-                         "definition": "algorithmic conv FLOPs of the timed steps / wall time of the timed region, per GPU",
-                         # FLOPs the launches execute / algorithmic FLOPs: < 1 because a checkerboard-output launch computes one
-                         # half of its layer and an anchor-input launch half of the taps as well (what the MFMA-busy counter
-                         # sees is `frac` x this)
-                         "executed_over_algorithmic": round(prof1["flops_executed"] / max(prof1["flops"], 1.0), 4),
-                         "executed_frac": round(job_tflops / PEAK_FP32_MFMA_TFLOPS * prof1["flops_executed"] / max(prof1["flops"], 1.0), 4),
-                         "hbm": None if traffic is None else {
-                             "achieved": round(traffic * launches_call / (elapsed / calls) / 1e9, 1), "peak": 8000.0,
-                             "unit": "GB/s", "frac": round(traffic * launches_call / (elapsed / calls) / 8e12, 4),
-                             "note": "PMC HBM bytes of the conv launches of one step / step time: the path is MFMA-bound"},
-                         "launches_per_call": launches_call, "launches_per_step": round(launches_step, 2),
-                         "gflop_per_step": round(flops_step / 1e9, 2),
-                         "isolated": {"achieved": round(iso_tflops, 3), "frac": round(iso_tflops / PEAK_FP32_MFMA_TFLOPS, 4),
-                                      "avg_launch_us": round(prof_lat["conv_ms"] * 1e3 / max(prof_lat["launches"], 1), 2),
-                                      "executed_frac": round(prof_lat["flops_executed"] / (prof_lat["conv_ms"] / 1e3) / 1e12 / PEAK_FP32_MFMA_TFLOPS, 4),
-                                      "conv_ms_per_step": round(prof_lat["conv_ms"] / 2 / G, 3), "conv_tiles": "latency",
-                                      "note": "HIP events around every conv launch on its stream, single engine instance, "
-                                              "no concurrent kernels, separate pass after the timed region, latency tiles "
-                                              "(what a lone instance runs); profiles/r05_bench_w1_summary.txt"},
-                         "isolated_timed_tiles": {"achieved": round(iso_tp_tflops, 3),
-                                                  "frac": round(iso_tp_tflops / PEAK_FP32_MFMA_TFLOPS, 4),
-                                                  "conv_ms_per_step": round(prof1["conv_ms"] / 2 / G, 3), "conv_tiles": tile_mode,
-                                                  "note": "the same pass with the tiles the timed region ran"}},
-        }
+            res["roofline"] = {"bound": "mfma", "kernel": "conv_mfma_kernel (all conv/deconv layers)",
+                               "achieved": round(job_tflops, 3), "peak": PEAK_FP32_MFMA_TFLOPS, "unit": "TFLOP/s",
+                               "frac": round(job_tflops / PEAK_FP32_MFMA_TFLOPS, 4), "traffic": traffic,
+                               "traffic_note": "HBM bytes per conv launch, rocprofv3 PMC passes committed under profiles/ "
+                                               "(not collectable from inside this process)",
+                               "definition": "algorithmic conv FLOPs of the timed steps / wall time of the timed region, per GPU",
+                               # FLOPs the launches execute / algorithmic FLOPs: < 1 because a checkerboard-output launch
+                               # computes one half of its layer and an anchor-input launch half of the taps as well (what the
+                               # MFMA-busy counter sees is `frac` x this)
+                               "executed_over_algorithmic": round(prof1["flops_executed"] / max(prof1["flops"], 1.0), 4),
+                               "executed_frac": round(job_tflops / PEAK_FP32_MFMA_TFLOPS * prof1["flops_executed"] / max(prof1["flops"], 1.0), 4),
+                               "hbm": None if traffic is None else {
+                                   "achieved": round(traffic * launches_call / (elapsed / calls) / 1e9, 1), "peak": 8000.0,
+                                   "unit": "GB/s", "frac": round(traffic * launches_call / (elapsed / calls) / 8e12, 4),
+                                   "note": "PMC HBM bytes of the conv launches of one step / step time: the path is MFMA-bound"},
+                               "launches_per_call": launches_call, "launches_per_step": round(launches_step, 2),
+                               "gflop_per_step": round(flops_step / 1e9, 2),
+                               "isolated": {"achieved": round(iso_tflops, 3), "frac": round(iso_tflops / PEAK_FP32_MFMA_TFLOPS, 4),
+                                            "avg_launch_us": round(prof_lat["conv_ms"] * 1e3 / max(prof_lat["launches"], 1), 2),
+                                            "executed_frac": round(prof_lat["flops_executed"] / (prof_lat["conv_ms"] / 1e3) / 1e12 / PEAK_FP32_MFMA_TFLOPS, 4),
+                                            "conv_ms_per_step": round(prof_lat["conv_ms"] / 2 / G, 3), "conv_tiles": "latency",
+                                            "note": "HIP events around every conv launch on its stream, single engine instance, "
+                                                    "no concurrent kernels, separate pass after the timed region, latency tiles "
+                                                    "(what a lone instance runs); profiles/r05_bench_w1_summary.txt"},
+                               "isolated_timed_tiles": {"achieved": round(iso_tp_tflops, 3),
+                                                        "frac": round(iso_tp_tflops / PEAK_FP32_MFMA_TFLOPS, 4),
+                                                        "conv_ms_per_step": round(prof1["conv_ms"] / 2 / G, 3), "conv_tiles": tile_mode,
+                                                        "note": "the same pass with the tiles the timed region ran"}}
         if entropy is not None:
             res["roofline"]["entropy"] = entropy
         if sustained is not None:
@@ -788,7 +800,7 @@ def main():
         if second is not None:
             res["workloads"] = [{"workload": args.workload, "value": res["value"], "unit": "Mpx/s",
                                  "ms_per_step": res["ms_per_step"], "images_per_gpu": B, "image": [H, W]}, second] + others
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             cpu = cpu_baseline(sd_main, H, W, cid, model, seconds_budget=args.cpu_budget, batch8=args.cpu_budget >= 20.0)
             res["cpu_baseline"] = cpu
             res["vs_cpu"] = {"throughput": round(res["value"] / cpu["value"], 2),

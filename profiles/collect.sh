@@ -16,15 +16,15 @@ root=$(pwd)
 out=$root/gpurun_out/prof_$tag
 mkdir -p "$out"
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/stats" -o run -- python3 "$root/bench.py" $bench_args --no-cpu-baseline --no-extras > "$out/stats.log" 2>&1
+timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/stats" -o run -- python3 "$root/bench.py" $bench_args --full --no-cpu-baseline --no-extras > "$out/stats.log" 2>&1
 echo "[collect] default done"
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/stats_w1" -o run -- python3 "$root/bench.py" --workers 1 --steps 8 --warmup 4 --no-cpu-baseline --no-extras > "$out/stats_w1.log" 2>&1
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/stats_w1" -o run -- python3 "$root/bench.py" --workers 1 --steps 8 --warmup 4 --full --no-cpu-baseline --no-extras > "$out/stats_w1.log" 2>&1
 echo "[collect] w1 done"
 export RGBD_NO_GRAPH=1
-timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$out/fetch_c3" -o run -- python3 "$root/bench.py" --steps 4 --warmup 4 --workers 1 --no-cpu-baseline --no-extras > "$out/fetch_c3.log" 2>&1
-timeout -k 10 300 rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$out/write_c3" -o run -- python3 "$root/bench.py" --steps 4 --warmup 4 --workers 1 --no-cpu-baseline --no-extras > "$out/write_c3.log" 2>&1
+timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$out/fetch_c3" -o run -- python3 "$root/bench.py" --steps 4 --warmup 4 --workers 1 --full --no-cpu-baseline --no-extras > "$out/fetch_c3.log" 2>&1
+timeout -k 10 300 rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$out/write_c3" -o run -- python3 "$root/bench.py" --steps 4 --warmup 4 --workers 1 --full --no-cpu-baseline --no-extras > "$out/write_c3.log" 2>&1
 echo "[collect] traffic done"
-timeout -k 10 300 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d "$out/mfma" -o run -- python3 "$root/bench.py" --steps 4 --warmup 4 --workers 1 --no-cpu-baseline --no-extras > "$out/mfma.log" 2>&1
+timeout -k 10 300 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d "$out/mfma" -o run -- python3 "$root/bench.py" --steps 4 --warmup 4 --workers 1 --full --no-cpu-baseline --no-extras > "$out/mfma.log" 2>&1
 echo "[collect] mfma done"
 unset RGBD_NO_GRAPH
 cd "$root"

@@ -1,6 +1,6 @@
-"""bench.py on the GPU box: the one-line JSON contract the driver parses (metric / value / roofline / cpu_baseline /
-latency), and the N-rank path end to end -- two ranks started by bench.py itself, sharing this box's one GPU, with gloo
-standing in for RCCL (two RCCL ranks cannot share a device)."""
+"""bench.py on the GPU box: the one-line JSON contract the driver parses (metric / value, and with --full roofline /
+cpu_baseline / latency), and the N-rank path end to end -- two ranks started by bench.py itself, sharing this box's one
+GPU, with gloo standing in for RCCL (two RCCL ranks cannot share a device)."""
 import json
 import os
 import subprocess
@@ -28,7 +28,7 @@ def _run(*argv, env=None, timeout=600):
 @pytest.mark.timeout(900)
 def test_single_rank_line_has_the_contract_fields():
     require_gpu()
-    r = _run("--steps", "8", "--warmup", "2", "--workers", "2")  # c3 codes four steps per engine call: two calls of 16 images
+    r = _run("--full", "--steps", "8", "--warmup", "2", "--workers", "2")  # c3 codes four steps per engine call: two calls of 16 images
     assert r["metric"].startswith("RGB-D Mpixels/s") and r["unit"] == "Mpx/s" and r["n_gpus"] == 1
     assert r["steps"] == 8 and r["warmup"] == 2 and r["higher_is_better"] is True and r["scaling"] == "weak"
     assert r["dtype"] == "f32" and r["data"] == "synthetic" and r["vs_baseline"] is None
@@ -60,10 +60,23 @@ def test_single_rank_line_has_the_contract_fields():
     assert "BATCH THROUGHPUT" in r["vs_cpu"]["note"]
 
 
+@pytest.mark.timeout(600)
+def test_plain_run_times_the_headline_only():
+    """Without --full the line carries the headline and nothing that needs a pass of its own (roofline, sustained rounds,
+    B=1 latency, secondary workloads, CPU baseline)."""
+    require_gpu()
+    r = _run("--steps", "4", "--warmup", "1", "--workers", "1")
+    assert r["metric"].startswith("RGB-D Mpixels/s") and r["unit"] == "Mpx/s" and r["higher_is_better"] is True
+    assert r["dtype"] == "f32" and r["steps"] == 4 and r["warmup"] == 1 and r["config"]["calls"] == 1
+    assert r["value"] > 1.0 and abs(r["value"] - 4 * 480 * 640 * 4 / (r["ms_per_step"] * 4e-3) / 1e6) < 0.02 * r["value"]
+    moved = {"roofline", "sustained", "latency", "latency_trained_like", "latency_high_rate", "workloads", "cpu_baseline", "vs_cpu"}
+    assert not moved & set(r), sorted(moved & set(r))
+
+
 @pytest.mark.timeout(900)
 def test_two_ranks_spawned_by_bench_itself():
     require_gpu()
-    r = _run("--gpus", "2", "--steps", "3", "--warmup", "2", "--workers", "2", env={"RGBD_DIST_BACKEND": "gloo"})
+    r = _run("--full", "--gpus", "2", "--steps", "3", "--warmup", "2", "--workers", "2", env={"RGBD_DIST_BACKEND": "gloo"})
     assert r["n_gpus"] == 2 and r["steps"] == 3 and r["config"]["images_per_gpu"] == 4
     assert r["value"] > 0.5 and "latency" not in r and "cpu_baseline" not in r
 

@@ -80,7 +80,7 @@ def test_two_ranks_rccl_when_two_gpus_are_visible():
 
     if torch.cuda.device_count() < 2:
         pytest.skip("one GPU visible: two RCCL ranks cannot share a device (the gloo twin runs in test_gpu_bench.py)")
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "2",
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "3", "--warmup", "2",
                         "--workers", "2"], env=_clean_env(), capture_output=True, text=True, timeout=840)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
