@@ -105,6 +105,28 @@ int rgbd_ckbd_quant_index(const float* y_dev, const float* means_dev, const floa
 int rgbd_ckbd_dequant(const int32_t* symbols_dev, const float* means_dev, int32_t n, int32_t c, int32_t h, int32_t w, int32_t anchor,
                       float* yhat_dev, void* stream);
 
+/* One raster channel slice of the single-modal STF's entropy model (models/stf.py:746-751, 796-800): C channels of NHWC fp32
+ * device tensors [B][h][w][channel stride], every pointer already offset to the slice's first channel; mean and scale come
+ * from two tensors (two nets).  symbol = rint(y - mean) (half to even), index = build_indexes(scale) on the raw scale,
+ * y_hat = symbol + mean written to yhat0_dev and, when not NULL, yhat1_dev.  Symbols / indexes land in stream order at
+ * slice_off * B + ((b * C + c) * h + row) * w + col (per_image == 0: the reference's one stream per call, slice-major;
+ * slice_off = symbols of one image's earlier slices) or at b * image_stride + slice_off + (c * h + row) * w + col
+ * (per_image != 0: image b's own stream of image_stride symbols).  scale_table: the 64 entries of get_scale_table() (host).
+ * rgbd_slice_dequant is the decoder's half (y_hat = symbol + mean).  Asynchronous on `stream`. */
+int rgbd_slice_quant_index(const float* y_dev, int32_t ycs, const float* means_dev, int32_t mcs, const float* scales_dev, int32_t scs,
+                           int32_t B, int32_t C, int32_t h, int32_t w, int32_t per_image, int64_t image_stride, int64_t slice_off,
+                           const float* scale_table, int32_t* symbols_dev, int32_t* indexes_dev, float* yhat0_dev, int32_t cs0,
+                           float* yhat1_dev, int32_t cs1, void* stream);
+int rgbd_slice_dequant(const int32_t* symbols_dev, const float* means_dev, int32_t mcs, int32_t B, int32_t C, int32_t h, int32_t w,
+                       int32_t per_image, int64_t image_stride, int64_t slice_off, float* yhat0_dev, int32_t cs0, float* yhat1_dev,
+                       int32_t cs1, void* stream);
+/* Latent residual prediction (stf.py:753-758): out = y_hat + 0.5 * tanh(lrp) for npix pixels of C channels (NHWC, channel
+ * strides lcs / ycs / cs*), written to out0_dev and, when not NULL, out1_dev / out2_dev; a destination may be yhat_dev itself.
+ * The sum is formed in double (tanh with explicit fused multiply-adds) and rounded once: within 0.5 ulp of the result,
+ * the same floats on every call. */
+int rgbd_lrp_update(const float* lrp_dev, int32_t lcs, const float* yhat_dev, int32_t ycs, int64_t npix, int32_t C, float* out0_dev,
+                    int32_t cs0, float* out1_dev, int32_t cs1, float* out2_dev, int32_t cs2, void* stream);
+
 /* ---------------------------------------------------------------------------------------------------------------
  * Single operators on device tensors (NCHW fp32, contiguous) -- used by the parity tests of the conv kernels.
  * Replaces torch.nn.functional.conv2d / conv_transpose2d as used by modules/layers/conv.py:7-34.
@@ -210,6 +232,13 @@ int rgbd_elic_compress_single(rgbd_elic* m, const float* x_dev, int32_t B, int32
 int rgbd_elic_decompress_single(rgbd_elic* m, const uint8_t* const* y, const int64_t* y_len, int32_t n_y,
                                 const uint8_t* const* z, const int64_t* z_len, int32_t B, int32_t zh, int32_t zw,
                                 float* x_dev, void* stream);
+/* The single-modal STF (models/stf.py: SymmetricalTransFormer :408-816; N = 192, M = 384, 12 slices of 32 channels): Swin
+ * analysis / synthesis transforms, two hyper-synthesis nets and the channel-slice entropy model with latent residual prediction.
+ * Served by the three *_single entry points of this section: compress puts all slices of all images of a call into ONE y
+ * stream (per_image_streams: one per image); decompress clamps x_hat to [0, 1] (stf.py:815) and, unlike the reference, is the
+ * inverse of compress for a batch as well; forward's x_hat is not clamped.  Debug tensors: y, z, zhat, yhat, latent_means,
+ * latent_scales. */
+int rgbd_elic_create_stf_single(int32_t in_ch, rgbd_elic** out);
 /* Eval-mode forward() of the single-modal model (models/elic.py:60-161 with config quant = "ste"): x_hat [B,in_ch,H,W]
  * (not clamped), likelihoods of y [B,M,H/16,W/16] and of z [B,N,H/64,W/64] ("y_likelihoods" / "z_likelihoods"). */
 int rgbd_elic_forward_single(rgbd_elic* m, const float* x_dev, int32_t B, int32_t H, int32_t W, float* xhat_dev, float* lik_y,

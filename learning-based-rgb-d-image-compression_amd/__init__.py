@@ -19,6 +19,9 @@ modelZoo.clear()
 modelZoo.update({"ELIC_united_R2D": ELIC_united_R2D, "ELIC_united": ELIC_united})
 modelZoo["ELIC"] = ELIC
 modelZoo["STF_united"] = SymmetricalTransFormerUnited  # models/__init__.py:11-20
+from .stf import STF, SymmetricalTransFormer  # noqa: F401,E402
+
+modelZoo["STF"] = SymmetricalTransFormer  # after "STF_united": the testers match model names by substring in zoo order
 from .pool import CodecPool  # noqa: F401,E402
 from . import datautils, ioutils, metrics, tester  # noqa: F401,E402
 from .tester import TesterSingle, TesterUnited  # noqa: F401,E402

@@ -471,6 +471,63 @@ def stf_united_entries(config=None) -> "OrderedDict[str, Entry]":
     return out
 
 
+STF_SLICES = 12        # models/stf.py:418 (num_slices); 384 / 12 = 32 channels per slice
+STF_SUPPORT_SLICES = 6  # stf.py:439 (max_support_slices = num_slices // 2)
+
+
+def stf_single_config() -> Config:
+    """The fixed widths of the single-modal STF (models/stf.py:431, 630): N = 192 hyper channels, M = 384 latent channels
+    in 12 raster slices of 32."""
+    cfg = model_config()
+    cfg["N"], cfg["M"] = 4 * STF_EMBED, 8 * STF_EMBED
+    cfg["slice_num"], cfg["slice_ch"] = STF_SLICES, [8 * STF_EMBED // STF_SLICES] * STF_SLICES
+    return cfg
+
+
+def stf_entries(channel: int = 3) -> "OrderedDict[str, Entry]":
+    """Every state_dict entry of the single-modal STF (reference: models/stf.py:408-585, SymmetricalTransFormer; 779 tensors,
+    99,855,639 parameters for channel=3): Swin analysis / synthesis transforms, a hyper analysis of five 3x3 convolutions,
+    two hyper-synthesis nets, and per slice two parameter nets plus the latent-residual-prediction net."""
+    b = _Builder()
+    E, depths, heads = STF_EMBED, STF_DEPTHS, STF_HEADS
+    M, C = 8 * E, 8 * E // STF_SLICES
+    b.conv("patch_embed.proj", channel, E, 2)
+    b.layernorm("patch_embed.norm", E)
+    dim = E
+    for i in range(4):  # stf.py:454-472
+        for k in range(depths[i]):
+            b.swin_block(f"layers.{i}.blocks.{k}", dim, heads[i])
+        if i < 3:
+            b.linear(f"layers.{i}.downsample.reduction", 4 * dim, 2 * dim, bias=False)
+            b.layernorm(f"layers.{i}.downsample.norm", 4 * dim)
+            dim *= 2
+    for i in range(4):  # stf.py:474-494
+        for k in range(depths[3 - i]):
+            b.swin_block(f"syn_layers.{i}.blocks.{k}", dim, heads[3 - i])
+        if i < 3:
+            b.linear(f"syn_layers.{i}.downsample.reduction", dim, 2 * dim, bias=False)
+            b.layernorm(f"syn_layers.{i}.downsample.norm", dim)
+            dim //= 2
+    b.conv("end_conv.0", E, 4 * E, 5)  # stf.py:496-500
+    b.conv("end_conv.2", E, channel, 3)
+    for j, (cin, cout) in enumerate(((384, 384), (384, 336), (336, 288), (288, 240), (240, 192))):  # stf.py:507-517
+        b.conv(f"h_a.{2 * j}", cin, cout, 3)
+    for fam in ("h_mean_s", "h_scale_s"):  # stf.py:519-540; subpel_conv3x3 = Sequential(conv to 4 C channels, PixelShuffle)
+        b.conv(f"{fam}.0", 192, 240, 3)
+        b.conv(f"{fam}.2.0", 240, 288 * 4, 3)
+        b.conv(f"{fam}.4", 288, 336, 3)
+        b.conv(f"{fam}.6.0", 336, 384 * 4, 3)
+        b.conv(f"{fam}.8", 384, 384, 3)
+    for fam, extra in (("cc_mean_transforms", 0), ("cc_scale_transforms", 0), ("lrp_transforms", 1)):  # stf.py:541-582
+        for i in range(STF_SLICES):
+            cin = M + C * min(i + extra, STF_SUPPORT_SLICES + extra)
+            for j, (a, o) in enumerate(((cin, 224), (224, 176), (176, 128), (128, 64), (64, C))):
+                b.conv(f"{fam}.{i}.{2 * j}", a, o, 3)
+    b.entropy_bottleneck("entropy_bottleneck", 4 * E)
+    b.gaussian_conditional("gaussian_conditional")
+    return b.entries
+
+
 def count_parameters(entries) -> int:
     n = 0
     for e in entries.values():

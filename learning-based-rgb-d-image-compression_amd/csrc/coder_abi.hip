@@ -494,4 +494,49 @@ int rgbd_ckbd_dequant(const int32_t* symbols_dev, const float* means_dev, int32_
                    stream);
 }
 
+// ---- raster channel slices and the LRP update (entropy.hip: slice_part_kernel, lrp_update_kernel) ----
+
+static bool slice_args_ok(int32_t B, int32_t C, int32_t h, int32_t w, int32_t per_image, int64_t image_stride, int64_t slice_off)
+{
+    if (B <= 0 || C <= 0 || h <= 0 || w <= 0 || slice_off < 0) return false;
+    if ((int64_t)B * C * h * w >= ((int64_t)1 << 31)) return false;
+    return !per_image || image_stride >= slice_off + (int64_t)C * h * w;
+}
+
+int rgbd_slice_quant_index(const float* y_dev, int32_t ycs, const float* means_dev, int32_t mcs, const float* scales_dev, int32_t scs,
+                           int32_t B, int32_t C, int32_t h, int32_t w, int32_t per_image, int64_t image_stride, int64_t slice_off,
+                           const float* scale_table, int32_t* symbols_dev, int32_t* indexes_dev, float* yhat0_dev, int32_t cs0,
+                           float* yhat1_dev, int32_t cs1, void* stream)
+{
+    if (!y_dev || !means_dev || !scales_dev || !scale_table || !symbols_dev || !indexes_dev || !yhat0_dev) return RGBD_EINVAL;
+    if (ycs < C || mcs < C || scs < C || cs0 < C || (yhat1_dev && cs1 < C)) return RGBD_EINVAL;
+    if (!slice_args_ok(B, C, h, w, per_image, image_stride, slice_off)) return RGBD_EINVAL;
+    ScaleTab tb{};
+    memcpy(tb.v, scale_table, sizeof(tb.v));
+    const SliceGeom g = {B, h, w, C, per_image ? 1 : 0, image_stride};
+    return launch_slice_encode(y_dev, ycs, means_dev, mcs, scales_dev, scs, tb, g, symbols_dev, indexes_dev, nullptr, slice_off,
+                               yhat0_dev, cs0, yhat1_dev, cs1, (hipStream_t)stream);
+}
+
+int rgbd_slice_dequant(const int32_t* symbols_dev, const float* means_dev, int32_t mcs, int32_t B, int32_t C, int32_t h, int32_t w,
+                       int32_t per_image, int64_t image_stride, int64_t slice_off, float* yhat0_dev, int32_t cs0, float* yhat1_dev,
+                       int32_t cs1, void* stream)
+{
+    if (!symbols_dev || !means_dev || !yhat0_dev || mcs < C || cs0 < C || (yhat1_dev && cs1 < C)) return RGBD_EINVAL;
+    if (!slice_args_ok(B, C, h, w, per_image, image_stride, slice_off)) return RGBD_EINVAL;
+    const SliceGeom g = {B, h, w, C, per_image ? 1 : 0, image_stride};
+    return launch_slice_decode(means_dev, mcs, g, symbols_dev, nullptr, slice_off, yhat0_dev, cs0, yhat1_dev, cs1,
+                               (hipStream_t)stream);
+}
+
+int rgbd_lrp_update(const float* lrp_dev, int32_t lcs, const float* yhat_dev, int32_t ycs, int64_t npix, int32_t C, float* out0_dev,
+                    int32_t cs0, float* out1_dev, int32_t cs1, float* out2_dev, int32_t cs2, void* stream)
+{
+    if (!lrp_dev || !yhat_dev || !out0_dev || npix <= 0 || C <= 0 || lcs < C || ycs < C || cs0 < C || (out1_dev && cs1 < C) ||
+        (out2_dev && cs2 < C))
+        return RGBD_EINVAL;
+    return launch_lrp_update(lrp_dev, lcs, yhat_dev, ycs, (size_t)npix, C, out0_dev, cs0, out1_dev, cs1, out2_dev, cs2,
+                             (hipStream_t)stream);
+}
+
 }  // extern "C"

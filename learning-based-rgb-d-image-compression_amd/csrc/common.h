@@ -306,6 +306,27 @@ int launch_ckbd_decode_part(const float* params, int pcs, float* yhat, int yhcs,
                             const int64_t* stream_base, int64_t part_off_per_image, hipStream_t s);
 int launch_ckbd_estimate_part(const float* y, int ycs, const float* params, int pcs, float* yhat, int yhcs, float* lik,
                               int lcs, PartGeom g, hipStream_t s);
+// raster channel slices and the LRP update (single-modal STF; entropy.hip: slice_part_kernel, lrp_update_kernel)
+struct ScaleTab {
+    float v[64];  // get_scale_table(), passed by value
+};
+struct SliceGeom {
+    int B, h, w;  // latent geometry
+    int C;        // channels of the slice (the tensor pointers are already offset to its first channel)
+    int per_image;  // 1: one stream per image; 0: one stream for the batch, slice-major (the reference's format)
+    int64_t image_stride;  // symbols between the images' streams when no stream_base array is given (per_image)
+};
+int launch_slice_encode(const float* y, int ycs, const float* mu, int mcs, const float* sg, int scs, const ScaleTab& table,
+                        SliceGeom g, int32_t* sym, int32_t* idx, const int64_t* stream_base, int64_t slice_off, float* d0,
+                        int d0cs, float* d1, int d1cs, hipStream_t s, float* dbg_x = nullptr, float* dbg_s = nullptr);
+int launch_slice_index(const float* sg, int scs, const ScaleTab& table, SliceGeom g, int32_t* idx, const int64_t* stream_base,
+                       int64_t slice_off, hipStream_t s);
+int launch_slice_decode(const float* mu, int mcs, SliceGeom g, const int32_t* sym, const int64_t* stream_base, int64_t slice_off,
+                        float* d0, int d0cs, float* d1, int d1cs, hipStream_t s);
+int launch_slice_estimate(const float* y, int ycs, const float* mu, int mcs, const float* sg, int scs, SliceGeom g, float* lik,
+                          int lcs, float* d0, int d0cs, float* d1, int d1cs, hipStream_t s);
+int launch_lrp_update(const float* lrp, int lcs, const float* src, int scs, size_t npix, int C, float* d0, int d0cs, float* d1,
+                      int d1cs, float* d2, int d2cs, hipStream_t s);
 // perm: z / zhat / lik store their channels permuted (rgbd_cperm); medians, prm and the symbol order are logical
 int launch_eb_forward(const float* z, int zcs, int B, int h, int w, int C, const float* med, const float* prm, float* zhat,
                       float* lik, hipStream_t s, int perm = 0);

@@ -1,5 +1,5 @@
 // Host runtime of the gfx950 codec engine, part 1 of 3: weight packing, the workspace arena and `struct rgbd_elic` -- the
-// layer graph of the four model variants (ELIC_united, single-modal ELIC, STF_united, ELIC_united_R2D) as inline methods
+// layer graph of the five model variants (ELIC_united, single-modal ELIC, STF_united, ELIC_united_R2D, single-modal STF) as inline methods
 // that plan and issue HIP kernel launches on one stream, the conv planner (tiles, split-K, reference arithmetic) and the
 // per-call-shape HIP-graph cache.  engine.hip holds the call paths (compress / decompress / forward), engine_abi.hip the
 // C ABI (include/rgbd_amd.h).  Everything shared between those two translation units is `inline` here (one instance).
@@ -370,7 +370,9 @@ using namespace rgbd_rt;
 struct rgbd_elic {
     int N = 192, M = 320;
     int tile_mode = 0;  // rgbd_elic_set_tile_mode: 0 latency tiles (isolated launches), 1 throughput tiles (shared chip)
-    int variant = 0;  // 0: ELIC_united (RGB + depth), 1: single-modal ELIC (models/elic.py)
+    int variant = 0;  // 0: ELIC_united (RGB + depth), 1: single-modal ELIC (models/elic.py), 2: STF_united, 3: ELIC_united_R2D,
+                      // 4: single-modal STF (models/stf.py)
+    bool single() const { return variant == 1 || variant == 4; }
     int in_ch = 3;    // image channels of the single-modal variant
     std::vector<int> slice_ch;
     std::map<std::string, HostTensor> raw;
@@ -2203,15 +2205,21 @@ struct rgbd_elic {
     // on independent data between two fusions, so every Linear is one grouped conv launch (conv2) and every LayerNorm /
     // window attention one launch over both tensors -- half the launches of a model whose launches are too small to fill the
     // chip (35 us on average at one 512x512 pair).  Each output keeps its arithmetic: bit-identical to the one-by-one form.
-    void layernorm2(const std::string p[2], const Act x[2], Act y[2])
+    // nm == 1 (the single-modal STF, models/stf.py): the same blocks on one tensor; arrays are read at [0, nm) only.
+    void layernorm2(int nm, const std::string p[2], const Act x[2], Act y[2])
     {
-        float *w[2], *b[2];
-        for (int m = 0; m < 2; ++m) {
+        float *w[2] = {}, *b[2] = {};
+        for (int m = 0; m < nm; ++m) {
             y[m] = alloc(x[m].n, x[m].h, x[m].w, x[m].c);
             w[m] = dense_of(p[m] + ".weight");
             b[m] = dense_of(p[m] + ".bias");
         }
-        if (dry() || rc || !w[0] || !b[0] || !w[1] || !b[1]) return;
+        if (dry() || rc || !w[0] || !b[0] || !w[nm - 1] || !b[nm - 1]) return;
+        if (nm == 1) {
+            const int r = launch_layernorm(x[0].p, (size_t)x[0].n * x[0].h * x[0].w, x[0].c, x[0].cs, w[0], b[0], y[0].p, y[0].cs, s);
+            if (r) fail(r);
+            return;
+        }
         const bool same = g_pair && x[0].n == x[1].n && x[0].h == x[1].h && x[0].w == x[1].w && x[0].c == x[1].c &&
                           x[0].cs == x[1].cs && y[0].cs == y[1].cs;
         const size_t ntok = (size_t)x[0].n * x[0].h * x[0].w;
@@ -2221,27 +2229,30 @@ struct rgbd_elic {
             r = launch_layernorm(x[1].p, (size_t)x[1].n * x[1].h * x[1].w, x[1].c, x[1].cs, w[1], b[1], y[1].p, y[1].cs, s);
         if (r) fail(r);
     }
-    void swin_block2(const std::string p[2], const Act x[2], int shift, int heads, Act out[2])
+    void swin_block2(int nm, const std::string p[2], const Act x[2], int shift, int heads, Act out[2])
     {
-        for (int m = 0; m < 2; ++m) out[m] = alloc(x[m].n, x[m].h, x[m].w, x[m].c);
+        for (int m = 0; m < nm; ++m) out[m] = alloc(x[m].n, x[m].h, x[m].w, x[m].c);
         const size_t mark = arena.top;
         auto names = [&](const char* suf, std::string n[2]) {
-            n[0] = p[0] + suf;
-            n[1] = p[1] + suf;
+            for (int m = 0; m < nm; ++m) n[m] = p[m] + suf;
         };
         std::string n[2];
         const Epi none[2];
         Act t[2], qkv[2], a[2], x1[2], t2[2], hdn[2], o[2];
         names(".norm1", n);
-        layernorm2(n, x, t);
+        layernorm2(nm, n, x, t);
         names(".attn.qkv", n);
-        conv2(2, n, t, 1, 0, none, nullptr, qkv);
-        float* rpb[2];
-        for (int m = 0; m < 2; ++m) {
+        conv2(nm, n, t, 1, 0, none, nullptr, qkv);
+        float* rpb[2] = {};
+        for (int m = 0; m < nm; ++m) {
             a[m] = alloc(x[m].n, x[m].h, x[m].w, x[m].c);
             rpb[m] = dense_of(p[m] + ".attn.relative_position_bias_table");
         }
-        if (!dry() && !rc && rpb[0] && rpb[1]) {
+        if (!dry() && !rc && rpb[0] && nm == 1) {
+            const int r = launch_window_attention(qkv[0].p, x[0].n, x[0].h, x[0].w, x[0].c, qkv[0].cs, heads, shift, rpb[0], a[0].p,
+                                                  a[0].cs, s);
+            if (r) fail(r);
+        } else if (!dry() && !rc && rpb[0] && rpb[1]) {
             const bool same = g_pair && x[0].n == x[1].n && x[0].h == x[1].h && x[0].w == x[1].w && x[0].c == x[1].c &&
                               qkv[0].cs == qkv[1].cs && a[0].cs == a[1].cs;
             int r = launch_window_attention(qkv[0].p, x[0].n, x[0].h, x[0].w, x[0].c, qkv[0].cs, heads, shift, rpb[0], a[0].p, a[0].cs,
@@ -2255,53 +2266,53 @@ struct rgbd_elic {
         e1[0].res1 = &x[0];
         e1[1].res1 = &x[1];
         names(".attn.proj", n);
-        conv2(2, n, a, 1, 0, e1, nullptr, x1);
+        conv2(nm, n, a, 1, 0, e1, nullptr, x1);
         names(".norm2", n);
-        layernorm2(n, x1, t2);
+        layernorm2(nm, n, x1, t2);
         Epi g[2];
         g[0].act = g[1].act = ACT_GELU;
         names(".mlp.fc1", n);
-        conv2(2, n, t2, 1, 0, g, nullptr, hdn);
+        conv2(nm, n, t2, 1, 0, g, nullptr, hdn);
         Epi e2[2];
         e2[0].res1 = &x1[0];
         e2[1].res1 = &x1[1];
         const Act* odst[2] = {&out[0], &out[1]};
         names(".mlp.fc2", n);
-        conv2(2, n, hdn, 1, 0, e2, odst, o);
+        conv2(nm, n, hdn, 1, 0, e2, odst, o);
         arena.top = mark;
     }
     // stf_united.py:270-366 for both modalities; down: 0 none, 1 PatchMerging (:217-249), 2 PatchSplit (:252-267)
-    void basic_layer2(const std::string p[2], const Act x_in[2], int depth, int heads, int down, Act out[2])
+    void basic_layer2(int nm, const std::string p[2], const Act x_in[2], int depth, int heads, int down, Act out[2])
     {
-        Act x[2] = {x_in[0], x_in[1]};
+        Act x[2] = {x_in[0], x_in[nm - 1]};
         for (int k = 0; k < depth; ++k) {
-            const std::string pb[2] = {p[0] + ".blocks." + std::to_string(k), p[1] + ".blocks." + std::to_string(k)};
+            const std::string pb[2] = {p[0] + ".blocks." + std::to_string(k), p[nm - 1] + ".blocks." + std::to_string(k)};
             Act o[2];
-            swin_block2(pb, x, (k & 1) ? 2 : 0, heads, o);
+            swin_block2(nm, pb, x, (k & 1) ? 2 : 0, heads, o);
             x[0] = o[0];
             x[1] = o[1];
         }
-        const std::string pn[2] = {p[0] + ".downsample.norm", p[1] + ".downsample.norm"};
-        const std::string prd[2] = {p[0] + ".downsample.reduction", p[1] + ".downsample.reduction"};
+        const std::string pn[2] = {p[0] + ".downsample.norm", p[nm - 1] + ".downsample.norm"};
+        const std::string prd[2] = {p[0] + ".downsample.reduction", p[nm - 1] + ".downsample.reduction"};
         const Epi none[2];
         if (down == 1) {
             Act g4[2], t[2];
-            for (int m = 0; m < 2; ++m) {
+            for (int m = 0; m < nm; ++m) {
                 g4[m] = alloc(x[m].n, x[m].h / 2, x[m].w / 2, 4 * x[m].c);
                 if (!dry() && !rc) {
                     const int r = launch_patch_merge_gather(x[m].p, x[m].n, x[m].h, x[m].w, x[m].c, x[m].cs, g4[m].p, g4[m].cs, s);
                     if (r) fail(r);
                 }
             }
-            layernorm2(pn, g4, t);
-            conv2(2, prd, t, 1, 0, none, nullptr, out);
+            layernorm2(nm, pn, g4, t);
+            conv2(nm, prd, t, 1, 0, none, nullptr, out);
             return;
         }
         if (down == 2) {
             Act t[2], r2[2];
-            layernorm2(pn, x, t);
-            conv2(2, prd, t, 1, 0, none, nullptr, r2);
-            for (int m = 0; m < 2; ++m) {
+            layernorm2(nm, pn, x, t);
+            conv2(nm, prd, t, 1, 0, none, nullptr, r2);
+            for (int m = 0; m < nm; ++m) {
                 out[m] = alloc(x[m].n, 2 * x[m].h, 2 * x[m].w, x[m].c / 2);
                 if (!dry() && !rc) {
                     const int r = launch_pixel_shuffle2(r2[m].p, x[m].n, x[m].h, x[m].w, x[m].c / 2, r2[m].cs, out[m].p, out[m].cs, s);
@@ -2324,7 +2335,7 @@ struct rgbd_elic {
                                        root + ".depth_" + kind + "_layers." + std::to_string(li)};
             const Act xin[2] = {r, d};
             Act o[2];
-            basic_layer2(pl, xin, depths[i], heads[i], dn, o);
+            basic_layer2(2, pl, xin, depths[i], heads[i], dn, o);
             r = o[0];
             d = o[1];
             ++li;
@@ -2618,6 +2629,156 @@ struct rgbd_elic {
             arena.top = mark;
         }
     }
+    // ---- single-modal STF (models/stf.py:408-816): the Swin transforms without the cross-modal fusion, and the channel-slice
+    // entropy model: 12 raster slices of 32 channels, two hyper-synthesis nets, per slice two parameter nets and latent
+    // residual prediction (LRP) -------------------------------------------------------------------------------------
+    static constexpr int kStfSlices = 12, kStfSliceCh = 32, kStfSupport = 6;  // num_slices, M / num_slices, max_support_slices
+    Act swin_stack1(const std::string& root, const Act& x_in, const int* depths, const int* heads, int down)
+    {
+        Act x[2] = {x_in, Act()};
+        for (int i = 0; i < 4; ++i) {
+            const std::string pl[2] = {root + "." + std::to_string(i), std::string()};
+            Act o[2];
+            basic_layer2(1, pl, x, depths[i], heads[i], i < 3 ? down : 0, o);
+            x[0] = o[0];
+        }
+        return x[0];
+    }
+    // stf.py:704-713
+    Act g_a_stf1(const Act& img)
+    {
+        static const int depths[4] = {2, 2, 6, 2}, heads[4] = {3, 6, 12, 24};
+        return swin_stack1("layers", layernorm("patch_embed.norm", conv("patch_embed.proj", img, 2, 0)), depths, heads, 1);
+    }
+    // stf.py:809-815 (end_conv: 5x5 conv, PixelShuffle(2), 3x3 conv)
+    Act g_s_stf1(const Act& yhat)
+    {
+        static const int depths[4] = {2, 6, 2, 2}, heads[4] = {24, 12, 6, 3};
+        const Act r = swin_stack1("syn_layers", yhat, depths, heads, 2);
+        const Act t = conv("end_conv.0", r, 1, 2);
+        Act u = alloc(t.n, 2 * t.h, 2 * t.w, t.c / 4);
+        if (!dry() && !rc) {
+            const int q = launch_pixel_shuffle2(t.p, t.n, t.h, t.w, t.c / 4, t.cs, u.p, u.cs, s);
+            if (q) fail(q);
+        }
+        return conv("end_conv.2", u, 1, 1);
+    }
+    // stf.py:507-517: five 3x3 convolutions (the third and the fifth with stride 2), GELU between them
+    Act h_a_stf1(const Act& y)
+    {
+        static const int strides[5] = {1, 1, 2, 1, 2};
+        Epi gelu;
+        gelu.act = ACT_GELU;
+        Act t = y;
+        for (int k = 0; k < 5; ++k) t = conv("h_a." + std::to_string(2 * k), t, strides[k], 1, k < 4 ? gelu : Epi());
+        return t;
+    }
+    // stf.py:519-540: h_mean_s and h_scale_s have the same layer shapes on the same input: ONE grouped launch per layer.
+    // subpel_conv3x3 = 3x3 conv to 4 C channels + PixelShuffle(2); the GELU behind it is pointwise, so it rides in the conv's
+    // epilogue.  The last layers write the first 384 channels of the two context buffers.
+    void h_s_stf1(const Act& zhat, const Act& means_dst, const Act& scales_dst)
+    {
+        Epi gelu[2];
+        gelu[0].act = gelu[1].act = ACT_GELU;
+        const Epi none[2];
+        auto names = [](const char* suf, std::string n[2]) {
+            n[0] = std::string("h_mean_s.") + suf;
+            n[1] = std::string("h_scale_s.") + suf;
+        };
+        std::string n[2];
+        Act x[2] = {zhat, zhat}, t[2];
+        static const char* const layer[4] = {"0", "2.0", "4", "6.0"};
+        for (int k = 0; k < 4; ++k) {
+            names(layer[k], n);
+            conv2(2, n, x, 1, 1, gelu, nullptr, t);
+            if (k & 1) {
+                for (int m = 0; m < 2; ++m) {
+                    x[m] = alloc(t[m].n, 2 * t[m].h, 2 * t[m].w, t[m].c / 4);
+                    if (!dry() && !rc) {
+                        const int q = launch_pixel_shuffle2(t[m].p, t[m].n, t[m].h, t[m].w, t[m].c / 4, t[m].cs, x[m].p, x[m].cs, s);
+                        if (q) fail(q);
+                    }
+                }
+            } else {
+                x[0] = t[0];
+                x[1] = t[1];
+            }
+        }
+        names("8", n);
+        const Act* dst[2] = {&means_dst, &scales_dst};
+        conv2(2, n, x, 1, 1, none, dst, t);
+    }
+
+    ScaleTab scale_tab{};  // host copy of the Gaussian scale table: the slice kernels take it by value
+
+    // one slice through the coder's side of the loop: symbols / indexes (encode), indexes + rANS + dequantise (decode) or
+    // quantise + likelihood (forward); the pre-LRP y_hat lands in `slot`
+    void code_slice(Coding& cd, int i, const Act& mu, const Act& sg, const Act& y_slice, const Act& slot)
+    {
+        if (dry() || rc) return;
+        SliceGeom g{};
+        g.B = mu.n;
+        g.h = mu.h;
+        g.w = mu.w;
+        g.C = kStfSliceCh;
+        g.per_image = cd.per_image;
+        const int64_t slice_off = (int64_t)i * g.C * g.h * g.w;
+        int r;
+        if (cd.estimate) {
+            const Act lk = view(cd.lik[0], i * g.C, g.C);
+            r = launch_slice_estimate(y_slice.p, y_slice.cs, mu.p, mu.cs, sg.p, sg.cs, g, lk.p, lk.cs, slot.p, slot.cs, nullptr, 0, s);
+        } else if (cd.encode) {
+            r = launch_slice_encode(y_slice.p, y_slice.cs, mu.p, mu.cs, sg.p, sg.cs, scale_tab, g, cd.sym, cd.idx, cd.stream_base,
+                                    slice_off, slot.p, slot.cs, nullptr, 0, s, dbg_x, dbg_s);
+        } else {
+            r = launch_slice_index(sg.p, sg.cs, scale_tab, g, cd.idx, cd.stream_base, slice_off, s);
+            const int64_t count = (int64_t)g.C * g.h * g.w * (cd.per_image ? 1 : g.B);
+            if (!r)
+                r = launch_rans_decode(cd.words, cd.stream_off, cd.stream_len, cd.nstreams, cd.state, cd.first[0] ? 1 : 0, cd.idx,
+                                       cd.sym, cd.stream_base, cd.per_image ? slice_off : slice_off * g.B, count, tables[0].d, s);
+            cd.first[0] = false;
+            if (!r) r = launch_slice_decode(mu.p, mu.cs, g, cd.sym, cd.stream_base, slice_off, slot.p, slot.cs, nullptr, 0, s);
+        }
+        if (r) fail(r);
+    }
+
+    // stf.py:735-758 / 786-807 / 647-667.  ctxm = [latent_means 384 | 7 x 32], ctxs = [latent_scales 384 | 6 x 32 (+ 32 unused:
+    // the two buffers share one channel stride so that the nets' first layers pair)]: slice i's pre-LRP y_hat goes to slot
+    // min(i, 6) of ctxm, the LRP net reads the prefix up to and including that slot, the LRP update finalises slots 0..5 in
+    // both buffers and slice i of yhat; the parameter nets of slice i read the prefix of min(i, 6) slots.  No concatenation.
+    void slice_loop(Coding& cd, const Act* y, const Act& ctxm, const Act& ctxs, const Act& yhat)
+    {
+        const int C = kStfSliceCh, M0 = M;
+        Epi gelu[2];
+        gelu[0].act = gelu[1].act = ACT_GELU;
+        const Epi none[2];
+        for (int i = 0; i < kStfSlices; ++i) {
+            const size_t mark = arena.top;
+            const int k = std::min(i, kStfSupport), sup = M0 + C * k;
+            const std::string si = std::to_string(i);
+            Act x[2] = {view(ctxm, 0, sup), view(ctxs, 0, sup)}, t[2];
+            for (int l = 0; l < 5; ++l) {  // cc_mean_transforms[i] and cc_scale_transforms[i]: one grouped launch per layer
+                const std::string n[2] = {"cc_mean_transforms." + si + "." + std::to_string(2 * l),
+                                          "cc_scale_transforms." + si + "." + std::to_string(2 * l)};
+                conv2(2, n, x, 1, 1, l < 4 ? gelu : none, nullptr, t);
+                x[0] = t[0];
+                x[1] = t[1];
+            }
+            const Act slot = view(ctxm, sup, C);
+            code_slice(cd, i, x[0], x[1], y ? view(*y, i * C, C) : Act(), slot);
+            Act l1 = view(ctxm, 0, sup + C);
+            for (int l = 0; l < 5; ++l) l1 = conv("lrp_transforms." + si + "." + std::to_string(2 * l), l1, 1, 1, l < 4 ? gelu[0] : Epi());
+            if (!dry() && !rc) {
+                const Act out = view(yhat, i * C, C), sslot = view(ctxs, sup, C);
+                const bool ctx = i < kStfSupport;  // later slices are nobody's context
+                const int r = launch_lrp_update(l1.p, l1.cs, slot.p, slot.cs, (size_t)slot.n * slot.h * slot.w, C, out.p, out.cs,
+                                                ctx ? slot.p : nullptr, slot.cs, ctx ? sslot.p : nullptr, sslot.cs, s);
+                if (r) fail(r);
+            }
+            arena.top = mark;
+        }
+    }
+
     // ---- stream I/O of the call paths (engine.hip), for nm = 1 (single-modal ELIC) or 2 modalities ----------------------
     // workspace of a compress call: symbols, indexes and stream slots of every modality, and the stream geometry
     struct EncBufs {
@@ -2651,6 +2812,11 @@ struct rgbd_elic {
     int run_forward1(const float* x_dev, int B, int H, int W, float* xhat_dev, float* ly, float* lz);
     int run_decompress1(const uint8_t* const* ys, const int64_t* ylen, int n_y, const uint8_t* const* zs, const int64_t* zlen,
                         int B, int zh, int zw, float* x_out);
+    // the single-modal STF (variant 4) behind the same entry points
+    int run_compress_stf1(const float* x_dev, int B, int H, int W, int per_image);
+    int run_forward_stf1(const float* x_dev, int B, int H, int W, float* xhat_dev, float* ly, float* lz);
+    int run_decompress_stf1(const uint8_t* const* ys, const int64_t* ylen, int n_y, const uint8_t* const* zs, const int64_t* zlen,
+                            int B, int zh, int zw, float* x_out);
 
     // lat != nullptr: the Bi-CEE stage alone (compress_united / decompress_united): latents and hyper parameters come
     // from the caller as NCHW device tensors, the transforms and the z path are skipped

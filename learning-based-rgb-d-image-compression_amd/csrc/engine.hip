@@ -769,3 +769,226 @@ int rgbd_elic::run_decompress1(const uint8_t* const* ys, const int64_t* ylen, in
     // ==== epilogue (never captured)
     return launch_nhwc_to_nchw_clamp(xh.p, B, in_ch, H, W, xh.cs, x_out, 0, s);  // elic.py:318-325: not clamped
 }
+
+// ---- single-modal STF (models/stf.py): compress :703-764, decompress :766-816, eval-mode forward :618-678 ---------------
+// The y stream is ONE stream for all slices of all images of the call (per-image streams: one per image), coded after the
+// last slice; the decoder resumes its rANS state slice by slice.  A batch decompresses as the inverse of compress() (the
+// reference's decompress handles one image only, stf.py:799).
+int rgbd_elic::run_compress_stf1(const float* x_dev, int B, int H, int W, int per_image)
+{
+    const int h = H / 16, w = W / 16, zh = H / 64, zw = W / 64;
+    const int64_t T = (int64_t)M * h * w, Tz = (int64_t)N * zh * zw;
+    ref_batch = per_image ? 1 : B;
+    named.clear();
+    pre_leads.clear();
+    arena.reset();
+    rc = 0;
+    EncBufs e;
+    if (const int r = enc_streams(1, B, T, Tz, per_image, &e)) return r;
+    Act x = alloc(B, H, W, in_ch);
+    if (!dry()) {
+        const int r = launch_nchw_to_nhwc16(x_dev, B, in_ch, H, W, x.p, x.cs, s);
+        if (r) return r;
+    }
+    // ==== body: captured into / replayed from a HIP graph per call shape ================================================
+    if (body_begin()) {
+        if (!dry()) {
+            const int zr = launch_fill_zero((float*)e.err, 64, s);  // (a kernel, not a memset node: DESIGN 3.5)
+            if (zr) fail(zr);
+        }
+        Act y = alloc(B, h, w, M);
+        {
+            const size_t mark = arena.top;
+            copy_ch(g_a_stf1(x), y);
+            arena.top = mark;
+        }
+        Act z = h_a_stf1(y);
+        named["y"] = y;
+        named["z"] = z;
+        Act zhat = alloc(B, zh, zw, N);
+        float* md = dense_of("entropy_bottleneck.medians");
+        if (!dry() && !rc && md) {
+            int r = launch_z_quant(z.p, z.cs, B, zh, zw, N, md, e.zsym, e.zidx, s, 0);
+            if (!r)
+                r = launch_rans_encode(e.zsym, e.zidx, e.meta + 2 * B, e.meta + 3 * B, B, B, tables[2].d, tables[2].d, e.zwords,
+                                       e.zcap, e.meta + 6 * B, e.err, s);
+            if (!r) r = launch_z_dequant(e.zsym, B, zh, zw, N, md, zhat.p, zhat.cs, s, 0);
+            if (r) fail(r);
+        }
+        named["zhat"] = zhat;
+        const int wide = M + (kStfSupport + 1) * kStfSliceCh;
+        Act ctxm = alloc(B, h, w, wide), ctxs = alloc(B, h, w, wide), yhat = alloc(B, h, w, M);
+        {
+            const size_t mark = arena.top;
+            h_s_stf1(zhat, view(ctxm, 0, M), view(ctxs, 0, M));
+            arena.top = mark;
+        }
+        named["latent_means"] = view(ctxm, 0, M);
+        named["latent_scales"] = view(ctxs, 0, M);
+        named["yhat"] = yhat;
+        Coding cd;
+        cd.encode = true;
+        cd.per_image = per_image;
+        cd.per_image_total = T;
+        cd.sym = e.sym;
+        cd.idx = e.idx;
+        cd.stream_base = e.meta;
+        slice_loop(cd, &y, ctxm, ctxs, yhat);
+        if (!dry() && !rc) {
+            const int ny = e.ny;
+            const int r = launch_rans_encode(e.sym, e.idx, e.meta + 8 * B, e.meta + 8 * B + ny, ny, ny, tables[0].d, tables[0].d,
+                                             e.ywords, e.ycap, e.meta + 8 * B + 2 * ny, e.err, s);
+            if (r) fail(r);
+        }
+    }  // body
+    {
+        const int r = body_end();
+        if (rc) return rc;
+        if (r) return r;
+    }
+    if (dry()) return RGBD_OK;
+    return fetch_streams(1, B, true, e);
+}
+
+int rgbd_elic::run_forward_stf1(const float* x_dev, int B, int H, int W, float* xhat_dev, float* ly, float* lz)
+{
+    const int h = H / 16, w = W / 16, zh = H / 64, zw = W / 64;
+    ref_batch = B;
+    named.clear();
+    pre_leads.clear();
+    arena.reset();
+    rc = 0;
+    dbg_sym = dbg_idx = nullptr;  // forward() keeps no symbols: the last compress()'s are gone with its workspace layout
+    dbg_x = dbg_s = nullptr;
+    Act x = alloc(B, H, W, in_ch);
+    if (!dry()) {
+        const int r = launch_nchw_to_nhwc16(x_dev, B, in_ch, H, W, x.p, x.cs, s);
+        if (r) return r;
+    }
+    Act xh, lik, zlik;
+    if (body_begin()) {
+        Act y = alloc(B, h, w, M);
+        {
+            const size_t mark = arena.top;
+            copy_ch(g_a_stf1(x), y);
+            arena.top = mark;
+        }
+        Act z = h_a_stf1(y);
+        Act zhat = alloc(B, zh, zw, N);
+        zlik = alloc(B, zh, zw, N);
+        if (!dry() && !rc) {
+            float* md = dense_of("entropy_bottleneck.medians");
+            float* prm = dense_of("entropy_bottleneck.cumulative");
+            if (md && prm) {
+                const int r = launch_eb_forward(z.p, z.cs, B, zh, zw, N, md, prm, zhat.p, zlik.p, s, 0);
+                if (r) fail(r);
+            }
+        }
+        const int wide = M + (kStfSupport + 1) * kStfSliceCh;
+        Act ctxm = alloc(B, h, w, wide), ctxs = alloc(B, h, w, wide), yhat = alloc(B, h, w, M);
+        {
+            const size_t mark = arena.top;
+            h_s_stf1(zhat, view(ctxm, 0, M), view(ctxs, 0, M));
+            arena.top = mark;
+        }
+        Coding cd;
+        cd.estimate = true;
+        cd.lik[0] = alloc(B, h, w, M);
+        slice_loop(cd, &y, ctxm, ctxs, yhat);
+        named["y"] = y;
+        named["z"] = z;
+        named["zhat"] = zhat;
+        named["latent_means"] = view(ctxm, 0, M);
+        named["latent_scales"] = view(ctxs, 0, M);
+        named["yhat"] = yhat;
+        xh = g_s_stf1(yhat);
+        lik = cd.lik[0];
+        if (cur_ge && !dry()) {
+            cur_ge->out[0] = xh;
+            cur_ge->out[1] = lik;
+            cur_ge->out[2] = zlik;
+        }
+    } else {
+        xh = cur_ge->out[0];
+        lik = cur_ge->out[1];
+        zlik = cur_ge->out[2];
+    }
+    {
+        const int r = body_end();
+        if (rc) return rc;
+        if (r) return r;
+    }
+    if (dry()) return RGBD_OK;
+    int r = launch_nhwc_to_nchw_clamp(xh.p, B, in_ch, H, W, xh.cs, xhat_dev, 0, s);  // stf.py:677: not clamped
+    if (!r) r = launch_nhwc_to_nchw_clamp(lik.p, B, M, h, w, lik.cs, ly, 0, s, 0);
+    if (!r) r = launch_nhwc_to_nchw_clamp(zlik.p, B, N, zh, zw, zlik.cs, lz, 0, s, 0);
+    if (!r) r = wait_stream();
+    return r;
+}
+
+int rgbd_elic::run_decompress_stf1(const uint8_t* const* ys, const int64_t* ylen, int n_y, const uint8_t* const* zs,
+                                   const int64_t* zlen, int B, int zh, int zw, float* x_out)
+{
+    const int h = zh * 4, w = zw * 4, H = zh * 64, W = zw * 64;
+    const int64_t T = (int64_t)M * h * w, Tz = (int64_t)N * zh * zw;
+    const int per_image = (n_y == B) ? 1 : 0;
+    ref_batch = per_image ? 1 : B;
+    named.clear();
+    pre_leads.clear();
+    arena.reset();
+    rc = 0;
+
+    // ==== prologue (never captured): upload the streams
+    DecBufs d;
+    if (const int r = dec_streams(1, &ys, &ylen, n_y, &zs, &zlen, B, B, T, Tz, per_image, &d)) return r;
+
+    // ==== body: captured into / replayed from a HIP graph per call shape ================================================
+    Act xh;
+    if (body_begin()) {
+        Act zhat = alloc(B, zh, zw, N);
+        float* md = dense_of("entropy_bottleneck.medians");
+        if (!dry() && md) {
+            int q = launch_fill_zero(zhat.p, zhat.elems(), s);
+            if (!q) q = launch_z_quant(zhat.p, zhat.cs, B, zh, zw, N, md, d.zsym, d.zidx, s, 0);  // indexes = channel id
+            if (!q) q = launch_rans_decode(d.words, d.zoff, d.zlen, B, d.zstate, 1, d.zidx, d.zsym, d.zbase, 0, Tz, tables[2].d, s);
+            if (!q) q = launch_z_dequant(d.zsym, B, zh, zw, N, md, zhat.p, zhat.cs, s, 0);
+            if (q) fail(q);
+        }
+        named["zhat"] = zhat;
+        const int wide = M + (kStfSupport + 1) * kStfSliceCh;
+        Act ctxm = alloc(B, h, w, wide), ctxs = alloc(B, h, w, wide), yhat = alloc(B, h, w, M);
+        {
+            const size_t mark = arena.top;
+            h_s_stf1(zhat, view(ctxm, 0, M), view(ctxs, 0, M));
+            arena.top = mark;
+        }
+        named["latent_means"] = view(ctxm, 0, M);
+        named["latent_scales"] = view(ctxs, 0, M);
+        named["yhat"] = yhat;
+        Coding cd;
+        cd.encode = false;
+        cd.per_image = per_image;
+        cd.per_image_total = T;
+        cd.sym = d.sym;
+        cd.idx = d.idx;
+        cd.stream_base = d.ybase;
+        cd.words = d.words;
+        cd.stream_off = d.yoff;
+        cd.stream_len = d.ylen;
+        cd.state = d.state;
+        cd.nstreams = n_y;
+        slice_loop(cd, nullptr, ctxm, ctxs, yhat);
+        xh = g_s_stf1(yhat);
+        if (cur_ge && !dry()) cur_ge->out[0] = xh;
+    } else {
+        xh = cur_ge->out[0];
+    }
+    {
+        const int r = body_end();
+        if (rc) return rc;
+        if (r) return r;
+    }
+    if (dry()) return RGBD_OK;
+    // ==== epilogue (never captured)
+    return launch_nhwc_to_nchw_clamp(xh.p, B, in_ch, H, W, xh.cs, x_out, 1, s);  // stf.py:815: clamped to [0, 1]
+}

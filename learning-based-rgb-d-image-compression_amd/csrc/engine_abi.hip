@@ -552,17 +552,32 @@ int rgbd_elic_create_single(int32_t N, int32_t M, const int32_t* slice_ch, int32
     return RGBD_OK;
 }
 
+int rgbd_elic_create_stf_single(int32_t in_ch, rgbd_elic** out)
+{
+    if (in_ch < 1 || in_ch > 16) return RGBD_EINVAL;
+    int32_t slices[rgbd_elic::kStfSlices];
+    for (int32_t& c : slices) c = rgbd_elic::kStfSliceCh;
+    const int r = rgbd_elic_create(192, rgbd_elic::kStfSlices * rgbd_elic::kStfSliceCh, slices, rgbd_elic::kStfSlices, out);  // stf.py:431,418
+    if (r) return r;
+    (*out)->variant = 4;
+    (*out)->in_ch = in_ch;
+    (*out)->refnum = false;  // (the STF family keeps the single-chain arithmetic, as STF_united)
+    return RGBD_OK;
+}
+
 int rgbd_elic_compress_single(rgbd_elic* m, const float* x_dev, int32_t B, int32_t H, int32_t W, int32_t per_image_streams,
                               void* stream)
 {
     int r = check_ready(m);
     if (r) return r;
-    if (m->variant != 1 || !x_dev || B <= 0 || H <= 0 || W <= 0 || H % 64 || W % 64) return RGBD_EINVAL;
+    if (!m->single() || !x_dev || B <= 0 || H <= 0 || W <= 0 || H % 64 || W % 64) return RGBD_EINVAL;
     if (const int ur = m->use_stream(stream)) return ur;
     const int per_image = (per_image_streams || B == 1) ? 1 : 0;
     char key[96];
     snprintf(key, sizeof(key), "c1|%d|%d|%d|%d", B, H, W, per_image);
-    r = run_sized(m, key, [&]() { return m->run_compress1(x_dev, B, H, W, per_image); });
+    r = run_sized(m, key, [&]() {
+        return m->variant == 4 ? m->run_compress_stf1(x_dev, B, H, W, per_image) : m->run_compress1(x_dev, B, H, W, per_image);
+    });
     if (m->profile) m->profile_collect();
     return r;
 }
@@ -572,12 +587,15 @@ int rgbd_elic_forward_single(rgbd_elic* m, const float* x_dev, int32_t B, int32_
 {
     int r = check_ready(m);
     if (r) return r;
-    if (m->variant != 1 || !x_dev || !xhat_dev || !lik_y || !lik_z || B <= 0 || H <= 0 || W <= 0 || H % 64 || W % 64)
+    if (!m->single() || !x_dev || !xhat_dev || !lik_y || !lik_z || B <= 0 || H <= 0 || W <= 0 || H % 64 || W % 64)
         return RGBD_EINVAL;
     if (const int ur = m->use_stream(stream)) return ur;
     char key[96];
     snprintf(key, sizeof(key), "f1|%d|%d|%d", B, H, W);
-    return run_sized(m, key, [&]() { return m->run_forward1(x_dev, B, H, W, xhat_dev, lik_y, lik_z); });
+    return run_sized(m, key, [&]() {
+        return m->variant == 4 ? m->run_forward_stf1(x_dev, B, H, W, xhat_dev, lik_y, lik_z)
+                               : m->run_forward1(x_dev, B, H, W, xhat_dev, lik_y, lik_z);
+    });
 }
 
 int rgbd_elic_decompress_single(rgbd_elic* m, const uint8_t* const* y, const int64_t* y_len, int32_t n_y,
@@ -586,12 +604,15 @@ int rgbd_elic_decompress_single(rgbd_elic* m, const uint8_t* const* y, const int
 {
     int r = check_ready(m);
     if (r) return r;
-    if (m->variant != 1 || !y || !y_len || !z || !z_len || !x_dev || B <= 0 || zh <= 0 || zw <= 0) return RGBD_EINVAL;
+    if (!m->single() || !y || !y_len || !z || !z_len || !x_dev || B <= 0 || zh <= 0 || zw <= 0) return RGBD_EINVAL;
     if (n_y != 1 && n_y != B) return RGBD_EINVAL;
     if (const int ur = m->use_stream(stream)) return ur;
     char key[96];
     snprintf(key, sizeof(key), "d1|%d|%d|%d|%d", B, zh, zw, n_y);
-    r = run_sized(m, key, [&]() { return m->run_decompress1(y, y_len, n_y, z, z_len, B, zh, zw, x_dev); });
+    r = run_sized(m, key, [&]() {
+        return m->variant == 4 ? m->run_decompress_stf1(y, y_len, n_y, z, z_len, B, zh, zw, x_dev)
+                               : m->run_decompress1(y, y_len, n_y, z, z_len, B, zh, zw, x_dev);
+    });
     if (!r) r = m->wait_stream();  // (the work may sit on the engine's own stream: return when x_hat is there)
     if (m->profile && !r) m->profile_collect();
     return r;
@@ -614,6 +635,7 @@ int rgbd_elic_clone_shared(const rgbd_elic* src, rgbd_elic** out)
     m->gen_w = src->gen_w;
     for (int i = 0; i < 4; ++i) m->tables[i] = src->tables[i];
     m->scale_table = src->scale_table;
+    m->scale_tab = src->scale_tab;
     m->gen_scale = src->gen_scale;
     m->finalized = true;
     m->is_clone = true;
@@ -696,6 +718,7 @@ int rgbd_elic_set_scale_table(rgbd_elic* m, const float* table, int32_t n)
     g->p.push_back(d);
     HIP_TRY(hipMemcpy(d, table, 64 * sizeof(float), hipMemcpyHostToDevice));
     m->scale_table = d;
+    memcpy(m->scale_tab.v, table, sizeof(m->scale_tab.v));
     m->gen_scale = g;
     m->graphs_invalidate();
     return RGBD_OK;
@@ -870,7 +893,7 @@ static int check_ready(const rgbd_elic* m)
 {
     if (!m || !m->finalized || !m->scale_table) return RGBD_ESTATE;
     for (int i = 0; i < 4; ++i)
-        if (!m->tables[i].ready && !(m->variant == 1 && (i & 1))) return RGBD_ESTATE;  // single-modal: slots 0 and 2
+        if (!m->tables[i].ready && !(m->single() && (i & 1))) return RGBD_ESTATE;  // single-modal: slots 0 and 2
     return RGBD_OK;
 }
 
@@ -1083,7 +1106,7 @@ int rgbd_elic_set_forced_symbols(rgbd_elic* m, int32_t modality, const int32_t* 
 {
     std::unique_lock<std::shared_mutex> cap_lk(g_capture_mu);
     if (!m || modality < 0 || modality > 1 || n_y < 0 || n_z < 0 || (n_y && !y_sym) || (n_z && !z_sym)) return RGBD_EINVAL;
-    if (m->variant == 1) return RGBD_EINVAL;  // (the two-modality codecs only)
+    if (m->single()) return RGBD_EINVAL;  // (the two-modality codecs only)
     m->graphs_invalidate();  // the workspace layout and the launch list change
     m->force_y[modality].assign(y_sym, y_sym + n_y);
     m->force_z[modality].assign(z_sym, z_sym + n_z);
@@ -1094,7 +1117,7 @@ int rgbd_elic_debug_floats(rgbd_elic* m, int32_t modality, float* x, float* scal
 {
     std::unique_lock<std::shared_mutex> cap_lk(g_capture_mu);  // frees / synchronous copies: not while a stream captures
     if (!m || !n || modality < 0 || modality > 1 || !m->dbg_x || !m->dbg_s) return RGBD_EINVAL;
-    if (m->variant == 1 && modality != 0) return RGBD_EINVAL;  // the single-modal model keeps one modality's floats
+    if (m->single() && modality != 0) return RGBD_EINVAL;  // the single-modal models keep one modality's floats
     *n = m->dbg_per_mod;
     if (!x || !scale) return RGBD_OK;
     if (cap < m->dbg_per_mod) return RGBD_ENOSPC;

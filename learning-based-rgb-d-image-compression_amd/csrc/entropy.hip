@@ -11,6 +11,7 @@
 #include <mutex>
 
 #include "common.h"
+#include "exact_math.h"
 
 #define PROB_BITS 16
 #define ESC_BITS 4
@@ -156,6 +157,156 @@ int launch_ckbd_estimate_part(const float* y, int ycs, const float* params, int 
     if (g.w % 2) return RGBD_EINVAL;
     hipLaunchKernelGGL(ckbd_estimate_kernel, dim3(part_grid(g)), dim3(256), 0, s, y, ycs, params, pcs, yhat, yhcs, lik, lcs,
                        g);
+    HIP_TRY(hipGetLastError());
+    return RGBD_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Raster channel slices (single-modal STF, models/stf.py:723-764, 786-807, 647-667): a slice of g.C channels of NHWC tensors,
+// mean and scale from two different tensors (two nets), no checkerboard.  Stream order: slice-major; inside a slice
+// (b, c, row, col) (stf.py:750-751), or with per_image (c, row, col) in image b's own stream.  slice_off = symbols of one
+// image's earlier slices.  The pre-LRP y_hat goes to d0 and, when given, d1.
+// mode 0: encode (quantise + index + y_hat), 1: index only, 2: decode (y_hat = symbol + mean)
+__device__ __forceinline__ int64_t slice_pos(const SliceGeom& g, const int64_t* stream_base, int64_t slice_off, int b, int c,
+                                             int row, int col)
+{
+    const int64_t in = ((int64_t)c * g.h + row) * g.w + col;
+    if (g.per_image) return (stream_base ? stream_base[b] : (int64_t)b * g.image_stride) + slice_off + in;
+    return (stream_base ? stream_base[0] : 0) + slice_off * g.B + (int64_t)b * g.C * g.h * g.w + in;
+}
+
+template <int MODE>
+__global__ void slice_part_kernel(const float* __restrict__ y, int ycs, const float* __restrict__ mu, int mcs,
+                                  const float* __restrict__ sg, int scs, ScaleTab table, SliceGeom g, int32_t* __restrict__ sym,
+                                  int32_t* __restrict__ idx, const int64_t* __restrict__ stream_base, int64_t slice_off,
+                                  float* __restrict__ d0, int d0cs, float* __restrict__ d1, int d1cs,
+                                  float* __restrict__ dbg_x = nullptr, float* __restrict__ dbg_s = nullptr)
+{
+    __shared__ float tbl[64];
+    if (threadIdx.x < 64) tbl[threadIdx.x] = table.v[threadIdx.x];
+    __syncthreads();
+    const size_t total = (size_t)g.B * g.h * g.w * g.C;
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        const int c = (int)(i % g.C);
+        const size_t pix = i / g.C;
+        const int col = (int)(pix % g.w);
+        const int row = (int)((pix / g.w) % g.h);
+        const int b = (int)(pix / ((size_t)g.w * g.h));
+        const int64_t pos = slice_pos(g, stream_base, slice_off, b, c, row, col);
+        if (MODE == 1) {
+            idx[pos] = scale_to_index(tbl, sg[pix * scs + c]);  // build_indexes on the raw net output
+            continue;
+        }
+        const float mean = mu[pix * mcs + c];
+        float out;
+        if (MODE == 0) {
+            const float xm = y[pix * ycs + c] - mean;
+            const int s = (int)rintf(xm);  // round half to even, like torch.round
+            if (dbg_x) {  // rgbd_elic_set_debug_floats: the rounded value and the indexed scale, in stream order
+                dbg_x[pos] = xm;
+                dbg_s[pos] = sg[pix * scs + c];
+            }
+            sym[pos] = s;
+            idx[pos] = scale_to_index(tbl, sg[pix * scs + c]);
+            out = (float)s + mean;
+        } else {
+            out = (float)sym[pos] + mean;
+        }
+        d0[pix * d0cs + c] = out;
+        if (d1) d1[pix * d1cs + c] = out;
+    }
+}
+
+static inline unsigned slice_grid(const SliceGeom& g)
+{
+    const size_t n = ((size_t)g.B * g.h * g.w * g.C + 255) / 256;
+    return (unsigned)(n < 1 ? 1 : (n > 2048 ? 2048 : n));
+}
+
+int launch_slice_encode(const float* y, int ycs, const float* mu, int mcs, const float* sg, int scs, const ScaleTab& table,
+                        SliceGeom g, int32_t* sym, int32_t* idx, const int64_t* stream_base, int64_t slice_off, float* d0,
+                        int d0cs, float* d1, int d1cs, hipStream_t s, float* dbg_x, float* dbg_s)
+{
+    hipLaunchKernelGGL(slice_part_kernel<0>, dim3(slice_grid(g)), dim3(256), 0, s, y, ycs, mu, mcs, sg, scs, table, g, sym, idx,
+                       stream_base, slice_off, d0, d0cs, d1, d1cs, dbg_x, dbg_s);
+    HIP_TRY(hipGetLastError());
+    return RGBD_OK;
+}
+
+int launch_slice_index(const float* sg, int scs, const ScaleTab& table, SliceGeom g, int32_t* idx, const int64_t* stream_base,
+                       int64_t slice_off, hipStream_t s)
+{
+    hipLaunchKernelGGL(slice_part_kernel<1>, dim3(slice_grid(g)), dim3(256), 0, s, (const float*)nullptr, 0, (const float*)nullptr,
+                       0, sg, scs, table, g, (int32_t*)nullptr, idx, stream_base, slice_off, (float*)nullptr, 0, (float*)nullptr, 0,
+                       (float*)nullptr, (float*)nullptr);
+    HIP_TRY(hipGetLastError());
+    return RGBD_OK;
+}
+
+int launch_slice_decode(const float* mu, int mcs, SliceGeom g, const int32_t* sym, const int64_t* stream_base, int64_t slice_off,
+                        float* d0, int d0cs, float* d1, int d1cs, hipStream_t s)
+{
+    hipLaunchKernelGGL(slice_part_kernel<2>, dim3(slice_grid(g)), dim3(256), 0, s, (const float*)nullptr, 0, mu, mcs,
+                       (const float*)nullptr, 0, ScaleTab{}, g, const_cast<int32_t*>(sym), (int32_t*)nullptr, stream_base, slice_off,
+                       d0, d0cs, d1, d1cs, (float*)nullptr, (float*)nullptr);
+    HIP_TRY(hipGetLastError());
+    return RGBD_OK;
+}
+
+// eval-mode forward() (stf.py:657-660): the encoder's quantisation plus the Gaussian likelihood, arithmetic as in
+// ckbd_estimate_kernel (lower_bound_scale 0.11, likelihood_lower_bound 1e-9)
+__global__ void slice_estimate_kernel(const float* __restrict__ y, int ycs, const float* __restrict__ mu, int mcs,
+                                      const float* __restrict__ sg, int scs, SliceGeom g, float* __restrict__ lik, int lcs,
+                                      float* __restrict__ d0, int d0cs, float* __restrict__ d1, int d1cs)
+{
+    const size_t total = (size_t)g.B * g.h * g.w * g.C;
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        const int c = (int)(i % g.C);
+        const size_t pix = i / g.C;
+        const float scale = fmaxf(sg[pix * scs + c], 0.11f);
+        const float mean = mu[pix * mcs + c];
+        const float out = __fadd_rn(rintf(y[pix * ycs + c] - mean), mean);
+        d0[pix * d0cs + c] = out;
+        if (d1) d1[pix * d1cs + c] = out;
+        const float v = fabsf(__fsub_rn(out, mean));
+        const float cst = -0.70710678118654752440f;  // -(2 ** -0.5)
+        const float upper = 0.5f * erfcf(cst * ((0.5f - v) / scale));
+        const float lower = 0.5f * erfcf(cst * ((-0.5f - v) / scale));
+        lik[pix * lcs + c] = fmaxf(upper - lower, 1e-9f);
+    }
+}
+
+int launch_slice_estimate(const float* y, int ycs, const float* mu, int mcs, const float* sg, int scs, SliceGeom g, float* lik,
+                          int lcs, float* d0, int d0cs, float* d1, int d1cs, hipStream_t s)
+{
+    hipLaunchKernelGGL(slice_estimate_kernel, dim3(slice_grid(g)), dim3(256), 0, s, y, ycs, mu, mcs, sg, scs, g, lik, lcs, d0, d0cs,
+                       d1, d1cs);
+    HIP_TRY(hipGetLastError());
+    return RGBD_OK;
+}
+
+// Latent residual prediction (stf.py:753-758): y_hat <- y_hat + 0.5 * tanh(lrp), written to every place the slice lives
+// (d0, and d1 / d2 when given; a destination may be `src` itself: each element is read and written by the thread that owns it)
+__global__ void lrp_update_kernel(const float* __restrict__ lrp, int lcs, const float* src, int scs, size_t npix, int C,
+                                  float* d0, int d0cs, float* d1, int d1cs, float* d2, int d2cs)
+{
+    const size_t total = npix * C;
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        const int c = (int)(i % C);
+        const size_t pix = i / C;
+        const float v = rgbd_lrp_add(src[pix * scs + c], lrp[pix * lcs + c]);
+        d0[pix * d0cs + c] = v;
+        if (d1) d1[pix * d1cs + c] = v;
+        if (d2) d2[pix * d2cs + c] = v;
+    }
+}
+
+int launch_lrp_update(const float* lrp, int lcs, const float* src, int scs, size_t npix, int C, float* d0, int d0cs, float* d1,
+                      int d1cs, float* d2, int d2cs, hipStream_t s)
+{
+    const size_t n = (npix * C + 255) / 256;
+    hipLaunchKernelGGL(lrp_update_kernel, dim3((unsigned)(n < 1 ? 1 : (n > 2048 ? 2048 : n))), dim3(256), 0, s, lrp, lcs, src, scs,
+                       npix, C, d0, d0cs, d1, d1cs, d2, d2cs);
     HIP_TRY(hipGetLastError());
     return RGBD_OK;
 }

@@ -83,3 +83,44 @@ __device__ __forceinline__ float rgbd_sigmoid_ref_scalar(float x)
 {
     return __fdiv_rn(1.0f, __fadd_rn(1.0f, rgbd_expf_libm(-x)));
 }
+
+// Latent residual prediction of the channel-slice entropy model (models/stf.py:755-756): y + 0.5 * tanh(x), in double with
+// explicit fused multiply-adds and ONE rounding to float at the end (<= 0.5 ulp of the RESULT, also where the two terms
+// cancel): the encoder, the decoder and forward() call this one function, so the decoder rebuilds the encoder's y_hat bit for
+// bit whatever the compiler's libm does.  E = exp(-2|x|) by a Cody-Waite reduction (ln 2 in two parts, fdlibm's split) and
+// the degree-13 Taylor polynomial on |r| <= ln 2 / 2; tanh|x| = (1 - E) / (1 + E) (relative error ~2^-50 above 2^-10); below
+// 2^-10 the series x - x^3 / 3 (relative error < 2^-41).
+__device__ __forceinline__ float rgbd_lrp_add(float y, float x)
+{
+    if (x != x) return x;
+    const double a = fabs((double)x);
+    double r;
+    if (a < 0x1p-10) {
+        const double a2 = __dmul_rn(a, a);
+        r = __fma_rn(__dmul_rn(a2, a), -0x1.5555555555555p-2, a);
+    } else if (a > 20.0) {
+        r = 1.0;
+    } else {
+        const double t = __dmul_rn(-2.0, a);
+        const double kd = rint(__dmul_rn(t, 0x1.71547652b82fep+0));
+        double s = __fma_rn(kd, -0x1.62e42fee00000p-1, t);
+        s = __fma_rn(kd, -0x1.a39ef35793c76p-33, s);
+        double u = 0x1.6124613a86d09p-33;             // 1 / 13!
+        u = __fma_rn(u, s, 0x1.1eed8eff8d898p-29);    // 1 / 12!
+        u = __fma_rn(u, s, 0x1.ae64567f544e4p-26);    // 1 / 11!
+        u = __fma_rn(u, s, 0x1.27e4fb7789f5cp-22);    // 1 / 10!
+        u = __fma_rn(u, s, 0x1.71de3a556c734p-19);    // 1 / 9!
+        u = __fma_rn(u, s, 0x1.a01a01a01a01ap-16);    // 1 / 8!
+        u = __fma_rn(u, s, 0x1.a01a01a01a01ap-13);    // 1 / 7!
+        u = __fma_rn(u, s, 0x1.6c16c16c16c17p-10);    // 1 / 6!
+        u = __fma_rn(u, s, 0x1.1111111111111p-7);     // 1 / 5!
+        u = __fma_rn(u, s, 0x1.5555555555555p-5);     // 1 / 4!
+        u = __fma_rn(u, s, 0x1.5555555555555p-3);     // 1 / 3!
+        u = __fma_rn(u, s, 0.5);
+        u = __fma_rn(u, s, 1.0);
+        u = __fma_rn(u, s, 1.0);
+        const double e = __dmul_rn(u, __longlong_as_double((long long)((int)kd + 1023) << 52));  // kd >= -58: a normal number
+        r = __ddiv_rn(__dsub_rn(1.0, e), __dadd_rn(1.0, e));
+    }
+    return __double2float_rn(__fma_rn(x < 0.f ? -0.5 : 0.5, r, (double)y));
+}

@@ -13,8 +13,8 @@ from collections import OrderedDict
 
 import numpy as np
 
-from .arch import (Entry, elic_entries, elic_united_entries, elic_united_r2d_entries, model_config, stf_config,
-                   stf_united_entries)
+from .arch import (STF_SLICES, Entry, elic_entries, elic_united_entries, elic_united_r2d_entries, model_config, stf_config,
+                   stf_entries, stf_single_config, stf_united_entries)
 
 _IH_STD = math.sqrt(4.0 * (65536.0**2 - 1.0) / 12.0)  # std of the sum of four uniform 16-bit ints
 _IH_MEAN = 2.0 * 65535.0
@@ -102,8 +102,8 @@ def make_tensor(name: str, e: Entry, seed: int) -> np.ndarray:
 
 def synthetic_state_dict(seed: int = 0, config=None, stress: bool = True, as_torch: bool = True,
                          model: str = "ELIC_united", channel: int = 3, recipe: str = None):
-    """Full state_dict (parameters + buffers) of ELIC_united (default) or the single-modal ELIC with deterministic
-    synthetic values.  `recipe`: "stress" (= stress=True, the default: ~22 bpp, wide CDF rows, 17 % escapes -- the worst
+    """Full state_dict (parameters + buffers) of ELIC_united (default), ELIC_united_R2D, STF_united, the single-modal STF
+    (model="STF": recipes "stress" and "plain") or the single-modal ELIC with deterministic synthetic values.  `recipe`: "stress" (= stress=True, the default: ~22 bpp, wide CDF rows, 17 % escapes -- the worst
     case for the entropy coder), "trained_like" (ELIC_united only: latents mostly inside the dead zone, scales near the
     bottom of the scale table, ~1 bpp per modality like a trained q=2_2 model -- the coder's realistic operating point),
     "high_rate" (ELIC_united only: latents of tens to hundreds, predicted scales of 10 ... 100 -- scale-table rows of 300 ...
@@ -116,6 +116,9 @@ def synthetic_state_dict(seed: int = 0, config=None, stress: bool = True, as_tor
     if model == "STF_united":
         cfg = stf_config()
         entries = stf_united_entries()
+    elif model == "STF":
+        cfg = stf_single_config()
+        entries = stf_entries(channel)
     else:
         cfg = model_config() if config is None else config
         entries = {"ELIC_united": elic_united_entries, "ELIC_united_R2D": elic_united_r2d_entries}.get(model)
@@ -129,6 +132,8 @@ def synthetic_state_dict(seed: int = 0, config=None, stress: bool = True, as_tor
         _apply_stress(sd, cfg, transforms=False)
         for mod in ("rgb", "depth"):  # latents of a few units: the last patch-merging projection feeds the final stage
             sd[f"g_a.{mod}_ana_layers.4.downsample.reduction.weight"] *= np.float32(STF_Y_GAIN)
+    elif stress and model == "STF":
+        _apply_stress_stf(sd)
     elif stress:
         _apply_stress_single(sd, cfg)
     if recipe == "trained_like":
@@ -212,6 +217,26 @@ def _apply_stress_single(sd, cfg):
         for i, c in enumerate(slice_ch):
             sd[f"{fam}.{i}.fusion.4.weight"] *= np.float32(6.0)
             sd[f"{fam}.{i}.fusion.4.bias"][:c] = np.float32(1.0)  # scale half
+
+
+# single-modal STF: y, z, hyper means / scales, scale head (weight, bias), mean head, LRP head
+STF1_GAINS = {"y": 4.0, "z": 200.0, "hyper": 30.0, "scale_w": 40.0, "scale_b": 1.0, "mean_w": 10.0, "lrp_w": 30.0}
+
+
+def _apply_stress_stf(sd):
+    """At the default initialisation the single-modal STF is degenerate (every z symbol and scale index 0, LRP of a few
+    hundredths).  These gains give latents of a few units, a busy z stream, a dozen or more scale-table rows per slice, means
+    that move the rounding, escape symbols, and an LRP correction of tenths that later slices depend on."""
+    g = {k: np.float32(v) for k, v in STF1_GAINS.items()}
+    sd["layers.2.downsample.reduction.weight"] *= g["y"]  # the last patch-merging projection feeds the final stage
+    sd["h_a.8.weight"] *= g["z"]
+    sd["h_mean_s.8.weight"] *= g["hyper"]
+    sd["h_scale_s.8.weight"] *= g["hyper"]
+    for i in range(STF_SLICES):
+        sd[f"cc_scale_transforms.{i}.8.weight"] *= g["scale_w"]
+        sd[f"cc_scale_transforms.{i}.8.bias"][:] = g["scale_b"]
+        sd[f"cc_mean_transforms.{i}.8.weight"] *= g["mean_w"]
+        sd[f"lrp_transforms.{i}.8.weight"] *= g["lrp_w"]
 
 
 def synthetic_pair(index: int, H: int, W: int, config_id: int = 0, smooth: bool = False):
