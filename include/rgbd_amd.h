@@ -329,6 +329,40 @@ int rgbd_debug_tile_override(const char* csv);
 int rgbd_pointwise_nchw(int32_t op, const float* x_dev, int32_t n, int32_t c, int32_t h, int32_t w, int32_t oh, int32_t ow,
                         const float* w0, const float* w1, float* y_dev, void* stream);
 
+/* The reference-arithmetic pointwise kernels alone (test hooks; tests/test_gpu_refpointwise.py compares each with
+ * oracle/cpu_arith.c bit for bit).  Device tensors are logical NCHW fp32 / vectors in logical channel order, weights and
+ * tables are host pointers; the engine's channel permutation stays inside.  Every argument is checked on the host before
+ * anything is launched: RGBD_EINVAL (-22) for a null pointer, a non-positive size or anything named below.
+ *
+ * rgbd_ref_channel_mean: mean over H x W per (image, channel) as ATen's cascade sum forms it (replaces x.mean((2, 3)) of
+ *   attention.py:63): mean_dev[image * mstride + channel]; only those n x c floats are written.  c % 16 == 0, mstride >= c.
+ * rgbd_ref_linear: y[n][J] = act(x[n][K] . weight[J][K]^T), nn.Linear(bias=False) of SE_Block (attention.py:56-60) in MKL's
+ *   summation orders.  row_class: per output row 0 / 1 / 2 (NULL = all 0), used when form == -1; form 3 = the batch-of-two
+ *   order for every row.  act 0 / 1 / 3.  stage 0 = fc.0 (the input vector is the engine's mean vector: K % 16 == 0),
+ *   stage 1 = fc.2 (the output vector is the engine's gate vector: J % 16 == 0).
+ * rgbd_ref_sigmoid_gate: y = sigmoid(t) [* mul] [+ res], each step one fp32 rounding; the sigmoid of element i of the
+ *   contiguous [n or 1, c, h, w] tensor is the form torch's CPU kernel run by `threads` threads applies there (vector body or
+ *   scalar tail).  per_image 1: every image is a tensor of its own.  mul_dev / res_dev may be NULL.
+ * rgbd_ref_small_conv_nchw: conv2d (k <= 3, stride 1 / 2) on ATen's small-tensor route (im2col + sgemm): kblocks = lengths of the
+ *   K blocks in k = c * k * k + ky * k + kx (at most 16, summing to cin * k * k; NULL = one block); then + res1, act (0..3),
+ *   * mul, + res2.  ckbd 1 / 2 (stride 1 only): only the positions with (row + col) odd / even are computed, the others read 0.
+ *   y2_dev (optional): a second copy of the output.  weight [cout][cin][k][k], bias [cout] or NULL (zeros).
+ * rgbd_ref_deconv_s2_nchw: conv_transpose2d(k 5, stride 2, pad 2, output_padding 1) in oneDNN brg_deconv's order: recipe = 4 * w
+ *   descriptors {ntaps, ntaps x (ky, kx, fresh)} for (phase py * 2 + px, input column), at most 16 taps and 16 chains each,
+ *   every tap of its phase's parity.  weight [cin][cout][5][5]; act 0 / 1 / 2. */
+int rgbd_ref_channel_mean(const float* x_dev, int32_t n, int32_t c, int32_t h, int32_t w, float* mean_dev, int32_t mstride,
+                          void* stream);
+int rgbd_ref_linear(const float* weight, const float* x_dev, int32_t n, int32_t K, int32_t J, const int32_t* row_class, int32_t form,
+                    int32_t act, int32_t stage, float* y_dev, void* stream);
+int rgbd_ref_sigmoid_gate(const float* t_dev, const float* mul_dev, const float* res_dev, int32_t n, int32_t c, int32_t h, int32_t w,
+                          int32_t per_image, int32_t threads, float* y_dev, void* stream);
+int rgbd_ref_small_conv_nchw(const float* x_dev, int32_t n, int32_t cin, int32_t h, int32_t w, const float* weight, const float* bias,
+                             int32_t cout, int32_t k, int32_t stride, int32_t pad, int32_t act, int32_t ckbd, const int32_t* kblocks,
+                             int32_t nkblocks, const float* res1_dev, const float* mul_dev, const float* res2_dev, float* y_dev,
+                             float* y2_dev, void* stream);
+int rgbd_ref_deconv_s2_nchw(const float* x_dev, int32_t n, int32_t cin, int32_t h, int32_t w, const float* weight, const float* bias,
+                            int32_t cout, int32_t act, const int32_t* recipe, int32_t nrecipe, float* y_dev, void* stream);
+
 /* Kernel-only timing of one convolution shape on NHWC scratch buffers (tools/conv_sweep.py, tools/tune_tiles.py): iters launches,
  * *ms_out = milliseconds per launch. */
 int rgbd_conv_bench(int32_t n, int32_t cin, int32_t h, int32_t w, int32_t cout, int32_t k, int32_t stride, int32_t pad,

@@ -97,6 +97,12 @@ def lib():
         "rgbd_conv2d_ref_nchw": (ctypes.c_int, [c_vp, c_i32, c_i32, c_i32, c_i32, f32p, f32p, c_i32, c_i32, c_i32, c_i32,
                                                 c_i32, c_i32, c_vp, c_vp, c_vp, i32p, c_i32, c_i32, c_i32]),
         "rgbd_pointwise_nchw": (ctypes.c_int, [c_i32, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, f32p, f32p, c_vp, c_vp]),
+        "rgbd_ref_channel_mean": (ctypes.c_int, [c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_i32, c_vp]),
+        "rgbd_ref_linear": (ctypes.c_int, [f32p, c_vp, c_i32, c_i32, c_i32, i32p, c_i32, c_i32, c_i32, c_vp, c_vp]),
+        "rgbd_ref_sigmoid_gate": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp]),
+        "rgbd_ref_small_conv_nchw": (ctypes.c_int, [c_vp, c_i32, c_i32, c_i32, c_i32, f32p, f32p, c_i32, c_i32, c_i32, c_i32, c_i32,
+                                                    c_i32, i32p, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+        "rgbd_ref_deconv_s2_nchw": (ctypes.c_int, [c_vp, c_i32, c_i32, c_i32, c_i32, f32p, f32p, c_i32, c_i32, i32p, c_i32, c_vp, c_vp]),
         "rgbd_elic_create": (ctypes.c_int, [c_i32, c_i32, i32p, c_i32, ctypes.POINTER(c_vp)]),
         "rgbd_elic_destroy": (None, [c_vp]),
         "rgbd_elic_set_ref_blocks": (ctypes.c_int, [c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, i32p, c_i32]),
@@ -173,7 +179,8 @@ def lib():
 
 EXPORTS = ["rgbd_abi_version", "rgbd_set_blocking_sync", "rgbd_get_blocking_sync", "rgbd_pmf_to_quantized_cdf", "rgbd_tables_create", "rgbd_tables_destroy",
            "rgbd_rans_max_bytes", "rgbd_rans_encode", "rgbd_rans_decoder_create", "rgbd_rans_decoder_set_stream",
-           "rgbd_rans_decoder_decode", "rgbd_rans_decoder_destroy", "rgbd_rans_encode_batch_dev", "rgbd_rans_decode_batch_dev", "rgbd_ckbd_quant_index", "rgbd_ckbd_dequant", "rgbd_conv2d_nchw", "rgbd_conv2d_ref_nchw", "rgbd_pointwise_nchw", "rgbd_elic_create",
+           "rgbd_rans_decoder_decode", "rgbd_rans_decoder_destroy", "rgbd_rans_encode_batch_dev", "rgbd_rans_decode_batch_dev", "rgbd_ckbd_quant_index", "rgbd_ckbd_dequant", "rgbd_conv2d_nchw", "rgbd_conv2d_ref_nchw", "rgbd_pointwise_nchw", "rgbd_ref_channel_mean", "rgbd_ref_linear", "rgbd_ref_sigmoid_gate",
+           "rgbd_ref_small_conv_nchw", "rgbd_ref_deconv_s2_nchw", "rgbd_elic_create",
            "rgbd_elic_destroy", "rgbd_elic_set_ref_blocks", "rgbd_elic_get_refnum", "rgbd_elic_ref_table_misses", "rgbd_elic_clone_shared", "rgbd_elic_set_tensor", "rgbd_elic_set_tables", "rgbd_elic_set_scale_table",
            "rgbd_elic_finalize", "rgbd_elic_compress", "rgbd_elic_forward", "rgbd_elic_stream_count", "rgbd_elic_stream",
            "rgbd_elic_decompress", "rgbd_elic_create_r2d", "rgbd_elic_create_stf", "rgbd_elic_create_single", "rgbd_elic_compress_single", "rgbd_elic_decompress_single", "rgbd_elic_forward_single", "rgbd_elic_compress_united", "rgbd_elic_decompress_united", "rgbd_elic_debug_tensor", "rgbd_elic_debug_symbols", "rgbd_elic_set_debug_floats", "rgbd_elic_debug_floats", "rgbd_elic_set_forced_symbols", "rgbd_elic_set_profile", "rgbd_elic_graph_count", "rgbd_elic_workspace_bytes", "rgbd_msssim_workspace_bytes", "rgbd_msssim_stats", "rgbd_layernorm", "rgbd_debug_force_layernorm_form",

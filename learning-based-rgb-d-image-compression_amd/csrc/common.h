@@ -202,6 +202,9 @@ int launch_se_fc(const float* mean, int N, int C, int hidden, const float* w0, c
 int launch_channel_mean_ref(const float* x, int N, int HW, int cs, int C, float* mean, int mstride, hipStream_t s);
 int launch_se_fc_ref(const float* mean, int N, int C, int hidden, const float* w0, const float* w1, const int* cls0,
                      const int* cls1, float* hid, float* scale, hipStream_t s, int mstride = 0, int form = -1);
+// one of its two layers alone: xperm / yperm = the input / output vector is indexed by channel POSITION (fc.0: 1, 0; fc.2: 0, 1)
+int launch_se_linear_ref(const float* w, const float* x, int N, int K, int J, int xstride, int xperm, const int* row_class, int act,
+                         float* y, int ystride, int yperm, int form, hipStream_t s);
 // mode 0: y = x*s ; mode 1: y = x + x*s   (s per (n, c))
 int launch_channel_scale_to(const float* x, int N, int HW, int xcs, int C, const float* scale, int mode, float* y, int ycs,
                             hipStream_t s);

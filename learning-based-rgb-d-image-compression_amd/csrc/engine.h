@@ -363,6 +363,131 @@ struct Epi {
 };
 
 
+// ------------------------------------------------------------------------------------------------
+// conv_transpose2d(k 5, stride 2, pad 2, output_padding 1) + activation in the reference's CPU arithmetic (oneDNN's
+// brg_deconv: DESIGN.md 4a; oracle/cpu_arith.c orc_deconv_s2): the taps of an output pixel are accumulated tap by tap over
+// all input channels, in chains whose membership depends on the layer shape and on the pixel's column block -- a measured
+// recipe per (phase, column), refarith_tables.json kind 3.  Per phase and column class (columns with the same recipe) this
+// is ONE GEMM whose K axis is (tap, channel): gathered input rows x gathered weight slabs, the chains as split-K ranges
+// whose sums the ordered reducer adds (+ bias, activation), rows scattered to the phase's output positions.
+// rec: the recipe's flat integers, 4 * w descriptors {n, n x (ky, kx, fresh)}.  x: NHWC with channel stride pc.cin_pad;
+// out: [B][2h][2w][ocs].  Scratch: mark() / take(bytes) / release(mark), stack-style per column class -- the engine's arena
+// (ArenaScratch) or device allocations of the stand-alone entry point.  launch = false: sizes only (the engine's dry pass).
+struct ArenaScratch {
+    Arena& a;
+    size_t mark() const { return a.top; }
+    float* take(size_t bytes) { return (float*)a.take(bytes); }
+    void release(size_t m) { a.top = m; }
+};
+template <class Scratch>
+inline int deconv_s2_ref_run(const PackedConv& pcv, const int* rec, size_t nrec, const float* x, int B, int h, int w, int act,
+                             float* out, int ocs, int tile_mode, bool launch, hipStream_t s, Scratch& scratch)
+{
+    const PackedConv* pc = &pcv;
+    // parse: 4 * w descriptors {n, n x (ky, kx, fresh)}
+    std::vector<const int*> desc(4 * (size_t)w, nullptr);
+    {
+        size_t pos = 0;
+        for (size_t i = 0; i < desc.size(); ++i) {
+            if (pos >= nrec || rec[pos] < 0 || (size_t)rec[pos] > (nrec - pos - 1) / 3) return RGBD_EINVAL;
+            desc[i] = rec + pos;
+            pos += 1 + 3 * (size_t)rec[pos];
+        }
+        if (pos != nrec) return RGBD_EINVAL;
+    }
+    auto same = [](const int* a, const int* b) { return a[0] == b[0] && memcmp(a, b, sizeof(int) * (1 + 3 * (size_t)a[0])) == 0; };
+    for (int ph = 0; ph < 4; ++ph) {
+        const int py = ph >> 1, px = ph & 1;
+        for (int j0 = 0; j0 < w;) {
+            const int* d = desc[(size_t)ph * w + j0];
+            int j1 = j0 + 1;
+            while (j1 < w && same(d, desc[(size_t)ph * w + j1])) ++j1;
+            const int jw = j1 - j0, nt = d[0];
+            if (nt < 1 || nt > 16) return RGBD_EINVAL;
+            int dy[16], dx[16], slab[16], nch = 0;
+            uint16_t bnd[18] = {0};
+            for (int t = 0; t < nt; ++t) {
+                const int ky = d[1 + 3 * t], kx = d[2 + 3 * t], fresh = d[3 + 3 * t];
+                // (a tap of another phase -- (py + 2 - ky) or (px + 2 - kx) odd -- never meets this phase's pixels)
+                if (ky < 0 || ky > 4 || kx < 0 || kx > 4 || ((py + ky) & 1) || ((px + kx) & 1) || (fresh != 0 && fresh != 1)) return RGBD_EINVAL;
+                dy[t] = (py + 2 - ky) / 2;  // input row of output row 2 ty + py under tap ky: ty + (py + pad - ky) / 2
+                dx[t] = (px + 2 - kx) / 2;
+                slab[t] = ky * 5 + kx;
+                if (fresh || t == 0) bnd[nch++] = (uint16_t)(t * (pc->cin_pad / 16));
+            }
+            bnd[nch] = (uint16_t)(nt * (pc->cin_pad / 16));
+            if (nch > 16) return RGBD_EINVAL;
+            const size_t mark = scratch.mark();
+            const size_t npx = (size_t)B * h * jw;
+            const int Kp = nt * pc->cin_pad;
+            float* col = scratch.take(npx * Kp * sizeof(float));
+            float* wsel = scratch.take((size_t)pc->cout_pad * Kp * sizeof(float));
+            float* tmp = scratch.take(npx * pc->cout_pad * sizeof(float));
+            float* part = nch > 1 ? scratch.take((size_t)nch * npx * pc->cout_pad * sizeof(float)) : nullptr;
+            if (launch) {
+                if (!col || !wsel || !tmp || (nch > 1 && !part)) return RGBD_ENOMEM;
+                int r = launch_gather_taps(x, B, h, w, pc->cin_pad, j0, jw, nt, dy, dx, col, s);
+                if (!r) r = launch_gather_wslabs(pc->w, pc->cout_pad, 25, pc->cin_pad, nt, slab, wsel, s);
+                if (!r) {
+                    ConvArgs a{};
+                    a.x = col;
+                    a.N = 1;
+                    a.H = B * h;
+                    a.W = jw;
+                    a.xcs = Kp;
+                    a.cin_pad = Kp;
+                    a.w = wsel;
+                    a.ntaps_total = 1;
+                    a.bias = pc->bias;
+                    a.y = tmp;
+                    a.OH = B * h;
+                    a.OW = jw;
+                    a.ycs = pc->cout_pad;
+                    a.cout_pad = pc->cout_pad;
+                    a.cout_store = pc->cout_pad;
+                    a.GH = B * h;
+                    a.GW = jw;
+                    a.IS = a.OS = 1;
+                    a.nphase = 1;
+                    a.taps.n[0] = 1;
+                    a.span_y = a.span_x = 1;
+                    a.act = act;
+                    a.loaded = tile_mode;
+                    a.exact_math = 1;
+                    a.splitk = nch;
+                    if (nch > 1) {
+                        a.partial = part;
+                        for (int c = 0; c <= nch; ++c) a.split_c16[c] = bnd[c];
+                    }
+                    r = launch_conv(a, s);
+                }
+                if (!r) r = launch_scatter_phase(tmp, B, h, jw, pc->cout_pad, j0, py, px, out, 2 * w, ocs, pc->cout_pad, s);
+                if (r) return r;
+            }
+            scratch.release(mark);
+            j0 = j1;
+        }
+    }
+    return RGBD_OK;
+}
+
+// K blocks of the small-tensor route: block lengths in k = c * K * K + ky * K + kx -> SmallConvArgs::kb / nb (nullptr = one block)
+inline int small_conv_set_kblocks(SmallConvArgs* a, const int* lens, int n, int Kt)
+{
+    a->nb = 1;
+    a->kb[0] = 0;
+    a->kb[1] = Kt;
+    if (!lens) return RGBD_OK;
+    if (n < 1 || n > 16) return RGBD_EINVAL;
+    int pos = 0;
+    a->nb = n;
+    for (int b = 0; b < n; ++b) {
+        if (lens[b] <= 0 || lens[b] > Kt - pos) return RGBD_EINVAL;
+        pos += lens[b];
+        a->kb[b + 1] = pos;
+    }
+    return pos == Kt ? RGBD_OK : RGBD_EINVAL;
+}
 
 }  // namespace rgbd_rt
 using namespace rgbd_rt;
@@ -1161,20 +1286,9 @@ struct rgbd_elic {
         if (ep.dup) a.y2 = ep.dup->p, a.y2cs = ep.dup->cs;
         const int Kt = pc->cin * k * k;
         const std::vector<int>* bl = ref_blocks(1, pc->cin, pc->cout, x.h, x.w, k * 100 + stride * 10 + pad);
-        a.nb = 1;
-        a.kb[0] = 0;
-        a.kb[1] = Kt;
-        if (bl && bl->size() <= 16) {
-            int pos = 0;
-            a.nb = (int)bl->size();
-            for (int b = 0; b < a.nb; ++b) {
-                pos += (*bl)[b];
-                a.kb[b + 1] = pos;
-            }
-            if (pos != Kt) {
-                fail(RGBD_EINVAL);
-                return y;
-            }
+        if (small_conv_set_kblocks(&a, bl && bl->size() <= 16 ? bl->data() : nullptr, bl ? (int)bl->size() : 0, Kt)) {
+            fail(RGBD_EINVAL);
+            return y;
         }
         const int r = launch_small_conv_ref(a, s);
         if (r) fail(r);
@@ -1829,12 +1943,8 @@ struct rgbd_elic {
         *out[1] = t2[1];
     }
 
-    // conv_transpose2d(k 5, stride 2, pad 2, output_padding 1) + activation in the reference's CPU arithmetic (oneDNN's
-    // brg_deconv: DESIGN.md 4a; oracle/cpu_arith.c orc_deconv_s2): the taps of an output pixel are accumulated tap by tap over
-    // all input channels, in chains whose membership depends on the layer shape and on the pixel's column block -- a measured
-    // recipe per (phase, column), refarith_tables.json kind 3.  Per phase and column class (columns with the same recipe) this
-    // is ONE GEMM whose K axis is (tap, channel): gathered input rows x gathered weight slabs, the chains as split-K ranges
-    // whose sums the ordered reducer adds (+ bias, activation), rows scattered to the phase's output positions.
+    // conv_transpose2d(k 5, stride 2, pad 2, output_padding 1) + activation in the reference's CPU arithmetic: the layer's
+    // measured recipe (refarith_tables.json kind 3) run by deconv_s2_ref_run(), scratch from the arena.
     // false = no recipe for this shape (the caller runs the sub-pixel-phase kernel).
     bool deconv_s2_ref(const std::string& name, const Act& x, int act, Act* out)
     {
@@ -1843,101 +1953,11 @@ struct rgbd_elic {
         if (!pc || !pc->transposed || pc->k != 5 || pc->subpix || x.cs != pc->cin_pad) return false;
         const std::vector<int>* rec = ref_blocks(3, pc->cin, pc->cout, x.h, x.w);
         if (!rec) return false;
-        const int h = x.h, w = x.w, B = x.n;
-        *out = alloc(B, 2 * h, 2 * w, pc->cout);
-        // parse: 4 * w descriptors {n, n x (ky, kx, fresh)}
-        std::vector<const int*> desc(4 * (size_t)w, nullptr);
-        {
-            size_t pos = 0;
-            for (size_t i = 0; i < desc.size(); ++i) {
-                if (pos >= rec->size()) {
-                    fail(RGBD_EINVAL);
-                    return true;
-                }
-                desc[i] = rec->data() + pos;
-                pos += 1 + 3 * (size_t)(*rec)[pos];
-            }
-            if (pos != rec->size()) {
-                fail(RGBD_EINVAL);
-                return true;
-            }
-        }
-        auto same = [](const int* a, const int* b) { return a[0] == b[0] && memcmp(a, b, sizeof(int) * (1 + 3 * (size_t)a[0])) == 0; };
-        for (int ph = 0; ph < 4; ++ph) {
-            const int py = ph >> 1, px = ph & 1;
-            for (int j0 = 0; j0 < w;) {
-                const int* d = desc[(size_t)ph * w + j0];
-                int j1 = j0 + 1;
-                while (j1 < w && same(d, desc[(size_t)ph * w + j1])) ++j1;
-                const int jw = j1 - j0, nt = d[0];
-                if (nt < 1 || nt > 16) {
-                    fail(RGBD_EINVAL);
-                    return true;
-                }
-                int dy[16], dx[16], slab[16], nch = 0;
-                uint16_t bnd[18] = {0};
-                for (int t = 0; t < nt; ++t) {
-                    const int ky = d[1 + 3 * t], kx = d[2 + 3 * t], fresh = d[3 + 3 * t];
-                    dy[t] = (py + 2 - ky) / 2;  // input row of output row 2 ty + py under tap ky: ty + (py + pad - ky) / 2
-                    dx[t] = (px + 2 - kx) / 2;
-                    slab[t] = ky * 5 + kx;
-                    if (fresh || t == 0) bnd[nch++] = (uint16_t)(t * (pc->cin_pad / 16));
-                }
-                bnd[nch] = (uint16_t)(nt * (pc->cin_pad / 16));
-                if (nch > 16) {
-                    fail(RGBD_EINVAL);
-                    return true;
-                }
-                const size_t mark = arena.top;
-                const size_t npx = (size_t)B * h * jw;
-                const int Kp = nt * pc->cin_pad;
-                float* col = (float*)arena.take(npx * Kp * sizeof(float));
-                float* wsel = (float*)arena.take((size_t)pc->cout_pad * Kp * sizeof(float));
-                float* tmp = (float*)arena.take(npx * pc->cout_pad * sizeof(float));
-                float* part = nch > 1 ? (float*)arena.take((size_t)nch * npx * pc->cout_pad * sizeof(float)) : nullptr;
-                if (!dry() && !rc) {
-                    int r = launch_gather_taps(x.p, B, h, w, x.cs, j0, jw, nt, dy, dx, col, s);
-                    if (!r) r = launch_gather_wslabs(pc->w, pc->cout_pad, 25, pc->cin_pad, nt, slab, wsel, s);
-                    if (!r) {
-                        ConvArgs a{};
-                        a.x = col;
-                        a.N = 1;
-                        a.H = B * h;
-                        a.W = jw;
-                        a.xcs = Kp;
-                        a.cin_pad = Kp;
-                        a.w = wsel;
-                        a.ntaps_total = 1;
-                        a.bias = pc->bias;
-                        a.y = tmp;
-                        a.OH = B * h;
-                        a.OW = jw;
-                        a.ycs = pc->cout_pad;
-                        a.cout_pad = pc->cout_pad;
-                        a.cout_store = pc->cout_pad;
-                        a.GH = B * h;
-                        a.GW = jw;
-                        a.IS = a.OS = 1;
-                        a.nphase = 1;
-                        a.taps.n[0] = 1;
-                        a.span_y = a.span_x = 1;
-                        a.act = act;
-                        a.loaded = tile_mode;
-                        a.exact_math = 1;
-                        a.splitk = nch;
-                        if (nch > 1) {
-                            a.partial = part;
-                            for (int c = 0; c <= nch; ++c) a.split_c16[c] = bnd[c];
-                        }
-                        r = launch_conv(a, s);
-                    }
-                    if (!r) r = launch_scatter_phase(tmp, B, h, jw, pc->cout_pad, j0, py, px, out->p, 2 * w, out->cs, pc->cout_pad, s);
-                    if (r) fail(r);
-                }
-                arena.top = mark;
-                j0 = j1;
-            }
-        }
+        *out = alloc(x.n, 2 * x.h, 2 * x.w, pc->cout);
+        ArenaScratch scratch{arena};
+        const int r = deconv_s2_ref_run(*pc, rec->data(), rec->size(), x.p, x.n, x.h, x.w, act, out->p, out->cs, tile_mode,
+                                        !dry() && !rc, s, scratch);
+        if (r) fail(r);
         return true;
     }
 

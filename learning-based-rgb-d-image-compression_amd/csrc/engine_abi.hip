@@ -289,6 +289,230 @@ int rgbd_pointwise_nchw(int32_t op, const float* x_dev, int32_t n, int32_t c, in
     return rc;
 }
 
+// ---- the reference-arithmetic pointwise kernels alone (test hooks: tests/test_gpu_refpointwise.py) ---------------------------
+// Each hook validates every argument on the host before anything is allocated or launched, converts its logical NCHW / logical
+// channel-order tensors to the engine's layout (NHWC, channels permuted: rgbd_cperm), calls the launcher the engine calls with
+// the engine's permutation arguments, and converts back.  Device scratch is released on every way out.
+namespace {
+struct DevBufs {
+    std::vector<void*> v;
+    float* get(size_t floats)
+    {
+        void* p = nullptr;
+        if (hipMalloc(&p, std::max<size_t>(floats, 1) * sizeof(float)) != hipSuccess) return nullptr;
+        v.push_back(p);
+        return (float*)p;
+    }
+    ~DevBufs()
+    {
+        for (void* p : v) (void)hipFree(p);
+    }
+};
+// deconv_s2_ref_run's scratch outside an engine: one device allocation per take, all released when the hook returns
+struct MallocScratch {
+    DevBufs& b;
+    size_t mark() const { return 0; }
+    float* take(size_t bytes) { return b.get((bytes + 3) / 4); }
+    void release(size_t) {}
+};
+// sizes only (the validation pass of the recipe: nothing is allocated, nothing launched)
+struct NoScratch {
+    size_t mark() const { return 0; }
+    float* take(size_t) { return nullptr; }
+    void release(size_t) {}
+};
+inline bool tensor_ok(int64_t n, int64_t c, int64_t h, int64_t w)
+{
+    return n > 0 && c > 0 && h > 0 && w > 0 && n <= 64 && c <= 65536 && h <= 65536 && w <= 65536 &&
+           n * round_up((int)c, 16) * h * w < ((int64_t)1 << 28);
+}
+}  // namespace
+
+int rgbd_ref_channel_mean(const float* x_dev, int32_t n, int32_t c, int32_t h, int32_t w, float* mean_dev, int32_t mstride,
+                          void* stream)
+{
+    std::unique_lock<std::shared_mutex> cap_lk(g_capture_mu);
+    if (!x_dev || !mean_dev || !tensor_ok(n, c, h, w) || c % 16 || mstride < c || mstride > (1 << 20)) return RGBD_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    DevBufs b;
+    const size_t mfloats = (size_t)(n - 1) * mstride + c;
+    float* xin = b.get((size_t)n * h * w * c);
+    float* mean = b.get(mfloats);
+    if (!xin || !mean) return RGBD_ENOMEM;
+    int rc = launch_nchw_to_nhwc16(x_dev, n, c, h, w, xin, c, s, 1);
+    if (!rc) rc = launch_channel_mean_ref(xin, n, h * w, c, c, mean, mstride, s);  // (mean[image * mstride + channel POSITION])
+    std::vector<float> hm(mfloats), row(c);
+    if (!rc) HIP_TRY(hipMemcpyAsync(hm.data(), mean, mfloats * sizeof(float), hipMemcpyDeviceToHost, s));
+    const hipError_t e = hipStreamSynchronize(s);
+    if (!rc && e != hipSuccess) rc = RGBD_EHIP;
+    for (int i = 0; i < n && !rc; ++i) {  // only the c means of every image are written: the rest of a row is the caller's
+        for (int ch = 0; ch < c; ++ch) row[ch] = hm[(size_t)i * mstride + rgbd_cperm(ch)];
+        HIP_TRY(hipMemcpy(mean_dev + (size_t)i * mstride, row.data(), (size_t)c * sizeof(float), hipMemcpyHostToDevice));
+    }
+    return rc;
+}
+
+int rgbd_ref_linear(const float* weight, const float* x_dev, int32_t n, int32_t K, int32_t J, const int32_t* row_class, int32_t form,
+                    int32_t act, int32_t stage, float* y_dev, void* stream)
+{
+    std::unique_lock<std::shared_mutex> cap_lk(g_capture_mu);
+    if (!weight || !x_dev || !y_dev || n <= 0 || n > 64 || K <= 0 || J <= 0 || K > 65536 || J > 65536) return RGBD_EINVAL;
+    if ((form != -1 && form != 3) || (act != ACT_NONE && act != ACT_RELU && act != ACT_SIGMOID) || stage < 0 || stage > 1) return RGBD_EINVAL;
+    if ((stage == 0 ? K : J) % 16) return RGBD_EINVAL;  // the side that lives in the permuted layout
+    if (row_class)
+        for (int j = 0; j < J; ++j)
+            if (row_class[j] < 0 || row_class[j] > 2) return RGBD_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    DevBufs b;
+    float* dw = b.get((size_t)J * K);
+    float* xp = b.get((size_t)n * K);
+    float* yp = b.get((size_t)n * J);
+    int* cls = row_class ? (int*)b.get(J) : nullptr;
+    if (!dw || !xp || !yp || (row_class && !cls)) return RGBD_ENOMEM;
+    HIP_TRY(hipMemcpy(dw, weight, (size_t)J * K * sizeof(float), hipMemcpyHostToDevice));
+    if (cls) HIP_TRY(hipMemcpy(cls, row_class, (size_t)J * sizeof(int), hipMemcpyHostToDevice));
+    int rc;
+    if (stage == 0) {  // fc.0: the input is the mean vector (by position), the output the hidden vector (plain)
+        rc = launch_nchw_to_nhwc16(x_dev, n, K, 1, 1, xp, K, s, 1);
+        if (!rc) rc = launch_se_linear_ref(dw, xp, n, K, J, K, 1, cls, act, y_dev, J, 0, form, s);
+    } else {           // fc.2: the input is the hidden vector (plain), the output the gate vector (by position)
+        rc = launch_se_linear_ref(dw, x_dev, n, K, J, K, 0, cls, act, yp, J, 1, form, s);
+        if (!rc) rc = launch_nhwc_to_nchw_clamp(yp, n, J, 1, 1, J, y_dev, 0, s, 1);
+    }
+    const hipError_t e = hipStreamSynchronize(s);
+    if (!rc && e != hipSuccess) rc = RGBD_EHIP;
+    return rc;
+}
+
+int rgbd_ref_sigmoid_gate(const float* t_dev, const float* mul_dev, const float* res_dev, int32_t n, int32_t c, int32_t h, int32_t w,
+                          int32_t per_image, int32_t threads, float* y_dev, void* stream)
+{
+    std::unique_lock<std::shared_mutex> cap_lk(g_capture_mu);
+    if (!t_dev || !y_dev || !tensor_ok(n, c, h, w) || threads < 1 || threads > 1024 || per_image < 0 || per_image > 1) return RGBD_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    const int cs = round_up(c, 16);
+    const size_t fl = (size_t)n * h * w * cs;
+    DevBufs b;
+    float *t = b.get(fl), *y = b.get(fl), *m = mul_dev ? b.get(fl) : nullptr, *r = res_dev ? b.get(fl) : nullptr;
+    if (!t || !y || (mul_dev && !m) || (res_dev && !r)) return RGBD_ENOMEM;
+    int rc = launch_nchw_to_nhwc16(t_dev, n, c, h, w, t, cs, s, 1);
+    if (!rc && m) rc = launch_nchw_to_nhwc16(mul_dev, n, c, h, w, m, cs, s, 1);
+    if (!rc && r) rc = launch_nchw_to_nhwc16(res_dev, n, c, h, w, r, cs, s, 1);
+    if (!rc) rc = launch_sigmoid_gate_ref(t, cs, m, m ? cs : 0, r, r ? cs : 0, y, cs, n, h * w, c, per_image, threads, s);
+    if (!rc) rc = launch_nhwc_to_nchw_clamp(y, n, c, h, w, cs, y_dev, 0, s, 1);
+    const hipError_t e = hipStreamSynchronize(s);
+    if (!rc && e != hipSuccess) rc = RGBD_EHIP;
+    return rc;
+}
+
+int rgbd_ref_small_conv_nchw(const float* x_dev, int32_t n, int32_t cin, int32_t h, int32_t w, const float* weight, const float* bias,
+                             int32_t cout, int32_t k, int32_t stride, int32_t pad, int32_t act, int32_t ckbd, const int32_t* kblocks,
+                             int32_t nkblocks, const float* res1_dev, const float* mul_dev, const float* res2_dev, float* y_dev,
+                             float* y2_dev, void* stream)
+{
+    std::unique_lock<std::shared_mutex> cap_lk(g_capture_mu);
+    if (!x_dev || !weight || !y_dev || !tensor_ok(n, cin, h, w) || cout <= 0 || cout > 65536 || k < 1 || k > 3 || stride < 1 ||
+        stride > 2 || pad < 0 || pad > k || act < ACT_NONE || act > ACT_SIGMOID || ckbd < 0 || ckbd > 2 || (ckbd && stride != 1))
+        return RGBD_EINVAL;
+    if (h + 2 * pad < k || w + 2 * pad < k) return RGBD_EINVAL;
+    const int OH = (h + 2 * pad - k) / stride + 1, OW = (w + 2 * pad - k) / stride + 1;
+    if (!tensor_ok(n, cout, OH, OW)) return RGBD_EINVAL;
+    SmallConvArgs a{};
+    if (small_conv_set_kblocks(&a, kblocks, nkblocks, cin * k * k)) return RGBD_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    HostTensor hw, hb;
+    hw.shape = {cout, cin, k, k};
+    hw.v.assign(weight, weight + (size_t)cin * cout * k * k);
+    if (bias) {
+        hb.shape = {cout};
+        hb.v.assign(bias, bias + cout);
+    }
+    DevBufs b;
+    DevGen gen;  // (owns the packed weights: released on every way out)
+    PackedConv pc;
+    int rc = pack_conv(hw, bias ? &hb : nullptr, false, &pc, &gen, 1, 1);
+    if (rc) return rc;
+    const size_t xf = (size_t)n * h * w * pc.cin_pad, yf = (size_t)n * OH * OW * pc.cout_pad;
+    float *xin = b.get(xf), *y = b.get(yf), *y2 = y2_dev ? b.get(yf) : nullptr;
+    float *r1 = res1_dev ? b.get(yf) : nullptr, *m = mul_dev ? b.get(yf) : nullptr, *r2 = res2_dev ? b.get(yf) : nullptr;
+    if (!xin || !y || (y2_dev && !y2) || (res1_dev && !r1) || (mul_dev && !m) || (res2_dev && !r2)) return RGBD_ENOMEM;
+    rc = launch_nchw_to_nhwc16(x_dev, n, cin, h, w, xin, pc.cin_pad, s, 1);
+    if (!rc && r1) rc = launch_nchw_to_nhwc16(res1_dev, n, cout, OH, OW, r1, pc.cout_pad, s, 1);
+    if (!rc && m) rc = launch_nchw_to_nhwc16(mul_dev, n, cout, OH, OW, m, pc.cout_pad, s, 1);
+    if (!rc && r2) rc = launch_nchw_to_nhwc16(res2_dev, n, cout, OH, OW, r2, pc.cout_pad, s, 1);
+    // (the kernel writes the real channels of the computed positions only: pad channels and the other checkerboard half read 0)
+    if (!rc) rc = launch_fill_zero(y, yf, s);
+    if (!rc && y2) rc = launch_fill_zero(y2, yf, s);
+    a.x = xin;
+    a.w = pc.w;
+    a.bias = pc.bias;
+    a.y = y;
+    a.N = n;
+    a.H = h;
+    a.W = w;
+    a.xcs = pc.cin_pad;
+    a.C = cin;
+    a.cin_pad = pc.cin_pad;
+    a.O = cout;
+    a.OH = OH;
+    a.OW = OW;
+    a.ycs = pc.cout_pad;
+    a.K = k;
+    a.stride = stride;
+    a.pad = pad;
+    a.act = act;
+    a.ckbd = ckbd;
+    if (r1) a.res1 = r1, a.r1cs = pc.cout_pad;
+    if (m) a.mul = m, a.mcs = pc.cout_pad;
+    if (r2) a.res2 = r2, a.r2cs = pc.cout_pad;
+    if (y2) a.y2 = y2, a.y2cs = pc.cout_pad;
+    if (!rc) rc = launch_small_conv_ref(a, s);
+    if (!rc) rc = launch_nhwc_to_nchw_clamp(y, n, cout, OH, OW, pc.cout_pad, y_dev, 0, s, 1);
+    if (!rc && y2) rc = launch_nhwc_to_nchw_clamp(y2, n, cout, OH, OW, pc.cout_pad, y2_dev, 0, s, 1);
+    const hipError_t e = hipStreamSynchronize(s);
+    if (!rc && e != hipSuccess) rc = RGBD_EHIP;
+    return rc;
+}
+
+int rgbd_ref_deconv_s2_nchw(const float* x_dev, int32_t n, int32_t cin, int32_t h, int32_t w, const float* weight, const float* bias,
+                            int32_t cout, int32_t act, const int32_t* recipe, int32_t nrecipe, float* y_dev, void* stream)
+{
+    std::unique_lock<std::shared_mutex> cap_lk(g_capture_mu);
+    if (!x_dev || !weight || !y_dev || !recipe || nrecipe <= 0 || !tensor_ok(n, cin, h, w) || !tensor_ok(n, cout, 2 * (int64_t)h, 2 * (int64_t)w) ||
+        cout > 65536 || (act != ACT_NONE && act != ACT_LEAKY && act != ACT_RELU))
+        return RGBD_EINVAL;
+    if (cin > 4096) return RGBD_EINVAL;  // (16 taps x cin_pad / 16 chunks must fit ConvArgs::split_c16)
+    PackedConv shape;  // the recipe is checked against the layer's shape before anything touches the device
+    shape.cin = cin, shape.cout = cout, shape.k = 5, shape.transposed = true;
+    shape.cin_pad = round_up(cin, 16), shape.cout_pad = round_up(cout, 16);
+    NoScratch none;
+    int rc = deconv_s2_ref_run(shape, recipe, (size_t)nrecipe, nullptr, n, h, w, act, nullptr, shape.cout_pad, 0, false, nullptr, none);
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    HostTensor hw, hb;
+    hw.shape = {cin, cout, 5, 5};
+    hw.v.assign(weight, weight + (size_t)cin * cout * 25);
+    if (bias) {
+        hb.shape = {cout};
+        hb.v.assign(bias, bias + cout);
+    }
+    DevBufs b;
+    DevGen gen;  // (owns the packed weights: released on every way out)
+    PackedConv pc;
+    rc = pack_conv(hw, bias ? &hb : nullptr, true, &pc, &gen, 1, 1);
+    if (rc) return rc;
+    const size_t xf = (size_t)n * h * w * pc.cin_pad, yf = (size_t)n * 4 * h * w * pc.cout_pad;
+    float *xin = b.get(xf), *y = b.get(yf);
+    if (!xin || !y) return RGBD_ENOMEM;
+    rc = launch_nchw_to_nhwc16(x_dev, n, cin, h, w, xin, pc.cin_pad, s, 1);
+    MallocScratch scratch{b};
+    if (!rc) rc = deconv_s2_ref_run(pc, recipe, (size_t)nrecipe, xin, n, h, w, act, y, pc.cout_pad, 0, true, s, scratch);
+    if (!rc) rc = launch_nhwc_to_nchw_clamp(y, n, cout, 2 * h, 2 * w, pc.cout_pad, y_dev, 0, s, 1);
+    const hipError_t e = hipStreamSynchronize(s);
+    if (!rc && e != hipSuccess) rc = RGBD_EHIP;
+    return rc;
+}
+
 int rgbd_debug_force_tile(const char* cfg)
 {
     snprintf(g_conv_force, sizeof(g_conv_force), "%s", cfg ? cfg : "");

@@ -604,16 +604,23 @@ __global__ __launch_bounds__(64) void se_linear_ref_kernel(const float* __restri
     }
 }
 
+// one Linear layer: y[n][j] = act(W[j] . x[n]) for N vectors (see se_linear_ref_kernel for xperm / yperm / row_class / form)
+int launch_se_linear_ref(const float* w, const float* x, int N, int K, int J, int xstride, int xperm, const int* row_class, int act,
+                         float* y, int ystride, int yperm, int form, hipStream_t s)
+{
+    hipLaunchKernelGGL(se_linear_ref_kernel, dim3(J, N), dim3(64), 0, s, w, x, K, J, xstride, xperm, row_class, act, y, ystride,
+                       yperm, form);
+    HIP_TRY(hipGetLastError());
+    return RGBD_OK;
+}
+
 int launch_se_fc_ref(const float* mean, int N, int C, int hidden, const float* w0, const float* w1, const int* cls0,
                      const int* cls1, float* hid, float* scale, hipStream_t s, int mstride, int form)
 {
     // fc.0: [hidden][C] on the means (by position) -> ReLU -> hid[n][hidden];  fc.2: [C][hidden] (NOT transposed) -> sigmoid
-    hipLaunchKernelGGL(se_linear_ref_kernel, dim3(hidden, N), dim3(64), 0, s, w0, mean, C, hidden, mstride > 0 ? mstride : C, 1,
-                       cls0, ACT_RELU, hid, hidden, 0, form);
-    hipLaunchKernelGGL(se_linear_ref_kernel, dim3(C, N), dim3(64), 0, s, w1, hid, hidden, C, hidden, 0, cls1, ACT_SIGMOID, scale,
-                       C, 1, form);
-    HIP_TRY(hipGetLastError());
-    return RGBD_OK;
+    const int r = launch_se_linear_ref(w0, mean, N, C, hidden, mstride > 0 ? mstride : C, 1, cls0, ACT_RELU, hid, hidden, 0, form, s);
+    if (r) return r;
+    return launch_se_linear_ref(w1, hid, N, hidden, C, hidden, 0, cls1, ACT_SIGMOID, scale, C, 1, form, s);
 }
 
 // ---------------------------------------------------------------------------------------------

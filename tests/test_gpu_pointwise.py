@@ -60,7 +60,8 @@ def test_bilinear_matches_torch(n, c, h, w, oh, ow):
     assert float((got - ref).abs().max()) <= 2e-6 * float(ref.abs().max())
 
 
-@pytest.mark.parametrize("n,c,h,w,op", [(1, 192, 16, 24, 2), (2, 384, 8, 10, 2), (4, 1280, 32, 40, 3), (1, 2432, 8, 12, 3)])
+@pytest.mark.parametrize("n,c,h,w,op", [(1, 192, 16, 24, 2), (2, 384, 8, 10, 2), (4, 1280, 32, 40, 3), (1, 2432, 8, 12, 3),
+                                        (1, 192, 96, 96, 2)])  # (96 x 96: the mean's cascade reaches its level 2)
 def test_se_block_matches_torch(n, c, h, w, op):
     g = torch.Generator().manual_seed(c + h)
     x = torch.randn(n, c, h, w, generator=g)
@@ -73,3 +74,22 @@ def test_se_block_matches_torch(n, c, h, w, op):
     # another order are not modelled by this entry point (the codec takes them from the measured tables): 1e-6-level
     assert float((got - ref).abs().max()) <= 2e-5 * float(ref.abs().max())
     assert torch.equal(got, _run(op, x, w0=w0, w1=w1))  # and it is deterministic
+    # ... and bit for bit the oracle's restatement of that arithmetic (every row of both Linear layers in the main order, which is
+    # what this entry point runs): mean -> fc.0 -> ReLU -> fc.2 -> vector sigmoid, then x * g resp. x + x * g in two roundings
+    from oracle import cpu_arith as ca
+
+    P = lambda a: a.ctypes.data_as(ctypes.c_void_p)  # noqa: E731
+    xn, w0n, w1n = np.ascontiguousarray(x.numpy()), np.ascontiguousarray(w0.numpy()), np.ascontiguousarray(w1.numpy())
+    gates = np.empty((n, c), np.float32)
+    for i in range(n):
+        mean, hid, lin = np.empty(c, np.float32), np.empty(c // 16, np.float32), np.empty(c, np.float32)
+        ca.lib().orc_mean_rows(P(xn[i]), c, h * w, P(mean))
+        ca.lib().orc_linear_b1(P(w0n), P(mean), c // 16, c, None, P(hid))
+        hid = np.maximum(hid, np.float32(0))
+        ca.lib().orc_linear_b1(P(w1n), P(hid), c, c // 16, None, P(lin))
+        gates[i] = ca.sigmoid(lin)
+    t = xn * gates[:, :, None, None]
+    want = t if op == 2 else xn + t
+    bad = np.flatnonzero(got.numpy().reshape(-1) != want.reshape(-1))
+    assert bad.size == 0, (f"{bad.size} of {want.size} elements differ from the oracle; first at flat index {int(bad[0])}: "
+                           f"got {got.numpy().reshape(-1)[bad[0]]!r}, want {want.reshape(-1)[bad[0]]!r}")

@@ -8,8 +8,10 @@ Sleef / ATen accumulation orders) -- pinned two ways:
   2. against frozen hashes (tests/golden/refarith_pins.json, recorded in the survey container where (1) holds), so the C
      code cannot drift on any machine.  RGBD_RECORD_PINS=1 re-records.
 
-The GPU kernels are compared with this file bit for bit in tests/test_gpu_refarith.py / test_gpu_pointwise.py, and end to end
-through the reference's golden streams in tests/test_gpu_parity_pinned.py."""
+The GPU kernels are compared with this file bit for bit in tests/test_gpu_refarith.py (the blocked convolutions),
+tests/test_gpu_refpointwise.py (mean, Linear, sigmoid gate, small-tensor conv, stride-2 deconv recipes) and
+tests/test_gpu_pointwise.py (bilinear, the SE block as a whole), and end to end through the reference's golden streams in
+tests/test_gpu_parity_pinned.py."""
 import ctypes
 import hashlib
 import json
@@ -166,7 +168,8 @@ def test_bilinear_both_kernels(c, h, w, oh, ow):
     _same_or_skip(got, F.interpolate(x, (oh, ow), mode="bilinear", align_corners=False)[0].numpy(), f"bilinear_{c}_{h}x{w}_{oh}x{ow}")
 
 
-@pytest.mark.parametrize("c,h,w", [(384, 2, 3), (384, 4, 4), (640, 8, 8), (384, 8, 10), (960, 32, 40), (100, 7, 9)])
+@pytest.mark.parametrize("c,h,w", [(384, 2, 3), (384, 4, 4), (640, 8, 8), (384, 8, 10), (960, 32, 40), (100, 7, 9),
+                                   (32, 96, 96), (16, 128, 160), (16, 512, 640)])  # (the last three: cascade levels 2 and 3)
 def test_mean_is_the_cascade_sum(c, h, w):
     x = _rnd(c, 1, c, h, w)
     got = np.empty(c, np.float32)
