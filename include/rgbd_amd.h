@@ -148,8 +148,67 @@ int rgbd_conv2d_ref_nchw(const float* x_dev, int32_t n, int32_t cin, int32_t h, 
                          int32_t act, const float* residual_dev, float* y_dev, void* stream, const int32_t* blocks,
                          int32_t nblocks, int32_t bias_mode, int32_t flags);
 
+/* The conv launchers in every form the engine issues them in (a test hook: tests/test_gpu_convforms.py).  A superset of the
+ * two operators above: it packs the host weights, converts the NCHW device tensors to the engine's layout, fills the
+ * launch descriptor as the engine's conv planner does and calls the launcher the engine calls -- the fused one when cout2 > 0.
+ *
+ *   first layer   n, cin, h, w, cout, k <= 5, stride 1 / 2, pad, transposed, act; refmode != 0: the reference's CPU arithmetic
+ *                 with blocks / nblocks / bias_mode / flags as in rgbd_conv2d_ref_nchw
+ *   plain form    (cout2 == 0)  y = act(conv(x) + bias + res1) * mul + res2, every operand optional; y2: a second copy of y
+ *   fused tail    (cout2 > 0)   t = act_mid(conv(x) + bias), y = act(w2 * t + bias2 + res1); w2 [cout2][cout][1][1],
+ *                 act_mid 0 / 1, act 0 / 1 / 2.  In refmode the chains of the 1x1 layers start from their bias.
+ *   lead layer    (cout3 > 0, with a fused tail)  u = relu(w3 * y + bias3) -> y3; w3 [cout3][cout2][1][1]
+ *   placement     the input is channels [x_off, x_off + cin) of x_dev [n, x_total, h, w] (x_off a multiple of 16); y is
+ *                 channels [y_off, y_off + cy) of y_dev [n, y_total, OH, OW], cy = cout2 when fused, else cout (offsets
+ *                 multiples of 4; of 16 in refmode); likewise y2 and y3 (cout3 channels) with their own off / total.  The
+ *                 channels a launch stores follow the engine's rule: the slice rounded up to 4 when it is narrower than its
+ *                 16-padded width inside a wider buffer, else the 16-padded width.  A destination whose stored channels
+ *                 would run over a neighbouring slice is refused.  The caller fills y_dev / y2_dev / y3_dev beforehand; the
+ *                 whole wide tensors come back, so what a launch did not write is visible.
+ *   groups == 2   set[1] is a second operand set of the same shapes (a pointer is NULL there exactly when its twin in
+ *                 set[0] is): both run as ONE grouped launch.  groups 0 / 1: set[0] alone.
+ *   res1_dev / mul_dev / res2_dev are [n, cy, OH, OW].
+ *
+ * The debug switches apply: the forced tile, the forced split-K factor (plain form outside refmode), the forced checkerboard
+ * half, and the forced fusing mode, whose value is the pixel-tile class of the fused forms (1 / 2 / 4 = 64 / 128 / 256
+ * pixels).  With the fusing mode left at -1 the plan decides; it returns 0 on small maps, and the fused forms then return
+ * -22 like the launcher itself.
+ *
+ * Every argument is checked on the host before anything is allocated or launched: a NULL required pointer, a bad size or any
+ * combination the launchers refuse (fused with stride 2 / k = 5 / a first layer whose padded cout is not 96 / act 3, a lead
+ * layer on a cout2 whose padded width is not a multiple of 32, y2 together with split-K, checkerboard output of a strided
+ * layer, a grouped call with a twin pointer missing, ...) returns -22.  A forced tile that cannot hold the layer returns -28.
+ * Every destination is followed on the device by a guard band of one output row and one pixel; -1 = a launch wrote into it. */
+typedef struct rgbd_conv_forms_ops {
+    const float* x_dev;    /* [n, x_total, h, w] */
+    const float* weight;   /* host: Conv2d layout, or ConvTranspose2d layout when transposed != 0 */
+    const float* bias;     /* host [cout], optional */
+    const float* w2;       /* host, fused tail */
+    const float* bias2;    /* host [cout2], optional */
+    const float* w3;       /* host, lead layer */
+    const float* bias3;    /* host [cout3], optional */
+    const float* res1_dev; /* optional */
+    const float* mul_dev;  /* optional, plain form */
+    const float* res2_dev; /* optional, plain form */
+    float* y_dev;          /* [n, y_total, OH, OW], in / out */
+    float* y2_dev;         /* [n, y2_total, OH, OW], in / out, optional, plain form */
+    float* y3_dev;         /* [n, y3_total, OH, OW], in / out, lead layer */
+} rgbd_conv_forms_ops;
+
+typedef struct rgbd_conv_forms_desc {
+    int32_t n, cin, h, w, cout, k, stride, pad, transposed, act;
+    int32_t refmode, nblocks, bias_mode, flags;
+    const int32_t* blocks;
+    int32_t cout2, act_mid, cout3;
+    int32_t x_off, x_total, y_off, y_total, y2_off, y2_total, y3_off, y3_total;
+    int32_t groups;
+    rgbd_conv_forms_ops set[2];
+} rgbd_conv_forms_desc;
+
+int rgbd_conv_forms_nchw(const rgbd_conv_forms_desc* d, void* stream);
+
 /* ---------------------------------------------------------------------------------------------------------------
- * The codec.  Replaces models/elic_united.py: ELIC_united.__init__ :14-86, load_state_dict :588-620,
+ * The codec. Replaces models/elic_united.py: ELIC_united.__init__ :14-86, load_state_dict :588-620,
  * update :580-586, compress :403-427 (+ compress_united :350-401, compress_one_slice :265-348),
  * decompress :429-452 (+ decompress_united :543-578, decompress_one_slice :454-541).
  * ------------------------------------------------------------------------------------------------------------- */

@@ -25,6 +25,23 @@ def check(rc: int, what: str = ""):
         raise RgbdError(f"librgbd_amd: {what} failed with {rc} ({ERRORS.get(rc, 'unknown')})")
 
 
+class ConvFormsOps(ctypes.Structure):
+    """rgbd_conv_forms_ops (include/rgbd_amd.h): one operand set of rgbd_conv_forms_nchw."""
+    _fields_ = [("x_dev", ctypes.c_void_p)] + [(n, ctypes.POINTER(ctypes.c_float)) for n in
+                                                 ("weight", "bias", "w2", "bias2", "w3", "bias3")] + \
+               [(n, ctypes.c_void_p) for n in ("res1_dev", "mul_dev", "res2_dev", "y_dev", "y2_dev", "y3_dev")]
+
+
+class ConvFormsDesc(ctypes.Structure):
+    """rgbd_conv_forms_desc (include/rgbd_amd.h)."""
+    _fields_ = [(n, ctypes.c_int32) for n in ("n", "cin", "h", "w", "cout", "k", "stride", "pad", "transposed", "act", "refmode",
+                                              "nblocks", "bias_mode", "flags")] + \
+               [("blocks", ctypes.POINTER(ctypes.c_int32))] + \
+               [(n, ctypes.c_int32) for n in ("cout2", "act_mid", "cout3", "x_off", "x_total", "y_off", "y_total", "y2_off", "y2_total",
+                                              "y3_off", "y3_total", "groups")] + \
+               [("set", ConvFormsOps * 2)]
+
+
 def build(force: bool = False, verbose: bool = False) -> str:
     """Compile the HIP sources for gfx950 into librgbd_amd.so (in-tree, next to this file): one object per source
     (only stale ones are recompiled, up to four at a time), then one link."""
@@ -96,6 +113,7 @@ def lib():
                                             c_i32, c_i32, c_vp, c_vp, c_vp]),
         "rgbd_conv2d_ref_nchw": (ctypes.c_int, [c_vp, c_i32, c_i32, c_i32, c_i32, f32p, f32p, c_i32, c_i32, c_i32, c_i32,
                                                 c_i32, c_i32, c_vp, c_vp, c_vp, i32p, c_i32, c_i32, c_i32]),
+        "rgbd_conv_forms_nchw": (ctypes.c_int, [ctypes.POINTER(ConvFormsDesc), c_vp]),
         "rgbd_pointwise_nchw": (ctypes.c_int, [c_i32, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, f32p, f32p, c_vp, c_vp]),
         "rgbd_ref_channel_mean": (ctypes.c_int, [c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_i32, c_vp]),
         "rgbd_ref_linear": (ctypes.c_int, [f32p, c_vp, c_i32, c_i32, c_i32, i32p, c_i32, c_i32, c_i32, c_vp, c_vp]),
@@ -179,7 +197,7 @@ def lib():
 
 EXPORTS = ["rgbd_abi_version", "rgbd_set_blocking_sync", "rgbd_get_blocking_sync", "rgbd_pmf_to_quantized_cdf", "rgbd_tables_create", "rgbd_tables_destroy",
            "rgbd_rans_max_bytes", "rgbd_rans_encode", "rgbd_rans_decoder_create", "rgbd_rans_decoder_set_stream",
-           "rgbd_rans_decoder_decode", "rgbd_rans_decoder_destroy", "rgbd_rans_encode_batch_dev", "rgbd_rans_decode_batch_dev", "rgbd_ckbd_quant_index", "rgbd_ckbd_dequant", "rgbd_conv2d_nchw", "rgbd_conv2d_ref_nchw", "rgbd_pointwise_nchw", "rgbd_ref_channel_mean", "rgbd_ref_linear", "rgbd_ref_sigmoid_gate",
+           "rgbd_rans_decoder_decode", "rgbd_rans_decoder_destroy", "rgbd_rans_encode_batch_dev", "rgbd_rans_decode_batch_dev", "rgbd_ckbd_quant_index", "rgbd_ckbd_dequant", "rgbd_conv2d_nchw", "rgbd_conv2d_ref_nchw", "rgbd_conv_forms_nchw", "rgbd_pointwise_nchw", "rgbd_ref_channel_mean", "rgbd_ref_linear", "rgbd_ref_sigmoid_gate",
            "rgbd_ref_small_conv_nchw", "rgbd_ref_deconv_s2_nchw", "rgbd_elic_create",
            "rgbd_elic_destroy", "rgbd_elic_set_ref_blocks", "rgbd_elic_get_refnum", "rgbd_elic_ref_table_misses", "rgbd_elic_clone_shared", "rgbd_elic_set_tensor", "rgbd_elic_set_tables", "rgbd_elic_set_scale_table",
            "rgbd_elic_finalize", "rgbd_elic_compress", "rgbd_elic_forward", "rgbd_elic_stream_count", "rgbd_elic_stream",

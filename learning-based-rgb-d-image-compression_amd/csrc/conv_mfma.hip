@@ -413,7 +413,8 @@ static int launch_conv_main(const ConvArgs& a, hipStream_t s)
 // ---- conv + fused trailing 1x1 ---------------------------------------------------------------------------------------
 // The pair (3x3 C->C, 1x1 C->C2) of a ResidualBottleneck / ResidualUnit as one launch: the first layer's whole cout range
 // is one workgroup tile (TM = cout_pad = 96), pixel tiles of 64 / 128 / 256.  Results are bit-identical to the two
-// stand-alone launches (tests/test_gpu_conv.py::test_fused_tail_bit_identical), so fusing is a speed decision only.
+// stand-alone launches (tests/test_gpu_fused.py::test_fused_tail_bit_identical on the model, tests/test_gpu_convforms.py on
+// the launch alone), so fusing is a speed decision only.
 static const bool g_fuse_off = getenv("RGBD_NO_FUSE") != nullptr;
 int g_fuse_force = -1;  // rgbd_debug_force_fuse: -1 = plan, 0 = never, 1 / 2 / 4 = always with that pixel-tile class
 int g_fuse_lead_off = 0;  // ... + 16: without the next block's leading 1x1

@@ -513,6 +513,266 @@ int rgbd_ref_deconv_s2_nchw(const float* x_dev, int32_t n, int32_t cin, int32_t 
     return rc;
 }
 
+// ---- the conv launchers in every form the engine issues (test hook: tests/test_gpu_convforms.py; include/rgbd_amd.h) ---------
+// conv2d_nchw_impl above always builds the plainest ConvArgs.  This one fills the fields Engine::conv_plan / conv_issue fill
+// -- fused tail, lead layer, gate / skip operands, second destination, channel-slice placement, second operand set -- and
+// calls launch_conv / launch_conv_fused, the functions conv_issue calls.
+namespace {
+// channels a launch stores: Engine::conv_plan's rule
+inline int forms_cout_store(int c, int cs) { return (c % 16 && cs != round_up(c, 16)) ? round_up(c, 4) : round_up(c, 16); }
+// channels [off, off + c) of a tensor of `total` channels as a destination of `store` channels: in bounds, and what is
+// stored past the slice lands in the buffer's own pad channels (permuted layout: whole groups of 16 only)
+inline bool forms_dst_ok(int off, int c, int total, int store, bool perm)
+{
+    if (total <= 0 || total > 65536 || off < 0 || off % (perm ? 16 : 4) || c <= 0 || off + c > total) return false;
+    if (store != c && off + c != total) return false;
+    if (perm && store != round_up(c, 16)) return false;
+    return off + store <= round_up(total, 16);
+}
+struct FormsSet {
+    PackedConv pc, pc2, pc3;
+    float *x = nullptr, *y = nullptr, *y2 = nullptr, *y3 = nullptr, *r1 = nullptr, *m = nullptr, *r2 = nullptr, *part = nullptr;
+};
+}  // namespace
+
+int rgbd_conv_forms_nchw(const rgbd_conv_forms_desc* d, void* stream)
+{
+    std::unique_lock<std::shared_mutex> cap_lk(g_capture_mu);  // frees / synchronous copies: not while a stream captures
+    // ---- host checks: nothing is allocated or launched before all of them have passed -----------------------------------------
+    if (!d || d->groups < 0 || d->groups > 2) return RGBD_EINVAL;
+    const int G = d->groups == 2 ? 2 : 1;
+    const int n = d->n, cin = d->cin, h = d->h, w = d->w, cout = d->cout, k = d->k, stride = d->stride, pad = d->pad;
+    const bool tr = d->transposed != 0, refmode = d->refmode != 0, fused = d->cout2 > 0, lead = d->cout3 > 0;
+    if (!tensor_ok(n, cin, h, w) || cout <= 0 || cout > 65536 || k < 1 || k > 5 || stride < 1 || stride > 2 || pad < 0 || pad > k ||
+        d->act < ACT_NONE || d->act > ACT_SIGMOID || d->cout2 < 0 || d->cout2 > 65536 || d->cout3 < 0 || d->cout3 > 65536 ||
+        (lead && !fused))
+        return RGBD_EINVAL;
+    if (!tr && (h + 2 * pad < k || w + 2 * pad < k)) return RGBD_EINVAL;
+    const int OH = tr ? (h - 1) * stride - 2 * pad + k + (stride - 1) : (h + 2 * pad - k) / stride + 1;
+    const int OW = tr ? (w - 1) * stride - 2 * pad + k + (stride - 1) : (w + 2 * pad - k) / stride + 1;
+    const int cy = fused ? d->cout2 : cout;  // channels of y
+    if (OH <= 0 || OW <= 0 || !tensor_ok(n, cy, OH, OW) || !tensor_ok(n, cout, OH, OW)) return RGBD_EINVAL;
+    const int perm = refmode ? 1 : 0;
+    const int cin_pad = round_up(cin, 16), cout_pad = round_up(cout, 16), cout2_pad = round_up(d->cout2, 16), cout3_pad = round_up(d->cout3, 16);
+    // placement
+    if (d->x_total <= 0 || d->x_total > 65536 || d->x_off < 0 || d->x_off % 16 || d->x_off + cin > d->x_total || !tensor_ok(n, d->x_total, h, w))
+        return RGBD_EINVAL;
+    const int xcs = round_up(d->x_total, 16), ycs = round_up(std::max(d->y_total, 1), 16), y2cs = round_up(std::max(d->y2_total, 1), 16),
+              y3cs = round_up(std::max(d->y3_total, 1), 16);
+    const int cout_store = forms_cout_store(cy, ycs);
+    if (!forms_dst_ok(d->y_off, cy, d->y_total, cout_store, perm) || !tensor_ok(n, d->y_total, OH, OW)) return RGBD_EINVAL;
+    const bool dup = d->set[0].y2_dev != nullptr;
+    if (dup && (forms_cout_store(cy, y2cs) != cout_store || !forms_dst_ok(d->y2_off, cy, d->y2_total, cout_store, perm) ||
+                !tensor_ok(n, d->y2_total, OH, OW)))
+        return RGBD_EINVAL;
+    if (lead && (!forms_dst_ok(d->y3_off, d->cout3, d->y3_total, cout3_pad, perm) || !tensor_ok(n, d->y3_total, OH, OW))) return RGBD_EINVAL;
+    // operand sets: required pointers, and a twin for every pointer of a grouped call (conv_groups_ok's rule, on the host tensors)
+    for (int g = 0; g < G; ++g) {
+        const rgbd_conv_forms_ops& o = d->set[g];
+        if (!o.x_dev || !o.weight || !o.y_dev || (fused && !o.w2) || (!fused && (o.w2 || o.bias2)) || (lead && (!o.w3 || !o.y3_dev)) ||
+            (!lead && (o.w3 || o.bias3 || o.y3_dev)))
+            return RGBD_EINVAL;
+        const rgbd_conv_forms_ops& z = d->set[0];
+        if (!o.bias != !z.bias || !o.bias2 != !z.bias2 || !o.bias3 != !z.bias3 || !o.res1_dev != !z.res1_dev || !o.mul_dev != !z.mul_dev ||
+            !o.res2_dev != !z.res2_dev || !o.y2_dev != !z.y2_dev)
+            return RGBD_EINVAL;
+    }
+    const rgbd_conv_forms_ops& o0 = d->set[0];
+    // what the launchers refuse (launch_conv / launch_conv_fused / launch_cfg)
+    ConvArgs a{};
+    a.cin_pad = cin_pad;
+    int splitk = 1, cls = 0;
+    const int ckbd = g_force_ckbd;
+    const int nphase = tr ? stride * stride : 1, IS = tr ? 1 : stride, OS = tr ? stride : 1;
+    if (ckbd && (nphase != 1 || IS != 1 || OS != 1)) return RGBD_EINVAL;
+    if (refmode) {
+        if (d->bias_mode < 0 || d->bias_mode > 2 || d->nblocks < 0 || d->nblocks > 256 || (d->nblocks > 0 && !d->blocks) || (tr && stride != 1))
+            return RGBD_EINVAL;
+        a.bias_mode = d->bias_mode;
+        a.exact_math = d->flags & 1;
+        if ((d->flags & 2) && d->blocks && d->nblocks > 1 && d->nblocks <= 16) {  // the blocks as split-K ranges (as conv2d_nchw_impl)
+            int pos = 0;
+            for (int b = 0; b < d->nblocks; ++b) {
+                if (d->blocks[b] <= 0 || d->blocks[b] % 16) return RGBD_EINVAL;
+                a.split_c16[b] = (uint16_t)(pos / 16);
+                pos += d->blocks[b];
+            }
+            a.split_c16[d->nblocks] = (uint16_t)((pos + 15) / 16);
+            if (d->bias_mode == 1 || fused || (pos + 15) / 16 != cin_pad / 16) return RGBD_EINVAL;
+            splitk = d->nblocks;
+        } else if (d->blocks && d->nblocks == 1) {
+            if (d->blocks[0] != cin) return RGBD_EINVAL;
+            if (a.bias_mode == 1) a.bias_mode = 0;  // (one block: S_0 + bias is the epilogue's add)
+        } else if (set_blocks(&a, d->blocks, d->nblocks)) {
+            return RGBD_EINVAL;
+        }
+        if (a.blocked && d->blocks) {  // (the table was checked against the padded width: the blocks must add up to cin itself)
+            long pos = 0;
+            for (int b = 0; b < d->nblocks; ++b) pos += d->blocks[b];
+            if (pos != cin) return RGBD_EINVAL;
+        }
+    } else {
+        if (d->nblocks || d->blocks || d->bias_mode || d->flags) return RGBD_EINVAL;
+        if (g_force_splitk > 0 && !fused) splitk = std::max(1, std::min(g_force_splitk, cin_pad / 16));
+    }
+    if (fused) {
+        if (tr || stride != 1 || k * k > 9 || cout_pad != 96 || cout2_pad % 96 || ckbd || o0.mul_dev || o0.res2_dev || dup ||
+            (d->act != ACT_NONE && d->act != ACT_RELU && d->act != ACT_LEAKY) || (d->act_mid != ACT_NONE && d->act_mid != ACT_RELU))
+            return RGBD_EINVAL;
+        if (lead && (cout3_pad != 96 || cout2_pad % 32)) return RGBD_EINVAL;
+        cls = conv_fused_plan(cout_pad, cout2_pad, k * k, n * G, OH, OW, 0);
+        if (cls != 1 && cls != 2 && cls != 4) return RGBD_EINVAL;  // (0: the plan would not fuse this pair on this grid)
+    } else {
+        if (d->act_mid) return RGBD_EINVAL;
+        if (dup && splitk > 1) return RGBD_EINVAL;  // the reducer has one destination
+        if (a.blocked && splitk > 1) return RGBD_EINVAL;
+    }
+    if ((size_t)cout_pad * k * k * cin_pad * 4 >= ((size_t)1 << 32)) return RGBD_EINVAL;
+
+    // ---- device side --------------------------------------------------------------------------------------------------------
+    hipStream_t s = (hipStream_t)stream;
+    DevBufs b;
+    DevGen gen;  // (owns the packed weights: released on every way out)
+    FormsSet fs[2];
+    const size_t opx = (size_t)n * OH * OW;
+    int rc = RGBD_OK;
+    // every destination is followed by a guard band of one output row and one pixel, checked after the launch: a store predicate
+    // that lets a tile run past the last image's last row or pixel is reported (RGBD_ESTATE), not left to land in foreign memory
+    const std::vector<uint32_t> guard_pat((size_t)(OW + 1) * std::max(ycs, std::max(y2cs, y3cs)), 0xC0FFEE42u);
+    auto guard_arm = [&](float* p, int cs) {
+        return hipMemcpy(p + opx * cs, guard_pat.data(), (size_t)(OW + 1) * cs * 4, hipMemcpyHostToDevice) == hipSuccess ? RGBD_OK : RGBD_EHIP;
+    };
+    auto guard_intact = [&](const float* p, int cs) {
+        std::vector<uint32_t> back((size_t)(OW + 1) * cs);
+        if (hipMemcpy(back.data(), p + opx * cs, back.size() * 4, hipMemcpyDeviceToHost) != hipSuccess) return RGBD_EHIP;
+        return memcmp(back.data(), guard_pat.data(), back.size() * 4) ? RGBD_ESTATE : RGBD_OK;
+    };
+    for (int g = 0; g < G && !rc; ++g) {
+        const rgbd_conv_forms_ops& o = d->set[g];
+        FormsSet& f = fs[g];
+        HostTensor hw, hb;
+        hw.shape = tr ? std::vector<int64_t>{cin, cout, k, k} : std::vector<int64_t>{cout, cin, k, k};
+        hw.v.assign(o.weight, o.weight + (size_t)cin * cout * k * k);
+        if (o.bias) hb.shape = {cout}, hb.v.assign(o.bias, o.bias + cout);
+        rc = pack_conv(hw, o.bias ? &hb : nullptr, tr, &f.pc, &gen, perm, perm);
+        if (!rc && fused) {
+            HostTensor hw2, hb2;
+            hw2.shape = {d->cout2, cout, 1, 1};
+            hw2.v.assign(o.w2, o.w2 + (size_t)d->cout2 * cout);
+            if (o.bias2) hb2.shape = {d->cout2}, hb2.v.assign(o.bias2, o.bias2 + d->cout2);
+            rc = pack_conv(hw2, o.bias2 ? &hb2 : nullptr, false, &f.pc2, &gen, perm, perm);
+        }
+        if (!rc && lead) {
+            HostTensor hw3, hb3;
+            hw3.shape = {d->cout3, d->cout2, 1, 1};
+            hw3.v.assign(o.w3, o.w3 + (size_t)d->cout3 * d->cout2);
+            if (o.bias3) hb3.shape = {d->cout3}, hb3.v.assign(o.bias3, o.bias3 + d->cout3);
+            rc = pack_conv(hw3, o.bias3 ? &hb3 : nullptr, false, &f.pc3, &gen, perm, perm);
+        }
+        if (rc) return rc;
+        const int cyp = round_up(cy, 16);
+        f.x = b.get((size_t)n * h * w * xcs);
+        f.y = b.get((opx + OW + 1) * ycs);
+        if (o.y2_dev) f.y2 = b.get((opx + OW + 1) * y2cs);
+        if (lead) f.y3 = b.get((opx + OW + 1) * y3cs);
+        if (o.res1_dev) f.r1 = b.get((opx + OW + 1) * cyp);  // (the same slack as behind the destinations: what is read there is not used)
+        if (o.mul_dev) f.m = b.get((opx + OW + 1) * cyp);
+        if (o.res2_dev) f.r2 = b.get((opx + OW + 1) * cyp);
+        if (splitk > 1) f.part = b.get((size_t)splitk * opx * cout_pad);
+        if (!f.x || !f.y || (o.y2_dev && !f.y2) || (lead && !f.y3) || (o.res1_dev && !f.r1) || (o.mul_dev && !f.m) || (o.res2_dev && !f.r2) ||
+            (splitk > 1 && !f.part))
+            return RGBD_ENOMEM;
+        rc = guard_arm(f.y, ycs);
+        if (!rc && f.y2) rc = guard_arm(f.y2, y2cs);
+        if (!rc && f.y3) rc = guard_arm(f.y3, y3cs);
+        if (!rc) rc = launch_nchw_to_nhwc16(o.x_dev, n, d->x_total, h, w, f.x, xcs, s, perm);
+        if (!rc) rc = launch_nchw_to_nhwc16(o.y_dev, n, d->y_total, OH, OW, f.y, ycs, s, perm);
+        if (!rc && f.y2) rc = launch_nchw_to_nhwc16(o.y2_dev, n, d->y2_total, OH, OW, f.y2, y2cs, s, perm);
+        if (!rc && f.y3) rc = launch_nchw_to_nhwc16(o.y3_dev, n, d->y3_total, OH, OW, f.y3, y3cs, s, perm);
+        if (!rc && f.r1) rc = launch_nchw_to_nhwc16(o.res1_dev, n, cy, OH, OW, f.r1, cyp, s, perm);
+        if (!rc && f.m) rc = launch_nchw_to_nhwc16(o.mul_dev, n, cy, OH, OW, f.m, cyp, s, perm);
+        if (!rc && f.r2) rc = launch_nchw_to_nhwc16(o.res2_dev, n, cy, OH, OW, f.r2, cyp, s, perm);
+    }
+    if (!rc) {
+        const FormsSet& f = fs[0];
+        const int cyp = round_up(cy, 16);
+        a.x = f.x + d->x_off;
+        a.N = n;
+        a.H = h;
+        a.W = w;
+        a.xcs = xcs;
+        a.w = f.pc.w;
+        a.ntaps_total = k * k;
+        a.bias = f.pc.bias;
+        a.y = f.y + d->y_off;
+        a.OH = OH;
+        a.OW = OW;
+        a.ycs = ycs;
+        a.cout_pad = cout_pad;
+        a.cout_store = cout_store;
+        make_taps(f.pc, stride, pad, &a);
+        a.GH = tr ? h : OH;
+        a.GW = tr ? w : OW;
+        a.act = d->act;
+        a.ckbd = ckbd;
+        a.splitk = splitk;
+        a.partial = f.part;
+        if (f.r1) a.res1 = f.r1, a.r1cs = cyp;
+        if (f.m) a.mul = f.m, a.mcs = cyp;
+        if (f.r2) a.res2 = f.r2, a.r2cs = cyp;
+        if (f.y2) a.y2 = f.y2 + d->y2_off, a.y2cs = y2cs;
+        if (fused) {
+            a.w2 = f.pc2.w;
+            a.bias2 = f.pc2.bias;
+            a.cout2_pad = cout2_pad;
+            a.act_mid = d->act_mid;
+            if (refmode) a.tail_bias_init = 1;  // (Engine::plan_refnum)
+        }
+        if (lead) {
+            a.w3 = f.pc3.w;
+            a.bias3 = f.pc3.bias;
+            a.y3 = f.y3 + d->y3_off;
+            a.y3cs = y3cs;
+            a.cout3_pad = cout3_pad;
+        }
+        if (G == 2) {  // (Engine::conv_issue)
+            const FormsSet& q = fs[1];
+            a.groups = 2;
+            a.g1.x = q.x + d->x_off;
+            a.g1.w = q.pc.w;
+            a.g1.bias = q.pc.bias;
+            a.g1.y = q.y + d->y_off;
+            a.g1.res1 = q.r1;
+            a.g1.mul = q.m;
+            a.g1.res2 = q.r2;
+            a.g1.partial = q.part;
+            a.g1.y2 = q.y2 ? q.y2 + d->y2_off : nullptr;
+            a.g1.w2 = fused ? q.pc2.w : nullptr;
+            a.g1.bias2 = fused ? q.pc2.bias : nullptr;
+            a.g1.w3 = lead ? q.pc3.w : nullptr;
+            a.g1.bias3 = lead ? q.pc3.bias : nullptr;
+            a.g1.y3 = lead ? q.y3 + d->y3_off : nullptr;
+        }
+        rc = fused ? launch_conv_fused(a, s) : launch_conv(a, s);
+    }
+    for (int g = 0; g < G && !rc; ++g) {
+        const rgbd_conv_forms_ops& o = d->set[g];
+        const FormsSet& f = fs[g];
+        rc = launch_nhwc_to_nchw_clamp(f.y, n, d->y_total, OH, OW, ycs, o.y_dev, 0, s, perm);
+        if (!rc && f.y2) rc = launch_nhwc_to_nchw_clamp(f.y2, n, d->y2_total, OH, OW, y2cs, o.y2_dev, 0, s, perm);
+        if (!rc && f.y3) rc = launch_nhwc_to_nchw_clamp(f.y3, n, d->y3_total, OH, OW, y3cs, o.y3_dev, 0, s, perm);
+    }
+    const hipError_t e = hipStreamSynchronize(s);
+    if (!rc && e != hipSuccess) rc = RGBD_EHIP;
+    for (int g = 0; g < G && !rc; ++g) {
+        const FormsSet& f = fs[g];
+        rc = guard_intact(f.y, ycs);
+        if (!rc && f.y2) rc = guard_intact(f.y2, y2cs);
+        if (!rc && f.y3) rc = guard_intact(f.y3, y3cs);
+    }
+    return rc;
+}
+
 int rgbd_debug_force_tile(const char* cfg)
 {
     snprintf(g_conv_force, sizeof(g_conv_force), "%s", cfg ? cfg : "");
