@@ -298,6 +298,18 @@ int rgbd_elic_decompress_single(rgbd_elic* m, const uint8_t* const* y, const int
  * inverse of compress for a batch as well; forward's x_hat is not clamped.  Debug tensors: y, z, zhat, yhat, latent_means,
  * latent_scales. */
 int rgbd_elic_create_stf_single(int32_t in_ch, rgbd_elic** out);
+/* The checkerboard Cheng2020 model (models/Cheng2020withCKBD.py:40-174: Cheng2020AnchorwithCheckerboard, on CompressAI's
+ * Cheng2020Anchor, compressai/models/waseda.py:22-81; N = 128 or 192, M = N, in_ch = 3 or 1): residual blocks of 3x3 / 1x1
+ * convolutions with GDN / IGDN (one fused launch each, see rgbd_gdn_nchw), sub-pixel up-sampling, a hyper prior and a two-pass
+ * checkerboard entropy model: entropy_parameters(cat(0, hyper)) codes the anchor half of y ((row + col) odd), the masked 5x5
+ * context convolution over the decoded anchors (the mask of :28-35 is applied when the weights are packed) feeds
+ * entropy_parameters(cat(ctx, hyper)) for the other half.  Served by the three *_single entry points of this section:
+ * compress (:101-136) puts both halves of all images of a call into ONE y stream, anchor half first, each in (n, c, row, w/2)
+ * order (per_image_streams: one stream per image); decompress (:138-174) does not clamp x_hat; forward is the eval forward()
+ * (:52-71): y_hat = round(y), the context over the whole grid with its anchor outputs zeroed, one parameter pass.
+ * rgbd_elic_get_refnum returns 0; rgbd_elic_set_forced_symbols works for modality 0.  Debug tensors: y, z, zhat, hyper, yhat,
+ * ctx, means, scales. */
+int rgbd_elic_create_ckbd(int32_t N, int32_t in_ch, rgbd_elic** out);
 /* Eval-mode forward() of the single-modal model (models/elic.py:60-161 with config quant = "ste"): x_hat [B,in_ch,H,W]
  * (not clamped), likelihoods of y [B,M,H/16,W/16] and of z [B,N,H/64,W/64] ("y_likelihoods" / "z_likelihoods"). */
 int rgbd_elic_forward_single(rgbd_elic* m, const float* x_dev, int32_t B, int32_t H, int32_t W, float* xhat_dev, float* lik_y,
@@ -484,6 +496,29 @@ int rgbd_patch_merge_gather(const float* x, int32_t B, int32_t H, int32_t W, int
                             void* stream);
 int rgbd_pixel_shuffle2(const float* x, int32_t B, int32_t H, int32_t W, int32_t Co, int32_t xcs, float* y, int32_t ycs,
                         void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------------
+ * GDN / IGDN (CompressAI/compressai/layers/gdn.py:22-67), the normalisation of Cheng2020's ResidualBlockWithStride /
+ * ResidualBlockUpsample (layers.py:67-126), as ONE launch on the fp32 MFMA:
+ *     y[n][i][p] = x[n][i][p] * f(beta'[i] + sum_j gamma'[i][j] * x[n][j][p]^2)  (+ res[n][i][p]),
+ * f = 1 / sqrt (inverse = 0) or sqrt (inverse = 1).  It replaces gdn.py:52-67 (parametrizers, x ** 2, F.conv2d, rsqrt / sqrt,
+ * multiply) and the `out += identity` of layers.py:97,125.  x_dev / res_dev (optional, may be NULL) / y_dev: device tensors,
+ * NCHW fp32, contiguous; beta [c] and gamma [c][c] are the RAW parameters of the state_dict on the host: beta' / gamma' =
+ * NonNegativeParametrizer.forward (ops/parametrizers.py:42-45) applied here in fp32, bit for bit torch's values.  Every
+ * element is one fp32 chain from beta' over j, a correctly rounded sqrt, an IEEE divide (inverse = 0), the multiply and the
+ * add; the bits do not depend on the batch or on the pixel tile.  c in [1, 512], not necessarily a multiple of 16.
+ * Returns RGBD_EINVAL (-22) before anything is launched or written on a NULL x / beta / gamma / y, c <= 0, c > 512, a
+ * non-positive extent or inverse outside {0, 1}.  Synchronous on return.
+ * rgbd_gdn_parametrize: the parameter map alone (host only; is_beta selects the lower bound: 1 = beta, 0 = gamma).
+ * rgbd_debug_force_gdn_tile: pixels per workgroup, 64 / 32 (one wave per 16 pixels) or 16 (the output channels spread over
+ * four waves: small grids), 0 = automatic (default).  Same bits for every tile.
+ * rgbd_gdn_bench: kernel-only time of one launch on NHWC scratch buffers, as rgbd_conv_bench (tools/gdn_probe.py).
+ * ------------------------------------------------------------------------------------------------------------- */
+int rgbd_gdn_nchw(const float* x_dev, int32_t n, int32_t c, int32_t h, int32_t w, const float* beta, const float* gamma,
+                  int32_t inverse, const float* res_dev, float* y_dev, void* stream);
+int rgbd_gdn_parametrize(const float* raw, int64_t n, int32_t is_beta, float* out);
+int rgbd_debug_force_gdn_tile(int32_t pixels);
+int rgbd_gdn_bench(int32_t n, int32_t c, int32_t h, int32_t w, int32_t inverse, int32_t with_residual, int32_t iters, float* ms_out);
 
 /* Bytes of HBM workspace this engine instance holds (grows with the largest call shape seen, never shrinks); the packed
  * weights, shared by all instances of a pool, are not included.  bench.py reports it as config.hbm_workspace_gib. */

@@ -22,6 +22,9 @@ modelZoo["STF_united"] = SymmetricalTransFormerUnited  # models/__init__.py:11-2
 from .stf import STF, SymmetricalTransFormer  # noqa: F401,E402
 
 modelZoo["STF"] = SymmetricalTransFormer  # after "STF_united": the testers match model names by substring in zoo order
+from .ckbd import Cheng2020AnchorwithCheckerboard  # noqa: F401,E402
+
+modelZoo["ckbd"] = Cheng2020AnchorwithCheckerboard  # last: no zoo name contains "ckbd" and "ckbd" contains none of them
 from .pool import CodecPool  # noqa: F401,E402
 from . import datautils, ioutils, metrics, tester  # noqa: F401,E402
 from .tester import TesterSingle, TesterUnited  # noqa: F401,E402

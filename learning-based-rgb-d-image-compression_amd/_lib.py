@@ -9,7 +9,7 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _SO = os.path.join(_HERE, "librgbd_amd.so")
 _SO = os.environ.get("RGBD_AMD_LIB", _SO)  # A/B builds: point at another librgbd_amd.so
-_SRCS = ["conv_mfma.hip", "conv_mfma_blk.hip", "pointwise.hip", "swin.hip", "entropy.hip", "metrics.hip", "coder_abi.hip", "engine.hip", "engine_abi.hip"]
+_SRCS = ["conv_mfma.hip", "conv_mfma_blk.hip", "pointwise.hip", "swin.hip", "entropy.hip", "metrics.hip", "coder_abi.hip", "gdn.hip", "engine.hip", "engine_abi.hip"]
 _LIB = None
 
 ERRORS = {-22: "invalid argument", -12: "out of memory", -5: "HIP runtime error", -28: "buffer too small",
@@ -56,7 +56,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
                                os.path.join(csrc, "tile_table_blk.h"), os.path.join(csrc, "tile_table_blk_loaded.h")],
              "conv_mfma_blk.hip": [body]}
     hdrs.append(os.path.join(csrc, "splitk_table.h"))
-    extra["coder_abi.hip"] = [os.path.join(csrc, "engine_internal.h")]
+    extra["coder_abi.hip"] = extra["gdn.hip"] = [os.path.join(csrc, "engine_internal.h")]
     extra["engine.hip"] = extra["engine_abi.hip"] = [os.path.join(csrc, "engine_internal.h"), os.path.join(csrc, "engine.h")]
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     os.makedirs(objdir, exist_ok=True)
@@ -144,11 +144,16 @@ def lib():
         "rgbd_elic_create_stf": (ctypes.c_int, [c_i32, c_i32, i32p, c_i32, ctypes.POINTER(c_vp)]),
         "rgbd_elic_create_single": (ctypes.c_int, [c_i32, c_i32, i32p, c_i32, c_i32, ctypes.POINTER(c_vp)]),
         "rgbd_elic_create_stf_single": (ctypes.c_int, [c_i32, ctypes.POINTER(c_vp)]),
+        "rgbd_elic_create_ckbd": (ctypes.c_int, [c_i32, c_i32, ctypes.POINTER(c_vp)]),
         "rgbd_slice_quant_index": (ctypes.c_int, [c_vp, c_i32, c_vp, c_i32, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i64,
                                                   c_i64, f32p, c_vp, c_vp, c_vp, c_i32, c_vp, c_i32, c_vp]),
         "rgbd_slice_dequant": (ctypes.c_int, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i64, c_i64, c_vp, c_i32,
                                               c_vp, c_i32, c_vp]),
         "rgbd_lrp_update": (ctypes.c_int, [c_vp, c_i32, c_vp, c_i32, c_i64, c_i32, c_vp, c_i32, c_vp, c_i32, c_vp, c_i32, c_vp]),
+        "rgbd_gdn_nchw": (ctypes.c_int, [c_vp, c_i32, c_i32, c_i32, c_i32, f32p, f32p, c_i32, c_vp, c_vp, c_vp]),
+        "rgbd_gdn_parametrize": (ctypes.c_int, [f32p, c_i64, c_i32, f32p]),
+        "rgbd_debug_force_gdn_tile": (ctypes.c_int, [c_i32]),
+        "rgbd_gdn_bench": (ctypes.c_int, [c_i32] * 7 + [f32p]),
         "rgbd_elic_compress_single": (ctypes.c_int, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp]),
         "rgbd_elic_forward_single": (ctypes.c_int, [c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
         "rgbd_elic_decompress_single": (ctypes.c_int, [c_vp, u8pp, i64p, c_i32, u8pp, i64p, c_i32, c_i32, c_i32, c_vp, c_vp]),
@@ -204,7 +209,8 @@ EXPORTS = ["rgbd_abi_version", "rgbd_set_blocking_sync", "rgbd_get_blocking_sync
            "rgbd_elic_decompress", "rgbd_elic_create_r2d", "rgbd_elic_create_stf", "rgbd_elic_create_single", "rgbd_elic_compress_single", "rgbd_elic_decompress_single", "rgbd_elic_forward_single", "rgbd_elic_compress_united", "rgbd_elic_decompress_united", "rgbd_elic_debug_tensor", "rgbd_elic_debug_symbols", "rgbd_elic_set_debug_floats", "rgbd_elic_debug_floats", "rgbd_elic_set_forced_symbols", "rgbd_elic_set_profile", "rgbd_elic_graph_count", "rgbd_elic_workspace_bytes", "rgbd_msssim_workspace_bytes", "rgbd_msssim_stats", "rgbd_layernorm", "rgbd_debug_force_layernorm_form",
            "rgbd_layernorm2", "rgbd_window_attention", "rgbd_patch_merge_gather", "rgbd_pixel_shuffle2",
            "rgbd_elic_profile_read", "rgbd_elic_profile_read_executed", "rgbd_debug_force_splitk", "rgbd_debug_force_fuse", "rgbd_debug_force_subpix", "rgbd_debug_force_pair", "rgbd_debug_fail_captures", "rgbd_debug_force_ckbd", "rgbd_debug_force_blocked", "rgbd_debug_bench_streams", "rgbd_elic_set_tile_mode", "rgbd_debug_force_tile", "rgbd_debug_conv_log", "rgbd_debug_conv_log_read", "rgbd_debug_tile_override", "rgbd_conv_bench",
-           "rgbd_elic_profile_dump", "rgbd_elic_create_stf_single", "rgbd_slice_quant_index", "rgbd_slice_dequant", "rgbd_lrp_update"]
+           "rgbd_elic_profile_dump", "rgbd_elic_create_stf_single", "rgbd_slice_quant_index", "rgbd_slice_dequant", "rgbd_lrp_update",
+           "rgbd_elic_create_ckbd", "rgbd_gdn_nchw", "rgbd_gdn_parametrize", "rgbd_debug_force_gdn_tile", "rgbd_gdn_bench"]
 
 
 _BS_HOLDERS = 0

@@ -528,6 +528,67 @@ def stf_entries(channel: int = 3) -> "OrderedDict[str, Entry]":
     return b.entries
 
 
+def ckbd_config(N: int = 192) -> Config:
+    """Cheng2020 anchor model with the checkerboard context (models/Cheng2020withCKBD.py:46-50): M = N, one slice."""
+    cfg = model_config()
+    cfg["N"], cfg["M"], cfg["slice_num"], cfg["slice_ch"] = int(N), int(N), 1, [int(N)]
+    return cfg
+
+
+def ckbd_entries(N: int = 192, channel: int = 3) -> "OrderedDict[str, Entry]":
+    """Every state_dict entry of Cheng2020AnchorwithCheckerboard (reference: models/Cheng2020withCKBD.py:40-50 on
+    CompressAI/compressai/models/waseda.py:22-81; 160 tensors, 26,598,956 parameters for N=192, channel=3): residual blocks
+    of 3x3 / 1x1 convolutions with GDN / IGDN, sub-pixel up-sampling, three 1x1 entropy-parameter layers and the 5x5
+    checkerboard context convolution (its mask is a buffer; the state_dict holds the unmasked weight)."""
+    b = _Builder()
+    b.entropy_bottleneck("entropy_bottleneck", N)
+
+    def gdn(name):  # layers/gdn.py:35-50, ops/parametrizers.py:28-37
+        b.entries[f"{name}.beta"] = Entry((N,), "gdn_beta")
+        b.entries[f"{name}.gamma"] = Entry((N, N), "gdn_gamma")
+        for r in ("beta_reparam", "gamma_reparam"):
+            b.buffer(f"{name}.{r}.pedestal", (1,))
+            b.buffer(f"{name}.{r}.lower_bound.bound", (1,))
+
+    def res_block(name):  # layers.py:129-159
+        b.conv(f"{name}.conv1", N, N, 3)
+        b.conv(f"{name}.conv2", N, N, 3)
+
+    for i in range(3):  # waseda.py:38-46
+        cin = channel if i == 0 else N
+        p = f"g_a.{2 * i}"  # ResidualBlockWithStride, layers.py:67-98
+        b.conv(f"{p}.conv1", cin, N, 3)
+        b.conv(f"{p}.conv2", N, N, 3)
+        gdn(f"{p}.gdn")
+        b.conv(f"{p}.skip", cin, N, 1)
+        res_block(f"g_a.{2 * i + 1}")
+    b.conv("g_a.6", N, N, 3)
+    for i in range(3):  # waseda.py:72-81
+        res_block(f"g_s.{2 * i}")
+        p = f"g_s.{2 * i + 1}"  # ResidualBlockUpsample, layers.py:101-126
+        b.conv(f"{p}.subpel_conv.0", N, 4 * N, 3)
+        b.conv(f"{p}.conv", N, N, 3)
+        gdn(f"{p}.igdn")
+        b.conv(f"{p}.upsample.0", N, 4 * N, 3)
+    res_block("g_s.6")
+    b.conv("g_s.7.0", N, 4 * channel, 3)
+    for k in range(5):  # waseda.py:48-58
+        b.conv(f"h_a.{2 * k}", N, N, 3)
+    b.conv("h_s.0", N, N, 3)  # waseda.py:60-70
+    b.conv("h_s.2.0", N, 4 * N, 3)
+    b.conv("h_s.4", N, N * 3 // 2, 3)
+    b.conv("h_s.6.0", N * 3 // 2, 4 * (N * 3 // 2), 3)
+    b.conv("h_s.8", N * 3 // 2, 2 * N, 3)
+    b.gaussian_conditional("gaussian_conditional")
+    M = N
+    b.conv("entropy_parameters.0", M * 12 // 3, M * 10 // 3, 1)  # priors.py:403-409
+    b.conv("entropy_parameters.2", M * 10 // 3, M * 8 // 3, 1)
+    b.conv("entropy_parameters.4", M * 8 // 3, M * 6 // 3, 1)
+    b.conv("context_prediction", M, 2 * M, 5)  # Cheng2020withCKBD.py:48-50
+    b.buffer("context_prediction.mask", (2 * M, M, 5, 5))
+    return b.entries
+
+
 def count_parameters(entries) -> int:
     n = 0
     for e in entries.values():

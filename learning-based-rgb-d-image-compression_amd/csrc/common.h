@@ -245,6 +245,24 @@ int launch_window_attention(const float* qkv, int B, int H, int W, int C, int qc
 int launch_patch_merge_gather(const float* x, int B, int H, int W, int C, int xcs, float* y, int ycs, hipStream_t s);
 int launch_pixel_shuffle2(const float* x, int B, int H, int W, int Co, int xcs, float* y, int ycs, hipStream_t s);
 
+// ---- GDN / IGDN (gdn.hip) -----------------------------------------------------------------------
+// out = x * f(beta + gamma * x^2) (+ res) per pixel; f = 1 / sqrt, or sqrt when inverse (gdn.py:52-67)
+struct GdnArgs {
+    const float* x;  // NHWC, pad channels zero
+    int xcs;
+    float* y;
+    int ycs;
+    const float* res;  // optional: added last (layers.py:97,125)
+    int rcs;
+    long npix;  // N * H * W
+    int cs;     // channels computed: the layer's channel count rounded up to 16
+    const float* beta;   // [cs], parametrized (gdn_pack)
+    const float* gamma;  // [cs / 16][cs / 16][64][4] MFMA fragments, parametrized (gdn_pack)
+    int inverse;
+};
+int launch_gdn(const GdnArgs& a, hipStream_t s);
+int gdn_tile_for(long npix, int cs);  // pixels per workgroup the launch uses (16 / 32 / 64); never changes a result
+
 // ---- entropy stage (entropy.hip) --------------------------------------------------------------
 struct DevTables {  // packed CDF rows for the device coder
     const uint16_t* cdf;  // concatenated rows, entries [0, size-1) (the final 65536 is implicit)

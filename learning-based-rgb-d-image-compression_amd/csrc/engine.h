@@ -1,5 +1,6 @@
 // Host runtime of the gfx950 codec engine, part 1 of 3: weight packing, the workspace arena and `struct rgbd_elic` -- the
-// layer graph of the five model variants (ELIC_united, single-modal ELIC, STF_united, ELIC_united_R2D, single-modal STF) as inline methods
+// layer graph of the six model variants (ELIC_united, single-modal ELIC, STF_united, ELIC_united_R2D, single-modal STF, checkerboard
+// Cheng2020) as inline methods
 // that plan and issue HIP kernel launches on one stream, the conv planner (tiles, split-K, reference arithmetic) and the
 // per-call-shape HIP-graph cache.  engine.hip holds the call paths (compress / decompress / forward), engine_abi.hip the
 // C ABI (include/rgbd_amd.h).  Everything shared between those two translation units is `inline` here (one instance).
@@ -9,6 +10,7 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -496,8 +498,8 @@ struct rgbd_elic {
     int N = 192, M = 320;
     int tile_mode = 0;  // rgbd_elic_set_tile_mode: 0 latency tiles (isolated launches), 1 throughput tiles (shared chip)
     int variant = 0;  // 0: ELIC_united (RGB + depth), 1: single-modal ELIC (models/elic.py), 2: STF_united, 3: ELIC_united_R2D,
-                      // 4: single-modal STF (models/stf.py)
-    bool single() const { return variant == 1 || variant == 4; }
+                      // 4: single-modal STF (models/stf.py), 5: checkerboard Cheng2020 (models/Cheng2020withCKBD.py)
+    bool single() const { return variant == 1 || variant == 4 || variant == 5; }
     int in_ch = 3;    // image channels of the single-modal variant
     std::vector<int> slice_ch;
     std::map<std::string, HostTensor> raw;
@@ -2799,6 +2801,201 @@ struct rgbd_elic {
         }
     }
 
+    // ---- checkerboard Cheng2020 (models/Cheng2020withCKBD.py:40-174 on compressai/models/waseda.py:22-81): residual blocks of
+    // 3x3 / 1x1 convolutions with GDN / IGDN, sub-pixel up-sampling, and a two-pass checkerboard entropy model on one slice of
+    // M = N channels ----------------------------------------------------------------------------------------------------
+    // GDN / IGDN (layers/gdn.py:52-67) + the block's `out += identity` (layers.py:97,125) as one launch (gdn.hip).  In the
+    // profile it counts as the 1x1 convolution it contains (2 C^2 FLOPs per pixel).
+    Act gdn(const std::string& name, const Act& x, bool inverse, const Act* res)
+    {
+        Act y = alloc(x.n, x.h, x.w, x.c);
+        if (dry() || rc) return y;
+        float* beta = dense_of(name + ".beta");
+        float* gamma = dense_of(name + ".gamma");
+        if (!beta || !gamma) return y;
+        GdnArgs a{};
+        a.x = x.p;
+        a.xcs = x.cs;
+        a.y = y.p;
+        a.ycs = y.cs;
+        a.res = res ? res->p : nullptr;
+        a.rcs = res ? res->cs : 0;
+        a.npix = (long)x.n * x.h * x.w;
+        a.cs = round_up(x.c, 16);
+        a.beta = beta;
+        a.gamma = gamma;
+        a.inverse = inverse ? 1 : 0;
+        hipEvent_t e1 = nullptr;
+        if (profile) {
+            if (ev_used + 2 > ev_pool.size()) {
+                for (int i = 0; i < 256; ++i) {
+                    hipEvent_t e;
+                    if (hipEventCreate(&e) != hipSuccess) {
+                        fail(RGBD_EHIP);
+                        return y;
+                    }
+                    ev_pool.push_back(e);
+                }
+            }
+            (void)hipEventRecord(ev_pool[ev_used++], s);
+            e1 = ev_pool[ev_used++];
+        }
+        const int r = launch_gdn(a, s);
+        if (profile) {
+            (void)hipEventRecord(e1, s);
+            const double fl = 2.0 * (double)a.npix * x.c * x.c;
+            prof_flops += fl;
+            prof_flops_exec += fl;
+            ++prof_launches;
+            ev_names.push_back({name, fl, fl});
+        }
+        if (r) fail(r);
+        return y;
+    }
+    Act pixel_shuffle(const Act& t)
+    {
+        Act u = alloc(t.n, 2 * t.h, 2 * t.w, t.c / 4);
+        if (!dry() && !rc) {
+            const int q = launch_pixel_shuffle2(t.p, t.n, t.h, t.w, t.c / 4, t.cs, u.p, u.cs, s);
+            if (q) fail(q);
+        }
+        return u;
+    }
+    // layers.py:129-159: leaky(conv2(leaky(conv1 x))) + x
+    Act ck_res_block(const std::string& p, const Act& x)
+    {
+        Epi e1, e2;
+        e1.act = e2.act = ACT_LEAKY;
+        e2.res2 = &x;
+        return conv(p + ".conv2", conv(p + ".conv1", x, 1, 1, e1), 1, 1, e2);
+    }
+    // layers.py:67-98: GDN(conv2(leaky(conv1 x, stride 2))) + skip(x) (1x1, stride 2)
+    Act ck_res_block_stride(const std::string& p, const Act& x)
+    {
+        Epi leaky;
+        leaky.act = ACT_LEAKY;
+        const Act t = conv(p + ".conv2", conv(p + ".conv1", x, 2, 1, leaky), 1, 1);
+        const Act id = conv(p + ".skip", x, 2, 0);
+        return gdn(p + ".gdn", t, false, &id);
+    }
+    // layers.py:101-126: IGDN(conv(leaky(subpel_conv x))) + upsample(x); the two sub-pixel convs read the same tensor with
+    // the same layer shape: one grouped launch.  LeakyReLU is pointwise, so it rides in front of the shuffle.
+    Act ck_res_block_up(const std::string& p, const Act& x)
+    {
+        const std::string n[2] = {p + ".subpel_conv.0", p + ".upsample.0"};
+        const Act xin[2] = {x, x};
+        Epi ep[2];
+        ep[0].act = ACT_LEAKY;
+        Act t[2];
+        conv2(2, n, xin, 1, 1, ep, nullptr, t);
+        const Act u = conv(p + ".conv", pixel_shuffle(t[0]), 1, 1);
+        const Act id = pixel_shuffle(t[1]);
+        return gdn(p + ".igdn", u, true, &id);
+    }
+    // waseda.py:38-46.  Every stage's temporaries are released once its output has been copied down.
+    Act ck_stage(const Act& x, const std::function<Act(const Act&)>& f, int oh, int ow, int oc)
+    {
+        Act out = alloc(x.n, oh, ow, oc);
+        const size_t mark = arena.top;
+        copy_ch(f(x), out);
+        arena.top = mark;
+        return out;
+    }
+    Act g_a_ckbd(const Act& img)
+    {
+        Act x = img;
+        for (int i = 0; i < 3; ++i) {
+            const std::string a = "g_a." + std::to_string(2 * i), b = "g_a." + std::to_string(2 * i + 1);
+            x = ck_stage(x, [&](const Act& t) { return ck_res_block(b, ck_res_block_stride(a, t)); }, x.h / 2, x.w / 2, N);
+        }
+        return conv("g_a.6", x, 2, 1);
+    }
+    // waseda.py:72-81
+    Act g_s_ckbd(const Act& yhat)
+    {
+        Act x = yhat;
+        for (int i = 0; i < 3; ++i) {
+            const std::string a = "g_s." + std::to_string(2 * i), b = "g_s." + std::to_string(2 * i + 1);
+            x = ck_stage(x, [&](const Act& t) { return ck_res_block_up(b, ck_res_block(a, t)); }, 2 * x.h, 2 * x.w, N);
+        }
+        return pixel_shuffle(conv("g_s.7.0", ck_res_block("g_s.6", x), 1, 1));
+    }
+    // waseda.py:48-58
+    Act h_a_ckbd(const Act& y)
+    {
+        static const int strides[5] = {1, 1, 2, 1, 2};
+        Epi leaky;
+        leaky.act = ACT_LEAKY;
+        Act t = y;
+        for (int k = 0; k < 5; ++k) t = conv("h_a." + std::to_string(2 * k), t, strides[k], 1, k < 4 ? leaky : Epi());
+        return t;
+    }
+    // waseda.py:60-70; the last layer writes the hyper half of the entropy-parameter input [ctx 2M | hyper 2M]
+    void h_s_ckbd(const Act& zhat, const Act& dst)
+    {
+        Epi leaky;
+        leaky.act = ACT_LEAKY;
+        const size_t mark = arena.top;
+        Act t = conv("h_s.0", zhat, 1, 1, leaky);
+        t = pixel_shuffle(conv("h_s.2.0", t, 1, 1, leaky));
+        t = conv("h_s.4", t, 1, 1, leaky);
+        t = pixel_shuffle(conv("h_s.6.0", t, 1, 1, leaky));
+        conv("h_s.8", t, 1, 1, Epi(), &dst);
+        arena.top = mark;
+    }
+    // priors.py:403-409: three 1x1 convolutions.  part 1 (anchor, Cheng2020withCKBD.py:122-124): the context half of the
+    // input is zero, so the first layer runs on the hyper half of its input channels only ("entropy_parameters.0.hyper": the
+    // same chain without terms that are exact zeros); 1x1 layers do not mix positions, so each pass computes and stores its
+    // own checkerboard half of `out` (part 0: the whole grid, forward()).
+    void ck_entropy_params(const Act& cat, int part, const Act& out)
+    {
+        Epi leaky, lin;
+        leaky.act = ACT_LEAKY;
+        leaky.ckbd = lin.ckbd = g_ckbd_conv ? part : 0;
+        const size_t mark = arena.top;
+        Act t = part == 1 ? conv("entropy_parameters.0.hyper", view(cat, 2 * M, 2 * M), 1, 0, leaky)
+                          : conv("entropy_parameters.0", cat, 1, 0, leaky);
+        t = conv("entropy_parameters.2", t, 1, 0, leaky);
+        conv("entropy_parameters.4", t, 1, 0, lin, &out);
+        arena.top = mark;
+    }
+    // CheckerboardContext (Cheng2020withCKBD.py:12-37): the weight is masked when packed; only the 12 taps with (ky + kx) odd
+    // are issued and only the non-anchor outputs computed (the anchor half of dst is left as it is: zeros)
+    void ck_context(const Act& yhat, const Act& dst)
+    {
+        Epi e;
+        e.ckbd = 2;
+        ConvPlan cp = conv_plan("context_prediction", yhat, 1, 2, e, &dst);
+        if (!dry() && cp.ok && cp.a.nphase == 1) {
+            TapTable& t = cp.a.taps;
+            int n = 0;
+            for (int k = 0; k < t.n[0]; ++k) {
+                if (!((t.dy[0][k] + t.dx[0][k]) & 1)) continue;
+                t.dy[0][n] = t.dy[0][k];
+                t.dx[0][n] = t.dx[0][k];
+                t.wt[0][n] = t.wt[0][k];
+                ++n;
+            }
+            cp.flops_exec = cp.flops * 0.5 * n / std::max(1, (int)t.n[0]);
+            for (int k = n; k < 25; ++k) t.dy[0][k] = t.dx[0][k] = t.wt[0][k] = 0;
+            t.n[0] = (int8_t)n;
+        }
+        conv_issue(cp);
+    }
+    // Cheng2020withCKBD.py:121-130 / 154-167: cat = [ctx 2M | hyper 2M] with the context half zeroed and the hyper half filled;
+    // params = [scales M | means M]: the anchor pass leaves its half there, the non-anchor pass the other half
+    void two_pass_ckbd(Coding& cd, const Act* y, const Act& cat, const Act& params, const Act& yhat)
+    {
+        yhat_base[0] = yhat.p;
+        const int64_t part_syms = (int64_t)M * cat.h * (cat.w / 2);
+        const Act ys = y ? *y : Act();
+        ck_entropy_params(cat, 1, params);
+        code_part(cd, 0, 1, params, ys, yhat, 0);
+        ck_context(yhat, view(cat, 0, 2 * M));
+        ck_entropy_params(cat, 2, params);
+        code_part(cd, 0, 0, params, ys, yhat, part_syms);
+    }
+
     // ---- stream I/O of the call paths (engine.hip), for nm = 1 (single-modal ELIC) or 2 modalities ----------------------
     // workspace of a compress call: symbols, indexes and stream slots of every modality, and the stream geometry
     struct EncBufs {
@@ -2836,6 +3033,11 @@ struct rgbd_elic {
     int run_compress_stf1(const float* x_dev, int B, int H, int W, int per_image);
     int run_forward_stf1(const float* x_dev, int B, int H, int W, float* xhat_dev, float* ly, float* lz);
     int run_decompress_stf1(const uint8_t* const* ys, const int64_t* ylen, int n_y, const uint8_t* const* zs, const int64_t* zlen,
+                            int B, int zh, int zw, float* x_out);
+    // the checkerboard Cheng2020 model (variant 5) behind the same entry points
+    int run_compress_ckbd(const float* x_dev, int B, int H, int W, int per_image);
+    int run_forward_ckbd(const float* x_dev, int B, int H, int W, float* xhat_dev, float* ly, float* lz);
+    int run_decompress_ckbd(const uint8_t* const* ys, const int64_t* ylen, int n_y, const uint8_t* const* zs, const int64_t* zlen,
                             int B, int zh, int zw, float* x_out);
 
     // lat != nullptr: the Bi-CEE stage alone (compress_united / decompress_united): latents and hyper parameters come

@@ -992,3 +992,261 @@ int rgbd_elic::run_decompress_stf1(const uint8_t* const* ys, const int64_t* ylen
     // ==== epilogue (never captured)
     return launch_nhwc_to_nchw_clamp(xh.p, B, in_ch, H, W, xh.cs, x_out, 1, s);  // stf.py:815: clamped to [0, 1]
 }
+
+// ---- checkerboard Cheng2020 (models/Cheng2020withCKBD.py): compress :101-136, decompress :138-174, eval-mode forward :52-71 ---
+// Both checkerboard halves of all images of the call go into ONE y stream, anchor half first (per-image streams: one per
+// image, each with its own two halves); the decoder resumes its rANS state between the halves.
+int rgbd_elic::run_compress_ckbd(const float* x_dev, int B, int H, int W, int per_image)
+{
+    const int h = H / 16, w = W / 16, zh = H / 64, zw = W / 64;
+    const int64_t T = (int64_t)M * h * w, Tz = (int64_t)N * zh * zw;
+    ref_batch = per_image ? 1 : B;
+    named.clear();
+    pre_leads.clear();
+    arena.reset();
+    rc = 0;
+    EncBufs e;
+    if (const int r = enc_streams(1, B, T, Tz, per_image, &e)) return r;
+    int32_t *fy = nullptr, *fz = nullptr;  // teacher forcing (rgbd_elic_set_forced_symbols, modality 0)
+    if (!force_y[0].empty()) {
+        if (force_y[0].size() != (size_t)(B * T)) return RGBD_EINVAL;
+        fy = (int32_t*)arena.take(sizeof(int32_t) * (size_t)(B * T));
+        if (!dry()) HIP_TRY(hipMemcpyAsync(fy, force_y[0].data(), sizeof(int32_t) * (size_t)(B * T), hipMemcpyHostToDevice, s));
+    }
+    if (!force_z[0].empty()) {
+        if (force_z[0].size() != (size_t)(B * Tz)) return RGBD_EINVAL;
+        fz = (int32_t*)arena.take(sizeof(int32_t) * (size_t)(B * Tz));
+        if (!dry()) HIP_TRY(hipMemcpyAsync(fz, force_z[0].data(), sizeof(int32_t) * (size_t)(B * Tz), hipMemcpyHostToDevice, s));
+    }
+    Act x = alloc(B, H, W, in_ch);
+    if (!dry()) {
+        const int r = launch_nchw_to_nhwc16(x_dev, B, in_ch, H, W, x.p, x.cs, s);
+        if (r) return r;
+    }
+    // ==== body: captured into / replayed from a HIP graph per call shape ================================================
+    if (body_begin()) {
+        if (!dry()) {
+            const int zr = launch_fill_zero((float*)e.err, 64, s);  // (a kernel, not a memset node: DESIGN 3.5)
+            if (zr) fail(zr);
+        }
+        Act y = alloc(B, h, w, M);
+        {
+            const size_t mark = arena.top;
+            copy_ch(g_a_ckbd(x), y);
+            arena.top = mark;
+        }
+        Act z = h_a_ckbd(y);
+        named["y"] = y;
+        named["z"] = z;
+        Act zhat = alloc(B, zh, zw, N);
+        float* md = dense_of("entropy_bottleneck.medians");
+        if (!dry() && !rc && md) {
+            int r = launch_z_quant(z.p, z.cs, B, zh, zw, N, md, e.zsym, e.zidx, s, 0);
+            if (!r)
+                r = launch_rans_encode(e.zsym, e.zidx, e.meta + 2 * B, e.meta + 3 * B, B, B, tables[2].d, tables[2].d, e.zwords,
+                                       e.zcap, e.meta + 6 * B, e.err, s);
+            if (!r) r = launch_z_dequant(fz ? fz : e.zsym, B, zh, zw, N, md, zhat.p, zhat.cs, s, 0);
+            if (r) fail(r);
+        }
+        named["zhat"] = zhat;
+        Act cat = alloc(B, h, w, 4 * M), params = alloc(B, h, w, 2 * M), yhat = alloc(B, h, w, M);
+        if (!dry() && !rc) {
+            const int r = launch_fill_zero(cat.p, cat.elems(), s);
+            if (r) fail(r);
+        }
+        h_s_ckbd(zhat, view(cat, 2 * M, 2 * M));
+        named["hyper"] = view(cat, 2 * M, 2 * M);
+        named["ctx"] = view(cat, 0, 2 * M);
+        named["scales"] = view(params, 0, M);
+        named["means"] = view(params, M, M);
+        named["yhat"] = yhat;
+        Coding cd;
+        cd.encode = true;
+        cd.per_image = per_image;
+        cd.per_image_total = T;
+        cd.sym = e.sym;
+        cd.idx = e.idx;
+        cd.stream_base = e.meta;
+        cd.force = fy;
+        two_pass_ckbd(cd, &y, cat, params, yhat);
+        if (!dry() && !rc) {
+            const int ny = e.ny;
+            const int r = launch_rans_encode(e.sym, e.idx, e.meta + 8 * B, e.meta + 8 * B + ny, ny, ny, tables[0].d, tables[0].d,
+                                             e.ywords, e.ycap, e.meta + 8 * B + 2 * ny, e.err, s);
+            if (r) fail(r);
+        }
+    }  // body
+    {
+        const int r = body_end();
+        if (rc) return rc;
+        if (r) return r;
+    }
+    if (dry()) return RGBD_OK;
+    return fetch_streams(1, B, true, e);
+}
+
+// y_hat = round(y) (quantize "dequantize" without means, :61), the context over the whole grid with its anchor outputs zeroed
+// (:63-66), ONE parameter pass (:67-68), likelihoods of round(y - mean) + mean (:69)
+int rgbd_elic::run_forward_ckbd(const float* x_dev, int B, int H, int W, float* xhat_dev, float* ly, float* lz)
+{
+    const int h = H / 16, w = W / 16, zh = H / 64, zw = W / 64;
+    ref_batch = B;
+    named.clear();
+    pre_leads.clear();
+    arena.reset();
+    rc = 0;
+    dbg_sym = dbg_idx = nullptr;  // forward() keeps no symbols: the last compress()'s are gone with its workspace layout
+    dbg_x = dbg_s = nullptr;
+    Act x = alloc(B, H, W, in_ch);
+    if (!dry()) {
+        const int r = launch_nchw_to_nhwc16(x_dev, B, in_ch, H, W, x.p, x.cs, s);
+        if (r) return r;
+    }
+    Act xh, lik, zlik;
+    if (body_begin()) {
+        Act y = alloc(B, h, w, M);
+        {
+            const size_t mark = arena.top;
+            copy_ch(g_a_ckbd(x), y);
+            arena.top = mark;
+        }
+        Act z = h_a_ckbd(y);
+        Act zhat = alloc(B, zh, zw, N);
+        zlik = alloc(B, zh, zw, N);
+        if (!dry() && !rc) {
+            float* md = dense_of("entropy_bottleneck.medians");
+            float* prm = dense_of("entropy_bottleneck.cumulative");
+            if (md && prm) {
+                const int r = launch_eb_forward(z.p, z.cs, B, zh, zw, N, md, prm, zhat.p, zlik.p, s, 0);
+                if (r) fail(r);
+            }
+        }
+        Act cat = alloc(B, h, w, 4 * M), params = alloc(B, h, w, 2 * M), yhat = alloc(B, h, w, M), scratch = alloc(B, h, w, M);
+        lik = alloc(B, h, w, M);
+        PartGeom g{};
+        g.B = B;
+        g.h = h;
+        g.w = w;
+        g.C = M;
+        g.per_image = 1;
+        g.perm = 0;
+        if (!dry() && !rc) {
+            int r = launch_fill_zero(cat.p, cat.elems(), s);
+            if (!r) r = launch_fill_zero(params.p, params.elems(), s);
+            // round(y): the quantiser of the parts with zero means (its likelihoods go to `lik`, overwritten below)
+            for (int anchor = 1; anchor >= 0 && !r; --anchor) {
+                g.anchor = anchor;
+                r = launch_ckbd_estimate_part(y.p, y.cs, params.p, params.cs, yhat.p, yhat.cs, lik.p, lik.cs, g, s);
+            }
+            if (r) fail(r);
+        }
+        h_s_ckbd(zhat, view(cat, 2 * M, 2 * M));
+        ck_context(yhat, view(cat, 0, 2 * M));
+        ck_entropy_params(cat, 0, params);
+        if (!dry() && !rc) {
+            int r = 0;
+            for (int anchor = 1; anchor >= 0 && !r; --anchor) {
+                g.anchor = anchor;
+                r = launch_ckbd_estimate_part(y.p, y.cs, params.p, params.cs, scratch.p, scratch.cs, lik.p, lik.cs, g, s);
+            }
+            if (r) fail(r);
+        }
+        named["y"] = y;
+        named["z"] = z;
+        named["zhat"] = zhat;
+        named["hyper"] = view(cat, 2 * M, 2 * M);
+        named["ctx"] = view(cat, 0, 2 * M);
+        named["scales"] = view(params, 0, M);
+        named["means"] = view(params, M, M);
+        named["yhat"] = yhat;
+        xh = g_s_ckbd(yhat);
+        if (cur_ge && !dry()) {
+            cur_ge->out[0] = xh;
+            cur_ge->out[1] = lik;
+            cur_ge->out[2] = zlik;
+        }
+    } else {
+        xh = cur_ge->out[0];
+        lik = cur_ge->out[1];
+        zlik = cur_ge->out[2];
+    }
+    {
+        const int r = body_end();
+        if (rc) return rc;
+        if (r) return r;
+    }
+    if (dry()) return RGBD_OK;
+    int r = launch_nhwc_to_nchw_clamp(xh.p, B, in_ch, H, W, xh.cs, xhat_dev, 0, s);
+    if (!r) r = launch_nhwc_to_nchw_clamp(lik.p, B, M, h, w, lik.cs, ly, 0, s, 0);
+    if (!r) r = launch_nhwc_to_nchw_clamp(zlik.p, B, N, zh, zw, zlik.cs, lz, 0, s, 0);
+    if (!r) r = wait_stream();
+    return r;
+}
+
+int rgbd_elic::run_decompress_ckbd(const uint8_t* const* ys, const int64_t* ylen, int n_y, const uint8_t* const* zs,
+                                   const int64_t* zlen, int B, int zh, int zw, float* x_out)
+{
+    const int h = zh * 4, w = zw * 4, H = zh * 64, W = zw * 64;
+    const int64_t T = (int64_t)M * h * w, Tz = (int64_t)N * zh * zw;
+    const int per_image = (n_y == B) ? 1 : 0;
+    ref_batch = per_image ? 1 : B;
+    named.clear();
+    pre_leads.clear();
+    arena.reset();
+    rc = 0;
+
+    // ==== prologue (never captured): upload the streams
+    DecBufs d;
+    if (const int r = dec_streams(1, &ys, &ylen, n_y, &zs, &zlen, B, B, T, Tz, per_image, &d)) return r;
+
+    // ==== body: captured into / replayed from a HIP graph per call shape ================================================
+    Act xh;
+    if (body_begin()) {
+        Act zhat = alloc(B, zh, zw, N);
+        float* md = dense_of("entropy_bottleneck.medians");
+        if (!dry() && md) {
+            int q = launch_fill_zero(zhat.p, zhat.elems(), s);
+            if (!q) q = launch_z_quant(zhat.p, zhat.cs, B, zh, zw, N, md, d.zsym, d.zidx, s, 0);  // indexes = channel id
+            if (!q) q = launch_rans_decode(d.words, d.zoff, d.zlen, B, d.zstate, 1, d.zidx, d.zsym, d.zbase, 0, Tz, tables[2].d, s);
+            if (!q) q = launch_z_dequant(d.zsym, B, zh, zw, N, md, zhat.p, zhat.cs, s, 0);
+            if (q) fail(q);
+        }
+        named["zhat"] = zhat;
+        Act cat = alloc(B, h, w, 4 * M), params = alloc(B, h, w, 2 * M), yhat = alloc(B, h, w, M);
+        if (!dry() && !rc) {
+            const int r = launch_fill_zero(cat.p, cat.elems(), s);
+            if (r) fail(r);
+        }
+        h_s_ckbd(zhat, view(cat, 2 * M, 2 * M));
+        named["hyper"] = view(cat, 2 * M, 2 * M);
+        named["ctx"] = view(cat, 0, 2 * M);
+        named["scales"] = view(params, 0, M);
+        named["means"] = view(params, M, M);
+        named["yhat"] = yhat;
+        Coding cd;
+        cd.encode = false;
+        cd.per_image = per_image;
+        cd.per_image_total = T;
+        cd.sym = d.sym;
+        cd.idx = d.idx;
+        cd.stream_base = d.ybase;
+        cd.words = d.words;
+        cd.stream_off = d.yoff;
+        cd.stream_len = d.ylen;
+        cd.state = d.state;
+        cd.nstreams = n_y;
+        two_pass_ckbd(cd, nullptr, cat, params, yhat);
+        xh = g_s_ckbd(yhat);
+        if (cur_ge && !dry()) cur_ge->out[0] = xh;
+    } else {
+        xh = cur_ge->out[0];
+    }
+    {
+        const int r = body_end();
+        if (rc) return rc;
+        if (r) return r;
+    }
+    if (dry()) return RGBD_OK;
+    // ==== epilogue (never captured)
+    return launch_nhwc_to_nchw_clamp(xh.p, B, in_ch, H, W, xh.cs, x_out, 0, s);  // Cheng2020withCKBD.py:167-174: not clamped
+}

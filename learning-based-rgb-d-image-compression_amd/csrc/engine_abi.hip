@@ -1049,6 +1049,19 @@ int rgbd_elic_create_stf_single(int32_t in_ch, rgbd_elic** out)
     return RGBD_OK;
 }
 
+// Cheng2020AnchorwithCheckerboard (models/Cheng2020withCKBD.py:46-50): M = N, one slice of N channels
+int rgbd_elic_create_ckbd(int32_t N, int32_t in_ch, rgbd_elic** out)
+{
+    if ((N != 128 && N != 192) || (in_ch != 3 && in_ch != 1)) return RGBD_EINVAL;
+    const int32_t slice = N;
+    const int r = rgbd_elic_create(N, N, &slice, 1, out);
+    if (r) return r;
+    (*out)->variant = 5;
+    (*out)->in_ch = in_ch;
+    (*out)->refnum = false;  // (this family keeps the single-chain arithmetic, like STF: DESIGN.md 4a)
+    return RGBD_OK;
+}
+
 int rgbd_elic_compress_single(rgbd_elic* m, const float* x_dev, int32_t B, int32_t H, int32_t W, int32_t per_image_streams,
                               void* stream)
 {
@@ -1060,6 +1073,7 @@ int rgbd_elic_compress_single(rgbd_elic* m, const float* x_dev, int32_t B, int32
     char key[96];
     snprintf(key, sizeof(key), "c1|%d|%d|%d|%d", B, H, W, per_image);
     r = run_sized(m, key, [&]() {
+        if (m->variant == 5) return m->run_compress_ckbd(x_dev, B, H, W, per_image);
         return m->variant == 4 ? m->run_compress_stf1(x_dev, B, H, W, per_image) : m->run_compress1(x_dev, B, H, W, per_image);
     });
     if (m->profile) m->profile_collect();
@@ -1077,6 +1091,7 @@ int rgbd_elic_forward_single(rgbd_elic* m, const float* x_dev, int32_t B, int32_
     char key[96];
     snprintf(key, sizeof(key), "f1|%d|%d|%d", B, H, W);
     return run_sized(m, key, [&]() {
+        if (m->variant == 5) return m->run_forward_ckbd(x_dev, B, H, W, xhat_dev, lik_y, lik_z);
         return m->variant == 4 ? m->run_forward_stf1(x_dev, B, H, W, xhat_dev, lik_y, lik_z)
                                : m->run_forward1(x_dev, B, H, W, xhat_dev, lik_y, lik_z);
     });
@@ -1094,6 +1109,7 @@ int rgbd_elic_decompress_single(rgbd_elic* m, const uint8_t* const* y, const int
     char key[96];
     snprintf(key, sizeof(key), "d1|%d|%d|%d|%d", B, zh, zw, n_y);
     r = run_sized(m, key, [&]() {
+        if (m->variant == 5) return m->run_decompress_ckbd(y, y_len, n_y, z, z_len, B, zh, zw, x_dev);
         return m->variant == 4 ? m->run_decompress_stf1(y, y_len, n_y, z, z_len, B, zh, zw, x_dev)
                                : m->run_decompress1(y, y_len, n_y, z, z_len, B, zh, zw, x_dev);
     });
@@ -1280,10 +1296,37 @@ int rgbd_elic_finalize(rgbd_elic* m)
             const int k0 = (int)t.shape[2];
             const int cin0 = transposed ? (int)t.shape[0] : (int)t.shape[1], cout0 = transposed ? (int)t.shape[1] : (int)t.shape[0];
             const bool image_in = !transposed && cin0 <= 3 && k0 == 5, image_out = transposed && cout0 <= 4 && k0 == 5;
-            const int r = pack_conv(t, bit == m->raw.end() ? nullptr : &bit->second, transposed, &pc, gen.get(), image_in ? 0 : pm,
+            const HostTensor* src = &t;
+            HostTensor masked;
+            if (m->variant == 5 && name == "context_prediction.weight") {
+                // CheckerboardContext (Cheng2020withCKBD.py:28-35): the state_dict holds the unmasked weight, the reference
+                // multiplies it by the mask at every call; only the taps with (ky + kx) odd survive
+                masked = t;
+                const size_t kk = (size_t)k0 * k0;
+                for (size_t i = 0; i < masked.v.size(); ++i) {
+                    const size_t tap = i % kk;
+                    if (!((tap / k0 + tap % k0) & 1)) masked.v[i] = 0.f;
+                }
+                src = &masked;
+            }
+            const int r = pack_conv(*src, bit == m->raw.end() ? nullptr : &bit->second, transposed, &pc, gen.get(), image_in ? 0 : pm,
                                     image_out ? 0 : pm);
             if (r) return r;
             convs[name] = pc;
+            if (m->variant == 5 && name == "entropy_parameters.0.weight") {
+                // the anchor pass (Cheng2020withCKBD.py:122-123) feeds zeros into the context half of this layer's input
+                // channels [ctx 2M | hyper 2M]: the same layer on the hyper half alone
+                const int half = cin0 / 2;
+                HostTensor hw;
+                hw.shape = {cout0, half, 1, 1};
+                hw.v.resize((size_t)cout0 * half);
+                for (int co = 0; co < cout0; ++co)
+                    for (int ci = 0; ci < half; ++ci) hw.v[(size_t)co * half + ci] = t.v[(size_t)co * cin0 + half + ci];
+                PackedConv ph;
+                const int r5 = pack_conv(hw, bit == m->raw.end() ? nullptr : &bit->second, false, &ph, gen.get(), 0, 0);
+                if (r5) return r5;
+                convs["entropy_parameters.0.hyper.weight"] = ph;
+            }
             if (!transposed && pc.cin <= 3 && pc.k == 5) {  // the image-consuming layer: also as a 1x1 over a K-packed input
                 PackedConv pk;
                 const int r4 = pack_kpack(t, bit == m->raw.end() ? nullptr : &bit->second, &pk, gen.get(), pm);
@@ -1296,6 +1339,19 @@ int rgbd_elic_finalize(rgbd_elic* m)
                 if (r3) return r3;
                 convs[name.substr(0, name.size() - 6) + "subpix.weight"] = ps;
             }
+        } else if (ends_with(name, ".gamma") && t.shape.size() == 2 && t.shape[0] == t.shape[1]) {
+            // GDN / IGDN (layers/gdn.py): NonNegativeParametrizer.forward applied once here, in fp32; packed for gdn.hip
+            const std::string bname = name.substr(0, name.size() - 5) + "beta";
+            auto bit = m->raw.find(bname);
+            const int C = (int)t.shape[0];
+            if (bit == m->raw.end() || (int)bit->second.v.size() != C || C > 512) return RGBD_EINVAL;
+            std::vector<float> hb, hg;
+            gdn_pack(bit->second.v.data(), t.v.data(), C, &hb, &hg);
+            float *db = nullptr, *dg = nullptr;
+            if (const int r = dev_copy(hb.data(), hb.size(), &db)) return r;
+            if (const int r = dev_copy(hg.data(), hg.size(), &dg)) return r;
+            dense[bname] = db;
+            dense[name] = dg;
         } else if (ends_with(name, ".weight") && t.shape.size() == 2) {
             // SE_Block linears; fc.2 ([C][hidden]) is kept transposed so the gate kernel reads it coalesced
             std::vector<float> hv = t.v;
@@ -1590,7 +1646,7 @@ int rgbd_elic_set_forced_symbols(rgbd_elic* m, int32_t modality, const int32_t* 
 {
     std::unique_lock<std::shared_mutex> cap_lk(g_capture_mu);
     if (!m || modality < 0 || modality > 1 || n_y < 0 || n_z < 0 || (n_y && !y_sym) || (n_z && !z_sym)) return RGBD_EINVAL;
-    if (m->single()) return RGBD_EINVAL;  // (the two-modality codecs only)
+    if (m->single() && (m->variant != 5 || modality != 0)) return RGBD_EINVAL;  // (the two-modality codecs, and modality 0 of the checkerboard Cheng2020 model)
     m->graphs_invalidate();  // the workspace layout and the launch list change
     m->force_y[modality].assign(y_sym, y_sym + n_y);
     m->force_z[modality].assign(z_sym, z_sym + n_z);

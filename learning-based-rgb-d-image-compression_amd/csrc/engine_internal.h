@@ -40,3 +40,8 @@ struct rgbd_tables {
 extern std::shared_mutex g_capture_mu;
 
 int64_t rgbd_enc_cap_words(int64_t n);  // worst-case words of one stream of n symbols (rgbd_rans_max_bytes / 4)
+
+// GDN parameters (gdn.hip): NonNegativeParametrizer.forward in fp32 on the host, and the packing of one layer's raw beta [c] /
+// gamma [c][c] into the operands of GdnArgs
+void gdn_parametrize(const float* raw, int64_t n, int is_beta, float* out);
+void gdn_pack(const float* beta_raw, const float* gamma_raw, int c, std::vector<float>* beta, std::vector<float>* gamma);

@@ -13,7 +13,7 @@ from collections import OrderedDict
 
 import numpy as np
 
-from .arch import (STF_SLICES, Entry, elic_entries, elic_united_entries, elic_united_r2d_entries, model_config, stf_config,
+from .arch import (STF_SLICES, Entry, ckbd_config, ckbd_entries, elic_entries, elic_united_entries, elic_united_r2d_entries, model_config, stf_config,
                    stf_entries, stf_single_config, stf_united_entries)
 
 _IH_STD = math.sqrt(4.0 * (65536.0**2 - 1.0) / 12.0)  # std of the sum of four uniform 16-bit ints
@@ -52,6 +52,9 @@ def _eb_matrix_init(shape, index: int, filters=(3, 3, 3, 3), init_scale=10.0) ->
     return np.full(shape, init, dtype=np.float32)
 
 
+GDN_PEDESTAL = np.float32((2.0 ** -18) ** 2)  # NonNegativeParametrizer: reparam_offset ** 2
+
+
 def make_tensor(name: str, e: Entry, seed: int) -> np.ndarray:
     if e.kind in ("conv_w", "deconv_w", "bias"):
         # torch's default Conv2d/ConvTranspose2d init, U(-1/sqrt(fan_in), 1/sqrt(fan_in)); the reference's
@@ -67,6 +70,11 @@ def make_tensor(name: str, e: Entry, seed: int) -> np.ndarray:
         return uniform_like(name, seed, e.shape, -0.1, 0.1)
     if e.kind == "rpb_table":  # trunc_normal_(std=0.02) in the reference; wider here so the bias matters
         return normal_like(name, seed, e.shape, 0.3)
+    if e.kind == "gdn_beta":  # layers/gdn.py:43-45: NonNegativeParametrizer(minimum=1e-6).init(ones)
+        return np.sqrt(np.maximum(np.ones(e.shape, np.float32) + GDN_PEDESTAL, GDN_PEDESTAL)).astype(np.float32)
+    if e.kind == "gdn_gamma":  # gdn.py:48-50: init(0.1 * eye)
+        g = np.float32(0.1) * np.eye(e.shape[0], dtype=np.float32)
+        return np.sqrt(np.maximum(g + GDN_PEDESTAL, GDN_PEDESTAL)).astype(np.float32)
     if e.kind == "eb_matrix":
         idx = int(name[-1])
         return _eb_matrix_init(e.shape, idx) + normal_like(name, seed, e.shape, 0.05)
@@ -89,6 +97,16 @@ def make_tensor(name: str, e: Entry, seed: int) -> np.ndarray:
             c = np.stack(np.meshgrid(np.arange(ws), np.arange(ws), indexing="ij")).reshape(2, -1)
             rel = (c[:, :, None] - c[:, None, :]).transpose(1, 2, 0) + (ws - 1)
             return (rel[:, :, 0] * (2 * ws - 1) + rel[:, :, 1]).astype(np.int64)
+        if name.endswith(".pedestal"):  # ops/parametrizers.py:34-37
+            return np.array([GDN_PEDESTAL], dtype=np.float32)
+        if name.endswith("_reparam.lower_bound.bound"):
+            minimum = 1e-6 if ".beta_reparam." in name else 0.0
+            return np.array([(minimum + (2.0 ** -18) ** 2) ** 0.5], dtype=np.float32)
+        if name.endswith("context_prediction.mask"):  # Cheng2020withCKBD.py:28-31
+            m = np.zeros(e.shape, dtype=np.float32)
+            m[:, :, 0::2, 1::2] = 1
+            m[:, :, 1::2, 0::2] = 1
+            return m
         if name.endswith(".target"):
             t = math.log(2.0 / 1e-9 - 1.0)  # entropy_models.py:309-310
             return np.array([-t, 0.0, t], dtype=np.float32)
@@ -101,9 +119,10 @@ def make_tensor(name: str, e: Entry, seed: int) -> np.ndarray:
 
 
 def synthetic_state_dict(seed: int = 0, config=None, stress: bool = True, as_torch: bool = True,
-                         model: str = "ELIC_united", channel: int = 3, recipe: str = None):
+                         model: str = "ELIC_united", channel: int = 3, recipe: str = None, N: int = 192):
     """Full state_dict (parameters + buffers) of ELIC_united (default), ELIC_united_R2D, STF_united, the single-modal STF
-    (model="STF": recipes "stress" and "plain") or the single-modal ELIC with deterministic synthetic values.  `recipe`: "stress" (= stress=True, the default: ~22 bpp, wide CDF rows, 17 % escapes -- the worst
+    (model="STF": recipes "stress" and "plain"), the checkerboard Cheng2020 model (model="ckbd", width N, the same two recipes)
+    or the single-modal ELIC with deterministic synthetic values.  `recipe`: "stress" (= stress=True, the default: ~22 bpp, wide CDF rows, 17 % escapes -- the worst
     case for the entropy coder), "trained_like" (ELIC_united only: latents mostly inside the dead zone, scales near the
     bottom of the scale table, ~1 bpp per modality like a trained q=2_2 model -- the coder's realistic operating point),
     "high_rate" (ELIC_united only: latents of tens to hundreds, predicted scales of 10 ... 100 -- scale-table rows of 300 ...
@@ -119,6 +138,9 @@ def synthetic_state_dict(seed: int = 0, config=None, stress: bool = True, as_tor
     elif model == "STF":
         cfg = stf_single_config()
         entries = stf_entries(channel)
+    elif model == "ckbd":
+        cfg = ckbd_config(N)
+        entries = ckbd_entries(N, channel)
     else:
         cfg = model_config() if config is None else config
         entries = {"ELIC_united": elic_united_entries, "ELIC_united_R2D": elic_united_r2d_entries}.get(model)
@@ -134,6 +156,8 @@ def synthetic_state_dict(seed: int = 0, config=None, stress: bool = True, as_tor
             sd[f"g_a.{mod}_ana_layers.4.downsample.reduction.weight"] *= np.float32(STF_Y_GAIN)
     elif stress and model == "STF":
         _apply_stress_stf(sd)
+    elif stress and model == "ckbd":
+        _apply_stress_ckbd(sd, seed, N)
     elif stress:
         _apply_stress_single(sd, cfg)
     if recipe == "trained_like":
@@ -237,6 +261,37 @@ def _apply_stress_stf(sd):
         sd[f"cc_scale_transforms.{i}.8.bias"][:] = g["scale_b"]
         sd[f"cc_mean_transforms.{i}.8.weight"] *= g["mean_w"]
         sd[f"lrp_transforms.{i}.8.weight"] *= g["lrp_w"]
+
+
+# checkerboard Cheng2020: y, z, hyper, scale head (weight, bias), mean head, context conv
+CKBD_GAINS = {"gdn_in": 6.0, "igdn_in": 2.0, "y": 5.0, "z": 150.0, "hyper": 80.0, "scale_w": 10.0, "scale_b": 2.0, "mean_w": 3.0, "ctx": 4.0}
+
+
+def _apply_stress_ckbd(sd, seed, N):
+    """From the reference's initialisation (GDN: beta = 1, gamma = 0.1 on the diagonal) to a model whose every stage matters:
+    GDN / IGDN with a beta per channel and a dense gamma with positive off-diagonal mass, part of it below the
+    parametrizer's bound (raw values <= 2^-18 clamp to gamma = 0), so that the gamma term exceeds beta somewhere in every
+    layer; latents of a few units, a busy z stream, a dozen or more scale-table rows in each checkerboard half, escape
+    symbols, and a context convolution whose MASKED taps are as large as the others in the state_dict (the reference masks the
+    weight at every call), so that a missing or reversed mask shows."""
+    g = {k: np.float32(v) for k, v in CKBD_GAINS.items()}
+    for name in [k for k in sd if k.endswith(".beta")]:
+        sd[name] = np.sqrt(uniform_like(name, seed, sd[name].shape, 0.5, 2.0) + GDN_PEDESTAL).astype(np.float32)
+    for name in [k for k in sd if k.endswith(".gamma")]:
+        c = sd[name].shape[0]
+        dense = uniform_like(name, seed, (c, c), -0.02, 0.08)  # a fifth of the raw values below the bound; gamma <= 0.0064
+        sd[name] = (sd[name] + dense).astype(np.float32)
+    for i in (0, 2, 4):  # activations of a few units in front of the analysis GDNs
+        sd[f"g_a.{i}.conv2.weight"] *= g["gdn_in"]
+    for i in (1, 3, 5):  # ... and in front of the synthesis IGDNs
+        sd[f"g_s.{i}.conv.weight"] *= g["igdn_in"]
+    sd["g_a.6.weight"] *= g["y"]
+    sd["h_a.8.weight"] *= g["z"]
+    sd["h_s.8.weight"] *= g["hyper"]
+    sd["entropy_parameters.4.weight"][:N] *= g["scale_w"]
+    sd["entropy_parameters.4.bias"][:N] = g["scale_b"]  # chunk(2, 1): scales first
+    sd["entropy_parameters.4.weight"][N:] *= g["mean_w"]
+    sd["context_prediction.weight"] *= g["ctx"]
 
 
 def synthetic_pair(index: int, H: int, W: int, config_id: int = 0, smooth: bool = False):
