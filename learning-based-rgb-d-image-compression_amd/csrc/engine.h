@@ -2,8 +2,10 @@
 // layer graph of the six model variants (ELIC_united, single-modal ELIC, STF_united, ELIC_united_R2D, single-modal STF, checkerboard
 // Cheng2020) as inline methods
 // that plan and issue HIP kernel launches on one stream, the conv planner (tiles, split-K, reference arithmetic) and the
-// per-call-shape HIP-graph cache.  engine.hip holds the call paths (compress / decompress / forward), engine_abi.hip the
-// C ABI (include/rgbd_amd.h).  Everything shared between those two translation units is `inline` here (one instance).
+// per-call-shape HIP-graph cache.  engine.hip holds the call paths (compress / decompress / forward: one per direction for the
+// two-modality codecs, one per direction for all single-modal families, which enter it through the four `*_single` hooks),
+// engine_abi.hip the C ABI (include/rgbd_amd.h).  Everything shared between those two translation units is `inline` here
+// (one instance).
 #pragma once
 #include <algorithm>
 #include <array>
@@ -2996,7 +2998,7 @@ struct rgbd_elic {
         code_part(cd, 0, 0, params, ys, yhat, part_syms);
     }
 
-    // ---- stream I/O of the call paths (engine.hip), for nm = 1 (single-modal ELIC) or 2 modalities ----------------------
+    // ---- stream I/O of the call paths (engine.hip), for nm = 1 (the single-modal families) or 2 modalities -------------
     // workspace of a compress call: symbols, indexes and stream slots of every modality, and the stream geometry
     struct EncBufs {
         // meta: [0,B) y stream base inside a modality region (checkerboard kernels); [2B,3B) z bases; [3B,4B) z counts;
@@ -3025,20 +3027,27 @@ struct rgbd_elic {
     int dec_streams(int nm, const uint8_t* const* ys[2], const int64_t* ylen[2], int ns_y, const uint8_t* const* zs[2],
                     const int64_t* zlen[2], int ns_z, int B, int64_t T, int64_t Tz, int per_image, DecBufs* d);
 
-    int run_compress1(const float* x_dev, int B, int H, int W, int per_image);
-    int run_forward1(const float* x_dev, int B, int H, int W, float* xhat_dev, float* ly, float* lz);
-    int run_decompress1(const uint8_t* const* ys, const int64_t* ylen, int n_y, const uint8_t* const* zs, const int64_t* zlen,
-                        int B, int zh, int zw, float* x_out);
-    // the single-modal STF (variant 4) behind the same entry points
-    int run_compress_stf1(const float* x_dev, int B, int H, int W, int per_image);
-    int run_forward_stf1(const float* x_dev, int B, int H, int W, float* xhat_dev, float* ly, float* lz);
-    int run_decompress_stf1(const uint8_t* const* ys, const int64_t* ylen, int n_y, const uint8_t* const* zs, const int64_t* zlen,
-                            int B, int zh, int zw, float* x_out);
-    // the checkerboard Cheng2020 model (variant 5) behind the same entry points
-    int run_compress_ckbd(const float* x_dev, int B, int H, int W, int per_image);
-    int run_forward_ckbd(const float* x_dev, int B, int H, int W, float* xhat_dev, float* ly, float* lz);
-    int run_decompress_ckbd(const uint8_t* const* ys, const int64_t* ylen, int n_y, const uint8_t* const* zs, const int64_t* zlen,
-                            int B, int zh, int zw, float* x_out);
+    // ---- the pieces every call path shares (engine.hip) ------------------------------------------------------------------
+    void begin_call(int ref_batch_of_call, bool forward);  // resets the per-call state; the first thing a call path does
+    int finish_body();                                     // body_end(), behind an error recorded inside the body
+    int upload_forced(int nm, const std::vector<int32_t>* f, size_t n, int32_t** out);
+    static Coding enc_coding(const EncBufs& e, int per_image, int64_t T, const int32_t* force);
+    static Coding dec_coding(const DecBufs& d, int per_image, int64_t T, int nstreams);
+    // the z stage of modality m; pfx = "", "rgb_" or "depth_"
+    void z_encode(int m, const char* pfx, const EncBufs& e, const Act& z, const Act& zhat, const int32_t* fz);
+    void z_decode(int m, const char* pfx, const DecBufs& d, const Act& zhat);
+    void z_estimate(const char* pfx, const Act& z, const Act& zhat, const Act& zlik);
+    void y_encode(int nm, int B, const EncBufs& e);
+
+    // the single-modal families (variants 1, 4, 5): one call path per direction; the family enters through four hooks
+    Act g_a_single(const Act& x);
+    Act h_a_single(const Act& y);
+    Act g_s_single(const Act& yhat);
+    void latent_single(Coding& cd, const Act* y, const Act& zhat, Act* yhat);
+    int run_compress_single(const float* x_dev, int B, int H, int W, int per_image);
+    int run_forward_single(const float* x_dev, int B, int H, int W, float* xhat_dev, float* ly, float* lz);
+    int run_decompress_single(const uint8_t* const* ys, const int64_t* ylen, int n_y, const uint8_t* const* zs,
+                              const int64_t* zlen, int B, int zh, int zw, float* x_out);
 
     // lat != nullptr: the Bi-CEE stage alone (compress_united / decompress_united): latents and hyper parameters come
     // from the caller as NCHW device tensors, the transforms and the z path are skipped

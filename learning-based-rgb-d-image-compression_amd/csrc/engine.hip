@@ -1,5 +1,6 @@
 // Host runtime of the gfx950 codec engine, part 2 of 3: the call paths -- compress(), decompress() and the eval forward of the
-// two-modality codecs and of the single-modal ELIC -- as sequences of kernel launches through the layer graph of engine.h
+// two-modality codecs and, once for all of them, of the single-modal families -- as sequences of kernel launches through the
+// layer graph of engine.h
 // (prologue: workspace of the call and stream geometry; body: captured into / replayed from a HIP graph; epilogue: fetch
 // the finished streams).  Mirrors the call structure of the reference's models/elic_united.py:350-578 but keeps every
 // tensor, symbol, index and bitstream resident in HBM; the only device->host traffic is the finished streams.
@@ -190,6 +191,137 @@ int rgbd_elic::dec_streams(int nm, const uint8_t* const* ys[2], const int64_t* y
     return pin_release();
 }
 
+// ---- the pieces every call path shares -------------------------------------------------------------------------------------
+void rgbd_elic::begin_call(int ref_batch_of_call, bool forward)
+{
+    ref_batch = ref_batch_of_call;
+    named.clear();
+    pre_leads.clear();
+    arena.reset();
+    rc = 0;
+    if (forward) {
+        dbg_sym = dbg_idx = nullptr;  // forward() keeps no symbols: the last compress()'s are gone with its workspace layout
+        dbg_x = dbg_s = nullptr;
+    }
+}
+
+// closes the body (ends the capture / launches the graph); an error recorded inside the body goes before body_end()'s own
+int rgbd_elic::finish_body()
+{
+    const int r = body_end();
+    return rc ? rc : r;
+}
+
+// teacher forcing (rgbd_elic_set_forced_symbols): the symbols of nm modalities, n each, into the workspace; *out stays null
+// when none are set
+int rgbd_elic::upload_forced(int nm, const std::vector<int32_t>* f, size_t n, int32_t** out)
+{
+    *out = nullptr;
+    bool any = false;
+    for (int m = 0; m < nm; ++m) any = any || !f[m].empty();
+    if (!any) return RGBD_OK;
+    for (int m = 0; m < nm; ++m)
+        if (f[m].size() != n) return RGBD_EINVAL;
+    *out = (int32_t*)arena.take(sizeof(int32_t) * nm * n);
+    if (!dry())
+        for (int m = 0; m < nm; ++m)
+            HIP_TRY(hipMemcpyAsync(*out + m * n, f[m].data(), sizeof(int32_t) * n, hipMemcpyHostToDevice, s));
+    return RGBD_OK;
+}
+
+rgbd_elic::Coding rgbd_elic::enc_coding(const EncBufs& e, int per_image, int64_t T, const int32_t* force)
+{
+    Coding cd;
+    cd.encode = true;
+    cd.per_image = per_image;
+    cd.per_image_total = T;
+    cd.sym = e.sym;
+    cd.idx = e.idx;
+    cd.stream_base = e.meta;
+    cd.force = force;
+    return cd;
+}
+
+rgbd_elic::Coding rgbd_elic::dec_coding(const DecBufs& d, int per_image, int64_t T, int nstreams)
+{
+    Coding cd;
+    cd.encode = false;
+    cd.per_image = per_image;
+    cd.per_image_total = T;
+    cd.sym = d.sym;
+    cd.idx = d.idx;
+    cd.stream_base = d.ybase;
+    cd.words = d.words;
+    cd.stream_off = d.yoff;
+    cd.stream_len = d.ylen;
+    cd.state = d.state;
+    cd.nstreams = nstreams;
+    return cd;
+}
+
+// The z stage of modality m; `pfx` ("", "rgb_", "depth_") names its entropy bottleneck.  A missing tensor ends the call with
+// the error dense_of() records and launches nothing of the stage.
+// compress: quantise, encode, dequantise (entropy_models.py:437-446); `fz`: forced symbols of all modalities, or null
+void rgbd_elic::z_encode(int m, const char* pfx, const EncBufs& e, const Act& z, const Act& zhat, const int32_t* fz)
+{
+    if (dry() || rc) return;
+    float* md = dense_of(std::string(pfx) + "entropy_bottleneck.medians");
+    if (!md) return;
+    const int B = zhat.n, zh = zhat.h, zw = zhat.w;
+    const int64_t Tz = (int64_t)N * zh * zw;
+    int32_t* zs = e.zsym + (size_t)m * B * Tz;
+    int32_t* zi = e.zidx + (size_t)m * B * Tz;
+    int r = launch_z_quant(z.p, z.cs, B, zh, zw, N, md, zs, zi, s, perm());
+    if (!r)
+        r = launch_rans_encode(zs, zi, e.meta + 2 * B, e.meta + 3 * B, B, B, tables[2 + m].d, tables[2 + m].d,
+                               e.zwords + (size_t)m * B * e.zcap, e.zcap, e.meta + 6 * B + (size_t)m * B, e.err, s);
+    if (!r) r = launch_z_dequant(fz ? fz + (size_t)m * B * Tz : zs, B, zh, zw, N, md, zhat.p, zhat.cs, s, perm());
+    if (r) fail(r);
+}
+
+// decompress (entropy_models.py:442-446): one z stream per image
+void rgbd_elic::z_decode(int m, const char* pfx, const DecBufs& d, const Act& zhat)
+{
+    if (dry() || rc) return;
+    float* md = dense_of(std::string(pfx) + "entropy_bottleneck.medians");
+    if (!md) return;
+    const int B = zhat.n, zh = zhat.h, zw = zhat.w;
+    const int64_t Tz = (int64_t)N * zh * zw;
+    int32_t* zs = d.zsym + (size_t)m * B * Tz;
+    int32_t* zi = d.zidx + (size_t)m * B * Tz;
+    // indexes = channel id in (c, row, col) order: the quantiser's index writer on a zeroed tensor
+    int r = launch_fill_zero(zhat.p, zhat.elems(), s);
+    if (!r) r = launch_z_quant(zhat.p, zhat.cs, B, zh, zw, N, md, zs, zi, s, perm());
+    if (!r)
+        r = launch_rans_decode(d.words, d.zoff + (size_t)m * B, d.zlen + (size_t)m * B, B, d.zstate + (size_t)m * B * 2, 1, zi, zs,
+                               d.zbase, 0, Tz, tables[2 + m].d, s);
+    if (!r) r = launch_z_dequant(zs, B, zh, zw, N, md, zhat.p, zhat.cs, s, perm());
+    if (r) fail(r);
+}
+
+// eval-mode forward: round and likelihood (entropy_models.py:391-428)
+void rgbd_elic::z_estimate(const char* pfx, const Act& z, const Act& zhat, const Act& zlik)
+{
+    if (dry() || rc) return;
+    float* md = dense_of(std::string(pfx) + "entropy_bottleneck.medians");
+    float* prm = dense_of(std::string(pfx) + "entropy_bottleneck.cumulative");
+    if (!md || !prm) return;
+    const int r = launch_eb_forward(z.p, z.cs, zhat.n, zhat.h, zhat.w, N, md, prm, zhat.p, zlik.p, s, perm());
+    if (r) fail(r);
+}
+
+// the y streams of all nm modalities in one launch, at the end of compress: streams [0, ny) are the first modality's,
+// [ny, 2 ny) the second's; bases are relative to `sym`
+void rgbd_elic::y_encode(int nm, int B, const EncBufs& e)
+{
+    if (dry() || rc) return;
+    const int ny = e.ny, ns = nm * ny;
+    const int r = launch_rans_encode(e.sym, e.idx, e.meta + 8 * B, e.meta + 8 * B + ns, ns, ny, tables[0].d, tables[nm - 1].d,
+                                     e.ywords, e.ycap, e.meta + 8 * B + 2 * ns, e.err, s);
+    if (r) fail(r);
+}
+
+// ---- the two-modality codecs ---------------------------------------------------------------------------------------------
 int rgbd_elic::run_compress(const float* rgb_dev, const float* depth_dev, int B, int H, int W, int per_image,
                             const Latents* lat)
 {
@@ -197,30 +329,15 @@ int rgbd_elic::run_compress(const float* rgb_dev, const float* depth_dev, int B,
     const int Ctot = M;
     const int64_t T = (int64_t)Ctot * h * w;  // y symbols per image per modality
     const int64_t Tz = (int64_t)N * zh * zw;
-    ref_batch = per_image ? 1 : B;  // per-image streams stand for the reference called image by image
-    named.clear();
-    pre_leads.clear();
-    arena.reset();
-    rc = 0;
+    begin_call(per_image ? 1 : B, false);  // per-image streams stand for the reference called image by image
 
     // ==== prologue (never captured): workspace of the call, upload of the stream geometry, input layout conversion ====
     EncBufs e;
     if (const int r = enc_streams(2, B, T, Tz, per_image, &e)) return r;
-    int32_t *fy = nullptr, *fz = nullptr;  // teacher forcing (rgbd_elic_set_forced_symbols)
-    if (!force_y[0].empty() || !force_y[1].empty()) {
-        if (force_y[0].size() != (size_t)(B * T) || force_y[1].size() != (size_t)(B * T)) return RGBD_EINVAL;
-        fy = (int32_t*)arena.take(sizeof(int32_t) * (size_t)(2 * B * T));
-        if (!dry())
-            for (int m = 0; m < 2; ++m)
-                HIP_TRY(hipMemcpyAsync(fy + (size_t)m * B * T, force_y[m].data(), sizeof(int32_t) * (size_t)(B * T), hipMemcpyHostToDevice, s));
-    }
-    if (!lat && (!force_z[0].empty() || !force_z[1].empty())) {
-        if (force_z[0].size() != (size_t)(B * Tz) || force_z[1].size() != (size_t)(B * Tz)) return RGBD_EINVAL;
-        fz = (int32_t*)arena.take(sizeof(int32_t) * (size_t)(2 * B * Tz));
-        if (!dry())
-            for (int m = 0; m < 2; ++m)
-                HIP_TRY(hipMemcpyAsync(fz + (size_t)m * B * Tz, force_z[m].data(), sizeof(int32_t) * (size_t)(B * Tz), hipMemcpyHostToDevice, s));
-    }
+    int32_t *fy = nullptr, *fz = nullptr;
+    if (const int r = upload_forced(2, force_y, (size_t)(B * T), &fy)) return r;
+    if (!lat)
+        if (const int r = upload_forced(2, force_z, (size_t)(B * Tz), &fz)) return r;
 
     Act y_r = alloc(B, h, w, M), y_d = alloc(B, h, w, M);
     Act hyp_r, hyp_d, rgb, depth;
@@ -270,25 +387,9 @@ int rgbd_elic::run_compress(const float* rgb_dev, const float* depth_dev, int B,
             named["z_r"] = z_r;
             named["z_d"] = z_d;
 
-            // ---- z: quantise, encode, dequantise (entropy_models.py:437-446)
             Act zh_r = alloc(B, zh, zw, N), zh_d = alloc(B, zh, zw, N);
-            if (!dry() && !rc) {
-                const Act* zz[2] = {&z_r, &z_d};
-                const Act* zo[2] = {&zh_r, &zh_d};
-                const char* med[2] = {"rgb_entropy_bottleneck.medians", "depth_entropy_bottleneck.medians"};
-                for (int m = 0; m < 2 && !rc; ++m) {
-                    float* md = dense_of(med[m]);
-                    if (!md) break;
-                    int32_t* zs = e.zsym + (size_t)m * B * Tz;
-                    int32_t* zi = e.zidx + (size_t)m * B * Tz;
-                    int r = launch_z_quant(zz[m]->p, zz[m]->cs, B, zh, zw, N, md, zs, zi, s, perm());
-                    if (!r)
-                        r = launch_rans_encode(zs, zi, e.meta + 2 * B, e.meta + 3 * B, B, B, tables[2 + m].d, tables[2 + m].d,
-                                               e.zwords + (size_t)m * B * e.zcap, e.zcap, e.meta + 6 * B + (size_t)m * B, e.err, s);
-                    if (!r) r = launch_z_dequant(fz ? fz + (size_t)m * B * Tz : zs, B, zh, zw, N, md, zo[m]->p, zo[m]->cs, s, perm());
-                    if (r) fail(r);
-                }
-            }
+            z_encode(0, "rgb_", e, z_r, zh_r, fz);
+            z_encode(1, "depth_", e, z_d, zh_d, fz);
             named["zhat_r"] = zh_r;
             named["zhat_d"] = zh_d;
 
@@ -306,30 +407,12 @@ int rgbd_elic::run_compress(const float* rgb_dev, const float* depth_dev, int B,
         }
         named["yhat_r"] = yhat_r;
         named["yhat_d"] = yhat_d;
-        Coding cd;
-        cd.encode = true;
-        cd.per_image = per_image;
-        cd.per_image_total = T;
-        cd.sym = e.sym;
-        cd.idx = e.idx;
-        cd.stream_base = e.meta;
-        cd.force = fy;
+        Coding cd = enc_coding(e, per_image, T, fy);
         if (variant == 3) bicee_r2d(cd, &y_r, &y_d, hyp_r, hyp_d, yhat_r, yhat_d);
         else bicee(cd, &y_r, &y_d, hyp_r, hyp_d, yhat_r, yhat_d);
-
-        if (!dry() && !rc) {
-            // both modalities in one launch: streams [0, ny) are rgb, [ny, 2ny) depth; bases are relative to `sym`
-            const int ny = e.ny;
-            const int r = launch_rans_encode(e.sym, e.idx, e.meta + 8 * B, e.meta + 8 * B + 2 * ny, 2 * ny, ny, tables[0].d,
-                                             tables[1].d, e.ywords, e.ycap, e.meta + 8 * B + 4 * ny, e.err, s);
-            if (r) fail(r);
-        }
+        y_encode(2, B, e);
     }
-    {
-        const int r = body_end();
-        if (rc) return rc;
-        if (r) return r;
-    }
+    if (const int r = finish_body()) return r;
     if (dry()) return RGBD_OK;
 
     // ==== epilogue (never captured): fetch the streams ================================================================
@@ -342,13 +425,7 @@ int rgbd_elic::run_forward(const float* rgb_dev, const float* depth_dev, int B, 
                            float* ly_r, float* ly_d, float* lz_r, float* lz_d)
 {
     const int h = H / 16, w = W / 16, zh = H / 64, zw = W / 64;
-    ref_batch = B;  // forward() is one reference call on the whole batch
-    named.clear();
-    pre_leads.clear();
-    arena.reset();
-    rc = 0;
-    dbg_sym = dbg_idx = nullptr;  // forward() keeps no symbols: the last compress()'s are gone with its workspace layout
-    dbg_x = dbg_s = nullptr;
+    begin_call(B, true);  // forward() is one reference call on the whole batch
     Act rgb = alloc(B, H, W, 3), depth = alloc(B, H, W, 1);
     if (!dry()) {
         int r = launch_nchw_to_nhwc16(rgb_dev, B, 3, H, W, rgb.p, rgb.cs, s);
@@ -376,19 +453,8 @@ int rgbd_elic::run_forward(const float* rgb_dev, const float* depth_dev, int B, 
         Act zh_r = alloc(B, zh, zw, N), zh_d = alloc(B, zh, zw, N);
         zl_r = alloc(B, zh, zw, N);
         zl_d = alloc(B, zh, zw, N);
-        if (!dry() && !rc) {
-            const Act* zz[2] = {&z_r, &z_d};
-            const Act* zo[2] = {&zh_r, &zh_d};
-            const Act* zl[2] = {&zl_r, &zl_d};
-            const char* mods[2] = {"rgb", "depth"};
-            for (int m = 0; m < 2 && !rc; ++m) {
-                float* md = dense_of(std::string(mods[m]) + "_entropy_bottleneck.medians");
-                float* prm = dense_of(std::string(mods[m]) + "_entropy_bottleneck.cumulative");
-                if (!md || !prm) break;
-                const int r = launch_eb_forward(zz[m]->p, zz[m]->cs, B, zh, zw, N, md, prm, zo[m]->p, zl[m]->p, s, perm());
-                if (r) fail(r);
-            }
-        }
+        z_estimate("rgb_", z_r, zh_r, zl_r);
+        z_estimate("depth_", z_d, zh_d, zl_d);
         Act hyp_r, hyp_d;
         if (variant == 3) h_s_r2d(zh_r, zh_d, &hyp_r, &hyp_d);
         else h_s(zh_r, zh_d, &hyp_r, &hyp_d);
@@ -425,12 +491,7 @@ int rgbd_elic::run_forward(const float* rgb_dev, const float* depth_dev, int B, 
         zl_r = cur_ge->out[4];
         zl_d = cur_ge->out[5];
     }
-    {
-        const int r = body_end();
-        if (rc) return rc;
-        if (r) return r;
-    }
-    if (rc) return rc;
+    if (const int r = finish_body()) return r;
     if (dry()) return RGBD_OK;
     int r = launch_nhwc_to_nchw_clamp(xr.p, B, 3, H, W, xr.cs, xr_dev, 0, s);
     if (!r) r = launch_nhwc_to_nchw_clamp(xd.p, B, 1, H, W, xd.cs, xd_dev, 0, s);
@@ -455,12 +516,8 @@ int rgbd_elic::run_decompress_impl(const uint8_t* const* ys[2], const int64_t* y
     const int zh = lat ? 1 : h / 4, zw = lat ? 1 : w / 4, H = h * 16, W = w * 16;
     const int64_t T = (int64_t)M * h * w, Tz = (int64_t)N * zh * zw;
     const int per_image = (n_y == B && !(B == 1)) ? 1 : (n_y == 1 ? (B == 1 ? 1 : 0) : -1);
-    ref_batch = per_image == 0 ? B : 1;
     if (per_image < 0) return RGBD_EINVAL;
-    named.clear();
-    pre_leads.clear();
-    arena.reset();
-    rc = 0;
+    begin_call(per_image == 0 ? B : 1, false);
 
     // ==== prologue (never captured): upload the streams ================================================================
     const int ns_y = n_y, ns_z = lat ? 0 : B;
@@ -482,26 +539,9 @@ int rgbd_elic::run_decompress_impl(const uint8_t* const* ys[2], const int64_t* y
     Act out0, out1;  // what the epilogue hands back: x_hat (or y_hat for decompress_united) per modality
     if (body_begin()) {
         if (!lat) {
-            // ---- z decode (entropy_models.py:442-446)
             Act zh_r = alloc(B, zh, zw, N), zh_d = alloc(B, zh, zw, N);
-            if (!dry()) {
-                const Act* zo[2] = {&zh_r, &zh_d};
-                const char* med[2] = {"rgb_entropy_bottleneck.medians", "depth_entropy_bottleneck.medians"};
-                for (int m = 0; m < 2 && !rc; ++m) {
-                    float* md = dense_of(med[m]);
-                    if (!md) break;
-                    int32_t* zs_ = d.zsym + (size_t)m * B * Tz;
-                    int32_t* zi_ = d.zidx + (size_t)m * B * Tz;
-                    // indexes = channel id in (c, row, col) order: the quantiser's index writer on a zeroed tensor
-                    int r = launch_fill_zero(zo[m]->p, zo[m]->elems(), s);
-                    if (!r) r = launch_z_quant(zo[m]->p, zo[m]->cs, B, zh, zw, N, md, zs_, zi_, s, perm());
-                    if (!r)
-                        r = launch_rans_decode(d.words, d.zoff + (size_t)m * ns_z, d.zlen + (size_t)m * ns_z, ns_z,
-                                               d.zstate + (size_t)m * ns_z * 2, 1, zi_, zs_, d.zbase, 0, Tz, tables[2 + m].d, s);
-                    if (!r) r = launch_z_dequant(zs_, B, zh, zw, N, md, zo[m]->p, zo[m]->cs, s, perm());
-                    if (r) fail(r);
-                }
-            }
+            z_decode(0, "rgb_", d, zh_r);
+            z_decode(1, "depth_", d, zh_d);
             named["zhat_r"] = zh_r;
             named["zhat_d"] = zh_d;
 
@@ -518,18 +558,7 @@ int rgbd_elic::run_decompress_impl(const uint8_t* const* ys[2], const int64_t* y
         }
         named["yhat_r"] = yhat_r;
         named["yhat_d"] = yhat_d;
-        Coding cd;
-        cd.encode = false;
-        cd.per_image = per_image;
-        cd.per_image_total = T;
-        cd.sym = d.sym;
-        cd.idx = d.idx;
-        cd.stream_base = d.ybase;
-        cd.words = d.words;
-        cd.stream_off = d.yoff;
-        cd.stream_len = d.ylen;
-        cd.state = d.state;
-        cd.nstreams = ns_y;
+        Coding cd = dec_coding(d, per_image, T, ns_y);
         if (variant == 3) bicee_r2d(cd, nullptr, nullptr, hyp_r, hyp_d, yhat_r, yhat_d);
         else bicee(cd, nullptr, nullptr, hyp_r, hyp_d, yhat_r, yhat_d);
         if (lat) {  // decompress_united ends here: y_hat back to the caller
@@ -548,11 +577,7 @@ int rgbd_elic::run_decompress_impl(const uint8_t* const* ys[2], const int64_t* y
         out0 = cur_ge->out[0];
         out1 = cur_ge->out[1];
     }
-    {
-        const int r = body_end();
-        if (rc) return rc;
-        if (r) return r;
-    }
+    if (const int r = finish_body()) return r;
     if (dry()) return RGBD_OK;
 
     // ==== epilogue (never captured): results into the caller's NCHW tensors ==========================================
@@ -566,18 +591,177 @@ int rgbd_elic::run_decompress_impl(const uint8_t* const* ys[2], const int64_t* y
     return r;
 }
 
-// ---- single-modal ELIC, eval-mode forward() (models/elic.py:60-161, quant = "ste"): y_hat = round(y - mean) + mean slice
-// by slice through the same two-part checkerboard loop as compress(), Gaussian / factorised likelihoods instead of symbols
-int rgbd_elic::run_forward1(const float* x_dev, int B, int H, int W, float* xhat_dev, float* ly, float* lz)
+// ---- the single-modal families: ELIC (variant 1, models/elic.py), STF (4, models/stf.py) and the checkerboard Cheng2020
+// (5, models/Cheng2020withCKBD.py) share one call path per direction; a family enters through the four hooks below ----------
+Act rgbd_elic::g_a_single(const Act& x)
+{
+    switch (variant) {
+    case 4: return g_a_stf1(x);
+    case 5: return g_a_ckbd(x);
+    default: return g_a1(x);
+    }
+}
+
+Act rgbd_elic::h_a_single(const Act& y)
+{
+    switch (variant) {
+    case 4: return h_a_stf1(y);
+    case 5: return h_a_ckbd(y);
+    default: return h_a1(y);
+    }
+}
+
+Act rgbd_elic::g_s_single(const Act& yhat)
+{
+    switch (variant) {
+    case 4: return g_s_stf1(yhat);
+    case 5: return g_s_ckbd(yhat);
+    default: return g_s1(yhat);
+    }
+}
+
+// The latent stage: everything between z_hat and y_hat -- the family's buffers, its hyper synthesis, its debug tensors and its
+// coding loop (symbols when cd.encode, from the streams when not, likelihoods into cd.lik[0] when cd.estimate).
+//   ELIC: y_hat = round(y - mean) + mean slice by slice through the two-part checkerboard loop (elic.py:180-251 / 268-316).
+//   STF: the y stream is ONE stream for all slices of all images of the call (per-image streams: one per image), coded after
+//     the last slice; the decoder resumes its rANS state slice by slice.  A batch decompresses as the inverse of compress()
+//     (the reference's decompress handles one image only, stf.py:799).
+//   Checkerboard: both halves of all images of the call go into ONE y stream, anchor half first (per-image streams: one per
+//     image, each with its own two halves); the decoder resumes its rANS state between the halves.
+void rgbd_elic::latent_single(Coding& cd, const Act* y, const Act& zhat, Act* yhat)
+{
+    const int B = zhat.n, h = 4 * zhat.h, w = 4 * zhat.w;
+    switch (variant) {
+    case 4: {
+        const int wide = M + (kStfSupport + 1) * kStfSliceCh;
+        Act ctxm = alloc(B, h, w, wide), ctxs = alloc(B, h, w, wide);
+        *yhat = alloc(B, h, w, M);
+        {
+            const size_t mark = arena.top;
+            h_s_stf1(zhat, view(ctxm, 0, M), view(ctxs, 0, M));
+            arena.top = mark;
+        }
+        named["latent_means"] = view(ctxm, 0, M);
+        named["latent_scales"] = view(ctxs, 0, M);
+        if (cd.estimate) cd.lik[0] = alloc(B, h, w, M);
+        slice_loop(cd, y, ctxm, ctxs, *yhat);
+        break;
+    }
+    case 5: {
+        Act cat = alloc(B, h, w, 4 * M), params = alloc(B, h, w, 2 * M);
+        *yhat = alloc(B, h, w, M);
+        named["hyper"] = view(cat, 2 * M, 2 * M);
+        named["ctx"] = view(cat, 0, 2 * M);
+        named["scales"] = view(params, 0, M);
+        named["means"] = view(params, M, M);
+        if (!cd.estimate) {
+            if (!dry() && !rc) {
+                const int r = launch_fill_zero(cat.p, cat.elems(), s);
+                if (r) fail(r);
+            }
+            h_s_ckbd(zhat, view(cat, 2 * M, 2 * M));
+            two_pass_ckbd(cd, y, cat, params, *yhat);
+            break;
+        }
+        // eval-mode forward (Cheng2020withCKBD.py:52-71): y_hat = round(y) (quantize "dequantize" without means, :61), the
+        // context over the whole grid with its anchor outputs zeroed (:63-66), ONE parameter pass (:67-68), likelihoods of
+        // round(y - mean) + mean (:69)
+        Act scratch = alloc(B, h, w, M), lik = alloc(B, h, w, M);
+        cd.lik[0] = lik;
+        PartGeom g{};
+        g.B = B;
+        g.h = h;
+        g.w = w;
+        g.C = M;
+        g.per_image = 1;
+        g.perm = perm();
+        if (!dry() && !rc) {
+            int r = launch_fill_zero(cat.p, cat.elems(), s);
+            if (!r) r = launch_fill_zero(params.p, params.elems(), s);
+            // round(y): the quantiser of the parts with zero means (its likelihoods go to `lik`, overwritten below)
+            for (int anchor = 1; anchor >= 0 && !r; --anchor) {
+                g.anchor = anchor;
+                r = launch_ckbd_estimate_part(y->p, y->cs, params.p, params.cs, yhat->p, yhat->cs, lik.p, lik.cs, g, s);
+            }
+            if (r) fail(r);
+        }
+        h_s_ckbd(zhat, view(cat, 2 * M, 2 * M));
+        ck_context(*yhat, view(cat, 0, 2 * M));
+        ck_entropy_params(cat, 0, params);
+        if (!dry() && !rc) {
+            int r = 0;
+            for (int anchor = 1; anchor >= 0 && !r; --anchor) {
+                g.anchor = anchor;
+                r = launch_ckbd_estimate_part(y->p, y->cs, params.p, params.cs, scratch.p, scratch.cs, lik.p, lik.cs, g, s);
+            }
+            if (r) fail(r);
+        }
+        break;
+    }
+    default: {
+        Act hyper = h_s1(zhat);
+        named["hyper"] = hyper;
+        *yhat = alloc(B, h, w, M);
+        if (cd.estimate) cd.lik[0] = alloc(B, h, w, M);
+        bicee1(cd, y, hyper, *yhat);
+    }
+    }
+    named["yhat"] = *yhat;
+}
+
+// compress: elic.py:161-253, stf.py:703-764, Cheng2020withCKBD.py:101-136
+int rgbd_elic::run_compress_single(const float* x_dev, int B, int H, int W, int per_image)
 {
     const int h = H / 16, w = W / 16, zh = H / 64, zw = W / 64;
-    ref_batch = B;
-    named.clear();
-    pre_leads.clear();
-    arena.reset();
-    rc = 0;
-    dbg_sym = dbg_idx = nullptr;  // forward() keeps no symbols: the last compress()'s are gone with its workspace layout
-    dbg_x = dbg_s = nullptr;
+    const int64_t T = (int64_t)M * h * w, Tz = (int64_t)N * zh * zw;
+    begin_call(per_image ? 1 : B, false);
+
+    // ==== prologue (never captured): workspace of the call, upload of the stream geometry, input layout conversion ====
+    EncBufs e;
+    if (const int r = enc_streams(1, B, T, Tz, per_image, &e)) return r;
+    int32_t *fy = nullptr, *fz = nullptr;  // (only the checkerboard family accepts forced symbols)
+    if (const int r = upload_forced(1, force_y, (size_t)(B * T), &fy)) return r;
+    if (const int r = upload_forced(1, force_z, (size_t)(B * Tz), &fz)) return r;
+    Act x = alloc(B, H, W, in_ch);
+    if (!dry()) {
+        const int r = launch_nchw_to_nhwc16(x_dev, B, in_ch, H, W, x.p, x.cs, s);
+        if (r) return r;
+    }
+    // ==== body: captured into / replayed from a HIP graph per call shape ================================================
+    if (body_begin()) {
+        if (!dry()) {
+            const int zr = launch_fill_zero((float*)e.err, 64, s);  // (a kernel, not a memset node: DESIGN 3.5)
+            if (zr) fail(zr);
+        }
+        Act y = alloc(B, h, w, M);
+        {
+            const size_t mark = arena.top;
+            copy_ch(g_a_single(x), y);
+            arena.top = mark;
+        }
+        Act z = h_a_single(y);
+        named["y"] = y;
+        named["z"] = z;
+        Act zhat = alloc(B, zh, zw, N), yhat;
+        z_encode(0, "", e, z, zhat, fz);
+        named["zhat"] = zhat;
+        Coding cd = enc_coding(e, per_image, T, fy);
+        latent_single(cd, &y, zhat, &yhat);
+        y_encode(1, B, e);
+    }
+    if (const int r = finish_body()) return r;
+    if (dry()) return RGBD_OK;
+
+    // ==== epilogue (never captured): fetch the streams ================================================================
+    return fetch_streams(1, B, true, e);
+}
+
+// eval-mode forward(): elic.py:60-161 (quant = "ste"), stf.py:618-678, Cheng2020withCKBD.py:52-71; Gaussian / factorised
+// likelihoods instead of symbols
+int rgbd_elic::run_forward_single(const float* x_dev, int B, int H, int W, float* xhat_dev, float* ly, float* lz)
+{
+    const int h = H / 16, w = W / 16, zh = H / 64, zw = W / 64;
+    begin_call(B, true);
     Act x = alloc(B, H, W, in_ch);
     if (!dry()) {
         const int r = launch_nchw_to_nhwc16(x_dev, B, in_ch, H, W, x.p, x.cs, s);
@@ -588,32 +772,20 @@ int rgbd_elic::run_forward1(const float* x_dev, int B, int H, int W, float* xhat
         Act y = alloc(B, h, w, M);
         {
             const size_t mark = arena.top;
-            copy_ch(g_a1(x), y);
+            copy_ch(g_a_single(x), y);
             arena.top = mark;
         }
-        Act z = h_a1(y);
-        Act zhat = alloc(B, zh, zw, N);
-        zlik = alloc(B, zh, zw, N);
-        if (!dry() && !rc) {
-            float* md = dense_of("entropy_bottleneck.medians");
-            float* prm = dense_of("entropy_bottleneck.cumulative");
-            if (md && prm) {
-                const int r = launch_eb_forward(z.p, z.cs, B, zh, zw, N, md, prm, zhat.p, zlik.p, s, perm());
-                if (r) fail(r);
-            }
-        }
-        Act hyper = h_s1(zhat);
-        Act yhat = alloc(B, h, w, M);
-        Coding cd;
-        cd.estimate = true;
-        cd.lik[0] = alloc(B, h, w, M);
-        bicee1(cd, &y, hyper, yhat);
+        Act z = h_a_single(y);
         named["y"] = y;
         named["z"] = z;
+        Act zhat = alloc(B, zh, zw, N), yhat;
+        zlik = alloc(B, zh, zw, N);
+        z_estimate("", z, zhat, zlik);
         named["zhat"] = zhat;
-        named["hyper"] = hyper;
-        named["yhat"] = yhat;
-        xh = g_s1(yhat);
+        Coding cd;
+        cd.estimate = true;
+        latent_single(cd, &y, zhat, &yhat);
+        xh = g_s_single(yhat);
         lik = cd.lik[0];
         if (cur_ge && !dry()) {
             cur_ge->out[0] = xh;
@@ -625,628 +797,45 @@ int rgbd_elic::run_forward1(const float* x_dev, int B, int H, int W, float* xhat
         lik = cur_ge->out[1];
         zlik = cur_ge->out[2];
     }
-    {
-        const int r = body_end();
-        if (rc) return rc;
-        if (r) return r;
-    }
+    if (const int r = finish_body()) return r;
     if (dry()) return RGBD_OK;
-    int r = launch_nhwc_to_nchw_clamp(xh.p, B, in_ch, H, W, xh.cs, xhat_dev, 0, s);
+    int r = launch_nhwc_to_nchw_clamp(xh.p, B, in_ch, H, W, xh.cs, xhat_dev, 0, s);  // (stf.py:677: not clamped)
     if (!r) r = launch_nhwc_to_nchw_clamp(lik.p, B, M, h, w, lik.cs, ly, 0, s, perm());
     if (!r) r = launch_nhwc_to_nchw_clamp(zlik.p, B, N, zh, zw, zlik.cs, lz, 0, s, perm());
     if (!r) r = wait_stream();
     return r;
 }
 
-// ---- single-modal ELIC: compress (models/elic.py:161-253) and decompress (:255-325) --------------------------------
-int rgbd_elic::run_compress1(const float* x_dev, int B, int H, int W, int per_image)
-{
-    const int h = H / 16, w = W / 16, zh = H / 64, zw = W / 64;
-    const int64_t T = (int64_t)M * h * w, Tz = (int64_t)N * zh * zw;
-    ref_batch = per_image ? 1 : B;
-    named.clear();
-    pre_leads.clear();
-    arena.reset();
-    rc = 0;
-    EncBufs e;
-    if (const int r = enc_streams(1, B, T, Tz, per_image, &e)) return r;
-    Act x = alloc(B, H, W, in_ch);
-    if (!dry()) {
-        const int r = launch_nchw_to_nhwc16(x_dev, B, in_ch, H, W, x.p, x.cs, s);
-        if (r) return r;
-    }
-    // ==== body: captured into / replayed from a HIP graph per call shape ================================================
-    if (body_begin()) {
-        if (!dry()) {
-            const int zr = launch_fill_zero((float*)e.err, 64, s);  // (a kernel, not a memset node: DESIGN 3.5)
-            if (zr) fail(zr);
-        }
-        Act y = alloc(B, h, w, M);
-        {
-            const size_t mark = arena.top;
-            copy_ch(g_a1(x), y);
-            arena.top = mark;
-        }
-        Act z = h_a1(y);
-        named["y"] = y;
-        named["z"] = z;
-        Act zhat = alloc(B, zh, zw, N);
-        float* md = dense_of("entropy_bottleneck.medians");
-        if (!dry() && !rc && md) {
-            int r = launch_z_quant(z.p, z.cs, B, zh, zw, N, md, e.zsym, e.zidx, s, perm());
-            if (!r)
-                r = launch_rans_encode(e.zsym, e.zidx, e.meta + 2 * B, e.meta + 3 * B, B, B, tables[2].d, tables[2].d, e.zwords,
-                                       e.zcap, e.meta + 6 * B, e.err, s);
-            if (!r) r = launch_z_dequant(e.zsym, B, zh, zw, N, md, zhat.p, zhat.cs, s, perm());
-            if (r) fail(r);
-        }
-        named["zhat"] = zhat;
-        Act hyper = h_s1(zhat);
-        named["hyper"] = hyper;
-        Act yhat = alloc(B, h, w, M);
-        named["yhat"] = yhat;
-        Coding cd;
-        cd.encode = true;
-        cd.per_image = per_image;
-        cd.per_image_total = T;
-        cd.sym = e.sym;
-        cd.idx = e.idx;
-        cd.stream_base = e.meta;
-        bicee1(cd, &y, hyper, yhat);
-        if (!dry() && !rc) {
-            const int ny = e.ny;
-            const int r = launch_rans_encode(e.sym, e.idx, e.meta + 8 * B, e.meta + 8 * B + ny, ny, ny, tables[0].d, tables[0].d,
-                                             e.ywords, e.ycap, e.meta + 8 * B + 2 * ny, e.err, s);
-            if (r) fail(r);
-        }
-    }  // body
-    {
-        const int r = body_end();
-        if (rc) return rc;
-        if (r) return r;
-    }
-    if (dry()) return RGBD_OK;
-    return fetch_streams(1, B, true, e);
-}
-
-int rgbd_elic::run_decompress1(const uint8_t* const* ys, const int64_t* ylen, int n_y, const uint8_t* const* zs,
-                               const int64_t* zlen, int B, int zh, int zw, float* x_out)
+// decompress: elic.py:255-325, stf.py:766-816, Cheng2020withCKBD.py:138-174
+int rgbd_elic::run_decompress_single(const uint8_t* const* ys, const int64_t* ylen, int n_y, const uint8_t* const* zs,
+                                     const int64_t* zlen, int B, int zh, int zw, float* x_out)
 {
     const int h = zh * 4, w = zw * 4, H = zh * 64, W = zw * 64;
     const int64_t T = (int64_t)M * h * w, Tz = (int64_t)N * zh * zw;
     const int per_image = (n_y == B) ? 1 : 0;
-    ref_batch = per_image ? 1 : B;
-    named.clear();
-    pre_leads.clear();
-    arena.reset();
-    rc = 0;
+    begin_call(per_image ? 1 : B, false);
 
-    // ==== prologue (never captured): upload the streams
+    // ==== prologue (never captured): upload the streams ================================================================
     DecBufs d;
     if (const int r = dec_streams(1, &ys, &ylen, n_y, &zs, &zlen, B, B, T, Tz, per_image, &d)) return r;
 
     // ==== body: captured into / replayed from a HIP graph per call shape ================================================
     Act xh;
     if (body_begin()) {
-        Act zhat = alloc(B, zh, zw, N);
-        float* md = dense_of("entropy_bottleneck.medians");
-        if (!dry() && md) {
-            int q = launch_fill_zero(zhat.p, zhat.elems(), s);
-            if (!q) q = launch_z_quant(zhat.p, zhat.cs, B, zh, zw, N, md, d.zsym, d.zidx, s, perm());  // indexes = channel id
-            if (!q) q = launch_rans_decode(d.words, d.zoff, d.zlen, B, d.zstate, 1, d.zidx, d.zsym, d.zbase, 0, Tz, tables[2].d, s);
-            if (!q) q = launch_z_dequant(d.zsym, B, zh, zw, N, md, zhat.p, zhat.cs, s, perm());
-            if (q) fail(q);
-        }
+        Act zhat = alloc(B, zh, zw, N), yhat;
+        z_decode(0, "", d, zhat);
         named["zhat"] = zhat;
-        Act hyper = h_s1(zhat);
-        named["hyper"] = hyper;
-        Act yhat = alloc(B, h, w, M);
-        named["yhat"] = yhat;
-        Coding cd;
-        cd.encode = false;
-        cd.per_image = per_image;
-        cd.per_image_total = T;
-        cd.sym = d.sym;
-        cd.idx = d.idx;
-        cd.stream_base = d.ybase;
-        cd.words = d.words;
-        cd.stream_off = d.yoff;
-        cd.stream_len = d.ylen;
-        cd.state = d.state;
-        cd.nstreams = n_y;
-        bicee1(cd, nullptr, hyper, yhat);
-        xh = g_s1(yhat);
+        Coding cd = dec_coding(d, per_image, T, n_y);
+        latent_single(cd, nullptr, zhat, &yhat);
+        xh = g_s_single(yhat);
         if (cur_ge && !dry()) cur_ge->out[0] = xh;
     } else {
         xh = cur_ge->out[0];
     }
-    {
-        const int r = body_end();
-        if (rc) return rc;
-        if (r) return r;
-    }
+    if (const int r = finish_body()) return r;
     if (dry()) return RGBD_OK;
-    // ==== epilogue (never captured)
-    return launch_nhwc_to_nchw_clamp(xh.p, B, in_ch, H, W, xh.cs, x_out, 0, s);  // elic.py:318-325: not clamped
-}
 
-// ---- single-modal STF (models/stf.py): compress :703-764, decompress :766-816, eval-mode forward :618-678 ---------------
-// The y stream is ONE stream for all slices of all images of the call (per-image streams: one per image), coded after the
-// last slice; the decoder resumes its rANS state slice by slice.  A batch decompresses as the inverse of compress() (the
-// reference's decompress handles one image only, stf.py:799).
-int rgbd_elic::run_compress_stf1(const float* x_dev, int B, int H, int W, int per_image)
-{
-    const int h = H / 16, w = W / 16, zh = H / 64, zw = W / 64;
-    const int64_t T = (int64_t)M * h * w, Tz = (int64_t)N * zh * zw;
-    ref_batch = per_image ? 1 : B;
-    named.clear();
-    pre_leads.clear();
-    arena.reset();
-    rc = 0;
-    EncBufs e;
-    if (const int r = enc_streams(1, B, T, Tz, per_image, &e)) return r;
-    Act x = alloc(B, H, W, in_ch);
-    if (!dry()) {
-        const int r = launch_nchw_to_nhwc16(x_dev, B, in_ch, H, W, x.p, x.cs, s);
-        if (r) return r;
-    }
-    // ==== body: captured into / replayed from a HIP graph per call shape ================================================
-    if (body_begin()) {
-        if (!dry()) {
-            const int zr = launch_fill_zero((float*)e.err, 64, s);  // (a kernel, not a memset node: DESIGN 3.5)
-            if (zr) fail(zr);
-        }
-        Act y = alloc(B, h, w, M);
-        {
-            const size_t mark = arena.top;
-            copy_ch(g_a_stf1(x), y);
-            arena.top = mark;
-        }
-        Act z = h_a_stf1(y);
-        named["y"] = y;
-        named["z"] = z;
-        Act zhat = alloc(B, zh, zw, N);
-        float* md = dense_of("entropy_bottleneck.medians");
-        if (!dry() && !rc && md) {
-            int r = launch_z_quant(z.p, z.cs, B, zh, zw, N, md, e.zsym, e.zidx, s, 0);
-            if (!r)
-                r = launch_rans_encode(e.zsym, e.zidx, e.meta + 2 * B, e.meta + 3 * B, B, B, tables[2].d, tables[2].d, e.zwords,
-                                       e.zcap, e.meta + 6 * B, e.err, s);
-            if (!r) r = launch_z_dequant(e.zsym, B, zh, zw, N, md, zhat.p, zhat.cs, s, 0);
-            if (r) fail(r);
-        }
-        named["zhat"] = zhat;
-        const int wide = M + (kStfSupport + 1) * kStfSliceCh;
-        Act ctxm = alloc(B, h, w, wide), ctxs = alloc(B, h, w, wide), yhat = alloc(B, h, w, M);
-        {
-            const size_t mark = arena.top;
-            h_s_stf1(zhat, view(ctxm, 0, M), view(ctxs, 0, M));
-            arena.top = mark;
-        }
-        named["latent_means"] = view(ctxm, 0, M);
-        named["latent_scales"] = view(ctxs, 0, M);
-        named["yhat"] = yhat;
-        Coding cd;
-        cd.encode = true;
-        cd.per_image = per_image;
-        cd.per_image_total = T;
-        cd.sym = e.sym;
-        cd.idx = e.idx;
-        cd.stream_base = e.meta;
-        slice_loop(cd, &y, ctxm, ctxs, yhat);
-        if (!dry() && !rc) {
-            const int ny = e.ny;
-            const int r = launch_rans_encode(e.sym, e.idx, e.meta + 8 * B, e.meta + 8 * B + ny, ny, ny, tables[0].d, tables[0].d,
-                                             e.ywords, e.ycap, e.meta + 8 * B + 2 * ny, e.err, s);
-            if (r) fail(r);
-        }
-    }  // body
-    {
-        const int r = body_end();
-        if (rc) return rc;
-        if (r) return r;
-    }
-    if (dry()) return RGBD_OK;
-    return fetch_streams(1, B, true, e);
-}
-
-int rgbd_elic::run_forward_stf1(const float* x_dev, int B, int H, int W, float* xhat_dev, float* ly, float* lz)
-{
-    const int h = H / 16, w = W / 16, zh = H / 64, zw = W / 64;
-    ref_batch = B;
-    named.clear();
-    pre_leads.clear();
-    arena.reset();
-    rc = 0;
-    dbg_sym = dbg_idx = nullptr;  // forward() keeps no symbols: the last compress()'s are gone with its workspace layout
-    dbg_x = dbg_s = nullptr;
-    Act x = alloc(B, H, W, in_ch);
-    if (!dry()) {
-        const int r = launch_nchw_to_nhwc16(x_dev, B, in_ch, H, W, x.p, x.cs, s);
-        if (r) return r;
-    }
-    Act xh, lik, zlik;
-    if (body_begin()) {
-        Act y = alloc(B, h, w, M);
-        {
-            const size_t mark = arena.top;
-            copy_ch(g_a_stf1(x), y);
-            arena.top = mark;
-        }
-        Act z = h_a_stf1(y);
-        Act zhat = alloc(B, zh, zw, N);
-        zlik = alloc(B, zh, zw, N);
-        if (!dry() && !rc) {
-            float* md = dense_of("entropy_bottleneck.medians");
-            float* prm = dense_of("entropy_bottleneck.cumulative");
-            if (md && prm) {
-                const int r = launch_eb_forward(z.p, z.cs, B, zh, zw, N, md, prm, zhat.p, zlik.p, s, 0);
-                if (r) fail(r);
-            }
-        }
-        const int wide = M + (kStfSupport + 1) * kStfSliceCh;
-        Act ctxm = alloc(B, h, w, wide), ctxs = alloc(B, h, w, wide), yhat = alloc(B, h, w, M);
-        {
-            const size_t mark = arena.top;
-            h_s_stf1(zhat, view(ctxm, 0, M), view(ctxs, 0, M));
-            arena.top = mark;
-        }
-        Coding cd;
-        cd.estimate = true;
-        cd.lik[0] = alloc(B, h, w, M);
-        slice_loop(cd, &y, ctxm, ctxs, yhat);
-        named["y"] = y;
-        named["z"] = z;
-        named["zhat"] = zhat;
-        named["latent_means"] = view(ctxm, 0, M);
-        named["latent_scales"] = view(ctxs, 0, M);
-        named["yhat"] = yhat;
-        xh = g_s_stf1(yhat);
-        lik = cd.lik[0];
-        if (cur_ge && !dry()) {
-            cur_ge->out[0] = xh;
-            cur_ge->out[1] = lik;
-            cur_ge->out[2] = zlik;
-        }
-    } else {
-        xh = cur_ge->out[0];
-        lik = cur_ge->out[1];
-        zlik = cur_ge->out[2];
-    }
-    {
-        const int r = body_end();
-        if (rc) return rc;
-        if (r) return r;
-    }
-    if (dry()) return RGBD_OK;
-    int r = launch_nhwc_to_nchw_clamp(xh.p, B, in_ch, H, W, xh.cs, xhat_dev, 0, s);  // stf.py:677: not clamped
-    if (!r) r = launch_nhwc_to_nchw_clamp(lik.p, B, M, h, w, lik.cs, ly, 0, s, 0);
-    if (!r) r = launch_nhwc_to_nchw_clamp(zlik.p, B, N, zh, zw, zlik.cs, lz, 0, s, 0);
-    if (!r) r = wait_stream();
-    return r;
-}
-
-int rgbd_elic::run_decompress_stf1(const uint8_t* const* ys, const int64_t* ylen, int n_y, const uint8_t* const* zs,
-                                   const int64_t* zlen, int B, int zh, int zw, float* x_out)
-{
-    const int h = zh * 4, w = zw * 4, H = zh * 64, W = zw * 64;
-    const int64_t T = (int64_t)M * h * w, Tz = (int64_t)N * zh * zw;
-    const int per_image = (n_y == B) ? 1 : 0;
-    ref_batch = per_image ? 1 : B;
-    named.clear();
-    pre_leads.clear();
-    arena.reset();
-    rc = 0;
-
-    // ==== prologue (never captured): upload the streams
-    DecBufs d;
-    if (const int r = dec_streams(1, &ys, &ylen, n_y, &zs, &zlen, B, B, T, Tz, per_image, &d)) return r;
-
-    // ==== body: captured into / replayed from a HIP graph per call shape ================================================
-    Act xh;
-    if (body_begin()) {
-        Act zhat = alloc(B, zh, zw, N);
-        float* md = dense_of("entropy_bottleneck.medians");
-        if (!dry() && md) {
-            int q = launch_fill_zero(zhat.p, zhat.elems(), s);
-            if (!q) q = launch_z_quant(zhat.p, zhat.cs, B, zh, zw, N, md, d.zsym, d.zidx, s, 0);  // indexes = channel id
-            if (!q) q = launch_rans_decode(d.words, d.zoff, d.zlen, B, d.zstate, 1, d.zidx, d.zsym, d.zbase, 0, Tz, tables[2].d, s);
-            if (!q) q = launch_z_dequant(d.zsym, B, zh, zw, N, md, zhat.p, zhat.cs, s, 0);
-            if (q) fail(q);
-        }
-        named["zhat"] = zhat;
-        const int wide = M + (kStfSupport + 1) * kStfSliceCh;
-        Act ctxm = alloc(B, h, w, wide), ctxs = alloc(B, h, w, wide), yhat = alloc(B, h, w, M);
-        {
-            const size_t mark = arena.top;
-            h_s_stf1(zhat, view(ctxm, 0, M), view(ctxs, 0, M));
-            arena.top = mark;
-        }
-        named["latent_means"] = view(ctxm, 0, M);
-        named["latent_scales"] = view(ctxs, 0, M);
-        named["yhat"] = yhat;
-        Coding cd;
-        cd.encode = false;
-        cd.per_image = per_image;
-        cd.per_image_total = T;
-        cd.sym = d.sym;
-        cd.idx = d.idx;
-        cd.stream_base = d.ybase;
-        cd.words = d.words;
-        cd.stream_off = d.yoff;
-        cd.stream_len = d.ylen;
-        cd.state = d.state;
-        cd.nstreams = n_y;
-        slice_loop(cd, nullptr, ctxm, ctxs, yhat);
-        xh = g_s_stf1(yhat);
-        if (cur_ge && !dry()) cur_ge->out[0] = xh;
-    } else {
-        xh = cur_ge->out[0];
-    }
-    {
-        const int r = body_end();
-        if (rc) return rc;
-        if (r) return r;
-    }
-    if (dry()) return RGBD_OK;
-    // ==== epilogue (never captured)
-    return launch_nhwc_to_nchw_clamp(xh.p, B, in_ch, H, W, xh.cs, x_out, 1, s);  // stf.py:815: clamped to [0, 1]
-}
-
-// ---- checkerboard Cheng2020 (models/Cheng2020withCKBD.py): compress :101-136, decompress :138-174, eval-mode forward :52-71 ---
-// Both checkerboard halves of all images of the call go into ONE y stream, anchor half first (per-image streams: one per
-// image, each with its own two halves); the decoder resumes its rANS state between the halves.
-int rgbd_elic::run_compress_ckbd(const float* x_dev, int B, int H, int W, int per_image)
-{
-    const int h = H / 16, w = W / 16, zh = H / 64, zw = W / 64;
-    const int64_t T = (int64_t)M * h * w, Tz = (int64_t)N * zh * zw;
-    ref_batch = per_image ? 1 : B;
-    named.clear();
-    pre_leads.clear();
-    arena.reset();
-    rc = 0;
-    EncBufs e;
-    if (const int r = enc_streams(1, B, T, Tz, per_image, &e)) return r;
-    int32_t *fy = nullptr, *fz = nullptr;  // teacher forcing (rgbd_elic_set_forced_symbols, modality 0)
-    if (!force_y[0].empty()) {
-        if (force_y[0].size() != (size_t)(B * T)) return RGBD_EINVAL;
-        fy = (int32_t*)arena.take(sizeof(int32_t) * (size_t)(B * T));
-        if (!dry()) HIP_TRY(hipMemcpyAsync(fy, force_y[0].data(), sizeof(int32_t) * (size_t)(B * T), hipMemcpyHostToDevice, s));
-    }
-    if (!force_z[0].empty()) {
-        if (force_z[0].size() != (size_t)(B * Tz)) return RGBD_EINVAL;
-        fz = (int32_t*)arena.take(sizeof(int32_t) * (size_t)(B * Tz));
-        if (!dry()) HIP_TRY(hipMemcpyAsync(fz, force_z[0].data(), sizeof(int32_t) * (size_t)(B * Tz), hipMemcpyHostToDevice, s));
-    }
-    Act x = alloc(B, H, W, in_ch);
-    if (!dry()) {
-        const int r = launch_nchw_to_nhwc16(x_dev, B, in_ch, H, W, x.p, x.cs, s);
-        if (r) return r;
-    }
-    // ==== body: captured into / replayed from a HIP graph per call shape ================================================
-    if (body_begin()) {
-        if (!dry()) {
-            const int zr = launch_fill_zero((float*)e.err, 64, s);  // (a kernel, not a memset node: DESIGN 3.5)
-            if (zr) fail(zr);
-        }
-        Act y = alloc(B, h, w, M);
-        {
-            const size_t mark = arena.top;
-            copy_ch(g_a_ckbd(x), y);
-            arena.top = mark;
-        }
-        Act z = h_a_ckbd(y);
-        named["y"] = y;
-        named["z"] = z;
-        Act zhat = alloc(B, zh, zw, N);
-        float* md = dense_of("entropy_bottleneck.medians");
-        if (!dry() && !rc && md) {
-            int r = launch_z_quant(z.p, z.cs, B, zh, zw, N, md, e.zsym, e.zidx, s, 0);
-            if (!r)
-                r = launch_rans_encode(e.zsym, e.zidx, e.meta + 2 * B, e.meta + 3 * B, B, B, tables[2].d, tables[2].d, e.zwords,
-                                       e.zcap, e.meta + 6 * B, e.err, s);
-            if (!r) r = launch_z_dequant(fz ? fz : e.zsym, B, zh, zw, N, md, zhat.p, zhat.cs, s, 0);
-            if (r) fail(r);
-        }
-        named["zhat"] = zhat;
-        Act cat = alloc(B, h, w, 4 * M), params = alloc(B, h, w, 2 * M), yhat = alloc(B, h, w, M);
-        if (!dry() && !rc) {
-            const int r = launch_fill_zero(cat.p, cat.elems(), s);
-            if (r) fail(r);
-        }
-        h_s_ckbd(zhat, view(cat, 2 * M, 2 * M));
-        named["hyper"] = view(cat, 2 * M, 2 * M);
-        named["ctx"] = view(cat, 0, 2 * M);
-        named["scales"] = view(params, 0, M);
-        named["means"] = view(params, M, M);
-        named["yhat"] = yhat;
-        Coding cd;
-        cd.encode = true;
-        cd.per_image = per_image;
-        cd.per_image_total = T;
-        cd.sym = e.sym;
-        cd.idx = e.idx;
-        cd.stream_base = e.meta;
-        cd.force = fy;
-        two_pass_ckbd(cd, &y, cat, params, yhat);
-        if (!dry() && !rc) {
-            const int ny = e.ny;
-            const int r = launch_rans_encode(e.sym, e.idx, e.meta + 8 * B, e.meta + 8 * B + ny, ny, ny, tables[0].d, tables[0].d,
-                                             e.ywords, e.ycap, e.meta + 8 * B + 2 * ny, e.err, s);
-            if (r) fail(r);
-        }
-    }  // body
-    {
-        const int r = body_end();
-        if (rc) return rc;
-        if (r) return r;
-    }
-    if (dry()) return RGBD_OK;
-    return fetch_streams(1, B, true, e);
-}
-
-// y_hat = round(y) (quantize "dequantize" without means, :61), the context over the whole grid with its anchor outputs zeroed
-// (:63-66), ONE parameter pass (:67-68), likelihoods of round(y - mean) + mean (:69)
-int rgbd_elic::run_forward_ckbd(const float* x_dev, int B, int H, int W, float* xhat_dev, float* ly, float* lz)
-{
-    const int h = H / 16, w = W / 16, zh = H / 64, zw = W / 64;
-    ref_batch = B;
-    named.clear();
-    pre_leads.clear();
-    arena.reset();
-    rc = 0;
-    dbg_sym = dbg_idx = nullptr;  // forward() keeps no symbols: the last compress()'s are gone with its workspace layout
-    dbg_x = dbg_s = nullptr;
-    Act x = alloc(B, H, W, in_ch);
-    if (!dry()) {
-        const int r = launch_nchw_to_nhwc16(x_dev, B, in_ch, H, W, x.p, x.cs, s);
-        if (r) return r;
-    }
-    Act xh, lik, zlik;
-    if (body_begin()) {
-        Act y = alloc(B, h, w, M);
-        {
-            const size_t mark = arena.top;
-            copy_ch(g_a_ckbd(x), y);
-            arena.top = mark;
-        }
-        Act z = h_a_ckbd(y);
-        Act zhat = alloc(B, zh, zw, N);
-        zlik = alloc(B, zh, zw, N);
-        if (!dry() && !rc) {
-            float* md = dense_of("entropy_bottleneck.medians");
-            float* prm = dense_of("entropy_bottleneck.cumulative");
-            if (md && prm) {
-                const int r = launch_eb_forward(z.p, z.cs, B, zh, zw, N, md, prm, zhat.p, zlik.p, s, 0);
-                if (r) fail(r);
-            }
-        }
-        Act cat = alloc(B, h, w, 4 * M), params = alloc(B, h, w, 2 * M), yhat = alloc(B, h, w, M), scratch = alloc(B, h, w, M);
-        lik = alloc(B, h, w, M);
-        PartGeom g{};
-        g.B = B;
-        g.h = h;
-        g.w = w;
-        g.C = M;
-        g.per_image = 1;
-        g.perm = 0;
-        if (!dry() && !rc) {
-            int r = launch_fill_zero(cat.p, cat.elems(), s);
-            if (!r) r = launch_fill_zero(params.p, params.elems(), s);
-            // round(y): the quantiser of the parts with zero means (its likelihoods go to `lik`, overwritten below)
-            for (int anchor = 1; anchor >= 0 && !r; --anchor) {
-                g.anchor = anchor;
-                r = launch_ckbd_estimate_part(y.p, y.cs, params.p, params.cs, yhat.p, yhat.cs, lik.p, lik.cs, g, s);
-            }
-            if (r) fail(r);
-        }
-        h_s_ckbd(zhat, view(cat, 2 * M, 2 * M));
-        ck_context(yhat, view(cat, 0, 2 * M));
-        ck_entropy_params(cat, 0, params);
-        if (!dry() && !rc) {
-            int r = 0;
-            for (int anchor = 1; anchor >= 0 && !r; --anchor) {
-                g.anchor = anchor;
-                r = launch_ckbd_estimate_part(y.p, y.cs, params.p, params.cs, scratch.p, scratch.cs, lik.p, lik.cs, g, s);
-            }
-            if (r) fail(r);
-        }
-        named["y"] = y;
-        named["z"] = z;
-        named["zhat"] = zhat;
-        named["hyper"] = view(cat, 2 * M, 2 * M);
-        named["ctx"] = view(cat, 0, 2 * M);
-        named["scales"] = view(params, 0, M);
-        named["means"] = view(params, M, M);
-        named["yhat"] = yhat;
-        xh = g_s_ckbd(yhat);
-        if (cur_ge && !dry()) {
-            cur_ge->out[0] = xh;
-            cur_ge->out[1] = lik;
-            cur_ge->out[2] = zlik;
-        }
-    } else {
-        xh = cur_ge->out[0];
-        lik = cur_ge->out[1];
-        zlik = cur_ge->out[2];
-    }
-    {
-        const int r = body_end();
-        if (rc) return rc;
-        if (r) return r;
-    }
-    if (dry()) return RGBD_OK;
-    int r = launch_nhwc_to_nchw_clamp(xh.p, B, in_ch, H, W, xh.cs, xhat_dev, 0, s);
-    if (!r) r = launch_nhwc_to_nchw_clamp(lik.p, B, M, h, w, lik.cs, ly, 0, s, 0);
-    if (!r) r = launch_nhwc_to_nchw_clamp(zlik.p, B, N, zh, zw, zlik.cs, lz, 0, s, 0);
-    if (!r) r = wait_stream();
-    return r;
-}
-
-int rgbd_elic::run_decompress_ckbd(const uint8_t* const* ys, const int64_t* ylen, int n_y, const uint8_t* const* zs,
-                                   const int64_t* zlen, int B, int zh, int zw, float* x_out)
-{
-    const int h = zh * 4, w = zw * 4, H = zh * 64, W = zw * 64;
-    const int64_t T = (int64_t)M * h * w, Tz = (int64_t)N * zh * zw;
-    const int per_image = (n_y == B) ? 1 : 0;
-    ref_batch = per_image ? 1 : B;
-    named.clear();
-    pre_leads.clear();
-    arena.reset();
-    rc = 0;
-
-    // ==== prologue (never captured): upload the streams
-    DecBufs d;
-    if (const int r = dec_streams(1, &ys, &ylen, n_y, &zs, &zlen, B, B, T, Tz, per_image, &d)) return r;
-
-    // ==== body: captured into / replayed from a HIP graph per call shape ================================================
-    Act xh;
-    if (body_begin()) {
-        Act zhat = alloc(B, zh, zw, N);
-        float* md = dense_of("entropy_bottleneck.medians");
-        if (!dry() && md) {
-            int q = launch_fill_zero(zhat.p, zhat.elems(), s);
-            if (!q) q = launch_z_quant(zhat.p, zhat.cs, B, zh, zw, N, md, d.zsym, d.zidx, s, 0);  // indexes = channel id
-            if (!q) q = launch_rans_decode(d.words, d.zoff, d.zlen, B, d.zstate, 1, d.zidx, d.zsym, d.zbase, 0, Tz, tables[2].d, s);
-            if (!q) q = launch_z_dequant(d.zsym, B, zh, zw, N, md, zhat.p, zhat.cs, s, 0);
-            if (q) fail(q);
-        }
-        named["zhat"] = zhat;
-        Act cat = alloc(B, h, w, 4 * M), params = alloc(B, h, w, 2 * M), yhat = alloc(B, h, w, M);
-        if (!dry() && !rc) {
-            const int r = launch_fill_zero(cat.p, cat.elems(), s);
-            if (r) fail(r);
-        }
-        h_s_ckbd(zhat, view(cat, 2 * M, 2 * M));
-        named["hyper"] = view(cat, 2 * M, 2 * M);
-        named["ctx"] = view(cat, 0, 2 * M);
-        named["scales"] = view(params, 0, M);
-        named["means"] = view(params, M, M);
-        named["yhat"] = yhat;
-        Coding cd;
-        cd.encode = false;
-        cd.per_image = per_image;
-        cd.per_image_total = T;
-        cd.sym = d.sym;
-        cd.idx = d.idx;
-        cd.stream_base = d.ybase;
-        cd.words = d.words;
-        cd.stream_off = d.yoff;
-        cd.stream_len = d.ylen;
-        cd.state = d.state;
-        cd.nstreams = n_y;
-        two_pass_ckbd(cd, nullptr, cat, params, yhat);
-        xh = g_s_ckbd(yhat);
-        if (cur_ge && !dry()) cur_ge->out[0] = xh;
-    } else {
-        xh = cur_ge->out[0];
-    }
-    {
-        const int r = body_end();
-        if (rc) return rc;
-        if (r) return r;
-    }
-    if (dry()) return RGBD_OK;
-    // ==== epilogue (never captured)
-    return launch_nhwc_to_nchw_clamp(xh.p, B, in_ch, H, W, xh.cs, x_out, 0, s);  // Cheng2020withCKBD.py:167-174: not clamped
+    // ==== epilogue (never captured): x_hat into the caller's NCHW tensor; not clamped in elic.py:318-325 and
+    // Cheng2020withCKBD.py:167-174, clamped to [0, 1] in stf.py:815
+    return launch_nhwc_to_nchw_clamp(xh.p, B, in_ch, H, W, xh.cs, x_out, variant == 4 ? 1 : 0, s);
 }

@@ -1045,7 +1045,8 @@ int rgbd_elic_create_stf_single(int32_t in_ch, rgbd_elic** out)
     if (r) return r;
     (*out)->variant = 4;
     (*out)->in_ch = in_ch;
-    (*out)->refnum = false;  // (the STF family keeps the single-chain arithmetic, as STF_united)
+    (*out)->refnum = false;  // (the STF family keeps the single-chain arithmetic, as STF_united; nothing sets it later, so
+                             // perm() is 0 in the shared single-modal call paths)
     return RGBD_OK;
 }
 
@@ -1058,7 +1059,7 @@ int rgbd_elic_create_ckbd(int32_t N, int32_t in_ch, rgbd_elic** out)
     if (r) return r;
     (*out)->variant = 5;
     (*out)->in_ch = in_ch;
-    (*out)->refnum = false;  // (this family keeps the single-chain arithmetic, like STF: DESIGN.md 4a)
+    (*out)->refnum = false;  // (this family keeps the single-chain arithmetic, like STF: DESIGN.md 4a; perm() is 0, as there)
     return RGBD_OK;
 }
 
@@ -1072,10 +1073,7 @@ int rgbd_elic_compress_single(rgbd_elic* m, const float* x_dev, int32_t B, int32
     const int per_image = (per_image_streams || B == 1) ? 1 : 0;
     char key[96];
     snprintf(key, sizeof(key), "c1|%d|%d|%d|%d", B, H, W, per_image);
-    r = run_sized(m, key, [&]() {
-        if (m->variant == 5) return m->run_compress_ckbd(x_dev, B, H, W, per_image);
-        return m->variant == 4 ? m->run_compress_stf1(x_dev, B, H, W, per_image) : m->run_compress1(x_dev, B, H, W, per_image);
-    });
+    r = run_sized(m, key, [&]() { return m->run_compress_single(x_dev, B, H, W, per_image); });
     if (m->profile) m->profile_collect();
     return r;
 }
@@ -1090,11 +1088,7 @@ int rgbd_elic_forward_single(rgbd_elic* m, const float* x_dev, int32_t B, int32_
     if (const int ur = m->use_stream(stream)) return ur;
     char key[96];
     snprintf(key, sizeof(key), "f1|%d|%d|%d", B, H, W);
-    return run_sized(m, key, [&]() {
-        if (m->variant == 5) return m->run_forward_ckbd(x_dev, B, H, W, xhat_dev, lik_y, lik_z);
-        return m->variant == 4 ? m->run_forward_stf1(x_dev, B, H, W, xhat_dev, lik_y, lik_z)
-                               : m->run_forward1(x_dev, B, H, W, xhat_dev, lik_y, lik_z);
-    });
+    return run_sized(m, key, [&]() { return m->run_forward_single(x_dev, B, H, W, xhat_dev, lik_y, lik_z); });
 }
 
 int rgbd_elic_decompress_single(rgbd_elic* m, const uint8_t* const* y, const int64_t* y_len, int32_t n_y,
@@ -1108,11 +1102,7 @@ int rgbd_elic_decompress_single(rgbd_elic* m, const uint8_t* const* y, const int
     if (const int ur = m->use_stream(stream)) return ur;
     char key[96];
     snprintf(key, sizeof(key), "d1|%d|%d|%d|%d", B, zh, zw, n_y);
-    r = run_sized(m, key, [&]() {
-        if (m->variant == 5) return m->run_decompress_ckbd(y, y_len, n_y, z, z_len, B, zh, zw, x_dev);
-        return m->variant == 4 ? m->run_decompress_stf1(y, y_len, n_y, z, z_len, B, zh, zw, x_dev)
-                               : m->run_decompress1(y, y_len, n_y, z, z_len, B, zh, zw, x_dev);
-    });
+    r = run_sized(m, key, [&]() { return m->run_decompress_single(y, y_len, n_y, z, z_len, B, zh, zw, x_dev); });
     if (!r) r = m->wait_stream();  // (the work may sit on the engine's own stream: return when x_hat is there)
     if (m->profile && !r) m->profile_collect();
     return r;
