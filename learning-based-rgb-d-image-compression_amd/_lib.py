@@ -57,7 +57,8 @@ def build(force: bool = False, verbose: bool = False) -> str:
              "conv_mfma_blk.hip": [body]}
     hdrs.append(os.path.join(csrc, "splitk_table.h"))
     extra["coder_abi.hip"] = extra["gdn.hip"] = [os.path.join(csrc, "engine_internal.h")]
-    extra["engine.hip"] = extra["engine_abi.hip"] = [os.path.join(csrc, "engine_internal.h"), os.path.join(csrc, "engine.h")]
+    extra["engine.hip"] = extra["engine_abi.hip"] = [os.path.join(csrc, "engine_internal.h"), os.path.join(csrc, "engine.h"),
+                                                     os.path.join(csrc, "conv_args.h")]
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     os.makedirs(objdir, exist_ok=True)
     jobs, objs = [], []

@@ -32,6 +32,7 @@
 
 #include "../../include/rgbd_amd.h"
 #include "common.h"
+#include "conv_args.h"
 #include "engine_internal.h"
 
 
@@ -46,14 +47,6 @@ namespace rgbd_rt {
 struct HostTensor {
     std::vector<float> v;
     std::vector<int64_t> shape;
-};
-
-struct PackedConv {
-    float* w = nullptr;  // [cout_pad][k*k][cin_pad]
-    float* bias = nullptr;
-    int cin = 0, cout = 0, cin_pad = 0, cout_pad = 0, k = 0;
-    bool transposed = false;
-    bool subpix = false;  // pack_subpix(): [16 = phase * 4 + cout][9 taps][cin_pad] of a k = 5, stride-2 transposed conv
 };
 
 // perm_in / perm_out: store the input / output channels at their permuted positions (rgbd_cperm)
@@ -150,72 +143,6 @@ inline int pack_kpack(const HostTensor& w, const HostTensor* b, PackedConv* pc, 
     const int rc = pack_conv(w1, b, false, pc, gen, 0, perm_out);
     pc->cin = nterm;  // FLOP accounting: the real reduction length
     return rc;
-}
-
-inline void make_taps_subpix(ConvArgs* a)
-{
-    memset(&a->taps, 0, sizeof(a->taps));
-    a->nphase = 1;
-    a->IS = 1;
-    a->OS = 2;
-    a->subpix = 1;
-    for (int u = 0; u < 9; ++u) {
-        a->taps.dy[0][u] = (int8_t)(1 - u / 3);
-        a->taps.dx[0][u] = (int8_t)(1 - u % 3);
-        a->taps.wt[0][u] = (int8_t)u;
-    }
-    a->taps.n[0] = 9;
-    a->min_dy = a->min_dx = -1;
-    a->span_y = a->span_x = 3;
-}
-
-inline void make_taps(const PackedConv& pc, int stride, int pad, ConvArgs* a)
-{
-    const int k = pc.k;
-    memset(&a->taps, 0, sizeof(a->taps));
-    if (!pc.transposed) {
-        a->nphase = 1;
-        a->IS = stride;
-        a->OS = 1;
-        int n = 0;
-        for (int ky = 0; ky < k; ++ky)
-            for (int kx = 0; kx < k; ++kx) {
-                a->taps.dy[0][n] = (int8_t)(ky - pad);
-                a->taps.dx[0][n] = (int8_t)(kx - pad);
-                a->taps.wt[0][n] = (int8_t)(ky * k + kx);
-                ++n;
-            }
-        a->taps.n[0] = (int8_t)n;
-        a->min_dy = a->min_dx = -pad;
-        a->span_y = a->span_x = k;
-        return;
-    }
-    // transposed: o = i*s - pad + k  =>  for o = s*t + r: i = t + (r + pad - k)/s for k == (r + pad) mod s
-    a->nphase = stride * stride;
-    a->IS = 1;
-    a->OS = stride;
-    int mn = 127, mx = -127;
-    for (int ry = 0; ry < stride; ++ry)
-        for (int rx = 0; rx < stride; ++rx) {
-            const int ph = ry * stride + rx;
-            int n = 0;
-            for (int ky = 0; ky < k; ++ky) {
-                if ((ry + pad - ky) % stride) continue;
-                for (int kx = 0; kx < k; ++kx) {
-                    if ((rx + pad - kx) % stride) continue;
-                    const int dy = (ry + pad - ky) / stride, dx = (rx + pad - kx) / stride;
-                    a->taps.dy[ph][n] = (int8_t)dy;
-                    a->taps.dx[ph][n] = (int8_t)dx;
-                    a->taps.wt[ph][n] = (int8_t)(ky * k + kx);
-                    mn = std::min(mn, std::min(dy, dx));
-                    mx = std::max(mx, std::max(dy, dx));
-                    ++n;
-                }
-            }
-            a->taps.n[ph] = (int8_t)n;
-        }
-    a->min_dy = a->min_dx = mn;
-    a->span_y = a->span_x = mx - mn + 1;
 }
 
 
@@ -408,8 +335,7 @@ inline int deconv_s2_ref_run(const PackedConv& pcv, const int* rec, size_t nrec,
             while (j1 < w && same(d, desc[(size_t)ph * w + j1])) ++j1;
             const int jw = j1 - j0, nt = d[0];
             if (nt < 1 || nt > 16) return RGBD_EINVAL;
-            int dy[16], dx[16], slab[16], nch = 0;
-            uint16_t bnd[18] = {0};
+            int dy[16], dx[16], slab[16], chain[16], nch = 0;  // chain: channels of the GEMM's K axis each fma chain reduces
             for (int t = 0; t < nt; ++t) {
                 const int ky = d[1 + 3 * t], kx = d[2 + 3 * t], fresh = d[3 + 3 * t];
                 // (a tap of another phase -- (py + 2 - ky) or (px + 2 - kx) odd -- never meets this phase's pixels)
@@ -417,10 +343,9 @@ inline int deconv_s2_ref_run(const PackedConv& pcv, const int* rec, size_t nrec,
                 dy[t] = (py + 2 - ky) / 2;  // input row of output row 2 ty + py under tap ky: ty + (py + pad - ky) / 2
                 dx[t] = (px + 2 - kx) / 2;
                 slab[t] = ky * 5 + kx;
-                if (fresh || t == 0) bnd[nch++] = (uint16_t)(t * (pc->cin_pad / 16));
+                if (fresh || t == 0) chain[nch++] = 0;
+                chain[nch - 1] += pc->cin_pad;
             }
-            bnd[nch] = (uint16_t)(nt * (pc->cin_pad / 16));
-            if (nch > 16) return RGBD_EINVAL;
             const size_t mark = scratch.mark();
             const size_t npx = (size_t)B * h * jw;
             const int Kp = nt * pc->cin_pad;
@@ -433,37 +358,24 @@ inline int deconv_s2_ref_run(const PackedConv& pcv, const int* rec, size_t nrec,
                 int r = launch_gather_taps(x, B, h, w, pc->cin_pad, j0, jw, nt, dy, dx, col, s);
                 if (!r) r = launch_gather_wslabs(pc->w, pc->cout_pad, 25, pc->cin_pad, nt, slab, wsel, s);
                 if (!r) {
+                    PackedConv gemm;  // the 1x1 layer over the gathered columns
+                    gemm.w = wsel;
+                    gemm.bias = pc->bias;
+                    gemm.cin_pad = Kp;
+                    gemm.cout_pad = pc->cout_pad;
+                    gemm.k = 1;
                     ConvArgs a{};
-                    a.x = col;
-                    a.N = 1;
-                    a.H = B * h;
-                    a.W = jw;
-                    a.xcs = Kp;
-                    a.cin_pad = Kp;
-                    a.w = wsel;
-                    a.ntaps_total = 1;
-                    a.bias = pc->bias;
-                    a.y = tmp;
-                    a.OH = B * h;
-                    a.OW = jw;
-                    a.ycs = pc->cout_pad;
-                    a.cout_pad = pc->cout_pad;
+                    conv_args_geometry(&a, gemm, col, 1, B * h, jw, Kp, tmp, pc->cout_pad, B * h, jw, 1, 0);
                     a.cout_store = pc->cout_pad;
-                    a.GH = B * h;
-                    a.GW = jw;
-                    a.IS = a.OS = 1;
-                    a.nphase = 1;
-                    a.taps.n[0] = 1;
-                    a.span_y = a.span_x = 1;
                     a.act = act;
                     a.loaded = tile_mode;
                     a.exact_math = 1;
-                    a.splitk = nch;
+                    a.splitk = 1;
                     if (nch > 1) {
                         a.partial = part;
-                        for (int c = 0; c <= nch; ++c) a.split_c16[c] = bnd[c];
+                        r = conv_set_split_ranges(&a, chain, nch);
                     }
-                    r = launch_conv(a, s);
+                    if (!r) r = launch_conv(a, s);
                 }
                 if (!r) r = launch_scatter_phase(tmp, B, h, jw, pc->cout_pad, j0, py, px, out, 2 * w, ocs, pc->cout_pad, s);
                 if (r) return r;
@@ -942,13 +854,7 @@ struct rgbd_elic {
         }
         const int k = pc->k;
         int OH, OW;
-        if (!pc->transposed) {
-            OH = (x.h + 2 * pad - k) / stride + 1;
-            OW = (x.w + 2 * pad - k) / stride + 1;
-        } else {
-            OH = (x.h - 1) * stride - 2 * pad + k + (stride - 1);
-            OW = (x.w - 1) * stride - 2 * pad + k + (stride - 1);
-        }
+        conv_out_hw(x.h, x.w, k, stride, pad, pc->transposed, &OH, &OW);
         const PackedConv* pcy = pc2 ? pc2 : pc;  // the layer that produces y
         Act y = dst ? *dst : alloc(x.n, OH, OW, pcy->cout);
         cp.y = y;
@@ -965,83 +871,28 @@ struct rgbd_elic {
         // (the sizing pass runs through the same planning -- pointers are placeholders there -- so that it books exactly the
         //  split-K planes the launch will use: a flat "8 planes per layer" used to be most of the workspace, 2 GB per big-map layer)
         ConvArgs& a = cp.a;
-        a.x = x.p;
-        a.N = x.n;
-        a.H = x.h;
-        a.W = x.w;
-        a.xcs = x.cs;
-        a.cin_pad = pc->cin_pad;
-        a.w = pc->w;
-        a.ntaps_total = k * k;
-        a.bias = pc->bias;
-        a.y = y.p;
-        a.OH = OH;
-        a.OW = OW;
-        a.ycs = y.cs;
-        a.cout_pad = pc->cout_pad;
         // the last transposed conv (N -> 3 / 1): one 9-tap sub-pixel conv instead of four phases of padded couts
         const PackedConv* sp = nullptr;
         if (pc->transposed && g_subpix && !pc2 && stride == 2 && pad == 2 && k == 5 && !ep.res1 && !ep.mul && !ep.res2) {
             auto it = convs.find(name + ".subpix.weight");
             if (it != convs.end()) sp = &it->second;
         }
-        if (sp) {
-            a.w = sp->w;
-            a.bias = sp->bias;
-            a.ntaps_total = 9;
-            a.cout_pad = 16;
-        }
-        // a channel slice narrower than its 16-padded width inside a wider buffer (STF_united: 24 of 48): stop at the
-        // slice end; a buffer of its own gets its pad channels zeroed as usual
-        a.cout_store = (pcy->cout % 16 && y.cs != round_up(pcy->cout, 16)) ? round_up(pcy->cout, 4) : pcy->cout_pad;
-        if (pc2) {
-            a.w2 = pc2->w;
-            a.bias2 = pc2->bias;
-            a.cout2_pad = pc2->cout_pad;
-            a.act_mid = ACT_RELU;
-        }
-        if (pc3) {
-            a.w3 = pc3->w;
-            a.bias3 = pc3->bias;
-            a.y3 = lead_dst->p;
-            a.y3cs = lead_dst->cs;
-            a.cout3_pad = pc3->cout_pad;
-        }
-        if (sp) {
-            make_taps_subpix(&a);
-            a.cout_store = 16;
-        } else {
-            make_taps(*pc, stride, pad, &a);
-        }
-        a.GH = pc->transposed ? x.h : OH;
-        a.GW = pc->transposed ? x.w : OW;
-        a.act = ep.act;
-        a.ckbd = ep.ckbd;
-        if (ep.dup) {
-            a.y2 = ep.dup->p;
-            a.y2cs = ep.dup->cs;
-        }
+        conv_args_geometry(&a, sp ? *sp : *pc, x.p, x.n, x.h, x.w, x.cs, y.p, y.cs, OH, OW, stride, pad);
+        a.cout_store = sp ? 16 : conv_cout_store(pcy->cout, y.cs);
+        if (pc2) conv_args_tail(&a, *pc2, ACT_RELU, refnum);  // (reference arithmetic: one reduce block, fusable() has checked)
+        if (pc3) conv_args_lead(&a, *pc3, lead_dst->p, lead_dst->cs);
+        const auto ptr = [](const Act* t) { return t ? t->p : nullptr; };
+        const auto cs = [](const Act* t) { return t ? t->cs : 0; };
+        conv_args_epilogue(&a, ep.act, ep.ckbd, ptr(ep.res1), cs(ep.res1), ptr(ep.mul), cs(ep.mul), ptr(ep.res2), cs(ep.res2),
+                           ptr(ep.dup), cs(ep.dup));
         a.loaded = tile_mode;
-        if (ep.res1) {
-            a.res1 = ep.res1->p;
-            a.r1cs = ep.res1->cs;
-        }
-        if (ep.mul) {
-            a.mul = ep.mul->p;
-            a.mcs = ep.mul->cs;
-        }
-        if (ep.res2) {
-            a.res2 = ep.res2->p;
-            a.r2cs = ep.res2->cs;
-        }
         // weight-heavy layers on the small latent grid (entropy model, hyper synthesis): split the reduction
         static const char* const kSplitPrefixes[] = {"rgb_entropy_parameters", "depth_entropy_parameters",
                                                      "rgb_channel_context", "depth_channel_context", "rgb_local_context",
                                                      "depth_local_context", "h_s."};
         a.splitk = 1;
         {
-            int mt = 1;
-            for (int ph = 0; ph < a.nphase; ++ph) mt = std::max(mt, (int)a.taps.n[ph]);
+            const int mt = conv_max_taps(a);
             bool listed = false;
             for (const char* pre : kSplitPrefixes) listed = listed || name.rfind(pre, 0) == 0;
             // a measured entry (csrc/splitk_table.h) applies to any layer of that shape; the rule only to the listed families.
@@ -1052,7 +903,7 @@ struct rgbd_elic {
             else if (splittable && g_force_splitk >= 0)
                 if (const int t = conv_splitk_table(a.cin_pad, a.cout_pad, mt, (long)OH * OW, a.nphase)) a.splitk = t;
         }
-        if (refnum) plan_refnum(cp, name, pc, pc2, pc3, sp != nullptr, x, stride, OH, OW);
+        if (refnum) plan_refnum(cp, name, pc, pc2, sp != nullptr, x, stride, OH, OW);
         // split-K partial planes; a GELU layer (STF_united's MLP) also goes through the reducer, with a single plane
         cp.partial_bytes = (a.splitk > 1 || a.act == ACT_GELU) ? (size_t)a.splitk * x.n * OH * OW * pc->cout_pad * sizeof(float) : 0;
         cp.flops = 2.0 * (double)x.n * OH * OW * (double)pc->cout * pc->cin * k * k /
@@ -1072,15 +923,13 @@ struct rgbd_elic {
     //   conv_transpose2d, stride 1                a block per 16 input channels; bias last
     // Layers with no decision behind them that have a faster special form keep it (the image-producing sub-pixel layer);
     // stride-2 transposed convs: see deconv_s2_ref().
-    void plan_refnum(ConvPlan& cp, const std::string& name, const PackedConv* pc, const PackedConv* pc2, const PackedConv* pc3,
-                     bool subpix, const Act& x, int stride, int OH, int OW)
+    void plan_refnum(ConvPlan& cp, const std::string& name, const PackedConv* pc, const PackedConv* pc2, bool subpix, const Act& x,
+                     int stride, int OH, int OW)
     {
         ConvArgs& a = cp.a;
         a.exact_math = 1;
         const bool kpacked = name.size() > 6 && name.compare(name.size() - 6, 6, ".kpack") == 0;
         if (subpix || kpacked || (pc->transposed && stride != 1)) return;  // (single chain, bias in the epilogue)
-        if (pc2) a.tail_bias_init = 1;  // the fused 1x1 tails: one reduce block (fusable_ref() has checked), chains start at the bias
-        (void)pc3;
         if (pc->k == 1 && !pc->transposed) {
             a.bias_mode = 2;
             const std::vector<int>* bl = ref_blocks(0, pc->cin, pc->cout, x.h, x.w);
@@ -1092,43 +941,16 @@ struct rgbd_elic {
             // small grids: the blocks as split-K ranges (the ordered reducer adds the block sums); large maps: in the kernel
             const bool split = (long)OH * OW <= 2048 && nb <= 16 && !pc2;
             if (split) {
-                a.splitk = nb;
-                int pos = 0;
-                for (int b = 0; b < nb; ++b) {
-                    a.split_c16[b] = (uint16_t)(pos / 16);
-                    pos += (*bl)[b];
-                }
-                a.split_c16[nb] = (uint16_t)((pos + 15) / 16);
+                if (conv_set_split_ranges(&a, bl->data(), nb)) fail(RGBD_EINVAL);
             } else {
                 a.splitk = 1;
-                if (set_blocks_of(&a, bl->data(), nb)) fail(RGBD_EINVAL);
+                if (conv_set_blocks(&a, bl->data(), nb)) fail(RGBD_EINVAL);
             }
             return;
         }
         a.splitk = 1;
         a.bias_mode = pc->transposed ? 0 : 1;
-        if (set_blocks_of(&a, nullptr, 0)) fail(RGBD_EINVAL);
-    }
-    static int set_blocks_of(ConvArgs* a, const int* blocks, int nblocks)
-    {
-        memset(a->blk_end, 0, sizeof(a->blk_end));
-        const int n16 = a->cin_pad / 16;
-        if (n16 > 256) return RGBD_EINVAL;
-        if (!blocks || nblocks <= 0) {
-            for (int c = 0; c < n16; ++c) a->blk_end[c >> 5] |= 1u << (c & 31);
-        } else {
-            int pos = 0;
-            for (int b = 0; b < nblocks; ++b) {
-                if (blocks[b] <= 0 || (blocks[b] % 16 && b + 1 < nblocks)) return RGBD_EINVAL;
-                pos += blocks[b];
-                const int c = (pos + 15) / 16 - 1;
-                if (c >= n16) return RGBD_EINVAL;
-                a->blk_end[c >> 5] |= 1u << (c & 31);
-            }
-            if ((pos + 15) / 16 != n16) return RGBD_EINVAL;
-        }
-        a->blocked = 1;
-        return RGBD_OK;
+        if (conv_set_blocks(&a, nullptr, 0)) fail(RGBD_EINVAL);
     }
 
     // can the two plans share a launch?  Same layer shape, strides and epilogue, operand by operand
@@ -1163,21 +985,7 @@ struct rgbd_elic {
         const size_t pmark = arena.top;
         if (p.partial_bytes) a.partial = (float*)arena.take(p.partial_bytes);
         if (q) {
-            const ConvArgs& b = q->a;
-            a.groups = 2;
-            a.g1.x = b.x;
-            a.g1.w = b.w;
-            a.g1.bias = b.bias;
-            a.g1.y = b.y;
-            a.g1.res1 = b.res1;
-            a.g1.mul = b.mul;
-            a.g1.res2 = b.res2;
-            a.g1.y2 = b.y2;
-            a.g1.w2 = b.w2;
-            a.g1.bias2 = b.bias2;
-            a.g1.w3 = b.w3;
-            a.g1.bias3 = b.bias3;
-            a.g1.y3 = b.y3;
+            conv_args_group1(&a, q->a);
             if (q->partial_bytes) a.g1.partial = (float*)arena.take(q->partial_bytes);
         }
         hipEvent_t e0 = nullptr, e1 = nullptr;
@@ -1230,7 +1038,8 @@ struct rgbd_elic {
         if (!(g_kpack && g_subpix && !pc->transposed && pc->k == 5 && stride == 2 && pad == 2 && x.c <= 3)) return false;
         auto kp = convs.find(name + ".kpack.weight");
         if (kp == convs.end()) return false;
-        const int OH = (x.h + 2 * pad - 5) / stride + 1, OW = (x.w + 2 * pad - 5) / stride + 1;
+        int OH, OW;
+        conv_out_hw(x.h, x.w, 5, stride, pad, false, &OH, &OW);
         *out = dst ? *dst : alloc(x.n, OH, OW, pc->cout);
         const size_t mark = arena.top;
         Act xk = alloc(x.n, OH, OW, kp->second.cin_pad);
@@ -1257,7 +1066,9 @@ struct rgbd_elic {
     {
         const PackedConv* pc = conv_of(name + ".weight");
         if (!pc) return Act();
-        const int k = pc->k, OH = (x.h + 2 * pad - k) / stride + 1, OW = (x.w + 2 * pad - k) / stride + 1;
+        const int k = pc->k;
+        int OH, OW;
+        conv_out_hw(x.h, x.w, k, stride, pad, false, &OH, &OW);
         Act y = dst ? *dst : alloc(x.n, OH, OW, pc->cout);
         if (dry() || rc) return y;
         if (y.h != OH || y.w != OW || y.c != pc->cout || (ep.ckbd && stride != 1)) {
@@ -1316,13 +1127,15 @@ struct rgbd_elic {
         auto it = convs.find(name + ".weight");
         if (it == convs.end() || it->second.transposed) return false;
         const PackedConv& pc = it->second;
-        const int OH = (x.h + 2 * pad - pc.k) / stride + 1, OW = (x.w + 2 * pad - pc.k) / stride + 1;
+        int OH, OW;
+        conv_out_hw(x.h, x.w, pc.k, stride, pad, false, &OH, &OW);
         return sigmoid_scalar_tails((long)(ref_batch == 1 ? 1 : x.n) * pc.cout * OH * OW);
     }
     Act conv_gated_ref(const std::string& name, const Act& x, int stride, int pad, const Epi& ep, const Act* dst)
     {
         const PackedConv& pc = convs.find(name + ".weight")->second;
-        const int OH = (x.h + 2 * pad - pc.k) / stride + 1, OW = (x.w + 2 * pad - pc.k) / stride + 1;
+        int OH, OW;
+        conv_out_hw(x.h, x.w, pc.k, stride, pad, false, &OH, &OW);
         Act out = dst ? *dst : alloc(x.n, OH, OW, pc.cout);
         const size_t mark = arena.top;
         Epi plain;

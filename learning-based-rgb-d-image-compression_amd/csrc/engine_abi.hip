@@ -69,29 +69,6 @@ int rgbd_get_blocking_sync(void)
     return (flags & hipDeviceScheduleMask) == hipDeviceScheduleBlockingSync ? 1 : 0;
 }
 
-// blocked accumulation for a layer of cin_pad channels: block boundaries (in channels, multiples of 16) -> ConvArgs::blk_end
-static int set_blocks(ConvArgs* a, const int32_t* blocks, int nblocks)
-{
-    memset(a->blk_end, 0, sizeof(a->blk_end));
-    const int n16 = a->cin_pad / 16;
-    if (n16 > 256) return RGBD_EINVAL;
-    if (!blocks || nblocks <= 0) {  // every 16-channel chunk is a block (the multi-tap kernels of the reference's CPU library)
-        for (int c = 0; c < n16; ++c) a->blk_end[c >> 5] |= 1u << (c & 31);
-    } else {
-        int pos = 0;
-        for (int b = 0; b < nblocks; ++b) {
-            if (blocks[b] <= 0 || (blocks[b] % 16 && b + 1 < nblocks)) return RGBD_EINVAL;
-            pos += blocks[b];
-            const int c = (pos + 15) / 16 - 1;
-            if (c >= n16) return RGBD_EINVAL;
-            a->blk_end[c >> 5] |= 1u << (c & 31);
-        }
-        if ((pos + 15) / 16 != n16) return RGBD_EINVAL;
-    }
-    a->blocked = 1;
-    return RGBD_OK;
-}
-
 static int conv2d_nchw_impl(const float* x_dev, int32_t n, int32_t cin, int32_t h, int32_t w, const float* weight,
                             const float* bias, int32_t cout, int32_t k, int32_t stride, int32_t pad, int32_t transposed,
                             int32_t act, const float* residual_dev, float* y_dev, void* stream, int refmode,
@@ -133,98 +110,47 @@ static int conv2d_nchw_impl(const float* x_dev, int32_t n, int32_t cin, int32_t 
         hb.shape = {cout};
         hb.v.assign(bias, bias + cout);
     }
-    PackedConv pc;
     const bool subpix = !refmode && transposed && g_subpix == 2 && cout <= 4 && k == 5 && stride == 2 && pad == 2 && !residual_dev;
     const int perm = refmode ? 1 : 0;
-    int rc = subpix ? pack_subpix(hw, bias ? &hb : nullptr, &pc, nullptr)
-                    : pack_conv(hw, bias ? &hb : nullptr, transposed != 0, &pc, nullptr, perm, perm);
+    DevBufs b;
+    DevGen gen;  // (owns the packed weights: released on every way out)
+    PackedConv pc;
+    int rc = subpix ? pack_subpix(hw, bias ? &hb : nullptr, &pc, &gen)
+                    : pack_conv(hw, bias ? &hb : nullptr, transposed != 0, &pc, &gen, perm, perm);
     if (rc) return rc;
     int OH, OW;
-    if (!transposed) {
-        OH = (h + 2 * pad - k) / stride + 1;
-        OW = (w + 2 * pad - k) / stride + 1;
-    } else {
-        OH = (h - 1) * stride - 2 * pad + k + (stride - 1);
-        OW = (w - 1) * stride - 2 * pad + k + (stride - 1);
-    }
-    float *xin = nullptr, *yout = nullptr, *res = nullptr;
-    const size_t xb = (size_t)n * h * w * pc.cin_pad * sizeof(float), yb = (size_t)n * OH * OW * pc.cout_pad * sizeof(float);
-    HIP_TRY(hipMalloc((void**)&xin, xb));
-    HIP_TRY(hipMalloc((void**)&yout, yb));
-    rc = launch_nchw_to_nhwc16(x_dev, n, cin, h, w, xin, pc.cin_pad, s, perm);
-    if (!rc && residual_dev) {
-        HIP_TRY(hipMalloc((void**)&res, yb));
-        rc = launch_nchw_to_nhwc16(residual_dev, n, cout, OH, OW, res, pc.cout_pad, s, perm);
-    }
-    if (!rc) {
-        ConvArgs a{};
-        a.x = xin;
-        a.N = n;
-        a.H = h;
-        a.W = w;
-        a.xcs = pc.cin_pad;
-        a.cin_pad = pc.cin_pad;
-        a.w = pc.w;
-        a.ntaps_total = subpix ? 9 : k * k;
-        a.bias = pc.bias;
-        a.y = yout;
-        a.OH = OH;
-        a.OW = OW;
-        a.ycs = pc.cout_pad;
-        a.cout_pad = pc.cout_pad;
-        if (subpix) {
-            make_taps_subpix(&a);
-            HIP_TRY(hipMemsetAsync(yout, 0, yb, s));  // channels 4..15 are not written in this form
+    conv_out_hw(h, w, k, stride, pad, transposed != 0, &OH, &OW);
+    const size_t xf = (size_t)n * h * w * pc.cin_pad, yf = (size_t)n * OH * OW * pc.cout_pad;
+    ConvArgs a{};
+    a.cin_pad = pc.cin_pad;  // (what the block helpers measure the blocks against)
+    a.splitk = (g_force_splitk > 0 && !refmode) ? std::min(g_force_splitk, pc.cin_pad / 16) : 1;
+    if (refmode) {
+        a.bias_mode = bias_mode;
+        a.exact_math = flags & 1;
+        if ((flags & 2) && blocks && nblocks > 1 && nblocks <= 16) {  // the blocks as split-K ranges of the single-chain kernel
+            rc = conv_set_split_ranges(&a, blocks, nblocks);
+            if (bias_mode == 1) rc = RGBD_EINVAL;
+        } else if (blocks && nblocks == 1) {
+            if (bias_mode == 1) a.bias_mode = 0;  // (one block: S_0 + bias is the epilogue's add)
         } else {
-            make_taps(pc, stride, pad, &a);
+            rc = conv_set_blocks(&a, blocks, nblocks);
         }
-        a.GH = transposed ? h : OH;
-        a.GW = transposed ? w : OW;
-        a.act = act;
-        if (res) {
-            a.res1 = res;
-            a.r1cs = pc.cout_pad;
-        }
-        float* part = nullptr;
-        a.splitk = (g_force_splitk > 0 && !refmode) ? std::min(g_force_splitk, pc.cin_pad / 16) : 1;
-        if (refmode) {
-            a.bias_mode = bias_mode;
-            a.exact_math = flags & 1;
-            if ((flags & 2) && blocks && nblocks > 1 && nblocks <= 16) {  // the blocks as split-K ranges of the single-chain kernel
-                a.splitk = nblocks;
-                int pos = 0;
-                for (int b = 0; b < nblocks; ++b) {
-                    a.split_c16[b] = (uint16_t)(pos / 16);
-                    pos += blocks[b];
-                }
-                a.split_c16[nblocks] = (uint16_t)((pos + 15) / 16);
-                if (bias_mode == 1) rc = RGBD_EINVAL;
-            } else if (blocks && nblocks == 1) {
-                if (bias_mode == 1) bias_mode = a.bias_mode = 0, rc = RGBD_OK;  // (one block: S_0 + bias is the epilogue's add)
-            } else {
-                rc = set_blocks(&a, blocks, nblocks);
-            }
-        }
-        if (a.splitk > 1) {
-            HIP_TRY(hipMalloc((void**)&part, (size_t)a.splitk * yb));
-            a.partial = part;
-        }
-        a.ckbd = g_force_ckbd;
-        if (a.ckbd) HIP_TRY(hipMemsetAsync(yout, 0, yb, s));  // the half that is not computed reads as zero
-        if (!rc) rc = launch_conv(a, s);
-        if (part) {
-            (void)hipStreamSynchronize(s);
-            (void)hipFree(part);
-        }
+        if (rc) return rc;
     }
+    float *xin = b.get(xf), *yout = b.get(yf), *res = residual_dev ? b.get(yf) : nullptr;
+    float* part = a.splitk > 1 ? b.get((size_t)a.splitk * yf) : nullptr;  // (read by the reducer: released after the stream has drained)
+    if (!xin || !yout || (residual_dev && !res) || (a.splitk > 1 && !part)) return RGBD_ENOMEM;
+    conv_args_geometry(&a, pc, xin, n, h, w, pc.cin_pad, yout, pc.cout_pad, OH, OW, stride, pad);
+    conv_args_epilogue(&a, act, g_force_ckbd, res, pc.cout_pad, nullptr, 0, nullptr, 0, nullptr, 0);
+    a.partial = part;
+    rc = launch_nchw_to_nhwc16(x_dev, n, cin, h, w, xin, pc.cin_pad, s, perm);
+    if (!rc && res) rc = launch_nchw_to_nhwc16(residual_dev, n, cout, OH, OW, res, pc.cout_pad, s, perm);
+    // (the sub-pixel form does not write channels 4..15; the half a checkerboard launch does not compute reads as zero)
+    if (!rc && (subpix || a.ckbd)) HIP_TRY(hipMemsetAsync(yout, 0, yf * sizeof(float), s));
+    if (!rc) rc = launch_conv(a, s);
     if (!rc) rc = launch_nhwc_to_nchw_clamp(yout, n, cout, OH, OW, pc.cout_pad, y_dev, 0, s, perm);
-    hipError_t e = hipStreamSynchronize(s);
+    const hipError_t e = hipStreamSynchronize(s);
     if (!rc && e != hipSuccess) rc = RGBD_EHIP;
-    (void)hipFree(xin);
-    (void)hipFree(yout);
-    (void)hipFree(res);
-    (void)hipFree(pc.w);
-    (void)hipFree(pc.bias);
     return rc;
 }
 
@@ -252,30 +178,17 @@ int rgbd_pointwise_nchw(int32_t op, const float* x_dev, int32_t n, int32_t c, in
     } else if (oh <= 0 || ow <= 0) {
         return RGBD_EINVAL;
     }
-    // (test / tool entry point, not the codec path.)  Every buffer is released on every way out.
-    struct Bufs {
-        float *xin = nullptr, *yout = nullptr, *aux = nullptr, *dw0 = nullptr, *dw1 = nullptr;
-        ~Bufs()
-        {
-            (void)hipFree(xin);
-            (void)hipFree(yout);
-            (void)hipFree(aux);
-            (void)hipFree(dw0);
-            (void)hipFree(dw1);
-        }
-    } b;
-    float *&xin = b.xin, *&yout = b.yout, *&aux = b.aux, *&dw0 = b.dw0, *&dw1 = b.dw1;
-    HIP_TRY(hipMalloc((void**)&xin, (size_t)n * h * w * cs * sizeof(float)));
-    HIP_TRY(hipMalloc((void**)&yout, (size_t)n * oh * ow * cs * sizeof(float)));
+    DevBufs b;  // (test / tool entry point, not the codec path: every buffer is released on every way out)
+    float *xin = b.get((size_t)n * h * w * cs), *yout = b.get((size_t)n * oh * ow * cs);
+    if (!xin || !yout) return RGBD_ENOMEM;
     // (the operators as the codec runs them: channels stored permuted, the reference's CPU arithmetic -- DESIGN.md 4a)
     int rc = launch_nchw_to_nhwc16(x_dev, n, c, h, w, xin, cs, s, 1);
     if (!rc && op == 0) rc = launch_maxpool7s3(xin, n, h, w, cs, yout, oh, ow, s);
     if (!rc && op == 1) rc = launch_bilinear(xin, n, h, w, cs, yout, oh, ow, s, nullptr, nullptr, c);
     if (!rc && op >= 2) {
         const int hid = c / 16;
-        HIP_TRY(hipMalloc((void**)&aux, (size_t)n * (2 * c + hid + 1) * sizeof(float)));
-        HIP_TRY(hipMalloc((void**)&dw0, (size_t)c * hid * sizeof(float)));
-        HIP_TRY(hipMalloc((void**)&dw1, (size_t)c * hid * sizeof(float)));
+        float *aux = b.get((size_t)n * (2 * c + hid + 1)), *dw0 = b.get((size_t)c * hid), *dw1 = b.get((size_t)c * hid);
+        if (!aux || !dw0 || !dw1) return RGBD_ENOMEM;
         HIP_TRY(hipMemcpy(dw0, w0, (size_t)c * hid * sizeof(float), hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(dw1, w1, (size_t)c * hid * sizeof(float), hipMemcpyHostToDevice));
         float *mean = aux, *sc = aux + (size_t)n * c, *hd = aux + (size_t)2 * n * c;
@@ -294,20 +207,6 @@ int rgbd_pointwise_nchw(int32_t op, const float* x_dev, int32_t n, int32_t c, in
 // channel-order tensors to the engine's layout (NHWC, channels permuted: rgbd_cperm), calls the launcher the engine calls with
 // the engine's permutation arguments, and converts back.  Device scratch is released on every way out.
 namespace {
-struct DevBufs {
-    std::vector<void*> v;
-    float* get(size_t floats)
-    {
-        void* p = nullptr;
-        if (hipMalloc(&p, std::max<size_t>(floats, 1) * sizeof(float)) != hipSuccess) return nullptr;
-        v.push_back(p);
-        return (float*)p;
-    }
-    ~DevBufs()
-    {
-        for (void* p : v) (void)hipFree(p);
-    }
-};
 // deconv_s2_ref_run's scratch outside an engine: one device allocation per take, all released when the hook returns
 struct MallocScratch {
     DevBufs& b;
@@ -415,7 +314,8 @@ int rgbd_ref_small_conv_nchw(const float* x_dev, int32_t n, int32_t cin, int32_t
         stride > 2 || pad < 0 || pad > k || act < ACT_NONE || act > ACT_SIGMOID || ckbd < 0 || ckbd > 2 || (ckbd && stride != 1))
         return RGBD_EINVAL;
     if (h + 2 * pad < k || w + 2 * pad < k) return RGBD_EINVAL;
-    const int OH = (h + 2 * pad - k) / stride + 1, OW = (w + 2 * pad - k) / stride + 1;
+    int OH, OW;
+    conv_out_hw(h, w, k, stride, pad, false, &OH, &OW);
     if (!tensor_ok(n, cout, OH, OW)) return RGBD_EINVAL;
     SmallConvArgs a{};
     if (small_conv_set_kblocks(&a, kblocks, nkblocks, cin * k * k)) return RGBD_EINVAL;
@@ -514,12 +414,10 @@ int rgbd_ref_deconv_s2_nchw(const float* x_dev, int32_t n, int32_t cin, int32_t 
 }
 
 // ---- the conv launchers in every form the engine issues (test hook: tests/test_gpu_convforms.py; include/rgbd_amd.h) ---------
-// conv2d_nchw_impl above always builds the plainest ConvArgs.  This one fills the fields Engine::conv_plan / conv_issue fill
-// -- fused tail, lead layer, gate / skip operands, second destination, channel-slice placement, second operand set -- and
-// calls launch_conv / launch_conv_fused, the functions conv_issue calls.
+// conv2d_nchw_impl above always builds the plainest ConvArgs.  This one builds, from the helpers the engine's planner builds
+// its launches from (conv_args.h), every other form -- fused tail, lead layer, gate / skip operands, second destination,
+// channel-slice placement, second operand set -- and calls launch_conv / launch_conv_fused, the functions conv_issue calls.
 namespace {
-// channels a launch stores: Engine::conv_plan's rule
-inline int forms_cout_store(int c, int cs) { return (c % 16 && cs != round_up(c, 16)) ? round_up(c, 4) : round_up(c, 16); }
 // channels [off, off + c) of a tensor of `total` channels as a destination of `store` channels: in bounds, and what is
 // stored past the slice lands in the buffer's own pad channels (permuted layout: whole groups of 16 only)
 inline bool forms_dst_ok(int off, int c, int total, int store, bool perm)
@@ -548,8 +446,8 @@ int rgbd_conv_forms_nchw(const rgbd_conv_forms_desc* d, void* stream)
         (lead && !fused))
         return RGBD_EINVAL;
     if (!tr && (h + 2 * pad < k || w + 2 * pad < k)) return RGBD_EINVAL;
-    const int OH = tr ? (h - 1) * stride - 2 * pad + k + (stride - 1) : (h + 2 * pad - k) / stride + 1;
-    const int OW = tr ? (w - 1) * stride - 2 * pad + k + (stride - 1) : (w + 2 * pad - k) / stride + 1;
+    int OH, OW;
+    conv_out_hw(h, w, k, stride, pad, tr, &OH, &OW);
     const int cy = fused ? d->cout2 : cout;  // channels of y
     if (OH <= 0 || OW <= 0 || !tensor_ok(n, cy, OH, OW) || !tensor_ok(n, cout, OH, OW)) return RGBD_EINVAL;
     const int perm = refmode ? 1 : 0;
@@ -559,10 +457,10 @@ int rgbd_conv_forms_nchw(const rgbd_conv_forms_desc* d, void* stream)
         return RGBD_EINVAL;
     const int xcs = round_up(d->x_total, 16), ycs = round_up(std::max(d->y_total, 1), 16), y2cs = round_up(std::max(d->y2_total, 1), 16),
               y3cs = round_up(std::max(d->y3_total, 1), 16);
-    const int cout_store = forms_cout_store(cy, ycs);
+    const int cout_store = conv_cout_store(cy, ycs);
     if (!forms_dst_ok(d->y_off, cy, d->y_total, cout_store, perm) || !tensor_ok(n, d->y_total, OH, OW)) return RGBD_EINVAL;
     const bool dup = d->set[0].y2_dev != nullptr;
-    if (dup && (forms_cout_store(cy, y2cs) != cout_store || !forms_dst_ok(d->y2_off, cy, d->y2_total, cout_store, perm) ||
+    if (dup && (conv_cout_store(cy, y2cs) != cout_store || !forms_dst_ok(d->y2_off, cy, d->y2_total, cout_store, perm) ||
                 !tensor_ok(n, d->y2_total, OH, OW)))
         return RGBD_EINVAL;
     if (lead && (!forms_dst_ok(d->y3_off, d->cout3, d->y3_total, cout3_pad, perm) || !tensor_ok(n, d->y3_total, OH, OW))) return RGBD_EINVAL;
@@ -579,9 +477,10 @@ int rgbd_conv_forms_nchw(const rgbd_conv_forms_desc* d, void* stream)
     }
     const rgbd_conv_forms_ops& o0 = d->set[0];
     // what the launchers refuse (launch_conv / launch_conv_fused / launch_cfg)
-    ConvArgs a{};
+    ConvArgs a{};  // (what the checks decide is kept: reference-arithmetic fields, blocks, split ranges)
     a.cin_pad = cin_pad;
-    int splitk = 1, cls = 0;
+    a.splitk = 1;
+    int cls = 0;
     const int ckbd = g_force_ckbd;
     const int nphase = tr ? stride * stride : 1, IS = tr ? 1 : stride, OS = tr ? stride : 1;
     if (ckbd && (nphase != 1 || IS != 1 || OS != 1)) return RGBD_EINVAL;
@@ -591,19 +490,14 @@ int rgbd_conv_forms_nchw(const rgbd_conv_forms_desc* d, void* stream)
         a.bias_mode = d->bias_mode;
         a.exact_math = d->flags & 1;
         if ((d->flags & 2) && d->blocks && d->nblocks > 1 && d->nblocks <= 16) {  // the blocks as split-K ranges (as conv2d_nchw_impl)
-            int pos = 0;
-            for (int b = 0; b < d->nblocks; ++b) {
-                if (d->blocks[b] <= 0 || d->blocks[b] % 16) return RGBD_EINVAL;
-                a.split_c16[b] = (uint16_t)(pos / 16);
-                pos += d->blocks[b];
-            }
-            a.split_c16[d->nblocks] = (uint16_t)((pos + 15) / 16);
-            if (d->bias_mode == 1 || fused || (pos + 15) / 16 != cin_pad / 16) return RGBD_EINVAL;
-            splitk = d->nblocks;
+            for (int b = 0; b < d->nblocks; ++b)
+                if (d->blocks[b] % 16) return RGBD_EINVAL;
+            if (conv_set_split_ranges(&a, d->blocks, d->nblocks)) return RGBD_EINVAL;
+            if (d->bias_mode == 1 || fused || a.split_c16[d->nblocks] != cin_pad / 16) return RGBD_EINVAL;
         } else if (d->blocks && d->nblocks == 1) {
             if (d->blocks[0] != cin) return RGBD_EINVAL;
             if (a.bias_mode == 1) a.bias_mode = 0;  // (one block: S_0 + bias is the epilogue's add)
-        } else if (set_blocks(&a, d->blocks, d->nblocks)) {
+        } else if (conv_set_blocks(&a, d->blocks, d->nblocks)) {
             return RGBD_EINVAL;
         }
         if (a.blocked && d->blocks) {  // (the table was checked against the padded width: the blocks must add up to cin itself)
@@ -613,7 +507,7 @@ int rgbd_conv_forms_nchw(const rgbd_conv_forms_desc* d, void* stream)
         }
     } else {
         if (d->nblocks || d->blocks || d->bias_mode || d->flags) return RGBD_EINVAL;
-        if (g_force_splitk > 0 && !fused) splitk = std::max(1, std::min(g_force_splitk, cin_pad / 16));
+        if (g_force_splitk > 0 && !fused) a.splitk = std::max(1, std::min(g_force_splitk, cin_pad / 16));
     }
     if (fused) {
         if (tr || stride != 1 || k * k > 9 || cout_pad != 96 || cout2_pad % 96 || ckbd || o0.mul_dev || o0.res2_dev || dup ||
@@ -624,8 +518,8 @@ int rgbd_conv_forms_nchw(const rgbd_conv_forms_desc* d, void* stream)
         if (cls != 1 && cls != 2 && cls != 4) return RGBD_EINVAL;  // (0: the plan would not fuse this pair on this grid)
     } else {
         if (d->act_mid) return RGBD_EINVAL;
-        if (dup && splitk > 1) return RGBD_EINVAL;  // the reducer has one destination
-        if (a.blocked && splitk > 1) return RGBD_EINVAL;
+        if (dup && a.splitk > 1) return RGBD_EINVAL;  // the reducer has one destination
+        if (a.blocked && a.splitk > 1) return RGBD_EINVAL;
     }
     if ((size_t)cout_pad * k * k * cin_pad * 4 >= ((size_t)1 << 32)) return RGBD_EINVAL;
 
@@ -678,9 +572,9 @@ int rgbd_conv_forms_nchw(const rgbd_conv_forms_desc* d, void* stream)
         if (o.res1_dev) f.r1 = b.get((opx + OW + 1) * cyp);  // (the same slack as behind the destinations: what is read there is not used)
         if (o.mul_dev) f.m = b.get((opx + OW + 1) * cyp);
         if (o.res2_dev) f.r2 = b.get((opx + OW + 1) * cyp);
-        if (splitk > 1) f.part = b.get((size_t)splitk * opx * cout_pad);
+        if (a.splitk > 1) f.part = b.get((size_t)a.splitk * opx * cout_pad);
         if (!f.x || !f.y || (o.y2_dev && !f.y2) || (lead && !f.y3) || (o.res1_dev && !f.r1) || (o.mul_dev && !f.m) || (o.res2_dev && !f.r2) ||
-            (splitk > 1 && !f.part))
+            (a.splitk > 1 && !f.part))
             return RGBD_ENOMEM;
         rc = guard_arm(f.y, ycs);
         if (!rc && f.y2) rc = guard_arm(f.y2, y2cs);
@@ -694,64 +588,23 @@ int rgbd_conv_forms_nchw(const rgbd_conv_forms_desc* d, void* stream)
         if (!rc && f.r2) rc = launch_nchw_to_nhwc16(o.res2_dev, n, cy, OH, OW, f.r2, cyp, s, perm);
     }
     if (!rc) {
-        const FormsSet& f = fs[0];
         const int cyp = round_up(cy, 16);
-        a.x = f.x + d->x_off;
-        a.N = n;
-        a.H = h;
-        a.W = w;
-        a.xcs = xcs;
-        a.w = f.pc.w;
-        a.ntaps_total = k * k;
-        a.bias = f.pc.bias;
-        a.y = f.y + d->y_off;
-        a.OH = OH;
-        a.OW = OW;
-        a.ycs = ycs;
-        a.cout_pad = cout_pad;
-        a.cout_store = cout_store;
-        make_taps(f.pc, stride, pad, &a);
-        a.GH = tr ? h : OH;
-        a.GW = tr ? w : OW;
-        a.act = d->act;
-        a.ckbd = ckbd;
-        a.splitk = splitk;
-        a.partial = f.part;
-        if (f.r1) a.res1 = f.r1, a.r1cs = cyp;
-        if (f.m) a.mul = f.m, a.mcs = cyp;
-        if (f.r2) a.res2 = f.r2, a.r2cs = cyp;
-        if (f.y2) a.y2 = f.y2 + d->y2_off, a.y2cs = y2cs;
-        if (fused) {
-            a.w2 = f.pc2.w;
-            a.bias2 = f.pc2.bias;
-            a.cout2_pad = cout2_pad;
-            a.act_mid = d->act_mid;
-            if (refmode) a.tail_bias_init = 1;  // (Engine::plan_refnum)
-        }
-        if (lead) {
-            a.w3 = f.pc3.w;
-            a.bias3 = f.pc3.bias;
-            a.y3 = f.y3 + d->y3_off;
-            a.y3cs = y3cs;
-            a.cout3_pad = cout3_pad;
-        }
-        if (G == 2) {  // (Engine::conv_issue)
-            const FormsSet& q = fs[1];
-            a.groups = 2;
-            a.g1.x = q.x + d->x_off;
-            a.g1.w = q.pc.w;
-            a.g1.bias = q.pc.bias;
-            a.g1.y = q.y + d->y_off;
-            a.g1.res1 = q.r1;
-            a.g1.mul = q.m;
-            a.g1.res2 = q.r2;
-            a.g1.partial = q.part;
-            a.g1.y2 = q.y2 ? q.y2 + d->y2_off : nullptr;
-            a.g1.w2 = fused ? q.pc2.w : nullptr;
-            a.g1.bias2 = fused ? q.pc2.bias : nullptr;
-            a.g1.w3 = lead ? q.pc3.w : nullptr;
-            a.g1.bias3 = lead ? q.pc3.bias : nullptr;
-            a.g1.y3 = lead ? q.y3 + d->y3_off : nullptr;
+        const ConvArgs checked = a;
+        auto args_of = [&](const FormsSet& f) {  // one operand set's launch, on top of what the host checks decided
+            ConvArgs r = checked;
+            conv_args_geometry(&r, f.pc, f.x + d->x_off, n, h, w, xcs, f.y + d->y_off, ycs, OH, OW, stride, pad);
+            r.cout_store = cout_store;
+            conv_args_epilogue(&r, d->act, ckbd, f.r1, cyp, f.m, cyp, f.r2, cyp, f.y2 ? f.y2 + d->y2_off : nullptr, y2cs);
+            r.partial = f.part;
+            if (fused) conv_args_tail(&r, f.pc2, d->act_mid, refmode);
+            if (lead) conv_args_lead(&r, f.pc3, f.y3 + d->y3_off, y3cs);
+            return r;
+        };
+        a = args_of(fs[0]);
+        if (G == 2) {
+            const ConvArgs q = args_of(fs[1]);
+            conv_args_group1(&a, q);
+            a.g1.partial = q.partial;
         }
         rc = fused ? launch_conv_fused(a, s) : launch_conv(a, s);
     }
@@ -829,7 +682,6 @@ int rgbd_debug_force_fuse(int32_t mode)
     return RGBD_OK;
 }
 
-// 0: per-phase form, 1: sub-pixel form inside the codec (default), 2: also in rgbd_conv2d_nchw (tests)
 int rgbd_debug_fail_captures(int32_t n)
 {
     std::unique_lock<std::shared_mutex> cap_lk(g_capture_mu);
@@ -847,6 +699,7 @@ int rgbd_debug_force_pair(int32_t mode)
     return RGBD_OK;
 }
 
+// 0: per-phase form, 1: sub-pixel form inside the codec (default), 2: also in rgbd_conv2d_nchw (tests)
 int rgbd_debug_force_subpix(int32_t mode)
 {
     if (mode < 0 || mode > 2) return RGBD_EINVAL;
@@ -871,77 +724,57 @@ int rgbd_conv_bench(int32_t n, int32_t cin, int32_t h, int32_t w, int32_t cout, 
     HostTensor hw;
     hw.shape = transposed ? std::vector<int64_t>{cin, cout, k, k} : std::vector<int64_t>{cout, cin, k, k};
     hw.v.assign((size_t)cin * cout * k * k, 0.01f);
+    DevBufs b;
+    DevGen gen;  // (owns the packed weights: released on every way out)
+    struct Sync {  // the call's events and streams: destroyed on every way out (before the buffers go)
+        std::vector<hipEvent_t> ev;
+        std::vector<hipStream_t> st;
+        ~Sync()
+        {
+            for (hipEvent_t e : ev)
+                if (e) (void)hipEventDestroy(e);
+            for (hipStream_t q : st)
+                if (q) (void)hipStreamDestroy(q);
+        }
+    } sync;
     PackedConv pc;
-    int rc = pack_conv(hw, nullptr, transposed != 0, &pc);
+    int rc = pack_conv(hw, nullptr, transposed != 0, &pc, &gen);
     if (rc) return rc;
     int OH, OW;
-    if (!transposed) {
-        OH = (h + 2 * pad - k) / stride + 1;
-        OW = (w + 2 * pad - k) / stride + 1;
-    } else {
-        OH = (h - 1) * stride - 2 * pad + k + (stride - 1);
-        OW = (w - 1) * stride - 2 * pad + k + (stride - 1);
-    }
-    float *x = nullptr, *y = nullptr, *r = nullptr;
-    const size_t xb = (size_t)n * h * w * pc.cin_pad * sizeof(float), yb = (size_t)n * OH * OW * pc.cout_pad * sizeof(float);
-    HIP_TRY(hipMalloc((void**)&x, xb));
-    HIP_TRY(hipMalloc((void**)&y, yb));
-    HIP_TRY(hipMemset(x, 0x3c, xb));  // small positive floats
-    if (with_residual) {
-        HIP_TRY(hipMalloc((void**)&r, yb));
-        HIP_TRY(hipMemset(r, 0x3c, yb));
-    }
+    conv_out_hw(h, w, k, stride, pad, transposed != 0, &OH, &OW);
+    const size_t xf = (size_t)n * h * w * pc.cin_pad, yf = (size_t)n * OH * OW * pc.cout_pad;
+    float *x = b.get(xf), *y = b.get(yf), *r = with_residual ? b.get(yf) : nullptr;
+    if (!x || !y || (with_residual && !r)) return RGBD_ENOMEM;
+    HIP_TRY(hipMemset(x, 0x3c, xf * sizeof(float)));  // small positive floats
+    if (r) HIP_TRY(hipMemset(r, 0x3c, yf * sizeof(float)));
     ConvArgs a{};
-    a.x = x;
-    a.N = n;
-    a.H = h;
-    a.W = w;
-    a.xcs = pc.cin_pad;
-    a.cin_pad = pc.cin_pad;
-    a.w = pc.w;
-    a.ntaps_total = k * k;
-    a.bias = pc.bias;
-    a.y = y;
-    a.OH = OH;
-    a.OW = OW;
-    a.ycs = pc.cout_pad;
-    a.cout_pad = pc.cout_pad;
-    make_taps(pc, stride, pad, &a);
-    a.GH = transposed ? h : OH;
-    a.GW = transposed ? w : OW;
-    a.act = ACT_RELU;
-    if (r) {
-        a.res1 = r;
-        a.r1cs = pc.cout_pad;
+    conv_args_geometry(&a, pc, x, n, h, w, pc.cin_pad, y, pc.cout_pad, OH, OW, stride, pad);
+    conv_args_epilogue(&a, ACT_RELU, g_force_ckbd, r, pc.cout_pad, nullptr, 0, nullptr, 0, nullptr, 0);
+    a.splitk = g_force_splitk > 0 ? std::min(g_force_splitk, pc.cin_pad / 16)
+                                  : (g_force_splitk < 0 ? conv_splitk_for(pc.cin_pad, pc.cout_pad, conv_max_taps(a), (long)OH * OW, a.nphase) : 1);
+    if (a.splitk > 1) {
+        a.partial = b.get((size_t)a.splitk * yf);
+        if (!a.partial) return RGBD_ENOMEM;
     }
-    float* part = nullptr;
-    {
-        int mt = 1;
-        for (int ph = 0; ph < a.nphase; ++ph) mt = std::max(mt, (int)a.taps.n[ph]);
-        a.splitk = g_force_splitk > 0 ? std::min(g_force_splitk, pc.cin_pad / 16)
-                                      : (g_force_splitk < 0 ? conv_splitk_for(pc.cin_pad, pc.cout_pad, mt, (long)OH * OW, a.nphase) : 1);
-        if (a.splitk > 1) {
-            HIP_TRY(hipMalloc((void**)&part, (size_t)a.splitk * yb));
-            a.partial = part;
-        }
-    }
-    a.ckbd = g_force_ckbd;
     a.loaded = g_bench_streams > 1 ? 1 : 0;
     if (g_force_blocked && a.splitk == 1) {  // blocked accumulation: a block per 16 channels (multi-tap) / per 96 (1x1)
         std::vector<int32_t> bl;
         if (k == 1)
             for (int c = 0; c < pc.cin_pad; c += 96) bl.push_back(std::min(96, pc.cin_pad - c));
-        rc = set_blocks(&a, bl.empty() ? nullptr : bl.data(), (int)bl.size());
+        rc = conv_set_blocks(&a, bl.empty() ? nullptr : bl.data(), (int)bl.size());
         a.bias_mode = k == 1 ? 2 : (transposed ? 0 : 1);
         if (rc) return rc;
     }
-    hipEvent_t e0, e1;
+    const int S = g_bench_streams > 1 ? g_bench_streams : 0;  // loaded mode: the same launch on S streams at once
+    sync.ev.resize(2 + S, nullptr);
+    sync.st.resize(S, nullptr);
+    hipEvent_t &e0 = sync.ev[0], &e1 = sync.ev[1];
     HIP_TRY(hipEventCreate(&e0));
     HIP_TRY(hipEventCreate(&e1));
     rc = launch_conv(a, nullptr);
     HIP_TRY(hipDeviceSynchronize());
     float ms = 0.f;
-    if (g_bench_streams <= 1) {
+    if (!S) {
         HIP_TRY(hipEventRecord(e0, nullptr));
         for (int i = 0; i < iters && !rc; ++i) rc = launch_conv(a, nullptr);
         HIP_TRY(hipEventRecord(e1, nullptr));
@@ -949,11 +782,10 @@ int rgbd_conv_bench(int32_t n, int32_t cin, int32_t h, int32_t w, int32_t cout, 
         HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
         *ms_out = ms / iters;
     } else {
-        // loaded mode (rgbd_debug_bench_streams): the same launch on S streams at once -- what a launch costs in CU time
-        // when the chip is shared with other engine instances, the regime the job throughput is measured in
-        const int S = g_bench_streams;
-        std::vector<hipStream_t> st(S);
-        std::vector<hipEvent_t> done(S);
+        // (rgbd_debug_bench_streams) what a launch costs in CU time when the chip is shared with other engine instances, the
+        // regime the job throughput is measured in
+        hipStream_t* st = sync.st.data();
+        hipEvent_t* done = sync.ev.data() + 2;
         for (int k = 0; k < S; ++k) {
             HIP_TRY(hipStreamCreateWithFlags(&st[k], hipStreamNonBlocking));
             HIP_TRY(hipEventCreateWithFlags(&done[k], hipEventDisableTiming));
@@ -970,19 +802,7 @@ int rgbd_conv_bench(int32_t n, int32_t cin, int32_t h, int32_t w, int32_t cout, 
         HIP_TRY(hipEventSynchronize(e1));
         HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
         *ms_out = ms / (iters * S);
-        for (int k = 0; k < S; ++k) {
-            (void)hipEventDestroy(done[k]);
-            (void)hipStreamDestroy(st[k]);
-        }
     }
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    (void)hipFree(x);
-    (void)hipFree(y);
-    (void)hipFree(r);
-    (void)hipFree(part);
-    (void)hipFree(pc.w);
-    (void)hipFree(pc.bias);
     return rc;
 }
 

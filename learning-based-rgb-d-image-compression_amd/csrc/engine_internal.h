@@ -1,6 +1,7 @@
 // Shared between the translation units of the host runtime (engine.h / engine.hip / engine_abi.hip: the codec; coder_abi.hip: the stand-alone coder and
 // checkerboard operators of the C ABI).  Not part of the ABI.
 #pragma once
+#include <algorithm>
 #include <memory>
 #include <shared_mutex>
 #include <vector>
@@ -15,6 +16,23 @@ struct DevGen {
     ~DevGen()
     {
         for (void* q : p) (void)hipFree(q);
+    }
+};
+
+// Device scratch of a stand-alone entry point of the C ABI (operator-level calls, test hooks, the bench entry points): one
+// allocation per get() (nullptr = out of memory), all released when the call returns, on every way out.
+struct DevBufs {
+    std::vector<void*> v;
+    float* get(size_t floats)
+    {
+        void* p = nullptr;
+        if (hipMalloc(&p, std::max<size_t>(floats, 1) * sizeof(float)) != hipSuccess) return nullptr;
+        v.push_back(p);
+        return (float*)p;
+    }
+    ~DevBufs()
+    {
+        for (void* p : v) (void)hipFree(p);
     }
 };
 

@@ -180,23 +180,6 @@ void gdn_pack(const float* beta_raw, const float* gamma_raw, int c, std::vector<
 // ================================================================================================
 // C ABI (include/rgbd_amd.h)
 // ================================================================================================
-namespace {
-struct GdnBufs {
-    std::vector<void*> v;
-    float* get(size_t floats)
-    {
-        void* p = nullptr;
-        if (hipMalloc(&p, (floats ? floats : 1) * sizeof(float)) != hipSuccess) return nullptr;
-        v.push_back(p);
-        return (float*)p;
-    }
-    ~GdnBufs()
-    {
-        for (void* p : v) (void)hipFree(p);
-    }
-};
-}  // namespace
-
 extern "C" {
 
 int rgbd_gdn_parametrize(const float* raw, int64_t n, int32_t is_beta, float* out)
@@ -225,7 +208,7 @@ int rgbd_gdn_nchw(const float* x_dev, int32_t n, int32_t c, int32_t h, int32_t w
     const size_t fl = (size_t)n * h * w * cs;
     std::vector<float> hb, hg;
     gdn_pack(beta, gamma, c, &hb, &hg);
-    GdnBufs b;
+    DevBufs b;
     float *x = b.get(fl), *y = b.get(fl), *r = res_dev ? b.get(fl) : nullptr, *db = b.get(hb.size()), *dg = b.get(hg.size());
     if (!x || !y || (res_dev && !r) || !db || !dg) return RGBD_ENOMEM;
     HIP_TRY(hipMemcpy(db, hb.data(), hb.size() * sizeof(float), hipMemcpyHostToDevice));
@@ -263,7 +246,7 @@ int rgbd_gdn_bench(int32_t n, int32_t c, int32_t h, int32_t w, int32_t inverse, 
     std::vector<float> rb(c, 1.0f), rg((size_t)c * c, sqrtf(0.001f)), hb, hg;
     for (int i = 0; i < c; ++i) rg[(size_t)i * c + i] = sqrtf(0.1f);
     gdn_pack(rb.data(), rg.data(), c, &hb, &hg);
-    GdnBufs b;
+    DevBufs b;
     float *x = b.get(fl), *y = b.get(fl), *r = with_residual ? b.get(fl) : nullptr, *db = b.get(hb.size()), *dg = b.get(hg.size());
     if (!x || !y || (with_residual && !r) || !db || !dg) return RGBD_ENOMEM;
     HIP_TRY(hipMemset(x, 0x3c, fl * sizeof(float)));  // small positive floats

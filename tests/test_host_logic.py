@@ -40,6 +40,26 @@ def test_abi_argument_errors_without_gpu():
     assert L.rgbd_rans_max_bytes(100) >= 4 * (100 + 2)
 
 
+def test_conv_entry_points_refuse_bad_arguments_before_any_device_call():
+    """rgbd_conv_bench / rgbd_conv2d_nchw: what they check on the host is refused (-22) before anything touches a device,
+    so also on a machine without one.  (rgbd_conv_bench does not check k: that case is left out.)"""
+    from rgbd_amd._lib import lib
+
+    L = lib()
+    ms = ctypes.c_float()
+    assert L.rgbd_conv_bench(1, 4, 8, 8, 4, 3, 1, 1, 0, 0, 0, ctypes.byref(ms)) == -22  # iters = 0
+    assert L.rgbd_conv_bench(1, 4, 8, 8, 4, 3, 1, 1, 0, 0, 2, None) == -22              # no place for the result
+    assert L.rgbd_conv_bench(0, 4, 8, 8, 4, 3, 1, 1, 0, 0, 2, ctypes.byref(ms)) == -22  # n = 0
+    w = (ctypes.c_float * (4 * 4 * 36))()
+    dev = 4096  # (stands for a device pointer: never dereferenced)
+
+    def conv2d(x=dev, wt=w, y=dev, n=1, k=3, stride=1):
+        return L.rgbd_conv2d_nchw(x, n, 4, 8, 8, wt, None, 4, k, stride, 1, 0, 0, None, y, None)
+
+    assert conv2d(x=None) == -22 and conv2d(wt=None) == -22 and conv2d(y=None) == -22
+    assert conv2d(k=6) == -22 and conv2d(k=0) == -22 and conv2d(stride=3) == -22 and conv2d(n=0) == -22
+
+
 def test_host_cdf_quantiser_matches_reference(kat):
     from rgbd_amd import ans
 
