@@ -127,6 +127,53 @@ int rgbd_slice_dequant(const int32_t* symbols_dev, const float* means_dev, int32
 int rgbd_lrp_update(const float* lrp_dev, int32_t lcs, const float* yhat_dev, int32_t ycs, int64_t npix, int32_t C, float* out0_dev,
                     int32_t cs0, float* out1_dev, int32_t cs1, float* out2_dev, int32_t cs2, void* stream);
 
+/* The entropy stage's kernels on the engine's own layout, one launcher each (test hooks: tests/test_gpu_entropy.py).  Every
+ * tensor is NHWC fp32 on the device, [B][h][w][channel stride], each with its own channel stride; with perm != 0 channel c of
+ * a tensor sits at position (c & ~15) | (c & 3) << 2 | (c >> 2) & 3 (the conv kernels' order inside groups of 16), while
+ * symbols, indexes, medians and parameters stay in logical channel order.  Each call checks its arguments on the host and
+ * returns -22 before any launch on a NULL pointer, a non-positive extent, a channel stride smaller than the channels it has to
+ * hold, odd w (checkerboard parts), perm with a channel count (z path: channel stride) that is no multiple of 16, or
+ * B * channels * h * w >= 2^31.  Asynchronous on `stream` unless stated.
+ *
+ * rgbd_ckbd_estimate_part: eval-mode forward() of one checkerboard half of a slice (models/elic_united.py:234-263 on
+ *   entropy_models.py:534-558): y_hat = rint(y - mean) + mean (half to even) and the Gaussian likelihood of the quantised
+ *   value with scale >= 0.11, floored at 1e-9, at the half's positions ((row + col) odd for anchor != 0, else even).
+ *   params_dev: [scale (C) | mean (C)] per pixel, pcs >= 2 * C.  The anchor pass also zeroes yhat_dev at the other half;
+ *   lik_dev is written at the half's positions only.
+ * rgbd_slice_estimate: the same for a raster channel slice (models/stf.py:657-660), mean / scale / y from three tensors,
+ *   y_hat to yhat0_dev and, when not NULL, yhat1_dev.
+ * rgbd_ckbd_part: the codec's integer step on the same layout.  mode 0: symbol = rint(y - mean), index =
+ *   build_indexes(scale), y_hat = symbol + mean; mode 1: indexes only; mode 2: y_hat = symbol + mean from symbols_dev.
+ *   Symbols / indexes land at stream_base_dev[b] + part_off + (c * h + row) * (w / 2) + k (per_image != 0: one stream per
+ *   image, stream_base_dev has B entries) or at stream_base_dev[0] + part_off * B + ((b * C + c) * h + row) * (w / 2) + k
+ *   (one stream for the batch); part_off >= 0 counts one image's earlier symbols.  scale_table_dev: the 64 entries of
+ *   get_scale_table() on the device (modes 0 / 1).  Modes 0 / 2 zero the other half of yhat_dev in the anchor pass.
+ * rgbd_z_quant / rgbd_z_dequant: the factorised prior's integer path (entropy_models.py:195-266, 431-446): symbol =
+ *   rint(z - median_c), index = c, at (b * C + c) * h * w + row * w + col; z_hat = symbol + median_c, 0 in the channel
+ *   positions that hold no channel (zcs > C).
+ * rgbd_eb_forward: the factorised prior in eval mode (entropy_models.py:369-428): z_hat = rint(z - median) + median and
+ *   |sigmoid(s * upper) - sigmoid(s * lower)|, s = -sign(lower + upper), floored at 1e-9; z_hat = lik = 0 in the positions
+ *   that hold no channel.  z_dev / zhat_dev / lik_dev share the stride zcs.  matrices[5] / biases[5] / factors[4] / medians
+ *   are HOST arrays of the raw parameters (_matrix{i} [C][f_{i+1}][f_i], _bias{i}, _factor{i} [C][f_{i+1}][1], filters
+ *   1-3-3-3-3-1); they are packed by the function rgbd_elic_finalize packs them with.  Synchronous: returns when done. */
+int rgbd_ckbd_estimate_part(const float* y_dev, int32_t ycs, const float* params_dev, int32_t pcs, float* yhat_dev, int32_t yhcs,
+                            float* lik_dev, int32_t lcs, int32_t B, int32_t h, int32_t w, int32_t C, int32_t anchor, int32_t perm,
+                            void* stream);
+int rgbd_slice_estimate(const float* y_dev, int32_t ycs, const float* means_dev, int32_t mcs, const float* scales_dev, int32_t scs,
+                        int32_t B, int32_t C, int32_t h, int32_t w, float* lik_dev, int32_t lcs, float* yhat0_dev, int32_t cs0,
+                        float* yhat1_dev, int32_t cs1, void* stream);
+int rgbd_ckbd_part(int32_t mode, const float* y_dev, int32_t ycs, const float* params_dev, int32_t pcs, float* yhat_dev, int32_t yhcs,
+                   const float* scale_table_dev, int32_t B, int32_t h, int32_t w, int32_t C, int32_t anchor, int32_t per_image,
+                   int32_t perm, int32_t* symbols_dev, int32_t* indexes_dev, const int64_t* stream_base_dev, int64_t part_off,
+                   void* stream);
+int rgbd_z_quant(const float* z_dev, int32_t zcs, int32_t B, int32_t h, int32_t w, int32_t C, const float* medians_dev,
+                 int32_t* symbols_dev, int32_t* indexes_dev, int32_t perm, void* stream);
+int rgbd_z_dequant(const int32_t* symbols_dev, int32_t B, int32_t h, int32_t w, int32_t C, const float* medians_dev, float* zhat_dev,
+                   int32_t zcs, int32_t perm, void* stream);
+int rgbd_eb_forward(const float* z_dev, int32_t zcs, int32_t B, int32_t h, int32_t w, int32_t C, const float* const* matrices,
+                    const float* const* biases, const float* const* factors, const float* medians, float* zhat_dev, float* lik_dev,
+                    int32_t perm, void* stream);
+
 /* ---------------------------------------------------------------------------------------------------------------
  * Single operators on device tensors (NCHW fp32, contiguous) -- used by the parity tests of the conv kernels.
  * Replaces torch.nn.functional.conv2d / conv_transpose2d as used by modules/layers/conv.py:7-34.

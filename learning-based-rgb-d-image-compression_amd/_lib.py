@@ -151,6 +151,16 @@ def lib():
         "rgbd_slice_dequant": (ctypes.c_int, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i64, c_i64, c_vp, c_i32,
                                               c_vp, c_i32, c_vp]),
         "rgbd_lrp_update": (ctypes.c_int, [c_vp, c_i32, c_vp, c_i32, c_i64, c_i32, c_vp, c_i32, c_vp, c_i32, c_vp, c_i32, c_vp]),
+        "rgbd_ckbd_estimate_part": (ctypes.c_int, [c_vp, c_i32, c_vp, c_i32, c_vp, c_i32, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32,
+                                                   c_i32, c_vp]),
+        "rgbd_slice_estimate": (ctypes.c_int, [c_vp, c_i32, c_vp, c_i32, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_i32, c_vp,
+                                               c_i32, c_vp, c_i32, c_vp]),
+        "rgbd_ckbd_part": (ctypes.c_int, [c_i32, c_vp, c_i32, c_vp, c_i32, c_vp, c_i32, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32,
+                                          c_i32, c_vp, c_vp, c_vp, c_i64, c_vp]),
+        "rgbd_z_quant": (ctypes.c_int, [c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_i32, c_vp]),
+        "rgbd_z_dequant": (ctypes.c_int, [c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_i32, c_i32, c_vp]),
+        "rgbd_eb_forward": (ctypes.c_int, [c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, ctypes.POINTER(f32p), ctypes.POINTER(f32p),
+                                           ctypes.POINTER(f32p), f32p, c_vp, c_vp, c_i32, c_vp]),
         "rgbd_gdn_nchw": (ctypes.c_int, [c_vp, c_i32, c_i32, c_i32, c_i32, f32p, f32p, c_i32, c_vp, c_vp, c_vp]),
         "rgbd_gdn_parametrize": (ctypes.c_int, [f32p, c_i64, c_i32, f32p]),
         "rgbd_debug_force_gdn_tile": (ctypes.c_int, [c_i32]),
@@ -211,6 +221,7 @@ EXPORTS = ["rgbd_abi_version", "rgbd_set_blocking_sync", "rgbd_get_blocking_sync
            "rgbd_layernorm2", "rgbd_window_attention", "rgbd_patch_merge_gather", "rgbd_pixel_shuffle2",
            "rgbd_elic_profile_read", "rgbd_elic_profile_read_executed", "rgbd_debug_force_splitk", "rgbd_debug_force_fuse", "rgbd_debug_force_subpix", "rgbd_debug_force_pair", "rgbd_debug_fail_captures", "rgbd_debug_force_ckbd", "rgbd_debug_force_blocked", "rgbd_debug_bench_streams", "rgbd_elic_set_tile_mode", "rgbd_debug_force_tile", "rgbd_debug_conv_log", "rgbd_debug_conv_log_read", "rgbd_debug_tile_override", "rgbd_conv_bench",
            "rgbd_elic_profile_dump", "rgbd_elic_create_stf_single", "rgbd_slice_quant_index", "rgbd_slice_dequant", "rgbd_lrp_update",
+           "rgbd_ckbd_estimate_part", "rgbd_slice_estimate", "rgbd_ckbd_part", "rgbd_z_quant", "rgbd_z_dequant", "rgbd_eb_forward",
            "rgbd_elic_create_ckbd", "rgbd_gdn_nchw", "rgbd_gdn_parametrize", "rgbd_debug_force_gdn_tile", "rgbd_gdn_bench"]
 
 

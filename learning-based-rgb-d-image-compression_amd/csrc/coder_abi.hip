@@ -263,6 +263,28 @@ int ckbd_op(int mode, const float* y_dev, const float* means_dev, const float* s
 
 }  // namespace
 
+// Factorised prior: the kernel's per-channel operands from the raw parameters (declared in engine_internal.h; used by
+// rgbd_elic_finalize and rgbd_eb_forward)
+void eb_pack_cumulative(const float* const matrix[5], const float* const bias[5], const float* const factor[4], int C, float* prm)
+{
+    const int fi[6] = {1, 3, 3, 3, 3, 1};
+    size_t off = 0;
+    for (int i = 0; i < 5; ++i) {
+        const int no = fi[i + 1], ni = fi[i];
+        for (int c = 0; c < C; ++c) {
+            float* p = prm + (size_t)c * 58 + off;
+            for (int k = 0; k < no * ni; ++k) {
+                const float v = matrix[i][(size_t)c * no * ni + k];
+                p[k] = v > 20.f ? v : std::log1p(std::exp(v));  // F.softplus (threshold 20)
+            }
+            for (int k = 0; k < no; ++k) p[no * ni + k] = bias[i][(size_t)c * no + k];
+            if (i < 4)
+                for (int k = 0; k < no; ++k) p[no * ni + no + k] = std::tanh(factor[i][(size_t)c * no + k]);
+        }
+        off += (size_t)no * ni + no + (i < 4 ? no : 0);
+    }
+}
+
 extern "C" {
 
 
@@ -537,6 +559,109 @@ int rgbd_lrp_update(const float* lrp_dev, int32_t lcs, const float* yhat_dev, in
         return RGBD_EINVAL;
     return launch_lrp_update(lrp_dev, lcs, yhat_dev, ycs, (size_t)npix, C, out0_dev, cs0, out1_dev, cs1, out2_dev, cs2,
                              (hipStream_t)stream);
+}
+
+// ---- the entropy stage's engine-layout kernels, one launcher each (entropy.hip; test hooks: tests/test_gpu_entropy.py) ----
+
+// a * b * c * d < 2^31 for positive int32 factors, without overflowing on the way
+static bool fits31(int64_t a, int64_t b, int64_t c, int64_t d)
+{
+    const int64_t lim = (int64_t)1 << 31;
+    int64_t p = a * b;
+    if (p >= lim) return false;
+    p *= c;
+    if (p >= lim) return false;
+    return p * d < lim;
+}
+
+static bool part_args_ok(int32_t B, int32_t h, int32_t w, int32_t C, int32_t perm)
+{
+    if (B <= 0 || h <= 0 || w <= 0 || C <= 0 || (w & 1) || (perm && C % 16)) return false;
+    return fits31(B, C, h, w);
+}
+
+int rgbd_ckbd_estimate_part(const float* y_dev, int32_t ycs, const float* params_dev, int32_t pcs, float* yhat_dev, int32_t yhcs,
+                            float* lik_dev, int32_t lcs, int32_t B, int32_t h, int32_t w, int32_t C, int32_t anchor, int32_t perm,
+                            void* stream)
+{
+    if (!y_dev || !params_dev || !yhat_dev || !lik_dev || !part_args_ok(B, h, w, C, perm)) return RGBD_EINVAL;
+    if (ycs < C || (int64_t)pcs < 2 * (int64_t)C || yhcs < C || lcs < C) return RGBD_EINVAL;
+    const PartGeom g = {B, h, w, C, anchor ? 1 : 0, 0, perm ? 1 : 0};
+    return launch_ckbd_estimate_part(y_dev, ycs, params_dev, pcs, yhat_dev, yhcs, lik_dev, lcs, g, (hipStream_t)stream);
+}
+
+int rgbd_slice_estimate(const float* y_dev, int32_t ycs, const float* means_dev, int32_t mcs, const float* scales_dev, int32_t scs,
+                        int32_t B, int32_t C, int32_t h, int32_t w, float* lik_dev, int32_t lcs, float* yhat0_dev, int32_t cs0,
+                        float* yhat1_dev, int32_t cs1, void* stream)
+{
+    if (!y_dev || !means_dev || !scales_dev || !lik_dev || !yhat0_dev) return RGBD_EINVAL;
+    if (B <= 0 || C <= 0 || h <= 0 || w <= 0 || !fits31(B, C, h, w)) return RGBD_EINVAL;
+    if (ycs < C || mcs < C || scs < C || lcs < C || cs0 < C || (yhat1_dev && cs1 < C)) return RGBD_EINVAL;
+    const SliceGeom g = {B, h, w, C, 0, 0};
+    return launch_slice_estimate(y_dev, ycs, means_dev, mcs, scales_dev, scs, g, lik_dev, lcs, yhat0_dev, cs0, yhat1_dev, cs1,
+                                 (hipStream_t)stream);
+}
+
+int rgbd_ckbd_part(int32_t mode, const float* y_dev, int32_t ycs, const float* params_dev, int32_t pcs, float* yhat_dev, int32_t yhcs,
+                   const float* scale_table_dev, int32_t B, int32_t h, int32_t w, int32_t C, int32_t anchor, int32_t per_image,
+                   int32_t perm, int32_t* symbols_dev, int32_t* indexes_dev, const int64_t* stream_base_dev, int64_t part_off,
+                   void* stream)
+{
+    if (mode < 0 || mode > 2 || !params_dev || !stream_base_dev || part_off < 0 || !part_args_ok(B, h, w, C, perm)) return RGBD_EINVAL;
+    if ((int64_t)pcs < 2 * (int64_t)C) return RGBD_EINVAL;
+    if (mode == 0 && (!y_dev || ycs < C)) return RGBD_EINVAL;
+    if (mode != 1 && (!yhat_dev || yhcs < C || !symbols_dev)) return RGBD_EINVAL;
+    if (mode != 2 && (!scale_table_dev || !indexes_dev)) return RGBD_EINVAL;
+    const PartGeom g = {B, h, w, C, anchor ? 1 : 0, per_image ? 1 : 0, perm ? 1 : 0};
+    hipStream_t s = (hipStream_t)stream;
+    if (mode == 0)
+        return launch_ckbd_encode_part(y_dev, ycs, params_dev, pcs, yhat_dev, yhcs, scale_table_dev, g, symbols_dev, indexes_dev,
+                                       stream_base_dev, part_off, s);
+    if (mode == 1) return launch_ckbd_index_part(params_dev, pcs, scale_table_dev, g, indexes_dev, stream_base_dev, part_off, s);
+    return launch_ckbd_decode_part(params_dev, pcs, yhat_dev, yhcs, g, symbols_dev, stream_base_dev, part_off, s);
+}
+
+static bool z_args_ok(int32_t zcs, int32_t B, int32_t h, int32_t w, int32_t C, int32_t perm)
+{
+    if (B <= 0 || h <= 0 || w <= 0 || C <= 0 || zcs < C || (perm && zcs % 16)) return false;
+    return fits31(B, zcs, h, w);
+}
+
+int rgbd_z_quant(const float* z_dev, int32_t zcs, int32_t B, int32_t h, int32_t w, int32_t C, const float* medians_dev,
+                 int32_t* symbols_dev, int32_t* indexes_dev, int32_t perm, void* stream)
+{
+    if (!z_dev || !medians_dev || !symbols_dev || !indexes_dev || !z_args_ok(zcs, B, h, w, C, perm)) return RGBD_EINVAL;
+    return launch_z_quant(z_dev, zcs, B, h, w, C, medians_dev, symbols_dev, indexes_dev, (hipStream_t)stream, perm ? 1 : 0);
+}
+
+int rgbd_z_dequant(const int32_t* symbols_dev, int32_t B, int32_t h, int32_t w, int32_t C, const float* medians_dev, float* zhat_dev,
+                   int32_t zcs, int32_t perm, void* stream)
+{
+    if (!symbols_dev || !medians_dev || !zhat_dev || !z_args_ok(zcs, B, h, w, C, perm)) return RGBD_EINVAL;
+    return launch_z_dequant(symbols_dev, B, h, w, C, medians_dev, zhat_dev, zcs, (hipStream_t)stream, perm ? 1 : 0);
+}
+
+int rgbd_eb_forward(const float* z_dev, int32_t zcs, int32_t B, int32_t h, int32_t w, int32_t C, const float* const* matrices,
+                    const float* const* biases, const float* const* factors, const float* medians, float* zhat_dev, float* lik_dev,
+                    int32_t perm, void* stream)
+{
+    std::unique_lock<std::shared_mutex> cap_lk(g_capture_mu);  // frees / synchronous copies: not while a stream captures
+    if (!z_dev || !matrices || !biases || !factors || !medians || !zhat_dev || !lik_dev || !z_args_ok(zcs, B, h, w, C, perm))
+        return RGBD_EINVAL;
+    for (int i = 0; i < 5; ++i)
+        if (!matrices[i] || !biases[i] || (i < 4 && !factors[i])) return RGBD_EINVAL;
+    std::vector<float> prm((size_t)C * 58);
+    eb_pack_cumulative(matrices, biases, factors, C, prm.data());
+    hipStream_t s = (hipStream_t)stream;
+    DevBufs b;
+    float *dmed = b.get((size_t)C), *dprm = b.get(prm.size());
+    if (!dmed || !dprm) return RGBD_ENOMEM;
+    HIP_TRY(hipMemcpy(dmed, medians, (size_t)C * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(dprm, prm.data(), prm.size() * sizeof(float), hipMemcpyHostToDevice));
+    int rc = launch_eb_forward(z_dev, zcs, B, h, w, C, dmed, dprm, zhat_dev, lik_dev, s, perm ? 1 : 0);
+    const hipError_t e = hipStreamSynchronize(s);  // the operands above are freed on return
+    if (!rc && e != hipSuccess) rc = RGBD_EHIP;
+    return rc;
 }
 
 }  // extern "C"

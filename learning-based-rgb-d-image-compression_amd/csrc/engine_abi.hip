@@ -1201,8 +1201,8 @@ int rgbd_elic_finalize(rgbd_elic* m)
             const std::string pre = name.substr(0, name.size() - 9);
             std::vector<float> prm((size_t)C * 58, 0.f);
             const int fi[6] = {1, 3, 3, 3, 3, 1};
+            const float *mat[5] = {}, *bias[5] = {}, *fac[4] = {};
             bool ok = true;
-            size_t off = 0;
             for (int i = 0; i < 5 && ok; ++i) {
                 auto mi = m->raw.find(pre + "_matrix" + std::to_string(i));
                 auto bi = m->raw.find(pre + "_bias" + std::to_string(i));
@@ -1211,20 +1211,15 @@ int rgbd_elic_finalize(rgbd_elic* m)
                     ok = false;
                     break;
                 }
-                const int no = fi[i + 1], ni = fi[i];
-                for (int c = 0; c < C; ++c) {
-                    float* p = prm.data() + (size_t)c * 58 + off;
-                    for (int k = 0; k < no * ni; ++k) {
-                        const float v = mi->second.v[(size_t)c * no * ni + k];
-                        p[k] = v > 20.f ? v : std::log1p(std::exp(v));  // F.softplus (threshold 20)
-                    }
-                    for (int k = 0; k < no; ++k) p[no * ni + k] = bi->second.v[(size_t)c * no + k];
-                    if (i < 4)
-                        for (int k = 0; k < no; ++k) p[no * ni + no + k] = std::tanh(fa->second.v[(size_t)c * no + k]);
-                }
-                off += (size_t)no * ni + no + (i < 4 ? no : 0);
+                const size_t no = (size_t)fi[i + 1], ni = (size_t)fi[i];
+                if (mi->second.v.size() != C * no * ni || bi->second.v.size() != C * no || (i < 4 && fa->second.v.size() != C * no))
+                    return RGBD_EINVAL;
+                mat[i] = mi->second.v.data();
+                bias[i] = bi->second.v.data();
+                if (i < 4) fac[i] = fa->second.v.data();
             }
             if (ok) {
+                eb_pack_cumulative(mat, bias, fac, C, prm.data());
                 float* dp = nullptr;
                 if (const int r = dev_copy(prm.data(), prm.size(), &dp)) return r;
                 dense[pre + "cumulative"] = dp;

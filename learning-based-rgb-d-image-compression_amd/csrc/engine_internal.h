@@ -63,3 +63,8 @@ int64_t rgbd_enc_cap_words(int64_t n);  // worst-case words of one stream of n s
 // gamma [c][c] into the operands of GdnArgs
 void gdn_parametrize(const float* raw, int64_t n, int is_beta, float* out);
 void gdn_pack(const float* beta_raw, const float* gamma_raw, int c, std::vector<float>* beta, std::vector<float>* gamma);
+
+// Factorised prior (entropy.hip: eb_forward_kernel): the raw per-channel parameters of the 1-3-3-3-3-1 cumulative network
+// (entropy_models.py:290-312: _matrix{i} [C][f_{i+1}][f_i], _bias{i} [C][f_{i+1}][1], _factor{i} [C][f_{i+1}][1]) as the
+// 58 floats per channel the kernel reads: softplus(matrix_i) / bias_i / tanh(factor_i) in layer order, fp32 on the host
+void eb_pack_cumulative(const float* const matrix[5], const float* const bias[5], const float* const factor[4], int C, float* prm);
