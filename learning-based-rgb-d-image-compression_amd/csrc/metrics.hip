@@ -8,6 +8,11 @@
 // one call per batch of planes does all five scales: per scale one kernel (tile staged in LDS, horizontal then vertical
 // 11-tap pass over the five maps, per-workgroup partial sums in a fixed order) plus one pooling kernel, and a final
 // reducer that adds the partials in workgroup order -- deterministic, no atomics.
+//
+// Checked alone by tests/test_gpu_msssim.py: out[P][5][2] statistic by statistic against the fp64 statement, within 4 x the
+// distance an fp32 CPU restatement of these kernels keeps on the same inputs (tests/msssim_cases.py, which repeats the order of
+// every sum below: change one here and change it there), plus the workspace promise, the guards round `out`, same bits on a side
+// stream and for one plane alone, and the refusals.  tests/test_gpu_harness.py compares the folded scalar only (< 2e-5).
 #include "common.h"
 
 namespace {

@@ -44,14 +44,16 @@ def _pool2(x):
     return 0.25 * (x[..., 0::2, 0::2] + x[..., 1::2, 0::2] + x[..., 0::2, 1::2] + x[..., 1::2, 1::2])
 
 
-def ms_ssim(a, b, data_range=1.0):
+def stats(a, b, data_range=1.0):
+    """[..., 5, 2] fp64: per plane (leading axes) and scale the mean of the SSIM map and the mean of the contrast-structure map
+    of a, b [..., H, W] -- no clamp at zero, no weights (what pytorch_msssim's _ssim returns per channel at every scale)"""
     x, y = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
-    assert x.shape == y.shape and x.ndim == 4
+    assert x.shape == y.shape and x.ndim >= 2
     if min(x.shape[-2:]) <= (11 - 1) * 2 ** 4:
         raise ValueError("image too small for 5-scale MS-SSIM (needs a side > 160)")
     g = _window()
     c1, c2 = (0.01 * data_range) ** 2, (0.03 * data_range) ** 2
-    terms = []
+    out = np.zeros(x.shape[:-2] + (5, 2), dtype=np.float64)
     for lvl in range(5):
         mu1, mu2 = _blur(x, g), _blur(y, g)
         s1 = _blur(x * x, g) - mu1 * mu1
@@ -59,12 +61,21 @@ def ms_ssim(a, b, data_range=1.0):
         s12 = _blur(x * y, g) - mu1 * mu2
         cs_map = (2 * s12 + c2) / (s1 + s2 + c2)
         ssim_map = ((2 * mu1 * mu2 + c1) / (mu1 * mu1 + mu2 * mu2 + c1)) * cs_map
+        out[..., lvl, 0] = ssim_map.mean(axis=(-2, -1))
+        out[..., lvl, 1] = cs_map.mean(axis=(-2, -1))
         if lvl < 4:
-            terms.append(np.maximum(cs_map.mean(axis=(-2, -1)), 0.0))
             x, y = _pool2(x), _pool2(y)
-        else:
-            terms.append(np.maximum(ssim_map.mean(axis=(-2, -1)), 0.0))
-    val = np.ones_like(terms[0])
-    for t, w in zip(terms, WEIGHTS):
-        val = val * t ** w
-    return float(val.mean())
+    return out
+
+
+def combine(st):
+    """[..., C, 5, 2] statistics -> [...]: contrast-structure of scales 0-3 and SSIM of scale 4, clamped at zero, to the power of
+    the weights, multiplied over the scales, then the mean over the channels"""
+    terms = np.maximum(np.concatenate([st[..., :4, 1], st[..., 4:, 0]], axis=-1), 0.0)
+    return np.prod(terms ** np.asarray(WEIGHTS), axis=-1).mean(axis=-1)
+
+
+def ms_ssim(a, b, data_range=1.0):
+    x = np.asarray(a, dtype=np.float64)
+    assert x.ndim == 4
+    return float(combine(stats(x, b, data_range)).mean())
