@@ -435,6 +435,9 @@ int rgbd_debug_force_ckbd(int32_t part); /* rgbd_conv2d_nchw / rgbd_conv_bench: 
 int rgbd_debug_conv_log(int32_t on);                      /* record the shape of every conv launch (tools/tune_tiles.py) */
 int64_t rgbd_debug_conv_log_read(char* buf, int64_t cap); /* CSV text of the recorded shapes; returns the size needed */
 int rgbd_debug_force_tile(const char* cfg); /* "wm,mt,nt,kc,dma" or "" = automatic (tools/tile_sweep.py) */
+/* every (wm,mt,nt,kc,dma) the conv dispatch can reach, one "wm,mt,nt,kc,dma\n" line each; blocked 0 / 1.
+ * Returns the bytes needed (like rgbd_debug_conv_log's reader); touches no device. */
+long rgbd_debug_tile_list(int32_t blocked, char* buf, long cap);
 /* In-situ tuning (tools/tune_insitu.py): tile / staging form per layer-shape key, lines of
  * "N,H,W,cin_pad,cout_pad,ntaps,stride,nphase,splitk,wm,mt,nt,kc,dma"; "" clears.  rgbd_elic_set_profile(m, 2) makes the profile's
  * layer names carry the shape key of every launch, so one codec call times every layer under its candidate. */

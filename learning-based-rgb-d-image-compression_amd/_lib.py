@@ -51,10 +51,10 @@ def build(force: bool = False, verbose: bool = False) -> str:
     objdir = os.path.join(csrc, "build")
     hdrs = [os.path.join(csrc, "common.h"), os.path.join(csrc, "exact_math.h"),
             os.path.join(os.path.dirname(_HERE), "include", "rgbd_amd.h")]
-    body = os.path.join(csrc, "conv_mfma_body.h")
-    extra = {"conv_mfma.hip": [body, os.path.join(csrc, "tile_table.h"), os.path.join(csrc, "tile_table_loaded.h"),
+    body, tiles = os.path.join(csrc, "conv_mfma_body.h"), os.path.join(csrc, "conv_tiles.h")
+    extra = {"conv_mfma.hip": [body, tiles, os.path.join(csrc, "tile_table.h"), os.path.join(csrc, "tile_table_loaded.h"),
                                os.path.join(csrc, "tile_table_blk.h"), os.path.join(csrc, "tile_table_blk_loaded.h")],
-             "conv_mfma_blk.hip": [body]}
+             "conv_mfma_blk.hip": [body, tiles]}
     hdrs.append(os.path.join(csrc, "splitk_table.h"))
     extra["coder_abi.hip"] = extra["gdn.hip"] = [os.path.join(csrc, "engine_internal.h")]
     extra["engine.hip"] = extra["engine_abi.hip"] = [os.path.join(csrc, "engine_internal.h"), os.path.join(csrc, "engine.h"),
@@ -197,6 +197,7 @@ def lib():
         "rgbd_debug_conv_log": (ctypes.c_int, [c_i32]),
         "rgbd_debug_conv_log_read": (c_i64, [ctypes.c_char_p, c_i64]),
         "rgbd_debug_tile_override": (ctypes.c_int, [ctypes.c_char_p]),
+        "rgbd_debug_tile_list": (ctypes.c_long, [c_i32, ctypes.c_char_p, ctypes.c_long]),
         "rgbd_conv_bench": (ctypes.c_int, [c_i32] * 11 + [f32p]),
         "rgbd_elic_profile_dump": (ctypes.c_int, [c_vp, ctypes.c_char_p]),
         "rgbd_elic_profile_read": (ctypes.c_int, [c_vp, ctypes.POINTER(ctypes.c_double), i64p,
@@ -219,7 +220,7 @@ EXPORTS = ["rgbd_abi_version", "rgbd_set_blocking_sync", "rgbd_get_blocking_sync
            "rgbd_elic_finalize", "rgbd_elic_compress", "rgbd_elic_forward", "rgbd_elic_stream_count", "rgbd_elic_stream",
            "rgbd_elic_decompress", "rgbd_elic_create_r2d", "rgbd_elic_create_stf", "rgbd_elic_create_single", "rgbd_elic_compress_single", "rgbd_elic_decompress_single", "rgbd_elic_forward_single", "rgbd_elic_compress_united", "rgbd_elic_decompress_united", "rgbd_elic_debug_tensor", "rgbd_elic_debug_symbols", "rgbd_elic_set_debug_floats", "rgbd_elic_debug_floats", "rgbd_elic_set_forced_symbols", "rgbd_elic_set_profile", "rgbd_elic_graph_count", "rgbd_elic_workspace_bytes", "rgbd_msssim_workspace_bytes", "rgbd_msssim_stats", "rgbd_layernorm", "rgbd_debug_force_layernorm_form",
            "rgbd_layernorm2", "rgbd_window_attention", "rgbd_patch_merge_gather", "rgbd_pixel_shuffle2",
-           "rgbd_elic_profile_read", "rgbd_elic_profile_read_executed", "rgbd_debug_force_splitk", "rgbd_debug_force_fuse", "rgbd_debug_force_subpix", "rgbd_debug_force_pair", "rgbd_debug_fail_captures", "rgbd_debug_force_ckbd", "rgbd_debug_force_blocked", "rgbd_debug_bench_streams", "rgbd_elic_set_tile_mode", "rgbd_debug_force_tile", "rgbd_debug_conv_log", "rgbd_debug_conv_log_read", "rgbd_debug_tile_override", "rgbd_conv_bench",
+           "rgbd_elic_profile_read", "rgbd_elic_profile_read_executed", "rgbd_debug_force_splitk", "rgbd_debug_force_fuse", "rgbd_debug_force_subpix", "rgbd_debug_force_pair", "rgbd_debug_fail_captures", "rgbd_debug_force_ckbd", "rgbd_debug_force_blocked", "rgbd_debug_bench_streams", "rgbd_elic_set_tile_mode", "rgbd_debug_force_tile", "rgbd_debug_conv_log", "rgbd_debug_conv_log_read", "rgbd_debug_tile_override", "rgbd_debug_tile_list", "rgbd_conv_bench",
            "rgbd_elic_profile_dump", "rgbd_elic_create_stf_single", "rgbd_slice_quant_index", "rgbd_slice_dequant", "rgbd_lrp_update",
            "rgbd_ckbd_estimate_part", "rgbd_slice_estimate", "rgbd_ckbd_part", "rgbd_z_quant", "rgbd_z_dequant", "rgbd_eb_forward",
            "rgbd_elic_create_ckbd", "rgbd_gdn_nchw", "rgbd_gdn_parametrize", "rgbd_debug_force_gdn_tile", "rgbd_gdn_bench"]

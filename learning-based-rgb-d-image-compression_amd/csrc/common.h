@@ -173,6 +173,7 @@ int launch_conv_fused(const ConvArgs& a, hipStream_t s);
 int conv_log_enable(int on);
 int conv_tile_override(const char* csv);  // in-situ tile overrides by shape key (tools/tune_insitu.py); nullptr / "" clears
 long conv_log_read(char* buf, long cap);  // CSV text; returns the size needed
+long conv_tile_list(int blocked, char* buf, long cap);  // the instantiated tile forms (conv_tiles.h) as text; returns the size needed
 
 // y = mul * sigmoid(t) + res2 with the reference's per-element choice of sigmoid form (vector / scalar tail of torch's CPU loop)
 int launch_sigmoid_gate_ref(const float* t, int tcs, const float* mul, int mcs, const float* res2, int r2cs, float* y, int ycs,

@@ -17,6 +17,7 @@
 #include <string>
 
 #include "conv_mfma_body.h"
+#include "conv_tiles.h"
 
 // conv_mfma_blk.hip: the blocked-accumulation instantiations (ConvArgs::blocked)
 bool conv_blk_tile_ok(int wm, int mt, int nt, int max_tiles);
@@ -113,6 +114,7 @@ Choice choose(const ConvArgs& a, int max_tiles = 16)
 }
 
 // ring staging: every tile with whole waves of patch slots (TP % 64 == 0); the 256-pixel tiles also with three buffers
+// (the tiles themselves: conv_tiles.h)
 #define RGBD_RING4(WM_, WN_, MT_, NT_)                                             \
     if (c.ring == 4 && c.wm == WM_ && c.mt == MT_ && c.nt == NT_)                  \
         return launch_cfg<WM_, WN_, MT_, NT_, 16, true, 0, false, 4>(a, c.tw_log2, s, 160 * 1024);
@@ -266,6 +268,35 @@ long conv_log_read(char* buf, long cap)
     return (long)out.size() + 1;
 }
 
+// every form the dispatch of launch_conv_main (blocked = 0) / launch_conv_blk (blocked = 1) can reach, from the lists it expands
+long conv_tile_list(int blocked, char* buf, long cap)
+{
+    std::string out;
+    auto forms = [&](int wm, int mt, int nt, bool ring) {
+        static const int modes[][2] = {{64, 0}, {16, 0}, {16, 1}, {16, 2}, {16, 3}, {16, 4}, {16, 5}};
+        for (int m = 0; m < (ring ? 7 : 5); ++m) {
+            char ln[64];
+            snprintf(ln, sizeof(ln), "%d,%d,%d,%d,%d\n", wm, mt, nt, modes[m][0], modes[m][1]);
+            out += ln;
+        }
+    };
+#define RGBD_LIST_RING(WM_, WN_, MT_, NT_) forms(WM_, MT_, NT_, true);
+#define RGBD_LIST_NO_RING(WM_, WN_, MT_, NT_) forms(WM_, MT_, NT_, false);
+    if (blocked) {
+        RGBD_TILES_BLK_RING(RGBD_LIST_RING) RGBD_TILES_NO_RING(RGBD_LIST_NO_RING)
+    } else {
+        RGBD_TILES_MAIN_RING(RGBD_LIST_RING) RGBD_TILES_NO_RING(RGBD_LIST_NO_RING)
+    }
+#undef RGBD_LIST_RING
+#undef RGBD_LIST_NO_RING
+    if (buf && cap > 0) {
+        const size_t n = out.size() < (size_t)cap - 1 ? out.size() : (size_t)cap - 1;
+        memcpy(buf, out.data(), n);
+        buf[n] = 0;
+    }
+    return (long)out.size() + 1;
+}
+
 // in-situ tile overrides (tools/tune_insitu.py): shape key (as in the conv log) -> tile / staging form.  Consulted before the
 // tables; a pure speed matter like every tile choice.  Lines "N,H,W,cin_pad,cout_pad,ntaps,stride,nphase,splitk,wm,mt,nt,kc,dma".
 static std::map<std::string, std::array<int, 5>> g_ovr;
@@ -390,23 +421,12 @@ static int launch_conv_main(const ConvArgs& a, hipStream_t s)
     // measured table entries only, the cost model does not propose them
     if (c.ring && !ring_ok(a)) return RGBD_ENOSPC;
     if (a.blocked) return launch_conv_blk(a, c, s);
-    RGBD_RING4(2, 2, 3, 8) RGBD_RING4(2, 2, 2, 8) RGBD_RING4(2, 2, 1, 8) RGBD_RING4(1, 4, 3, 4) RGBD_RING4(1, 4, 2, 4) RGBD_RING4(1, 4, 1, 4)
-    RGBD_RING4(2, 2, 5, 4) RGBD_RING4(2, 2, 4, 4) RGBD_RING4(2, 2, 3, 4) RGBD_RING4(2, 2, 2, 4) RGBD_RING4(2, 2, 1, 4)
-    RGBD_RING4(2, 2, 5, 2) RGBD_RING4(2, 2, 4, 2) RGBD_RING4(2, 2, 3, 2) RGBD_RING4(2, 2, 2, 2) RGBD_RING4(2, 2, 1, 2)
-    RGBD_RING4(1, 4, 3, 2) RGBD_RING4(1, 4, 2, 2) RGBD_RING4(1, 4, 1, 2) RGBD_RING4(1, 4, 3, 1) RGBD_RING4(1, 4, 2, 1) RGBD_RING4(1, 4, 1, 1)
+    RGBD_TILES_MAIN_RING(RGBD_RING4)
     // three buffers (two stages in flight, a quarter less LDS: one more workgroup per CU on the small tiles, and the only
     // form of the 256-pixel tiles that leaves room for two)
-    RGBD_RING3(2, 2, 3, 8) RGBD_RING3(2, 2, 2, 8) RGBD_RING3(2, 2, 1, 8) RGBD_RING3(1, 4, 3, 4) RGBD_RING3(1, 4, 2, 4) RGBD_RING3(1, 4, 1, 4)
-    RGBD_RING3(2, 2, 5, 4) RGBD_RING3(2, 2, 4, 4) RGBD_RING3(2, 2, 3, 4) RGBD_RING3(2, 2, 2, 4) RGBD_RING3(2, 2, 1, 4)
-    RGBD_RING3(2, 2, 5, 2) RGBD_RING3(2, 2, 4, 2) RGBD_RING3(2, 2, 3, 2) RGBD_RING3(2, 2, 2, 2) RGBD_RING3(2, 2, 1, 2)
-    RGBD_RING3(1, 4, 3, 2) RGBD_RING3(1, 4, 2, 2) RGBD_RING3(1, 4, 1, 2) RGBD_RING3(1, 4, 3, 1) RGBD_RING3(1, 4, 2, 1) RGBD_RING3(1, 4, 1, 1)
+    RGBD_TILES_MAIN_RING(RGBD_RING3)
     if (c.ring) return RGBD_ENOSPC;
-    RGBD_CASE(2, 2, 3, 8) RGBD_CASE(2, 2, 2, 8) RGBD_CASE(2, 2, 1, 8) RGBD_CASE(1, 4, 3, 4) RGBD_CASE(1, 4, 2, 4) RGBD_CASE(1, 4, 1, 4)
-    RGBD_CASE(2, 2, 5, 4) RGBD_CASE(2, 2, 4, 4) RGBD_CASE(2, 2, 3, 4) RGBD_CASE(2, 2, 2, 4) RGBD_CASE(2, 2, 1, 4)
-    RGBD_CASE(2, 2, 5, 2) RGBD_CASE(2, 2, 4, 2) RGBD_CASE(2, 2, 3, 2) RGBD_CASE(2, 2, 2, 2) RGBD_CASE(2, 2, 1, 2)
-    RGBD_CASE(2, 2, 5, 1) RGBD_CASE(2, 2, 4, 1) RGBD_CASE(2, 2, 3, 1) RGBD_CASE(2, 2, 2, 1) RGBD_CASE(2, 2, 1, 1)
-    RGBD_CASE(1, 4, 3, 2) RGBD_CASE(1, 4, 2, 2) RGBD_CASE(1, 4, 1, 2)
-    RGBD_CASE(1, 4, 3, 1) RGBD_CASE(1, 4, 2, 1) RGBD_CASE(1, 4, 1, 1)
+    RGBD_TILES_MAIN(RGBD_CASE)
     return RGBD_EINVAL;
 }
 

@@ -4,6 +4,7 @@
 // order.  Two accumulator sets per output tile, so only tiles of at most 16 MFMA result tiles per wave are instantiated
 // (2 x 64 of the 256 registers a wave has at two workgroups per CU).  Tile choice never changes a result.
 #include "conv_mfma_body.h"
+#include "conv_tiles.h"
 
 namespace {
 
@@ -31,21 +32,10 @@ bool conv_blk_tile_ok(int wm, int mt, int nt, int max_tiles)
 int launch_conv_blk(const ConvArgs& a, const Choice& c, hipStream_t s)
 {
     if (!conv_blk_tile_ok(c.wm, c.mt, c.nt, 16) || a.splitk > 1 || a.partial) return RGBD_EINVAL;
-    RGBD_BRING4(2, 2, 2, 8) RGBD_BRING4(2, 2, 1, 8) RGBD_BRING4(1, 4, 3, 4) RGBD_BRING4(1, 4, 2, 4) RGBD_BRING4(1, 4, 1, 4)
-    RGBD_BRING4(2, 2, 4, 4) RGBD_BRING4(2, 2, 3, 4) RGBD_BRING4(2, 2, 2, 4) RGBD_BRING4(2, 2, 1, 4)
-    RGBD_BRING4(2, 2, 5, 2) RGBD_BRING4(2, 2, 4, 2) RGBD_BRING4(2, 2, 3, 2) RGBD_BRING4(2, 2, 2, 2) RGBD_BRING4(2, 2, 1, 2)
-    RGBD_BRING4(1, 4, 3, 2) RGBD_BRING4(1, 4, 2, 2) RGBD_BRING4(1, 4, 1, 2) RGBD_BRING4(1, 4, 3, 1) RGBD_BRING4(1, 4, 2, 1) RGBD_BRING4(1, 4, 1, 1)
-    RGBD_BRING3(2, 2, 2, 8) RGBD_BRING3(2, 2, 1, 8) RGBD_BRING3(1, 4, 3, 4) RGBD_BRING3(1, 4, 2, 4) RGBD_BRING3(1, 4, 1, 4)
-    RGBD_BRING3(2, 2, 4, 4) RGBD_BRING3(2, 2, 3, 4) RGBD_BRING3(2, 2, 2, 4) RGBD_BRING3(2, 2, 1, 4)
-    RGBD_BRING3(2, 2, 5, 2) RGBD_BRING3(2, 2, 4, 2) RGBD_BRING3(2, 2, 3, 2) RGBD_BRING3(2, 2, 2, 2) RGBD_BRING3(2, 2, 1, 2)
-    RGBD_BRING3(1, 4, 3, 2) RGBD_BRING3(1, 4, 2, 2) RGBD_BRING3(1, 4, 1, 2) RGBD_BRING3(1, 4, 3, 1) RGBD_BRING3(1, 4, 2, 1) RGBD_BRING3(1, 4, 1, 1)
+    RGBD_TILES_BLK_RING(RGBD_BRING4)
+    RGBD_TILES_BLK_RING(RGBD_BRING3)
     if (c.ring) return RGBD_ENOSPC;
-    RGBD_BCASE(2, 2, 2, 8) RGBD_BCASE(2, 2, 1, 8) RGBD_BCASE(1, 4, 3, 4) RGBD_BCASE(1, 4, 2, 4) RGBD_BCASE(1, 4, 1, 4)
-    RGBD_BCASE(2, 2, 4, 4) RGBD_BCASE(2, 2, 3, 4) RGBD_BCASE(2, 2, 2, 4) RGBD_BCASE(2, 2, 1, 4)
-    RGBD_BCASE(2, 2, 5, 2) RGBD_BCASE(2, 2, 4, 2) RGBD_BCASE(2, 2, 3, 2) RGBD_BCASE(2, 2, 2, 2) RGBD_BCASE(2, 2, 1, 2)
-    RGBD_BCASE(2, 2, 5, 1) RGBD_BCASE(2, 2, 4, 1) RGBD_BCASE(2, 2, 3, 1) RGBD_BCASE(2, 2, 2, 1) RGBD_BCASE(2, 2, 1, 1)
-    RGBD_BCASE(1, 4, 3, 2) RGBD_BCASE(1, 4, 2, 2) RGBD_BCASE(1, 4, 1, 2)
-    RGBD_BCASE(1, 4, 3, 1) RGBD_BCASE(1, 4, 2, 1) RGBD_BCASE(1, 4, 1, 1)
+    RGBD_TILES_BLK(RGBD_BCASE)
     return RGBD_EINVAL;
 }
 

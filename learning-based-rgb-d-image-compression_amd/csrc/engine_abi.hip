@@ -641,6 +641,7 @@ int rgbd_debug_tile_override(const char* csv)
 
 int rgbd_debug_conv_log(int32_t on) { return conv_log_enable(on); }
 int64_t rgbd_debug_conv_log_read(char* buf, int64_t cap) { return conv_log_read(buf, (long)cap); }
+long rgbd_debug_tile_list(int32_t blocked, char* buf, long cap) { return conv_tile_list(blocked, buf, cap); }
 
 int rgbd_elic_set_tile_mode(rgbd_elic* m, int32_t mode)
 {

@@ -167,7 +167,8 @@ def test_tile_choice_never_changes_a_bit(tile):
     """The determinism contract behind the tile table / cost model: every tile shape, stage depth and
     staging mode produces the same fp32 bits, so tile selection is a pure speed matter (256-pixel tiles included).
     Staging modes 4 / 5 are the ring of four / three DMA stage buffers of the single-tap layers (round 4); the baseline is
-    a register-staged tile, whatever the cost model would pick."""
+    a register-staged tile, whatever the cost model would pick.  (These 13 forms at the workload's sizes; every form the
+    dispatch instantiates, on small maps chosen for their partial tiles: tests/test_gpu_conv_tiles.py.)"""
     dev = require_gpu()
     from rgbd_amd._lib import check, lib
 

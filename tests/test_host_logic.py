@@ -173,17 +173,31 @@ def test_synthetic_weights_are_reproducible():
                                                               synth.elic_united_entries()["g_a.rgb_analysis_transform.0.weight"], 0).tobytes()).hexdigest()[:16]
 
 
-@pytest.mark.parametrize("table", ["tile_table.h", "tile_table_loaded.h"])
+def _exported_tile_forms(blocked):
+    from rgbd_amd._lib import lib
+
+    need = lib().rgbd_debug_tile_list(blocked, None, 0)
+    buf = ctypes.create_string_buffer(need)
+    assert lib().rgbd_debug_tile_list(blocked, buf, need) == need
+    return {tuple(int(x) for x in ln.split(",")) for ln in buf.value.decode().splitlines()}
+
+
+@pytest.mark.parametrize("table", ["tile_table.h", "tile_table_loaded.h", "tile_table_blk.h", "tile_table_blk_loaded.h"])
 def test_tile_table_is_well_formed(table):
-    """csrc/tile_table*.h are generated by tools/tune_tiles.py: 14 integers per entry, tile shapes that exist, unique keys."""
+    """csrc/tile_table*.h are generated by tools/tune_tiles.py: 14 integers per entry, forms that the dispatch instantiates
+    (rgbd_debug_tile_list: the lists of csrc/conv_tiles.h), unique keys.  The blocked tables (key nphase + 100) were measured on the
+    single-chain kernels: launch_conv_main drops an entry whose tile has no blocked form -- counted here, a tuning matter."""
     import os
     import re
 
     path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
                         "learning-based-rgb-d-image-compression_amd", "csrc", table)
-    tiles = ({(2, m, 8) for m in (3, 2, 1)} | {(2, m, n) for n in (4, 2, 1) for m in (5, 4, 3, 2, 1)} |
-             {(1, m, n) for n in (4, 2, 1) for m in (3, 2, 1)})
-    keys = set()
+    blk = "_blk" in table
+    forms = _exported_tile_forms(0)
+    blk_tiles = {f[:3] for f in _exported_tile_forms(1)}
+    tiles = {f[:3] for f in forms}
+    assert len(tiles) == 27 and len(forms) == 179 and len(blk_tiles) == 25 and blk_tiles < tiles
+    keys, dead = set(), []
     for ln in open(path):
         ln = ln.strip()
         if not ln.startswith("{"):
@@ -196,10 +210,22 @@ def test_tile_table_is_well_formed(table):
         # staging modes: 0 registers, 1 / 2 / 3 direct-to-LDS double buffer (78 / 52 / 38 KiB cap), 4 / 5 ring of four / three
         # direct-to-LDS stages (single-tap layers; needs whole waves of patch slots: 64 | pixels per tile)
         assert (wm, mt, nt) in tiles and kc in (16, 64) and dma in (0, 1, 2, 3, 4, 5) and not (dma and kc == 64), ln
+        assert (wm, mt, nt, kc, dma) in forms, ln
         if dma >= 4:
-            assert key[5] == 1 and key[6] == 1 and key[7] == 1 and (16 * nt * (2 if wm == 2 else 4)) % 64 == 0, ln
-        assert all(x > 0 for x in key) and key[3] % 16 == 0 and key[4] % 16 == 0 and key[7] in (1, 4, 11, 21), ln  # 11 / 21: checkerboard-output launches (nphase + 10 * ckbd)
+            assert key[5] == 1 and key[6] == 1 and key[7] in ((101,) if blk else (1,)) and (16 * nt * (2 if wm == 2 else 4)) % 64 == 0, ln
+        # 11 / 21: checkerboard-output launches (nphase + 10 * ckbd); + 100: the blocked-accumulation kernels, in their tables only
+        nphases = (101, 104, 111, 121) if blk else (1, 4, 11, 21)
+        assert all(x > 0 for x in key) and key[3] % 16 == 0 and key[4] % 16 == 0 and key[7] in nphases, ln
+        if blk:  # what launch_conv_main does with the entry of a blocked launch (csrc/conv_mfma.hip)
+            ring, staged = kc == 16 and dma in (4, 5), kc == 16 and dma != 0
+            if (wm, mt, nt) not in blk_tiles or (mt * nt > 12 and not ring) or (mt * nt > 10 and not staged):
+                dead.append(ln)
     assert keys
+    if blk:
+        print(f"{table}: {len(dead)} of {len(keys)} entries name a form the blocked kernels do not have (the cost model's pick runs instead)")
+        for ln in dead:
+            print("   ", ln)
+        assert len(dead) < len(keys)
 
 
 def test_ms_ssim_against_the_definition():
