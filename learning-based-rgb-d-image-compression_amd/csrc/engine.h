@@ -2,9 +2,9 @@
 // layer graph of the six model variants (ELIC_united, single-modal ELIC, STF_united, ELIC_united_R2D, single-modal STF, checkerboard
 // Cheng2020) as inline methods
 // that plan and issue HIP kernel launches on one stream, the conv planner (tiles, split-K, reference arithmetic) and the
-// per-call-shape HIP-graph cache.  engine.hip holds the call paths (compress / decompress / forward: one per direction for the
-// two-modality codecs, one per direction for all single-modal families, which enter it through the four `*_single` hooks),
-// engine_abi.hip the C ABI (include/rgbd_amd.h).  Everything shared between those two translation units is `inline` here
+// per-call-shape HIP-graph cache.  engine.hip holds the call paths (compress / decompress / forward: one per direction for
+// one or two modalities; a family enters them through the four `*_family` hooks), engine_abi.hip the C ABI
+// (include/rgbd_amd.h).  Everything shared between those two translation units is `inline` here
 // (one instance).
 #pragma once
 #include <algorithm>
@@ -415,6 +415,22 @@ struct rgbd_elic {
                       // 4: single-modal STF (models/stf.py), 5: checkerboard Cheng2020 (models/Cheng2020withCKBD.py)
     bool single() const { return variant == 1 || variant == 4 || variant == 5; }
     int in_ch = 3;    // image channels of the single-modal variant
+    // what the call paths (engine.hip) need to know about one versus two modalities; arrays are read at [0, nm)
+    struct Modes {
+        int nm;
+        const char* sfx[2];  // suffix of the debug-tensor names: "y" / "y_r", "y_d"
+        const char* eb[2];   // prefix of the entropy bottleneck's tensors
+        int img_ch[2];       // image channels
+        int clamp;           // decompress() clamps x_hat to [0, 1] (elic_united.py, stf.py:815; not elic.py:318-325 nor
+                             // Cheng2020withCKBD.py:167-174); forward() and the Latents epilogue never clamp
+        bool forward_names_z;  // forward() names z and z_hat too: the single-modal paths always did, the two-modality one never
+                               // (it names y and y_hat only); kept so that the debug-tensor key sets stay what they were
+    };
+    Modes modes() const
+    {
+        if (single()) return {1, {"", ""}, {"", ""}, {in_ch, in_ch}, variant == 4 ? 1 : 0, true};
+        return {2, {"_r", "_d"}, {"rgb_", "depth_"}, {3, 1}, 1, false};
+    }
     std::vector<int> slice_ch;
     std::map<std::string, HostTensor> raw;
     std::map<std::string, PackedConv> convs;
@@ -749,7 +765,7 @@ struct rgbd_elic {
         a.p = (float*)arena.take(a.elems() * sizeof(float));
         return a;
     }
-    // ---- two-ended workspace (Arena): the stage loops of g_a / g_s -------------------------------------------------
+    // ---- two-ended workspace (Arena): the stage loop of stages() ----------------------------------------------------
     // A stage reads tensors on one end and puts its output and temporaries on the other, which is emptied first: what it
     // held -- the previous stage's input -- is dead by then.  `cur_hi`: the end the stage's input lives on.  A fusion stage
     // (its inputs ARE its outputs: the concat buffers) only puts its temporaries there.
@@ -1626,118 +1642,89 @@ struct rgbd_elic {
     }
 
     // ---- transforms -----------------------------------------------------------------------------
-    // analysis.py:116-174
-    void g_a(const Act& rgb_in, const Act& depth_in, Act* y_r, Act* y_d)
+    // The ELIC-type analysis / synthesis transforms are lists of stages -- "conv" / "deconv" (k 5, stride 2), "rb"
+    // (bottleneck2), "attn" (attention2), "spf" (cross-modal fusion) -- walked by stages().  What a family decides about the
+    // walk is in its descriptor; ends and leads are on for ELIC_united only (open for the other families).
+    // an "spf" stage: none, bi_spf (both branches widen), bi_spf_single (depth only)
+    enum Fusion { kNoFusion, kBiSpf, kBiSpfDepth };
+    struct Stages {
+        const char* const* kinds;
+        int n;
+        int nm;
+        const char* prefix[2];  // layer-name prefix per modality
+        Fusion fusion;
+        bool grouped;  // the branches of a stage go as one grouped launch (conv2(2, ...)), not one after the other
+        bool ends;     // the stage loop alternates the workspace ends (ends_begin / ends_stage / ends_finish)
+        bool leads;    // an "rb" stage hands the next block's .branch.0 to its fused tail (next_lead)
+    };
+    static constexpr const char* kAna18[18] = {"conv", "rb", "rb", "rb", "spf", "conv", "rb", "rb", "rb",
+                                               "attn", "spf", "conv", "rb", "rb", "rb", "spf", "conv", "attn"};
+    static constexpr const char* kSyn18[18] = {"attn", "deconv", "spf", "rb", "rb", "rb", "deconv", "attn", "spf",
+                                               "rb", "rb", "rb", "deconv", "spf", "rb", "rb", "rb", "deconv"};
+    static constexpr const char* kAna15[15] = {"conv", "rb", "rb", "rb", "conv", "rb", "rb", "rb",
+                                               "attn", "conv", "rb", "rb", "rb", "conv", "attn"};
+    static constexpr const char* kSyn15[15] = {"attn", "deconv", "rb", "rb", "rb", "deconv", "attn", "rb",
+                                               "rb", "rb", "deconv", "rb", "rb", "rb", "deconv"};
+    void stages(const Stages& sd, const Act in[2], Act out[2])
     {
-        static const char* kinds[18] = {"conv", "rb", "rb", "rb", "spf", "conv", "rb", "rb", "rb",
-                                        "attn", "spf", "conv", "rb", "rb", "rb", "spf", "conv", "attn"};
-        const std::string pr = "g_a.rgb_analysis_transform.", pd = "g_a.depth_analysis_transform.";
-        Act r = rgb_in, d = depth_in;
-        Ends ends = ends_begin();
-        for (int i = 0; i < 18; ++i) {
-            const std::string k = kinds[i], si = std::to_string(i);
-            const bool next_spf = (i + 1 < 18) && std::string(kinds[i + 1]) == "spf";
-            ends_stage(ends, k != "spf");
-            Act rdst, ddst;
-            const Act *pr_dst = nullptr, *pd_dst = nullptr;
-            Act rcat, dcat;
-            if (next_spf) {  // the stage feeding a fusion writes into the first half of the concat buffer
-                rcat = alloc(r.n, r.h, r.w, 2 * N);
-                dcat = alloc(d.n, d.h, d.w, 2 * N);
-                rdst = view(rcat, 0, N);
-                ddst = view(dcat, 0, N);
-                pr_dst = &rdst;
-                pd_dst = &ddst;
-            }
-            const std::string names[2] = {pr + si, pd + si};
-            const Act xin[2] = {r, d};
-            const Act* dsts[2] = {pr_dst, pd_dst};
-            Act o[2];
-            if (k == "conv") {
-                const Epi none[2];
-                conv2(2, names, xin, 2, 2, none, nullptr, o);
-                r = o[0];
-                d = o[1];
-            } else if (k == "rb") {
-                const bool next_rb = (i + 1 < 18) && std::string(kinds[i + 1]) == "rb";
-                const std::string sn = std::to_string(i + 1) + ".branch.0";
-                const std::string nl[2] = {next_rb ? pr + sn : std::string(), next_rb ? pd + sn : std::string()};
-                bottleneck2(2, names, xin, dsts, nl, o);
-                r = o[0];
-                d = o[1];
-                if (next_spf) {
-                    r = rcat;
-                    d = dcat;
-                }
-            } else if (k == "attn") {
-                attention2(2, names, xin, dsts, o);
-                r = o[0];
-                d = o[1];
-                if (next_spf) {
-                    r = rcat;
-                    d = dcat;
-                }
-            } else {  // spf: r and d are the 2N-channel concat buffers whose first half is filled
-                bi_spf(pr + si, view(r, 0, N), view(d, 0, N), view(r, N, N), view(d, N, N));
-            }
-        }
-        ends_finish(ends);
-        *y_r = r;
-        *y_d = d;
-    }
-
-    // synthesis.py:126-184
-    void g_s(const Act& yr, const Act& yd, Act* xr, Act* xd)
-    {
-        static const char* kinds[18] = {"attn", "deconv", "spf", "rb", "rb", "rb", "deconv", "attn", "spf",
-                                        "rb", "rb", "rb", "deconv", "spf", "rb", "rb", "rb", "deconv"};
-        const std::string pr = "g_s.rgb_synthesis_transform.", pd = "g_s.depth_synthesis_transform.";
-        Act r = yr, d = yd;
-        Ends ends = ends_begin();
-        for (int i = 0; i < 18; ++i) {
-            const std::string k = kinds[i], si = std::to_string(i);
-            const bool next_spf = (i + 1 < 18) && std::string(kinds[i + 1]) == "spf";
-            ends_stage(ends, k != "spf");
-            if (k == "spf") {
-                bi_spf(pr + si, view(r, 0, N), view(d, 0, N), view(r, N, N), view(d, N, N));
+        const int nm = sd.nm;
+        Act x[2];
+        for (int m = 0; m < nm; ++m) x[m] = in[m];
+        Ends ends;
+        if (sd.ends) ends = ends_begin();
+        for (int i = 0; i < sd.n; ++i) {
+            const std::string k = sd.kinds[i], si = std::to_string(i);
+            const bool next_spf = (i + 1 < sd.n) && std::string(sd.kinds[i + 1]) == "spf";
+            if (sd.ends) ends_stage(ends, k != "spf");
+            if (k == "spf") {  // the widened branches are 2N-channel concat buffers whose first half is filled
+                if (sd.fusion == kBiSpf)
+                    bi_spf(sd.prefix[0] + si, view(x[0], 0, N), view(x[1], 0, N), view(x[0], N, N), view(x[1], N, N));
+                else
+                    bi_spf_single(sd.prefix[0] + si, x[0], view(x[1], 0, N), view(x[1], N, N));
                 continue;
             }
-            Act rcat, dcat, rdst, ddst;
-            const Act *pr_dst = nullptr, *pd_dst = nullptr;
-            if (next_spf) {
-                const int oh = (k == "deconv") ? r.h * 2 : r.h, ow = (k == "deconv") ? r.w * 2 : r.w;
-                rcat = alloc(r.n, oh, ow, 2 * N);
-                dcat = alloc(d.n, oh, ow, 2 * N);
-                rdst = view(rcat, 0, N);
-                ddst = view(dcat, 0, N);
-                pr_dst = &rdst;
-                pd_dst = &ddst;
+            // the stage feeding a fusion writes into the first half of the concat buffer of every branch the fusion widens
+            Act cat[2], half[2];
+            const Act* dsts[2] = {nullptr, nullptr};
+            if (next_spf)
+                for (int m = sd.fusion == kBiSpfDepth ? 1 : 0; m < nm; ++m) {
+                    const int oh = (k == "deconv") ? x[m].h * 2 : (k == "conv" ? x[m].h / 2 : x[m].h);
+                    const int ow = (k == "deconv") ? x[m].w * 2 : (k == "conv" ? x[m].w / 2 : x[m].w);
+                    cat[m] = alloc(x[m].n, oh, ow, 2 * N);
+                    half[m] = view(cat[m], 0, N);
+                    dsts[m] = &half[m];
+                }
+            const bool next_rb = sd.leads && (i + 1 < sd.n) && std::string(sd.kinds[i + 1]) == "rb";
+            std::string names[2], nl[2];
+            for (int m = 0; m < nm; ++m) {
+                names[m] = sd.prefix[m] + si;
+                if (next_rb) nl[m] = sd.prefix[m] + std::to_string(i + 1) + ".branch.0";
             }
-            const std::string names[2] = {pr + si, pd + si};
-            const Act xin[2] = {r, d};
-            const Act* dsts[2] = {pr_dst, pd_dst};
+            const Epi none[2];
             Act o[2];
-            if (k == "deconv") {
-                const Epi none[2];
-                conv2(2, names, xin, 2, 2, none, next_spf ? dsts : nullptr, o);
-            } else if (k == "rb") {
-                const bool next_rb = (i + 1 < 18) && std::string(kinds[i + 1]) == "rb";
-                const std::string sn = std::to_string(i + 1) + ".branch.0";
-                const std::string nl[2] = {next_rb ? pr + sn : std::string(), next_rb ? pd + sn : std::string()};
-                bottleneck2(2, names, xin, dsts, nl, o);
-            } else {
-                attention2(2, names, xin, dsts, o);
+            const int g = sd.grouped ? nm : 1;  // branches per launch
+            for (int m = 0; m < nm; m += g) {
+                if (k == "conv" || k == "deconv") conv2(g, names + m, x + m, 2, 2, none, dsts + m, o + m);
+                else if (k == "rb") bottleneck2(g, names + m, x + m, dsts + m, nl + m, o + m);
+                else attention2(g, names + m, x + m, dsts + m, o + m);
             }
-            r = o[0];
-            d = o[1];
-            if (next_spf) {
-                r = rcat;
-                d = dcat;
-            }
+            for (int m = 0; m < nm; ++m) x[m] = dsts[m] ? cat[m] : o[m];
         }
-        ends_finish(ends);
-        *xr = r;
-        *xd = d;
+        if (sd.ends) ends_finish(ends);
+        for (int m = 0; m < nm; ++m) out[m] = x[m];
+    }
+    // ELIC_united: analysis.py:116-174 / synthesis.py:126-184
+    void g_a(const Act x[2], Act y[2])
+    {
+        const Stages sd = {kAna18, 18, 2, {"g_a.rgb_analysis_transform.", "g_a.depth_analysis_transform."},
+                           kBiSpf, true, true, true};
+        stages(sd, x, y);
+    }
+    void g_s(const Act yhat[2], Act xhat[2])
+    {
+        const Stages sd = {kSyn18, 18, 2, {"g_s.rgb_synthesis_transform.", "g_s.depth_synthesis_transform."},
+                           kBiSpf, true, true, true};
+        stages(sd, yhat, xhat);
     }
 
     // analysis.py:231-242
@@ -2233,53 +2220,19 @@ struct rgbd_elic {
         esa2(1, &n, &dr, &d_dst, nullptr);
         arena.top = mark;
     }
-    // analysis.py:56-112 / synthesis.py:186-242: the same 18 stages as ELIC_united; the fusion stage only widens depth
-    void stack_r2d(const std::string& root, const char* kind, const char* const* kinds, const Act& r_in, const Act& d_in,
-                   Act* r_out, Act* d_out)
+    // analysis.py:56-112 / synthesis.py:186-242: the same 18 stages as ELIC_united, one branch after the other; the fusion
+    // stage only widens depth
+    void g_a_r2d(const Act x[2], Act y[2])
     {
-        const std::string pr = root + ".rgb_" + kind + "_transform.", pd = root + ".depth_" + kind + "_transform.";
-        Act r = r_in, d = d_in;
-        for (int i = 0; i < 18; ++i) {
-            const std::string k = kinds[i], si = std::to_string(i);
-            const bool next_spf = (i + 1 < 18) && std::string(kinds[i + 1]) == "spf";
-            if (k == "spf") {  // d is the 2N-channel concat buffer whose first half is filled
-                bi_spf_single(pr + si, r, view(d, 0, N), view(d, N, N));
-                continue;
-            }
-            Act dcat, ddst;
-            const Act* dsts[2] = {nullptr, nullptr};
-            if (next_spf) {
-                const int oh = (k == "deconv") ? d.h * 2 : (k == "conv" ? d.h / 2 : d.h);
-                const int ow = (k == "deconv") ? d.w * 2 : (k == "conv" ? d.w / 2 : d.w);
-                dcat = alloc(d.n, oh, ow, 2 * N);
-                ddst = view(dcat, 0, N);
-                dsts[1] = &ddst;
-            }
-            const std::string names[2] = {pr + si, pd + si}, no_lead;
-            Act* cur[2] = {&r, &d};
-            for (int m = 0; m < 2; ++m) {  // one branch after the other
-                Act o;
-                if (k == "conv" || k == "deconv") o = conv(names[m], *cur[m], 2, 2, Epi(), dsts[m]);
-                else if (k == "rb") bottleneck2(1, &names[m], cur[m], &dsts[m], &no_lead, &o);
-                else attention2(1, &names[m], cur[m], &dsts[m], &o);
-                *cur[m] = o;
-            }
-            if (next_spf) d = dcat;
-        }
-        *r_out = r;
-        *d_out = d;
+        const Stages sd = {kAna18, 18, 2, {"g_a.rgb_analysis_transform.", "g_a.depth_analysis_transform."},
+                           kBiSpfDepth, false, false, false};
+        stages(sd, x, y);
     }
-    void g_a_r2d(const Act& rgb, const Act& depth, Act* y_r, Act* y_d)
+    void g_s_r2d(const Act yhat[2], Act xhat[2])
     {
-        static const char* const kinds[18] = {"conv", "rb", "rb", "rb", "spf", "conv", "rb", "rb", "rb",
-                                              "attn", "spf", "conv", "rb", "rb", "rb", "spf", "conv", "attn"};
-        stack_r2d("g_a", "analysis", kinds, rgb, depth, y_r, y_d);
-    }
-    void g_s_r2d(const Act& yr, const Act& yd, Act* xr, Act* xd)
-    {
-        static const char* const kinds[18] = {"attn", "deconv", "spf", "rb", "rb", "rb", "deconv", "attn", "spf",
-                                              "rb", "rb", "rb", "deconv", "spf", "rb", "rb", "rb", "deconv"};
-        stack_r2d("g_s", "synthesis", kinds, yr, yd, xr, xd);
+        const Stages sd = {kSyn18, 18, 2, {"g_s.rgb_synthesis_transform.", "g_s.depth_synthesis_transform."},
+                           kBiSpfDepth, false, false, false};
+        stages(sd, yhat, xhat);
     }
     // synthesis.py:364-380
     Act hs_block_single(const std::string& p, const Act& x, bool last)
@@ -2371,31 +2324,17 @@ struct rgbd_elic {
 
     // ---- single-modal ELIC (models/elic.py:15-57; BASELINE config 1) ------------------------------------------
     // analysis.py:29-52 / synthesis.py:32-70: the same blocks as above without the cross-modal fusion stages
-    Act stack1(const std::string& prefix, const char* const* kinds, int n, const Act& x_in)
-    {
-        Act x = x_in;
-        const std::string no_lead;
-        for (int i = 0; i < n; ++i) {
-            const std::string k = kinds[i], name = prefix + std::to_string(i);
-            Act o;
-            if (k == "conv" || k == "deconv") o = conv(name, x, 2, 2);
-            else if (k == "rb") bottleneck2(1, &name, &x, nullptr, &no_lead, &o);
-            else attention2(1, &name, &x, nullptr, &o);
-            x = o;
-        }
-        return x;
-    }
     Act g_a1(const Act& x)
     {
-        static const char* const kinds[15] = {"conv", "rb", "rb", "rb", "conv", "rb", "rb", "rb",
-                                              "attn", "conv", "rb", "rb", "rb", "conv", "attn"};
-        return stack1("g_a.analysis_transform.", kinds, 15, x);
+        Act y[2];
+        stages({kAna15, 15, 1, {"g_a.analysis_transform.", ""}, kNoFusion, false, false, false}, &x, y);
+        return y[0];
     }
-    Act g_s1(const Act& y)
+    Act g_s1(const Act& yhat)
     {
-        static const char* const kinds[15] = {"attn", "deconv", "rb", "rb", "rb", "deconv", "attn", "rb",
-                                              "rb", "rb", "deconv", "rb", "rb", "rb", "deconv"};
-        return stack1("g_s.synthesis_transform.", kinds, 15, y);
+        Act xhat[2];
+        stages({kSyn15, 15, 1, {"g_s.synthesis_transform.", ""}, kNoFusion, false, false, false}, &yhat, xhat);
+        return xhat[0];
     }
     // analysis.py:207-216
     Act h_a1(const Act& y)
@@ -2852,15 +2791,20 @@ struct rgbd_elic {
     void z_estimate(const char* pfx, const Act& z, const Act& zhat, const Act& zlik);
     void y_encode(int nm, int B, const EncBufs& e);
 
-    // the single-modal families (variants 1, 4, 5): one call path per direction; the family enters through four hooks
-    Act g_a_single(const Act& x);
-    Act h_a_single(const Act& y);
-    Act g_s_single(const Act& yhat);
-    void latent_single(Coding& cd, const Act* y, const Act& zhat, Act* yhat);
-    int run_compress_single(const float* x_dev, int B, int H, int W, int per_image);
-    int run_forward_single(const float* x_dev, int B, int H, int W, float* xhat_dev, float* ly, float* lz);
-    int run_decompress_single(const uint8_t* const* ys, const int64_t* ylen, int n_y, const uint8_t* const* zs,
-                              const int64_t* zlen, int B, int zh, int zw, float* x_out);
+    void name(const Modes& mo, const char* base, const Act a[2])  // a debug tensor per modality: "y" / "y_r", "y_d"
+    {
+        for (int m = 0; m < mo.nm; ++m) named[std::string(base) + mo.sfx[m]] = a[m];
+    }
+
+    // A family (variant) enters the call paths through these four hooks, which switch on `variant`; Act arrays are read at
+    // [0, nm).  latent_family owns everything between z_hat and y_hat: the family's buffers, its hyper synthesis (skipped when
+    // the caller hands in `hyp`, the Latents path), its debug tensors and its coding loop.
+    void g_a_family(const Act x[2], Act y[2]);
+    void h_a_family(const Act y[2], Act z[2]);
+    void g_s_family(const Act yhat[2], Act xhat[2]);
+    void latent_family(Coding& cd, int B, int h, int w, const Act* y, const Act* zhat, const Act* hyp, Act yhat[2]);
+
+    void analysis(const Act x[2], const Act y[2]);  // y = g_a(x), into the caller's buffers
 
     // lat != nullptr: the Bi-CEE stage alone (compress_united / decompress_united): latents and hyper parameters come
     // from the caller as NCHW device tensors, the transforms and the z path are skipped
@@ -2869,14 +2813,14 @@ struct rgbd_elic {
         const float* hyp[2];  // [B,2M,h,w]
         float* yhat[2];       // [B,M,h,w]     (decompress only)
     };
-    int run_compress(const float* rgb_dev, const float* depth_dev, int B, int H, int W, int per_image,
-                     const Latents* lat = nullptr);
-    int run_forward(const float* rgb_dev, const float* depth_dev, int B, int H, int W, float* xr_dev, float* xd_dev,
-                    float* ly_r, float* ly_d, float* lz_r, float* lz_d);
-    int run_decompress_impl(const uint8_t* const* ys[2], const int64_t* ylen[2], int n_y, const uint8_t* const* zs[2],
-                            const int64_t* zlen[2], int B, int h, int w, float* xr_dev, float* xd_dev, const Latents* lat);
-    int run_decompress(const uint8_t* const* ys[2], const int64_t* ylen[2], int n_y, const uint8_t* const* zs[2],
-                       const int64_t* zlen[2], int B, int zh, int zw, float* xr_dev, float* xd_dev);
+    // the call paths: nm tensors per argument.  A model with another number of modalities is refused with RGBD_ESTATE, the
+    // code such a call always ended with (a single-modal engine has none of the rgb_ / depth_ layers: conv_of)
+    using In2 = std::array<const float*, 2>;
+    using Out2 = std::array<float*, 2>;
+    int run_compress(int nm, In2 x_dev, int B, int H, int W, int per_image, const Latents* lat = nullptr);
+    int run_forward(int nm, In2 x_dev, int B, int H, int W, Out2 xhat_dev, Out2 ly, Out2 lz);
+    int run_decompress(int nm, const uint8_t* const* ys[2], const int64_t* ylen[2], int n_y, const uint8_t* const* zs[2],
+                       const int64_t* zlen[2], int B, int h, int w, Out2 xhat_dev, const Latents* lat = nullptr);
     int ensure_arena(size_t bytes);
 };
 

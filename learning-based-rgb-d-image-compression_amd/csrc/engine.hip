@@ -1,6 +1,5 @@
-// Host runtime of the gfx950 codec engine, part 2 of 3: the call paths -- compress(), decompress() and the eval forward of the
-// two-modality codecs and, once for all of them, of the single-modal families -- as sequences of kernel launches through the
-// layer graph of engine.h
+// Host runtime of the gfx950 codec engine, part 2 of 3: the call paths -- compress(), decompress() and the eval forward, once
+// for every family of one or two modalities -- as sequences of kernel launches through the layer graph of engine.h
 // (prologue: workspace of the call and stream geometry; body: captured into / replayed from a HIP graph; epilogue: fetch
 // the finished streams).  Mirrors the call structure of the reference's models/elic_united.py:350-578 but keeps every
 // tensor, symbol, index and bitstream resident in HBM; the only device->host traffic is the finished streams.
@@ -321,335 +320,83 @@ void rgbd_elic::y_encode(int nm, int B, const EncBufs& e)
     if (r) fail(r);
 }
 
-// ---- the two-modality codecs ---------------------------------------------------------------------------------------------
-int rgbd_elic::run_compress(const float* rgb_dev, const float* depth_dev, int B, int H, int W, int per_image,
-                            const Latents* lat)
-{
-    const int h = H / 16, w = W / 16, zh = lat ? 1 : H / 64, zw = lat ? 1 : W / 64;
-    const int Ctot = M;
-    const int64_t T = (int64_t)Ctot * h * w;  // y symbols per image per modality
-    const int64_t Tz = (int64_t)N * zh * zw;
-    begin_call(per_image ? 1 : B, false);  // per-image streams stand for the reference called image by image
-
-    // ==== prologue (never captured): workspace of the call, upload of the stream geometry, input layout conversion ====
-    EncBufs e;
-    if (const int r = enc_streams(2, B, T, Tz, per_image, &e)) return r;
-    int32_t *fy = nullptr, *fz = nullptr;
-    if (const int r = upload_forced(2, force_y, (size_t)(B * T), &fy)) return r;
-    if (!lat)
-        if (const int r = upload_forced(2, force_z, (size_t)(B * Tz), &fz)) return r;
-
-    Act y_r = alloc(B, h, w, M), y_d = alloc(B, h, w, M);
-    Act hyp_r, hyp_d, rgb, depth;
-    if (lat) {
-        hyp_r = alloc(B, h, w, 2 * M);
-        hyp_d = alloc(B, h, w, 2 * M);
-        if (!dry()) {
-            int r = launch_nchw_to_nhwc16(lat->y[0], B, M, h, w, y_r.p, y_r.cs, s, perm());
-            if (!r) r = launch_nchw_to_nhwc16(lat->y[1], B, M, h, w, y_d.p, y_d.cs, s, perm());
-            if (!r) r = launch_nchw_to_nhwc16(lat->hyp[0], B, 2 * M, h, w, hyp_r.p, hyp_r.cs, s, perm());
-            if (!r) r = launch_nchw_to_nhwc16(lat->hyp[1], B, 2 * M, h, w, hyp_d.p, hyp_d.cs, s, perm());
-            if (r) return r;
-        }
-    } else {
-        rgb = alloc(B, H, W, 3);
-        depth = alloc(B, H, W, 1);
-        if (!dry()) {
-            int r = launch_nchw_to_nhwc16(rgb_dev, B, 3, H, W, rgb.p, rgb.cs, s);
-            if (!r) r = launch_nchw_to_nhwc16(depth_dev, B, 1, H, W, depth.p, depth.cs, s);
-            if (r) return r;
-        }
-    }
-
-    // ==== body: every kernel of the call, in stream order; captured into / replayed from a HIP graph per call shape ====
-    if (body_begin()) {
-        if (!dry()) {
-            const int zr = launch_fill_zero((float*)e.err, 64, s);  // (a kernel, not a memset node: see launch_fill_zero)
-            if (zr) fail(zr);
-        }
-        named["y_r"] = y_r;
-        named["y_d"] = y_d;
-        if (!lat) {
-            // ---- analysis
-            Act z_r, z_d;
-            {
-                const size_t mark = arena.top;
-                Act yr_t, yd_t;
-                if (variant == 2) g_a_stf(rgb, depth, &yr_t, &yd_t);
-                else if (variant == 3) g_a_r2d(rgb, depth, &yr_t, &yd_t);
-                else g_a(rgb, depth, &yr_t, &yd_t);
-                copy_ch(yr_t, y_r);
-                copy_ch(yd_t, y_d);
-                arena.top = mark;
-                ends_release();
-            }
-            h_a(y_r, y_d, &z_r, &z_d);
-            named["z_r"] = z_r;
-            named["z_d"] = z_d;
-
-            Act zh_r = alloc(B, zh, zw, N), zh_d = alloc(B, zh, zw, N);
-            z_encode(0, "rgb_", e, z_r, zh_r, fz);
-            z_encode(1, "depth_", e, z_d, zh_d, fz);
-            named["zhat_r"] = zh_r;
-            named["zhat_d"] = zh_d;
-
-            // ---- hyper synthesis
-            if (variant == 3) h_s_r2d(zh_r, zh_d, &hyp_r, &hyp_d);
-            else h_s(zh_r, zh_d, &hyp_r, &hyp_d);
-        }
-        named["hyper_r"] = hyp_r;
-        named["hyper_d"] = hyp_d;
-        Act yhat_r = alloc(B, h, w, M), yhat_d = alloc(B, h, w, M);
-        if (variant == 2 && !dry()) {  // 24-wide slices: a 16-channel read chunk may straddle into a slice not coded yet
-            int zr = launch_fill_zero(yhat_r.p, yhat_r.elems(), s);
-            if (!zr) zr = launch_fill_zero(yhat_d.p, yhat_d.elems(), s);
-            if (zr) fail(zr);
-        }
-        named["yhat_r"] = yhat_r;
-        named["yhat_d"] = yhat_d;
-        Coding cd = enc_coding(e, per_image, T, fy);
-        if (variant == 3) bicee_r2d(cd, &y_r, &y_d, hyp_r, hyp_d, yhat_r, yhat_d);
-        else bicee(cd, &y_r, &y_d, hyp_r, hyp_d, yhat_r, yhat_d);
-        y_encode(2, B, e);
-    }
-    if (const int r = finish_body()) return r;
-    if (dry()) return RGBD_OK;
-
-    // ==== epilogue (never captured): fetch the streams ================================================================
-    return fetch_streams(2, B, !lat, e);
-}
-
-// eval-mode forward(): models/elic_united.py:234-263 with quant == "ste" (round in eval), likelihoods as in
-// entropy_models.py:391-428 (factorised prior) and :534-558 (Gaussian conditional)
-int rgbd_elic::run_forward(const float* rgb_dev, const float* depth_dev, int B, int H, int W, float* xr_dev, float* xd_dev,
-                           float* ly_r, float* ly_d, float* lz_r, float* lz_d)
-{
-    const int h = H / 16, w = W / 16, zh = H / 64, zw = W / 64;
-    begin_call(B, true);  // forward() is one reference call on the whole batch
-    Act rgb = alloc(B, H, W, 3), depth = alloc(B, H, W, 1);
-    if (!dry()) {
-        int r = launch_nchw_to_nhwc16(rgb_dev, B, 3, H, W, rgb.p, rgb.cs, s);
-        if (!r) r = launch_nchw_to_nhwc16(depth_dev, B, 1, H, W, depth.p, depth.cs, s);
-        if (r) return r;
-    }
-    // ==== body: captured into / replayed from a HIP graph per call shape (the prologue above reads the caller's pointers,
-    // the epilogue below writes them) ====
-    Act xr, xd, lik_r, lik_d, zl_r, zl_d;
-    if (body_begin()) {
-        Act y_r = alloc(B, h, w, M), y_d = alloc(B, h, w, M);
-        Act z_r, z_d;
-        {
-            const size_t mark = arena.top;
-            Act yr_t, yd_t;
-            if (variant == 2) g_a_stf(rgb, depth, &yr_t, &yd_t);
-            else if (variant == 3) g_a_r2d(rgb, depth, &yr_t, &yd_t);
-            else g_a(rgb, depth, &yr_t, &yd_t);
-            copy_ch(yr_t, y_r);
-            copy_ch(yd_t, y_d);
-            arena.top = mark;
-            ends_release();
-        }
-        h_a(y_r, y_d, &z_r, &z_d);
-        Act zh_r = alloc(B, zh, zw, N), zh_d = alloc(B, zh, zw, N);
-        zl_r = alloc(B, zh, zw, N);
-        zl_d = alloc(B, zh, zw, N);
-        z_estimate("rgb_", z_r, zh_r, zl_r);
-        z_estimate("depth_", z_d, zh_d, zl_d);
-        Act hyp_r, hyp_d;
-        if (variant == 3) h_s_r2d(zh_r, zh_d, &hyp_r, &hyp_d);
-        else h_s(zh_r, zh_d, &hyp_r, &hyp_d);
-        Act yhat_r = alloc(B, h, w, M), yhat_d = alloc(B, h, w, M);
-        if (variant == 2 && !dry()) {  // 24-wide slices: a 16-channel read chunk may straddle into a slice not coded yet
-            int zr = launch_fill_zero(yhat_r.p, yhat_r.elems(), s);
-            if (!zr) zr = launch_fill_zero(yhat_d.p, yhat_d.elems(), s);
-            if (zr) fail(zr);
-        }
-        Coding cd;
-        cd.estimate = true;
-        cd.lik[0] = alloc(B, h, w, M);
-        cd.lik[1] = alloc(B, h, w, M);
-        if (variant == 3) bicee_r2d(cd, &y_r, &y_d, hyp_r, hyp_d, yhat_r, yhat_d);
-        else bicee(cd, &y_r, &y_d, hyp_r, hyp_d, yhat_r, yhat_d);
-        named["y_r"] = y_r;
-        named["y_d"] = y_d;
-        named["yhat_r"] = yhat_r;
-        named["yhat_d"] = yhat_d;
-        if (variant == 2) g_s_stf(yhat_r, yhat_d, &xr, &xd);
-        else if (variant == 3) g_s_r2d(yhat_r, yhat_d, &xr, &xd);
-        else g_s(yhat_r, yhat_d, &xr, &xd);
-        lik_r = cd.lik[0];
-        lik_d = cd.lik[1];
-        if (cur_ge && !dry()) {
-            const Act o[6] = {xr, xd, lik_r, lik_d, zl_r, zl_d};
-            for (int k = 0; k < 6; ++k) cur_ge->out[k] = o[k];
-        }
-    } else {
-        xr = cur_ge->out[0];
-        xd = cur_ge->out[1];
-        lik_r = cur_ge->out[2];
-        lik_d = cur_ge->out[3];
-        zl_r = cur_ge->out[4];
-        zl_d = cur_ge->out[5];
-    }
-    if (const int r = finish_body()) return r;
-    if (dry()) return RGBD_OK;
-    int r = launch_nhwc_to_nchw_clamp(xr.p, B, 3, H, W, xr.cs, xr_dev, 0, s);
-    if (!r) r = launch_nhwc_to_nchw_clamp(xd.p, B, 1, H, W, xd.cs, xd_dev, 0, s);
-    if (!r) r = launch_nhwc_to_nchw_clamp(lik_r.p, B, M, h, w, lik_r.cs, ly_r, 0, s, perm());
-    if (!r) r = launch_nhwc_to_nchw_clamp(lik_d.p, B, M, h, w, lik_d.cs, ly_d, 0, s, perm());
-    if (!r) r = launch_nhwc_to_nchw_clamp(zl_r.p, B, N, zh, zw, zl_r.cs, lz_r, 0, s, perm());
-    if (!r) r = launch_nhwc_to_nchw_clamp(zl_d.p, B, N, zh, zw, zl_d.cs, lz_d, 0, s, perm());
-    if (!r) r = wait_stream();
-    return r;
-}
-
-int rgbd_elic::run_decompress(const uint8_t* const* ys[2], const int64_t* ylen[2], int n_y, const uint8_t* const* zs[2],
-                              const int64_t* zlen[2], int B, int zh, int zw, float* xr_dev, float* xd_dev)
-{
-    return run_decompress_impl(ys, ylen, n_y, zs, zlen, B, zh * 4, zw * 4, xr_dev, xd_dev, nullptr);
-}
-
-int rgbd_elic::run_decompress_impl(const uint8_t* const* ys[2], const int64_t* ylen[2], int n_y,
-                                   const uint8_t* const* zs[2], const int64_t* zlen[2], int B, int h, int w,
-                                   float* xr_dev, float* xd_dev, const Latents* lat)
-{
-    const int zh = lat ? 1 : h / 4, zw = lat ? 1 : w / 4, H = h * 16, W = w * 16;
-    const int64_t T = (int64_t)M * h * w, Tz = (int64_t)N * zh * zw;
-    const int per_image = (n_y == B && !(B == 1)) ? 1 : (n_y == 1 ? (B == 1 ? 1 : 0) : -1);
-    if (per_image < 0) return RGBD_EINVAL;
-    begin_call(per_image == 0 ? B : 1, false);
-
-    // ==== prologue (never captured): upload the streams ================================================================
-    const int ns_y = n_y, ns_z = lat ? 0 : B;
-    DecBufs d;
-    if (const int r = dec_streams(2, ys, ylen, ns_y, zs, zlen, ns_z, B, T, Tz, per_image, &d)) return r;
-
-    Act hyp_r, hyp_d;
-    if (lat) {
-        hyp_r = alloc(B, h, w, 2 * M);
-        hyp_d = alloc(B, h, w, 2 * M);
-        if (!dry()) {
-            int r = launch_nchw_to_nhwc16(lat->hyp[0], B, 2 * M, h, w, hyp_r.p, hyp_r.cs, s, perm());
-            if (!r) r = launch_nchw_to_nhwc16(lat->hyp[1], B, 2 * M, h, w, hyp_d.p, hyp_d.cs, s, perm());
-            if (r) return r;
-        }
-    }
-
-    // ==== body: captured into / replayed from a HIP graph per call shape ================================================
-    Act out0, out1;  // what the epilogue hands back: x_hat (or y_hat for decompress_united) per modality
-    if (body_begin()) {
-        if (!lat) {
-            Act zh_r = alloc(B, zh, zw, N), zh_d = alloc(B, zh, zw, N);
-            z_decode(0, "rgb_", d, zh_r);
-            z_decode(1, "depth_", d, zh_d);
-            named["zhat_r"] = zh_r;
-            named["zhat_d"] = zh_d;
-
-            if (variant == 3) h_s_r2d(zh_r, zh_d, &hyp_r, &hyp_d);
-            else h_s(zh_r, zh_d, &hyp_r, &hyp_d);
-        }
-        named["hyper_r"] = hyp_r;
-        named["hyper_d"] = hyp_d;
-        Act yhat_r = alloc(B, h, w, M), yhat_d = alloc(B, h, w, M);
-        if (variant == 2 && !dry()) {  // 24-wide slices: a 16-channel read chunk may straddle into a slice not coded yet
-            int zr = launch_fill_zero(yhat_r.p, yhat_r.elems(), s);
-            if (!zr) zr = launch_fill_zero(yhat_d.p, yhat_d.elems(), s);
-            if (zr) fail(zr);
-        }
-        named["yhat_r"] = yhat_r;
-        named["yhat_d"] = yhat_d;
-        Coding cd = dec_coding(d, per_image, T, ns_y);
-        if (variant == 3) bicee_r2d(cd, nullptr, nullptr, hyp_r, hyp_d, yhat_r, yhat_d);
-        else bicee(cd, nullptr, nullptr, hyp_r, hyp_d, yhat_r, yhat_d);
-        if (lat) {  // decompress_united ends here: y_hat back to the caller
-            out0 = yhat_r;
-            out1 = yhat_d;
-        } else {
-            if (variant == 2) g_s_stf(yhat_r, yhat_d, &out0, &out1);
-            else if (variant == 3) g_s_r2d(yhat_r, yhat_d, &out0, &out1);
-            else g_s(yhat_r, yhat_d, &out0, &out1);
-        }
-        if (cur_ge && !dry()) {
-            cur_ge->out[0] = out0;
-            cur_ge->out[1] = out1;
-        }
-    } else {
-        out0 = cur_ge->out[0];
-        out1 = cur_ge->out[1];
-    }
-    if (const int r = finish_body()) return r;
-    if (dry()) return RGBD_OK;
-
-    // ==== epilogue (never captured): results into the caller's NCHW tensors ==========================================
-    if (lat) {
-        int r = launch_nhwc_to_nchw_clamp(out0.p, B, M, h, w, out0.cs, lat->yhat[0], 0, s, perm());
-        if (!r) r = launch_nhwc_to_nchw_clamp(out1.p, B, M, h, w, out1.cs, lat->yhat[1], 0, s, perm());
-        return r;
-    }
-    int r = launch_nhwc_to_nchw_clamp(out0.p, B, 3, H, W, out0.cs, xr_dev, 1, s);
-    if (!r) r = launch_nhwc_to_nchw_clamp(out1.p, B, 1, H, W, out1.cs, xd_dev, 1, s);
-    return r;
-}
-
-// ---- the single-modal families: ELIC (variant 1, models/elic.py), STF (4, models/stf.py) and the checkerboard Cheng2020
+// ---- the family hooks: ELIC_united (variant 0, models/elic_united.py), ELIC (1, models/elic.py), STF_united (2,
+// models/stf_united.py), ELIC_united_R2D (3, models/elic_united_R2D.py), STF (4, models/stf.py) and the checkerboard Cheng2020
 // (5, models/Cheng2020withCKBD.py) share one call path per direction; a family enters through the four hooks below ----------
-Act rgbd_elic::g_a_single(const Act& x)
+void rgbd_elic::g_a_family(const Act x[2], Act y[2])
 {
     switch (variant) {
-    case 4: return g_a_stf1(x);
-    case 5: return g_a_ckbd(x);
-    default: return g_a1(x);
+    case 1: y[0] = g_a1(x[0]); break;
+    case 2: g_a_stf(x[0], x[1], &y[0], &y[1]); break;
+    case 3: g_a_r2d(x, y); break;
+    case 4: y[0] = g_a_stf1(x[0]); break;
+    case 5: y[0] = g_a_ckbd(x[0]); break;
+    default: g_a(x, y);
     }
 }
 
-Act rgbd_elic::h_a_single(const Act& y)
+void rgbd_elic::h_a_family(const Act y[2], Act z[2])
 {
     switch (variant) {
-    case 4: return h_a_stf1(y);
-    case 5: return h_a_ckbd(y);
-    default: return h_a1(y);
+    case 1: z[0] = h_a1(y[0]); break;
+    case 4: z[0] = h_a_stf1(y[0]); break;
+    case 5: z[0] = h_a_ckbd(y[0]); break;
+    default: h_a(y[0], y[1], &z[0], &z[1]);
     }
 }
 
-Act rgbd_elic::g_s_single(const Act& yhat)
+void rgbd_elic::g_s_family(const Act yhat[2], Act xhat[2])
 {
     switch (variant) {
-    case 4: return g_s_stf1(yhat);
-    case 5: return g_s_ckbd(yhat);
-    default: return g_s1(yhat);
+    case 1: xhat[0] = g_s1(yhat[0]); break;
+    case 2: g_s_stf(yhat[0], yhat[1], &xhat[0], &xhat[1]); break;
+    case 3: g_s_r2d(yhat, xhat); break;
+    case 4: xhat[0] = g_s_stf1(yhat[0]); break;
+    case 5: xhat[0] = g_s_ckbd(yhat[0]); break;
+    default: g_s(yhat, xhat);
     }
 }
 
 // The latent stage: everything between z_hat and y_hat -- the family's buffers, its hyper synthesis, its debug tensors and its
-// coding loop (symbols when cd.encode, from the streams when not, likelihoods into cd.lik[0] when cd.estimate).
+// coding loop (symbols when cd.encode, from the streams when not, likelihoods into cd.lik[m] when cd.estimate).  y: the
+// latents (null when decoding); hyp: the hyper tensors when the caller has them already (the Latents path; zhat is null then).
 //   ELIC: y_hat = round(y - mean) + mean slice by slice through the two-part checkerboard loop (elic.py:180-251 / 268-316).
 //   STF: the y stream is ONE stream for all slices of all images of the call (per-image streams: one per image), coded after
 //     the last slice; the decoder resumes its rANS state slice by slice.  A batch decompresses as the inverse of compress()
 //     (the reference's decompress handles one image only, stf.py:799).
 //   Checkerboard: both halves of all images of the call go into ONE y stream, anchor half first (per-image streams: one per
 //     image, each with its own two halves); the decoder resumes its rANS state between the halves.
-void rgbd_elic::latent_single(Coding& cd, const Act* y, const Act& zhat, Act* yhat)
+//   The two-modality codecs: hyper synthesis and the Bi-CEE loop over both modalities (elic_united.py:265-348).
+void rgbd_elic::latent_family(Coding& cd, int B, int h, int w, const Act* y, const Act* zhat, const Act* hyp, Act yhat[2])
 {
-    const int B = zhat.n, h = 4 * zhat.h, w = 4 * zhat.w;
+    const Modes mo = modes();
     switch (variant) {
+    case 1: {
+        Act hyper = h_s1(zhat[0]);
+        named["hyper"] = hyper;
+        yhat[0] = alloc(B, h, w, M);
+        if (cd.estimate) cd.lik[0] = alloc(B, h, w, M);
+        bicee1(cd, y, hyper, yhat[0]);
+        break;
+    }
     case 4: {
         const int wide = M + (kStfSupport + 1) * kStfSliceCh;
         Act ctxm = alloc(B, h, w, wide), ctxs = alloc(B, h, w, wide);
-        *yhat = alloc(B, h, w, M);
+        yhat[0] = alloc(B, h, w, M);
         {
             const size_t mark = arena.top;
-            h_s_stf1(zhat, view(ctxm, 0, M), view(ctxs, 0, M));
+            h_s_stf1(zhat[0], view(ctxm, 0, M), view(ctxs, 0, M));
             arena.top = mark;
         }
         named["latent_means"] = view(ctxm, 0, M);
         named["latent_scales"] = view(ctxs, 0, M);
         if (cd.estimate) cd.lik[0] = alloc(B, h, w, M);
-        slice_loop(cd, y, ctxm, ctxs, *yhat);
+        slice_loop(cd, y, ctxm, ctxs, yhat[0]);
         break;
     }
     case 5: {
         Act cat = alloc(B, h, w, 4 * M), params = alloc(B, h, w, 2 * M);
-        *yhat = alloc(B, h, w, M);
+        yhat[0] = alloc(B, h, w, M);
         named["hyper"] = view(cat, 2 * M, 2 * M);
         named["ctx"] = view(cat, 0, 2 * M);
         named["scales"] = view(params, 0, M);
@@ -659,8 +406,8 @@ void rgbd_elic::latent_single(Coding& cd, const Act* y, const Act& zhat, Act* yh
                 const int r = launch_fill_zero(cat.p, cat.elems(), s);
                 if (r) fail(r);
             }
-            h_s_ckbd(zhat, view(cat, 2 * M, 2 * M));
-            two_pass_ckbd(cd, y, cat, params, *yhat);
+            h_s_ckbd(zhat[0], view(cat, 2 * M, 2 * M));
+            two_pass_ckbd(cd, y, cat, params, yhat[0]);
             break;
         }
         // eval-mode forward (Cheng2020withCKBD.py:52-71): y_hat = round(y) (quantize "dequantize" without means, :61), the
@@ -681,12 +428,12 @@ void rgbd_elic::latent_single(Coding& cd, const Act* y, const Act& zhat, Act* yh
             // round(y): the quantiser of the parts with zero means (its likelihoods go to `lik`, overwritten below)
             for (int anchor = 1; anchor >= 0 && !r; --anchor) {
                 g.anchor = anchor;
-                r = launch_ckbd_estimate_part(y->p, y->cs, params.p, params.cs, yhat->p, yhat->cs, lik.p, lik.cs, g, s);
+                r = launch_ckbd_estimate_part(y->p, y->cs, params.p, params.cs, yhat[0].p, yhat[0].cs, lik.p, lik.cs, g, s);
             }
             if (r) fail(r);
         }
-        h_s_ckbd(zhat, view(cat, 2 * M, 2 * M));
-        ck_context(*yhat, view(cat, 0, 2 * M));
+        h_s_ckbd(zhat[0], view(cat, 2 * M, 2 * M));
+        ck_context(yhat[0], view(cat, 0, 2 * M));
         ck_entropy_params(cat, 0, params);
         if (!dry() && !rc) {
             int r = 0;
@@ -699,143 +446,214 @@ void rgbd_elic::latent_single(Coding& cd, const Act* y, const Act& zhat, Act* yh
         break;
     }
     default: {
-        Act hyper = h_s1(zhat);
-        named["hyper"] = hyper;
-        *yhat = alloc(B, h, w, M);
-        if (cd.estimate) cd.lik[0] = alloc(B, h, w, M);
-        bicee1(cd, y, hyper, *yhat);
+        Act hy[2];
+        if (hyp) {
+            hy[0] = hyp[0];
+            hy[1] = hyp[1];
+        } else if (variant == 3) {
+            h_s_r2d(zhat[0], zhat[1], &hy[0], &hy[1]);
+        } else {
+            h_s(zhat[0], zhat[1], &hy[0], &hy[1]);
+        }
+        if (!cd.estimate) name(mo, "hyper", hy);  // (deliberate: forward() of these codecs never named hyper_r / hyper_d; Modes)
+        for (int m = 0; m < 2; ++m) yhat[m] = alloc(B, h, w, M);
+        if (variant == 2 && !dry()) {  // 24-wide slices: a 16-channel read chunk may straddle into a slice not coded yet
+            int zr = launch_fill_zero(yhat[0].p, yhat[0].elems(), s);
+            if (!zr) zr = launch_fill_zero(yhat[1].p, yhat[1].elems(), s);
+            if (zr) fail(zr);
+        }
+        if (cd.estimate)
+            for (int m = 0; m < 2; ++m) cd.lik[m] = alloc(B, h, w, M);
+        if (variant == 3) bicee_r2d(cd, y, y ? y + 1 : nullptr, hy[0], hy[1], yhat[0], yhat[1]);
+        else bicee(cd, y, y ? y + 1 : nullptr, hy[0], hy[1], yhat[0], yhat[1]);
     }
     }
-    named["yhat"] = *yhat;
+    name(mo, "yhat", yhat);
 }
 
-// compress: elic.py:161-253, stf.py:703-764, Cheng2020withCKBD.py:101-136
-int rgbd_elic::run_compress_single(const float* x_dev, int B, int H, int W, int per_image)
+// ---- the call paths, for nm = 1 or 2 modalities ---------------------------------------------------------------------------
+// y = g_a(x) into buffers the caller keeps; the transform's own workspace goes back
+void rgbd_elic::analysis(const Act x[2], const Act y[2])
 {
-    const int h = H / 16, w = W / 16, zh = H / 64, zw = W / 64;
-    const int64_t T = (int64_t)M * h * w, Tz = (int64_t)N * zh * zw;
-    begin_call(per_image ? 1 : B, false);
+    const size_t mark = arena.top;
+    Act yt[2];
+    g_a_family(x, yt);
+    for (int m = 0; m < modes().nm; ++m) copy_ch(yt[m], y[m]);
+    arena.top = mark;
+    ends_release();
+}
+
+// compress: elic_united.py:350-460, elic.py:161-253, stf.py:703-764, Cheng2020withCKBD.py:101-136
+int rgbd_elic::run_compress(int nm, In2 x_dev, int B, int H, int W, int per_image, const Latents* lat)
+{
+    const Modes mo = modes();
+    if (nm != mo.nm) return RGBD_ESTATE;
+    const int h = H / 16, w = W / 16, zh = lat ? 1 : H / 64, zw = lat ? 1 : W / 64;
+    const int64_t T = (int64_t)M * h * w;  // y symbols per image per modality
+    const int64_t Tz = (int64_t)N * zh * zw;
+    begin_call(per_image ? 1 : B, false);  // per-image streams stand for the reference called image by image
 
     // ==== prologue (never captured): workspace of the call, upload of the stream geometry, input layout conversion ====
     EncBufs e;
-    if (const int r = enc_streams(1, B, T, Tz, per_image, &e)) return r;
-    int32_t *fy = nullptr, *fz = nullptr;  // (only the checkerboard family accepts forced symbols)
-    if (const int r = upload_forced(1, force_y, (size_t)(B * T), &fy)) return r;
-    if (const int r = upload_forced(1, force_z, (size_t)(B * Tz), &fz)) return r;
-    Act x = alloc(B, H, W, in_ch);
-    if (!dry()) {
-        const int r = launch_nchw_to_nhwc16(x_dev, B, in_ch, H, W, x.p, x.cs, s);
+    if (const int r = enc_streams(nm, B, T, Tz, per_image, &e)) return r;
+    int32_t *fy = nullptr, *fz = nullptr;  // (of the single-modal families only the checkerboard one accepts forced symbols)
+    if (const int r = upload_forced(nm, force_y, (size_t)(B * T), &fy)) return r;
+    if (!lat)
+        if (const int r = upload_forced(nm, force_z, (size_t)(B * Tz), &fz)) return r;
+
+    Act y[2], hyp[2], x[2];
+    for (int m = 0; m < nm; ++m) y[m] = alloc(B, h, w, M);
+    if (lat) {
+        for (int m = 0; m < nm; ++m) hyp[m] = alloc(B, h, w, 2 * M);
+        int r = 0;
+        for (int m = 0; m < nm && !r && !dry(); ++m)
+            r = launch_nchw_to_nhwc16(lat->y[m], B, M, h, w, y[m].p, y[m].cs, s, perm());
+        for (int m = 0; m < nm && !r && !dry(); ++m)
+            r = launch_nchw_to_nhwc16(lat->hyp[m], B, 2 * M, h, w, hyp[m].p, hyp[m].cs, s, perm());
+        if (r) return r;
+    } else {
+        for (int m = 0; m < nm; ++m) x[m] = alloc(B, H, W, mo.img_ch[m]);
+        int r = 0;
+        for (int m = 0; m < nm && !r && !dry(); ++m)
+            r = launch_nchw_to_nhwc16(x_dev[m], B, mo.img_ch[m], H, W, x[m].p, x[m].cs, s);
         if (r) return r;
     }
-    // ==== body: captured into / replayed from a HIP graph per call shape ================================================
+
+    // ==== body: every kernel of the call, in stream order; captured into / replayed from a HIP graph per call shape ====
     if (body_begin()) {
         if (!dry()) {
-            const int zr = launch_fill_zero((float*)e.err, 64, s);  // (a kernel, not a memset node: DESIGN 3.5)
+            const int zr = launch_fill_zero((float*)e.err, 64, s);  // (a kernel, not a memset node: see launch_fill_zero)
             if (zr) fail(zr);
         }
-        Act y = alloc(B, h, w, M);
-        {
-            const size_t mark = arena.top;
-            copy_ch(g_a_single(x), y);
-            arena.top = mark;
+        name(mo, "y", y);
+        Act zhat[2], yhat[2];
+        if (!lat) {
+            analysis(x, y);
+            Act z[2];
+            h_a_family(y, z);
+            name(mo, "z", z);
+            for (int m = 0; m < nm; ++m) zhat[m] = alloc(B, zh, zw, N);
+            for (int m = 0; m < nm; ++m) z_encode(m, mo.eb[m], e, z[m], zhat[m], fz);
+            name(mo, "zhat", zhat);
         }
-        Act z = h_a_single(y);
-        named["y"] = y;
-        named["z"] = z;
-        Act zhat = alloc(B, zh, zw, N), yhat;
-        z_encode(0, "", e, z, zhat, fz);
-        named["zhat"] = zhat;
         Coding cd = enc_coding(e, per_image, T, fy);
-        latent_single(cd, &y, zhat, &yhat);
-        y_encode(1, B, e);
+        latent_family(cd, B, h, w, y, lat ? nullptr : zhat, lat ? hyp : nullptr, yhat);
+        y_encode(nm, B, e);
     }
     if (const int r = finish_body()) return r;
     if (dry()) return RGBD_OK;
 
     // ==== epilogue (never captured): fetch the streams ================================================================
-    return fetch_streams(1, B, true, e);
+    return fetch_streams(nm, B, !lat, e);
 }
 
-// eval-mode forward(): elic.py:60-161 (quant = "ste"), stf.py:618-678, Cheng2020withCKBD.py:52-71; Gaussian / factorised
-// likelihoods instead of symbols
-int rgbd_elic::run_forward_single(const float* x_dev, int B, int H, int W, float* xhat_dev, float* ly, float* lz)
+// eval-mode forward(): elic_united.py:234-263 with quant == "ste" (round in eval), elic.py:60-161, stf.py:618-678,
+// Cheng2020withCKBD.py:52-71; likelihoods as in entropy_models.py:391-428 (factorised prior) and :534-558 (Gaussian
+// conditional) instead of symbols
+int rgbd_elic::run_forward(int nm, In2 x_dev, int B, int H, int W, Out2 xhat_dev, Out2 ly, Out2 lz)
 {
+    const Modes mo = modes();
+    if (nm != mo.nm) return RGBD_ESTATE;
     const int h = H / 16, w = W / 16, zh = H / 64, zw = W / 64;
-    begin_call(B, true);
-    Act x = alloc(B, H, W, in_ch);
+    begin_call(B, true);  // forward() is one reference call on the whole batch
+    Act x[2];
+    for (int m = 0; m < nm; ++m) x[m] = alloc(B, H, W, mo.img_ch[m]);
     if (!dry()) {
-        const int r = launch_nchw_to_nhwc16(x_dev, B, in_ch, H, W, x.p, x.cs, s);
+        int r = 0;
+        for (int m = 0; m < nm && !r; ++m) r = launch_nchw_to_nhwc16(x_dev[m], B, mo.img_ch[m], H, W, x[m].p, x[m].cs, s);
         if (r) return r;
     }
-    Act xh, lik, zlik;
-    if (body_begin()) {  // (captured / replayed per call shape like every other body)
-        Act y = alloc(B, h, w, M);
-        {
-            const size_t mark = arena.top;
-            copy_ch(g_a_single(x), y);
-            arena.top = mark;
+    // ==== body: captured into / replayed from a HIP graph per call shape (the prologue above reads the caller's pointers,
+    // the epilogue below writes them) ====
+    Act out[3][2];  // x_hat, likelihoods of y, likelihoods of z: cur_ge->out[2 * k + m]
+    if (body_begin()) {
+        Act y[2], z[2], zhat[2], yhat[2];
+        for (int m = 0; m < nm; ++m) y[m] = alloc(B, h, w, M);
+        analysis(x, y);
+        h_a_family(y, z);
+        for (int m = 0; m < nm; ++m) zhat[m] = alloc(B, zh, zw, N);
+        for (int m = 0; m < nm; ++m) out[2][m] = alloc(B, zh, zw, N);
+        for (int m = 0; m < nm; ++m) z_estimate(mo.eb[m], z[m], zhat[m], out[2][m]);
+        name(mo, "y", y);
+        if (mo.forward_names_z) {
+            name(mo, "z", z);
+            name(mo, "zhat", zhat);
         }
-        Act z = h_a_single(y);
-        named["y"] = y;
-        named["z"] = z;
-        Act zhat = alloc(B, zh, zw, N), yhat;
-        zlik = alloc(B, zh, zw, N);
-        z_estimate("", z, zhat, zlik);
-        named["zhat"] = zhat;
         Coding cd;
         cd.estimate = true;
-        latent_single(cd, &y, zhat, &yhat);
-        xh = g_s_single(yhat);
-        lik = cd.lik[0];
-        if (cur_ge && !dry()) {
-            cur_ge->out[0] = xh;
-            cur_ge->out[1] = lik;
-            cur_ge->out[2] = zlik;
-        }
+        latent_family(cd, B, h, w, y, zhat, nullptr, yhat);
+        g_s_family(yhat, out[0]);
+        for (int m = 0; m < nm; ++m) out[1][m] = cd.lik[m];
+        if (cur_ge && !dry())
+            for (int k = 0; k < 3; ++k)
+                for (int m = 0; m < nm; ++m) cur_ge->out[2 * k + m] = out[k][m];
     } else {
-        xh = cur_ge->out[0];
-        lik = cur_ge->out[1];
-        zlik = cur_ge->out[2];
+        for (int k = 0; k < 3; ++k)
+            for (int m = 0; m < nm; ++m) out[k][m] = cur_ge->out[2 * k + m];
     }
     if (const int r = finish_body()) return r;
     if (dry()) return RGBD_OK;
-    int r = launch_nhwc_to_nchw_clamp(xh.p, B, in_ch, H, W, xh.cs, xhat_dev, 0, s);  // (stf.py:677: not clamped)
-    if (!r) r = launch_nhwc_to_nchw_clamp(lik.p, B, M, h, w, lik.cs, ly, 0, s, perm());
-    if (!r) r = launch_nhwc_to_nchw_clamp(zlik.p, B, N, zh, zw, zlik.cs, lz, 0, s, perm());
+    int r = 0;  // (not clamped: stf.py:677)
+    for (int m = 0; m < nm && !r; ++m)
+        r = launch_nhwc_to_nchw_clamp(out[0][m].p, B, mo.img_ch[m], H, W, out[0][m].cs, xhat_dev[m], 0, s);
+    for (int m = 0; m < nm && !r; ++m) r = launch_nhwc_to_nchw_clamp(out[1][m].p, B, M, h, w, out[1][m].cs, ly[m], 0, s, perm());
+    for (int m = 0; m < nm && !r; ++m) r = launch_nhwc_to_nchw_clamp(out[2][m].p, B, N, zh, zw, out[2][m].cs, lz[m], 0, s, perm());
     if (!r) r = wait_stream();
     return r;
 }
 
-// decompress: elic.py:255-325, stf.py:766-816, Cheng2020withCKBD.py:138-174
-int rgbd_elic::run_decompress_single(const uint8_t* const* ys, const int64_t* ylen, int n_y, const uint8_t* const* zs,
-                                     const int64_t* zlen, int B, int zh, int zw, float* x_out)
+// decompress: elic_united.py:462-578, elic.py:255-325, stf.py:766-816, Cheng2020withCKBD.py:138-174; h x w: the latent grid
+int rgbd_elic::run_decompress(int nm, const uint8_t* const* ys[2], const int64_t* ylen[2], int n_y, const uint8_t* const* zs[2],
+                              const int64_t* zlen[2], int B, int h, int w, Out2 xhat_dev, const Latents* lat)
 {
-    const int h = zh * 4, w = zw * 4, H = zh * 64, W = zw * 64;
+    const Modes mo = modes();
+    if (nm != mo.nm) return RGBD_ESTATE;
+    const int zh = lat ? 1 : h / 4, zw = lat ? 1 : w / 4, H = h * 16, W = w * 16;
     const int64_t T = (int64_t)M * h * w, Tz = (int64_t)N * zh * zw;
-    const int per_image = (n_y == B) ? 1 : 0;
-    begin_call(per_image ? 1 : B, false);
+    const int per_image = (n_y == B && !(B == 1)) ? 1 : (n_y == 1 ? (B == 1 ? 1 : 0) : -1);
+    if (per_image < 0) return RGBD_EINVAL;
+    begin_call(per_image == 0 ? B : 1, false);
 
     // ==== prologue (never captured): upload the streams ================================================================
+    const int ns_y = n_y, ns_z = lat ? 0 : B;
     DecBufs d;
-    if (const int r = dec_streams(1, &ys, &ylen, n_y, &zs, &zlen, B, B, T, Tz, per_image, &d)) return r;
+    if (const int r = dec_streams(nm, ys, ylen, ns_y, zs, zlen, ns_z, B, T, Tz, per_image, &d)) return r;
+
+    Act hyp[2];
+    if (lat) {
+        for (int m = 0; m < nm; ++m) hyp[m] = alloc(B, h, w, 2 * M);
+        int r = 0;
+        for (int m = 0; m < nm && !r && !dry(); ++m)
+            r = launch_nchw_to_nhwc16(lat->hyp[m], B, 2 * M, h, w, hyp[m].p, hyp[m].cs, s, perm());
+        if (r) return r;
+    }
 
     // ==== body: captured into / replayed from a HIP graph per call shape ================================================
-    Act xh;
+    Act out[2];  // what the epilogue hands back: x_hat (or y_hat for decompress_united) per modality: cur_ge->out[m]
     if (body_begin()) {
-        Act zhat = alloc(B, zh, zw, N), yhat;
-        z_decode(0, "", d, zhat);
-        named["zhat"] = zhat;
-        Coding cd = dec_coding(d, per_image, T, n_y);
-        latent_single(cd, nullptr, zhat, &yhat);
-        xh = g_s_single(yhat);
-        if (cur_ge && !dry()) cur_ge->out[0] = xh;
+        Act zhat[2], yhat[2];
+        if (!lat) {
+            for (int m = 0; m < nm; ++m) zhat[m] = alloc(B, zh, zw, N);
+            for (int m = 0; m < nm; ++m) z_decode(m, mo.eb[m], d, zhat[m]);
+            name(mo, "zhat", zhat);
+        }
+        Coding cd = dec_coding(d, per_image, T, ns_y);
+        latent_family(cd, B, h, w, nullptr, lat ? nullptr : zhat, lat ? hyp : nullptr, yhat);
+        if (lat)  // decompress_united ends here: y_hat back to the caller
+            for (int m = 0; m < nm; ++m) out[m] = yhat[m];
+        else g_s_family(yhat, out);
+        if (cur_ge && !dry())
+            for (int m = 0; m < nm; ++m) cur_ge->out[m] = out[m];
     } else {
-        xh = cur_ge->out[0];
+        for (int m = 0; m < nm; ++m) out[m] = cur_ge->out[m];
     }
     if (const int r = finish_body()) return r;
     if (dry()) return RGBD_OK;
 
-    // ==== epilogue (never captured): x_hat into the caller's NCHW tensor; not clamped in elic.py:318-325 and
-    // Cheng2020withCKBD.py:167-174, clamped to [0, 1] in stf.py:815
-    return launch_nhwc_to_nchw_clamp(xh.p, B, in_ch, H, W, xh.cs, x_out, variant == 4 ? 1 : 0, s);
+    // ==== epilogue (never captured): results into the caller's NCHW tensors ==========================================
+    int r = 0;
+    for (int m = 0; m < nm && !r; ++m)
+        r = lat ? launch_nhwc_to_nchw_clamp(out[m].p, B, M, h, w, out[m].cs, lat->yhat[m], 0, s, perm())
+                : launch_nhwc_to_nchw_clamp(out[m].p, B, mo.img_ch[m], H, W, out[m].cs, xhat_dev[m], mo.clamp, s);
+    return r;
 }

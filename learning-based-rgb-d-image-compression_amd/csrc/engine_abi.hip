@@ -866,8 +866,7 @@ int rgbd_elic_create_stf_single(int32_t in_ch, rgbd_elic** out)
     if (r) return r;
     (*out)->variant = 4;
     (*out)->in_ch = in_ch;
-    (*out)->refnum = false;  // (the STF family keeps the single-chain arithmetic, as STF_united; nothing sets it later, so
-                             // perm() is 0 in the shared single-modal call paths)
+    (*out)->refnum = false;  // (single-chain arithmetic, as STF_united; nothing sets it later: perm() is 0 in the call paths)
     return RGBD_OK;
 }
 
@@ -894,7 +893,7 @@ int rgbd_elic_compress_single(rgbd_elic* m, const float* x_dev, int32_t B, int32
     const int per_image = (per_image_streams || B == 1) ? 1 : 0;
     char key[96];
     snprintf(key, sizeof(key), "c1|%d|%d|%d|%d", B, H, W, per_image);
-    r = run_sized(m, key, [&]() { return m->run_compress_single(x_dev, B, H, W, per_image); });
+    r = run_sized(m, key, [&]() { return m->run_compress(1, {x_dev}, B, H, W, per_image); });
     if (m->profile) m->profile_collect();
     return r;
 }
@@ -909,7 +908,7 @@ int rgbd_elic_forward_single(rgbd_elic* m, const float* x_dev, int32_t B, int32_
     if (const int ur = m->use_stream(stream)) return ur;
     char key[96];
     snprintf(key, sizeof(key), "f1|%d|%d|%d", B, H, W);
-    return run_sized(m, key, [&]() { return m->run_forward_single(x_dev, B, H, W, xhat_dev, lik_y, lik_z); });
+    return run_sized(m, key, [&]() { return m->run_forward(1, {x_dev}, B, H, W, {xhat_dev}, {lik_y}, {lik_z}); });
 }
 
 int rgbd_elic_decompress_single(rgbd_elic* m, const uint8_t* const* y, const int64_t* y_len, int32_t n_y,
@@ -923,7 +922,7 @@ int rgbd_elic_decompress_single(rgbd_elic* m, const uint8_t* const* y, const int
     if (const int ur = m->use_stream(stream)) return ur;
     char key[96];
     snprintf(key, sizeof(key), "d1|%d|%d|%d|%d", B, zh, zw, n_y);
-    r = run_sized(m, key, [&]() { return m->run_decompress_single(y, y_len, n_y, z, z_len, B, zh, zw, x_dev); });
+    r = run_sized(m, key, [&]() { return m->run_decompress(1, &y, &y_len, n_y, &z, &z_len, B, zh * 4, zw * 4, {x_dev}); });
     if (!r) r = m->wait_stream();  // (the work may sit on the engine's own stream: return when x_hat is there)
     if (m->profile && !r) m->profile_collect();
     return r;
@@ -1253,7 +1252,7 @@ int rgbd_elic_compress(rgbd_elic* m, const float* rgb_dev, const float* depth_de
     const int per_image = (per_image_streams || B == 1) ? 1 : 0;
     char key[96];
     snprintf(key, sizeof(key), "c|%d|%d|%d|%d", B, H, W, per_image);
-    r = run_sized(m, key, [&]() { return m->run_compress(rgb_dev, depth_dev, B, H, W, per_image); });
+    r = run_sized(m, key, [&]() { return m->run_compress(2, {rgb_dev, depth_dev}, B, H, W, per_image); });
     if (m->profile) m->profile_collect();  // run_compress ends with a stream synchronise
     return r;
 }
@@ -1271,7 +1270,8 @@ int rgbd_elic_forward(rgbd_elic* m, const float* rgb_dev, const float* depth_dev
     char key[96];
     snprintf(key, sizeof(key), "f|%d|%d|%d", B, H, W);
     return run_sized(m, key, [&]() {
-        return m->run_forward(rgb_dev, depth_dev, B, H, W, xr_dev, xd_dev, lik_y_rgb, lik_y_depth, lik_z_rgb, lik_z_depth);
+        return m->run_forward(2, {rgb_dev, depth_dev}, B, H, W, {xr_dev, xd_dev}, {lik_y_rgb, lik_y_depth},
+                              {lik_z_rgb, lik_z_depth});
     });
 }
 
@@ -1308,7 +1308,7 @@ int rgbd_elic_decompress(rgbd_elic* m, const uint8_t* const* y_rgb, const int64_
     const int64_t* zl[2] = {z_rgb_len, z_depth_len};
     char key[96];
     snprintf(key, sizeof(key), "d|%d|%d|%d|%d", B, zh, zw, n_y);
-    r = run_sized(m, key, [&]() { return m->run_decompress(ys, yl, n_y, zs, zl, B, zh, zw, xr_dev, xd_dev); });
+    r = run_sized(m, key, [&]() { return m->run_decompress(2, ys, yl, n_y, zs, zl, B, zh * 4, zw * 4, {xr_dev, xd_dev}); });
     // the caller's wait for x_hat happens here, on an event the host thread sleeps on (a pooled rank has 16 of them)
     if (!r) r = m->wait_stream();
     if (m->profile && !r) m->profile_collect();
@@ -1328,7 +1328,7 @@ int rgbd_elic_compress_united(rgbd_elic* m, const float* y_rgb_dev, const float*
     rgbd_elic::Latents lat = {{y_rgb_dev, y_depth_dev}, {hyper_rgb_dev, hyper_depth_dev}, {nullptr, nullptr}};
     char key[96];
     snprintf(key, sizeof(key), "cu|%d|%d|%d|%d", B, h, w, per_image);
-    r = run_sized(m, key, [&]() { return m->run_compress(nullptr, nullptr, B, h * 16, w * 16, per_image, &lat); });
+    r = run_sized(m, key, [&]() { return m->run_compress(2, {}, B, h * 16, w * 16, per_image, &lat); });
     if (m->profile) m->profile_collect();
     return r;
 }
@@ -1352,7 +1352,7 @@ int rgbd_elic_decompress_united(rgbd_elic* m, const uint8_t* const* y_rgb, const
     rgbd_elic::Latents lat = {{nullptr, nullptr}, {hyper_rgb_dev, hyper_depth_dev}, {yhat_rgb_dev, yhat_depth_dev}};
     char key[96];
     snprintf(key, sizeof(key), "du|%d|%d|%d|%d", B, h, w, n_y);
-    r = run_sized(m, key, [&]() { return m->run_decompress_impl(ys, yl, n_y, zs, zl, B, h, w, nullptr, nullptr, &lat); });
+    r = run_sized(m, key, [&]() { return m->run_decompress(2, ys, yl, n_y, zs, zl, B, h, w, {}, &lat); });
     if (!r) r = m->wait_stream();
     if (m->profile && !r) m->profile_collect();
     return r;

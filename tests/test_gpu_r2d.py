@@ -114,3 +114,37 @@ def test_r2d_forward_and_stage_entry_points(net_r2d, sd_r2d):
     lat2 = [torch.from_numpy(a).cuda() for a in synth.synthetic_latents(1, 8, 12, 320, 77)]
     sr2, _ = net_r2d.compress_united(lat[0], lat[1], lat2[2], lat2[3])
     assert sr2[0] == sr[0]
+
+
+def test_r2d_eager_capture_replay_agree(net_r2d):
+    """compress() -> decompress() -> forward() of one shape four times on a torch side stream: eager, captured, replayed, and
+    replayed on another input.  What a replayed graph hands back -- streams, x_hat, the forward outputs -- is what the eager
+    call gave, bit for bit.  B = 2 at 128 x 128, the smallest size the codec takes: the ESA block of the third fusion stage
+    pools 7 x 7 windows of the stride-2 map of its H/8 x W/8 grid (8 -> 3 at 64 pixels), so a 64-pixel side is refused with
+    RGBD_EINVAL."""
+    from rgbd_amd import synth
+
+    def one_round(r, d):
+        out = net_r2d.compress(r, d)
+        rec = net_r2d.decompress(out["r_strings"], out["d_strings"], out["shape"])
+        fw = net_r2d(r, d)
+        tensors = [rec["x_hat"]["r"], rec["x_hat"]["d"], fw["x_hat"]["r"], fw["x_hat"]["d"]]
+        tensors += [fw[f"{mod}_likelihoods"][k] for mod in ("r", "d") for k in ("y", "z")]
+        return (out["r_strings"], out["d_strings"]), [t.clone() for t in tensors]
+
+    def same(p, q):
+        return p[0] == q[0] and all(torch.equal(s, t) for s, t in zip(p[1], q[1]))
+
+    g0 = net_r2d.graph_count()
+    with torch.cuda.stream(torch.cuda.Stream()):  # (the NULL stream cannot be captured)
+        a = [torch.from_numpy(t).cuda() for t in synth.synthetic_batch(2, 128, 128, config_id=51)]
+        b = [torch.from_numpy(t).cuda() for t in synth.synthetic_batch(2, 128, 128, config_id=52)]
+        eager_a = one_round(*a)
+        cap_a = one_round(*a)
+        rep_a = one_round(*a)
+        assert net_r2d.graph_count() >= g0 + 3  # compress, decompress and forward of this shape are cached graphs now
+        rep_b = one_round(*b)
+    torch.cuda.synchronize()
+    assert same(cap_a, eager_a) and same(rep_a, eager_a)
+    assert rep_b[0] != eager_a[0]  # a replayed graph reads the NEW inputs ...
+    assert same(rep_b, one_round(*b))  # ... and gives what the eager call (the NULL stream never captures) gives for them
