@@ -987,6 +987,34 @@ struct rgbd_elic {
                memcmp(a.blk_end, b.blk_end, sizeof(a.blk_end)) == 0 && memcmp(a.split_c16, b.split_c16, sizeof(a.split_c16)) == 0;
     }
 
+    // The profiler's event pair around one launch.  prof_begin() records the first event of the pool's next pair and hands
+    // back the second (the pool grows by 256 events at a time; false: an event could not be created, the call has failed);
+    // prof_end() records that one behind the launch and books the launch: name, algorithmic and executed FLOPs.
+    bool prof_begin(hipEvent_t* e1)
+    {
+        if (ev_used + 2 > ev_pool.size()) {
+            for (int i = 0; i < 256; ++i) {
+                hipEvent_t e;
+                if (hipEventCreate(&e) != hipSuccess) {
+                    fail(RGBD_EHIP);
+                    return false;
+                }
+                ev_pool.push_back(e);
+            }
+        }
+        (void)hipEventRecord(ev_pool[ev_used++], s);
+        *e1 = ev_pool[ev_used++];
+        return true;
+    }
+    void prof_end(hipEvent_t e1, const std::string& name, double fl, double fx)
+    {
+        (void)hipEventRecord(e1, s);
+        prof_flops += fl;
+        prof_flops_exec += fx;
+        ++prof_launches;
+        ev_names.push_back({name, fl, fx});
+    }
+
     // launch one plan, or two plans as one grouped launch (q != nullptr: the caller has checked pairable())
     void conv_issue(ConvPlan& p, ConvPlan* q = nullptr)
     {
@@ -1004,38 +1032,16 @@ struct rgbd_elic {
             conv_args_group1(&a, q->a);
             if (q->partial_bytes) a.g1.partial = (float*)arena.take(q->partial_bytes);
         }
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        if (profile) {
-            if (ev_used + 2 > ev_pool.size()) {
-                for (int i = 0; i < 256; ++i) {
-                    hipEvent_t e;
-                    if (hipEventCreate(&e) != hipSuccess) {
-                        fail(RGBD_EHIP);
-                        return;
-                    }
-                    ev_pool.push_back(e);
-                }
-            }
-            e0 = ev_pool[ev_used++];
-            e1 = ev_pool[ev_used++];
-            (void)hipEventRecord(e0, s);
-        }
+        hipEvent_t e1 = nullptr;
+        if (profile && !prof_begin(&e1)) return;
         const int r = p.fused ? launch_conv_fused(a, s) : launch_conv(a, s);
         if (profile) {
-            (void)hipEventRecord(e1, s);
-            const double fl = p.flops + (q ? q->flops : 0.0), fx = p.flops_exec + (q ? q->flops_exec : 0.0);
-            prof_flops += fl;
-            prof_flops_exec += fx;
-            ++prof_launches;
-            if (profile_keys) {
-                char key[200];
+            char key[200] = "";
+            if (profile_keys)
                 snprintf(key, sizeof(key), "|%d,%d,%d,%d,%d,%d,%d,%d,%d|%d", a.N * (a.groups == 2 ? 2 : 1), a.H, a.W, a.cin_pad, a.cout_pad,
                          a.ntaps_total, a.nphase > 1 ? a.OS : a.IS, a.nphase + 10 * a.ckbd + (a.blocked ? 100 : 0),
                          std::max(1, std::min(a.splitk, a.cin_pad / 16)), p.fused ? 1 : 0);
-                ev_names.push_back({p.name + key, fl, fx});
-            } else {
-                ev_names.push_back({p.name, fl, fx});
-            }
+            prof_end(e1, p.name + key, p.flops + (q ? q->flops : 0.0), p.flops_exec + (q ? q->flops_exec : 0.0));
         }
         arena.top = pmark;  // stream order protects the scratch: later kernels of this stream run after the reducer
         if (r) {
@@ -1183,6 +1189,23 @@ struct rgbd_elic {
         return cp.y;
     }
 
+    // Keep the taps of a (one-phase) tap table whose dy + dx has parity `odd`, in their order; the rest of the table is
+    // zeroed.  Returns the number kept.
+    static int keep_taps(TapTable& t, int odd)
+    {
+        int n = 0;
+        for (int k = 0; k < t.n[0]; ++k) {
+            if (((t.dy[0][k] + t.dx[0][k]) & 1) != odd) continue;
+            t.dy[0][n] = t.dy[0][k];
+            t.dx[0][n] = t.dx[0][k];
+            t.wt[0][n] = t.wt[0][k];
+            ++n;
+        }
+        for (int k = n; k < 25; ++k) t.dy[0][k] = t.dx[0][k] = t.wt[0][k] = 0;
+        t.n[0] = (int8_t)n;
+        return n;
+    }
+
     // A stride-1 k x k conv whose INPUT is non-zero at the anchor positions only ((row + col) odd: the slice right after its
     // anchor pass, utils/ckbd.py:37-48 -- what the local-context convs read, elic_united.py:296,309).  An output pixel of
     // parity q then only meets non-zero inputs under the taps with (dy + dx) & 1 == 1 - q: the anchor outputs need the 13
@@ -1201,18 +1224,7 @@ struct rgbd_elic {
         for (int par = 1; par <= 2; ++par) {
             ConvPlan h = cp;
             if (!dry()) {
-                TapTable& t = h.a.taps;
-                int n = 0;
-                for (int k = 0; k < cp.a.taps.n[0]; ++k) {
-                    const int odd = (cp.a.taps.dy[0][k] + cp.a.taps.dx[0][k]) & 1;
-                    if (odd != (par == 1 ? 0 : 1)) continue;  // anchor outputs (parity 1): dy + dx even
-                    t.dy[0][n] = cp.a.taps.dy[0][k];
-                    t.dx[0][n] = cp.a.taps.dx[0][k];
-                    t.wt[0][n] = cp.a.taps.wt[0][k];
-                    ++n;
-                }
-                for (int k = n; k < 25; ++k) t.dy[0][k] = t.dx[0][k] = t.wt[0][k] = 0;
-                t.n[0] = (int8_t)n;
+                const int n = keep_taps(h.a.taps, par == 1 ? 0 : 1);  // anchor outputs (parity 1): dy + dx even
                 h.a.ckbd = par;
                 h.flops = cp.flops * 0.5;
                 h.flops_exec = cp.flops * 0.5 * n / std::max(1, (int)cp.a.taps.n[0]);  // half the outputs, n of the taps
@@ -1809,28 +1821,75 @@ struct rgbd_elic {
         *hd = cur[1];
     }
 
-    // entropy.py:69-78.  `ctx` is a channel-slice view of the slice's context buffer
-    // [r_loc | d_loc | hyper_r | hyper_d | ch_ctx_r | ch_ctx_d]: every EntropyParametersEX input of the reference
-    // (elic_united.py:288-333) is a suffix of that layout, so no concatenation copy is needed; SE-rescaling writes the
-    // rescaled copy the 1x1 conv reads (params + se(params), keeping the reference's association).
-    // `part` (1 anchor / 2 non-anchor): the caller only reads that checkerboard half of (scales, means)
-    // (ckbd.py:83-125), so the last -- and largest -- conv computes just that half; the values are those of the full conv.
-    Act entropy_params(const std::string& p, const Act& ctx, int part, const Act* dst = nullptr, const float* means = nullptr,
-                       int mstride = 0)
+    // ---- the checkerboard slice loop (Bi-CEE, elic_united.py:265-348 / 454-541; elic_united_R2D.py:149-326; elic.py:180-251 /
+    // 268-316) --------------------------------------------------------------------------------------------------------
+    // y is coded slice by slice (slice_ch), every slice in two checkerboard parts per modality: anchor part of RGB, of depth,
+    // non-anchor part of RGB, of depth.  The (scales, means) of a part come from a parameter net over everything known by then,
+    // kept side by side in a context buffer per slice so that a net's input is a channel view of it, not a concatenation:
+    // the hyper tensors (2M channels each), the channel contexts (a net over the slices coded so far, 2C channels, from the
+    // second slice on) and the local contexts (a 5x5 conv over the slice's y_hat as decoded so far, 2C channels).  A net
+    // reads its buffer from one segment to the end; the one input that is not such a suffix (the depth anchor net's: RGB's
+    // local context, then hyper tensors and channel contexts, with depth's local-context slot in between) is gathered.
+    // slice_loop_ckbd() is that loop for every family; what a family decides about it is in its SliceLoop descriptor.
+    enum Seg : int8_t { kLocR, kLocD, kHypR, kHypD, kChR, kChD, kSegEnd = -1 };  // local ctx / hyper / channel ctx of RGB, depth
+    struct CtxNet {
+        int8_t buf;     // the context buffer the net reads ...
+        Seg first;      // ... from this segment to the buffer's end
+        bool gathered;  // buffer 0's kLocR slot in front of that suffix, copied together (they are not adjacent)
+    };
+    struct SliceLoop {
+        Seg layout[2][7];       // segment order of each context buffer, kSegEnd-terminated (an unused buffer starts with it);
+                                // the single-modal family's segments are the RGB ones
+        CtxNet net[2][2];       // [anchor, non-anchor][modality]: input of each parameter net of a slice
+        int8_t loc_buf[3];      // the buffer whose slot takes <m>local_context of RGB (kLocR), of depth (kLocD), and
+                                // rgb_local_context_anchor_with_nonanchor (kLocR again)
+        const char* prefix[2];  // layer-name prefix per modality
+        // parameter-net form: SE rescale in front of the three layers (entropy.py:69-78) or not (entropy.py:7-29), and the
+        // checkerboard half (Epi::ckbd) on all three layers (1x1: no layer mixes positions) or on the last one only
+        bool se, ckbd_all;
+        // Speed levers, on for ELIC_united / STF_united only (open for the other families).  mean_cache: the SE
+        // gates' channel means are kept per segment (needs one buffer with the modalities' hyper segments, and their
+        // channel contexts, side by side: one launch covers both); anchor_taps: conv_anchor_in() for the local contexts of the
+        // anchor half; grouped_ch: the modalities' channel-context nets as grouped launches
+        bool mean_cache, anchor_taps, grouped_ch;
+    };
+    static constexpr SliceLoop kLoopUnited = {{{kLocR, kLocD, kHypR, kHypD, kChR, kChD, kSegEnd}, {kSegEnd}},
+                                              {{{0, kHypR, false}, {0, kHypR, true}}, {{0, kLocR, false}, {0, kLocR, false}}},
+                                              {0, 0, 0}, {"rgb_", "depth_"}, true, false, true, true, true};
+    // RGB's nets see no depth: their own buffer; depth's as in ELIC_united, its kLocR slot written by the second RGB conv only
+    static constexpr SliceLoop kLoopR2D = {{{kLocR, kHypR, kChR, kSegEnd}, {kLocR, kLocD, kHypR, kHypD, kChR, kChD, kSegEnd}},
+                                           {{{0, kHypR, false}, {1, kHypR, true}}, {{0, kLocR, false}, {1, kLocR, false}}},
+                                           {0, 1, 1}, {"rgb_", "depth_"}, true, false, false, false, false};
+    static constexpr SliceLoop kLoopSingle = {{{kLocR, kChR, kHypR, kSegEnd}, {kSegEnd}},
+                                              {{{0, kChR, false}, {}}, {{0, kLocR, false}, {}}},
+                                              {0, 0, 0}, {"", ""}, false, true, false, false, false};
+    const SliceLoop& slice_loop_family() const { return variant == 1 ? kLoopSingle : variant == 3 ? kLoopR2D : kLoopUnited; }
+
+    // The parameter net of one part: [SE rescale,] three convs (1x1 / 3x3 / 5x5 or 1x1 x 3; padding k / 2) with ReLU between.
+    // SE writes the rescaled copy the first conv reads (params + se(params), keeping the reference's association); `means`:
+    // the input's channel means where the caller has them already.  `part` (1 anchor / 2 non-anchor): the caller only reads
+    // that checkerboard half of (scales, means) (ckbd.py:83-125), so the last -- and largest -- conv computes just that half,
+    // and so do the layers in front of it where none mixes positions; the values are those of the full convs.
+    Act entropy_params(const SliceLoop& d, const std::string& p, const Act& ctx, int part, const Act* dst = nullptr,
+                       const float* means = nullptr, int mstride = 0)
     {
         const PackedConv* last = conv_of(p + ".fusion.4.weight");
         if (!last) return Act();
         Act out = dst ? *dst : alloc(ctx.n, ctx.h, ctx.w, last->cout);
         const size_t mark = arena.top;
-        Act cat = alloc(ctx.n, ctx.h, ctx.w, ctx.c);
-        se_scale_to(p + ".se", ctx, 1, cat, means, mstride);
-        Epi relu;
-        relu.act = ACT_RELU;
-        Act t = conv(p + ".fusion.0", cat, 1, 0, relu);
-        t = conv(p + ".fusion.2", t, 1, 1, relu);
-        Epi last_e;
-        last_e.ckbd = g_ckbd_conv ? part : 0;
-        conv(p + ".fusion.4", t, 1, 2, last_e, &out);
+        Act t = ctx;
+        if (d.se) {
+            t = alloc(ctx.n, ctx.h, ctx.w, ctx.c);
+            se_scale_to(p + ".se", ctx, 1, t, means, mstride);
+        }
+        for (int l = 0; l < 3; ++l) {
+            const std::string n = p + ".fusion." + std::to_string(2 * l);
+            const PackedConv* pc = conv_of(n + ".weight");
+            Epi e;
+            if (l < 2) e.act = ACT_RELU;
+            if (g_ckbd_conv && (l == 2 || d.ckbd_all)) e.ckbd = part;
+            t = conv(n, t, 1, pc ? pc->k / 2 : 0, e, l == 2 ? &out : nullptr);
+        }
         arena.top = mark;
         return out;
     }
@@ -1856,7 +1915,7 @@ struct rgbd_elic {
         arena.top = mark;
     }
 
-    // ---- Bi-CEE loop (elic_united.py:265-348 / 454-541) -----------------------------------------
+    // what the coding loops (slice_loop_ckbd, slice_loop, two_pass_ckbd) hand to code_part()
     struct Coding {
         bool encode = true;
         bool estimate = false;      // eval-mode forward(): quantise + likelihood, no symbols
@@ -1920,93 +1979,117 @@ struct rgbd_elic {
 
     float* yhat_base[2] = {nullptr, nullptr};
 
-    void bicee(Coding& cd, const Act* y_r, const Act* y_d, const Act& hyp_r, const Act& hyp_d, const Act& yhat_r,
-               const Act& yhat_d)
+    // y, hyp, yhat: read at [0, nm); y is null when decoding
+    void slice_loop_ckbd(Coding& cd, const SliceLoop& d, int nm, const Act* y, const Act hyp[2], const Act yhat[2])
     {
-        yhat_base[0] = yhat_r.p;
-        yhat_base[1] = yhat_d.p;
+        for (int m = 0; m < nm; ++m) yhat_base[m] = yhat[m].p;
         int c0 = 0;
         int64_t part_off = 0;
-        const int B = hyp_r.n, h = hyp_r.h, w = hyp_r.w;
+        const int B = hyp[0].n, h = hyp[0].h, w = hyp[0].w, HC = hyp[0].c;  // HC = 2M
         // SE gates of the entropy-parameter nets (entropy.py:75) need the channel means of their whole input -- 1280 ... 2816
         // channels, of which 2 x 2M are the hyper parameters, the same tensor for all 20 nets of a call.  A mean is a function
         // of its own channel only (channel_mean_kernel: one fixed chain per channel), so the means are kept per segment of
         // the context buffer and only what changed is recomputed: the hyper parameters' once per call, the channel contexts'
         // once per slice, the local contexts' (2C channels) per part -- the same floats as a pass over the whole input, for
-        // 1/10 of the traffic (round 4; 1.6 GB per c3 step).  hm: [B][2 HC] hyper means; sm: [B][wide] in ctx layout.
-        static const bool mean_cache = getenv("RGBD_NO_MEAN_CACHE") == nullptr;  // A/B switch
-        const int HC2 = 2 * hyp_r.c;
-        float* hm = (float*)arena.take((size_t)B * HC2 * sizeof(float));
+        // 1/10 of the traffic (round 4; 1.6 GB per c3 step).  hm: [B][nm HC] hyper means; sm[b]: [B][wide] in buffer b's layout.
+        static const bool mean_cache_on = getenv("RGBD_NO_MEAN_CACHE") == nullptr;  // A/B switch (the workspace stays as it is)
+        const bool mc = d.mean_cache && mean_cache_on;
+        float* hm = d.mean_cache ? (float*)arena.take((size_t)B * nm * HC * sizeof(float)) : nullptr;
         auto means_of = [&](const Act& t, float* dstm, int stride) {
-            if (dry() || rc || !mean_cache) return;
+            if (dry() || rc || !mc) return;
             const int r = refnum ? launch_channel_mean_ref(t.p, t.n, t.h * t.w, t.cs, t.c, dstm, stride, s)
                                  : launch_channel_mean_strided(t.p, t.n, t.h * t.w, t.cs, t.c, dstm, stride, s);
             if (r) fail(r);
         };
-        means_of(hyp_r, hm, HC2);
-        means_of(hyp_d, hm + hyp_r.c, HC2);
+        auto copy_means = [&](const float* src, int sstride, float* dstm, int dstride, int n) {
+            if (dry() || rc || !mc) return;
+            const int r = launch_copy_channels(src, sstride, dstm, dstride, B, n, s);
+            if (r) fail(r);
+        };
+        for (int m = 0; m < nm && d.mean_cache; ++m) means_of(hyp[m], hm + m * HC, nm * HC);
         for (size_t i = 0; i < slice_ch.size(); ++i) {
             const int C = slice_ch[i];
             const size_t mark = arena.top;
             const std::string si = std::to_string(i);
-            // context buffer of this slice: [r_loc 2C | d_loc 2C | hyper_r 2M | hyper_d 2M | ch_r 2C | ch_d 2C]
-            const int HC = hyp_r.c;  // 2M
-            const int wide = 4 * C + 2 * HC + (i ? 4 * C : 0);
-            Act ctx = alloc(hyp_r.n, h, w, wide);
-            float* sm = (float*)arena.take((size_t)B * wide * sizeof(float));
-            copy_ch(hyp_r, view(ctx, 4 * C, HC));
-            copy_ch(hyp_d, view(ctx, 4 * C + HC, HC));
-            if (!dry() && !rc && mean_cache) {
-                const int r = launch_copy_channels(hm, HC2, sm + 4 * C, wide, B, HC2, s);
-                if (r) fail(r);
-            }
-            if (i) {
-                const Act cr = view(ctx, 4 * C + 2 * HC, 2 * C), cdv = view(ctx, 6 * C + 2 * HC, 2 * C);
-                const std::string cn[2] = {"rgb_channel_context." + si, "depth_channel_context." + si};
-                const Act cx[2] = {view(yhat_r, 0, c0), view(yhat_d, 0, c0)};
-                const Act cdst[2] = {cr, cdv};
-                channel_context2(2, cn, cx, cdst);
-                means_of(view(ctx, 4 * C + 2 * HC, 4 * C), sm + 4 * C + 2 * HC, wide);  // both channel contexts: adjacent
-            }
-            const float* smc = mean_cache ? sm : nullptr;
-            const Act yr = y_r ? view(*y_r, c0, C) : Act();
-            const Act yd = y_d ? view(*y_d, c0, C) : Act();
-            const Act hr = view(yhat_r, c0, C), hd = view(yhat_d, c0, C);
-            const int64_t part_syms = (int64_t)C * h * (w / 2);
-            const Act r_loc = view(ctx, 0, 2 * C), d_loc = view(ctx, 2 * C, 2 * C);
-            // rgb anchor: [hyper, ch ctx]
-            Act p_ra = entropy_params("rgb_entropy_parameters_anchor." + si, view(ctx, 4 * C, wide - 4 * C), 1, nullptr,
-                                      smc ? smc + 4 * C : nullptr, wide);
-            code_part(cd, 0, 1, p_ra, yr, hr, part_off);
-            conv_anchor_in("rgb_local_context." + si, hr, 2, r_loc);  // (hr holds the anchor half only so far)
-            means_of(r_loc, sm, wide);
-            // depth anchor: [r_loc, hyper, ch ctx] -- d_loc's slot sits between them, so this one input is gathered
-            Act p_da = alloc(hyp_r.n, h, w, 2 * C);
-            {
-                const size_t m2 = arena.top;
-                Act in = alloc(hyp_r.n, h, w, wide - 2 * C);
-                copy_ch(r_loc, view(in, 0, 2 * C));
-                copy_ch(view(ctx, 4 * C, wide - 4 * C), view(in, 2 * C, wide - 4 * C));
-                float* im = (float*)arena.take((size_t)B * (wide - 2 * C) * sizeof(float));  // the gathered input's means, gathered alike
-                if (!dry() && !rc && mean_cache) {
-                    int r = launch_copy_channels(sm, wide, im, wide - 2 * C, B, 2 * C, s);
-                    if (!r) r = launch_copy_channels(sm + 4 * C, wide, im + 2 * C, wide - 2 * C, B, wide - 4 * C, s);
-                    if (r) fail(r);
+            const int width[3] = {2 * C, HC, i ? 2 * C : 0};  // of a local-context, a hyper, a channel-context segment
+            Act buf[2];
+            float* sm[2] = {nullptr, nullptr};
+            int nbuf = 0, wide[2] = {0, 0}, off[2][6];
+            for (; nbuf < 2 && d.layout[nbuf][0] != kSegEnd; ++nbuf) {
+                for (int& o : off[nbuf]) o = -1;  // (segment not in this buffer)
+                for (const Seg* sg = d.layout[nbuf]; *sg != kSegEnd; ++sg) {
+                    off[nbuf][*sg] = wide[nbuf];
+                    wide[nbuf] += width[*sg / 2];
                 }
-                entropy_params("depth_entropy_parameters_anchor." + si, in, 1, &p_da, mean_cache ? im : nullptr, wide - 2 * C);
-                arena.top = m2;
+                buf[nbuf] = alloc(B, h, w, wide[nbuf]);
+                if (d.mean_cache) sm[nbuf] = (float*)arena.take((size_t)B * wide[nbuf] * sizeof(float));
             }
-            code_part(cd, 1, 1, p_da, yd, hd, part_off);
-            conv_anchor_in("depth_local_context." + si, hd, 2, d_loc);
-            means_of(d_loc, sm + 2 * C, wide);
-            // rgb non-anchor: the whole buffer
-            Act p_rn = entropy_params("rgb_entropy_parameters_nonanchor." + si, ctx, 2, nullptr, smc, wide);
-            code_part(cd, 0, 0, p_rn, yr, hr, part_off + part_syms);
-            conv("rgb_local_context_anchor_with_nonanchor." + si, hr, 1, 2, Epi(), &r_loc);  // replaces r_loc
-            means_of(r_loc, sm, wide);
-            // depth non-anchor
-            Act p_dn = entropy_params("depth_entropy_parameters_nonanchor." + si, ctx, 2, nullptr, smc, wide);
-            code_part(cd, 1, 0, p_dn, yd, hd, part_off + part_syms);
+            auto seg = [&](int b, int sg) { return view(buf[b], off[b][sg], width[sg / 2]); };
+            for (int b = 0; b < nbuf; ++b) {
+                for (int m = 0; m < nm; ++m)
+                    if (off[b][kHypR + m] >= 0) copy_ch(hyp[m], seg(b, kHypR + m));
+                if (d.mean_cache) copy_means(hm, nm * HC, sm[b] + off[b][kHypR], wide[b], nm * HC);
+            }
+            if (i) {  // the channel contexts go into the last buffer; an earlier one that has the segment gets a copy
+                const int home = nbuf - 1;
+                std::string cn[2];
+                Act cx[2], cdst[2];
+                for (int m = 0; m < nm; ++m) {
+                    cn[m] = d.prefix[m] + ("channel_context." + si);
+                    cx[m] = view(yhat[m], 0, c0);
+                    cdst[m] = seg(home, kChR + m);
+                }
+                if (d.grouped_ch) channel_context2(nm, cn, cx, cdst);
+                else
+                    for (int m = 0; m < nm; ++m) channel_context2(1, cn + m, cx + m, cdst + m);
+                for (int b = 0; b < home; ++b)
+                    for (int m = 0; m < nm; ++m)
+                        if (off[b][kChR + m] >= 0) copy_ch(cdst[m], seg(b, kChR + m));
+                for (int b = 0; b < nbuf && d.mean_cache; ++b)  // all modalities' channel contexts: adjacent
+                    means_of(view(buf[b], off[b][kChR], nm * 2 * C), sm[b] + off[b][kChR], wide[b]);
+            }
+            Act ys[2], hs[2];
+            for (int m = 0; m < nm; ++m) {
+                ys[m] = y ? view(y[m], c0, C) : Act();
+                hs[m] = view(yhat[m], c0, C);
+            }
+            const int64_t part_syms = (int64_t)C * h * (w / 2);
+            for (int part = 0; part < 2; ++part)  // anchor, non-anchor
+                for (int m = 0; m < nm; ++m) {
+                    const CtxNet& n = d.net[part][m];
+                    const std::string pn = d.prefix[m] + ((part ? "entropy_parameters_nonanchor." : "entropy_parameters_anchor.") + si);
+                    const int o = off[n.buf][n.first], wd = wide[n.buf] - o;
+                    const Act suffix = view(buf[n.buf], o, wd);
+                    Act prm;
+                    if (n.gathered) {
+                        prm = alloc(B, h, w, 2 * C);
+                        const size_t m2 = arena.top;
+                        Act in = alloc(B, h, w, 2 * C + wd);
+                        copy_ch(seg(0, kLocR), view(in, 0, 2 * C));
+                        copy_ch(suffix, view(in, 2 * C, wd));
+                        float* im = nullptr;  // the gathered input's means, gathered alike
+                        if (d.mean_cache) {
+                            im = (float*)arena.take((size_t)B * (2 * C + wd) * sizeof(float));
+                            copy_means(sm[0] + off[0][kLocR], wide[0], im, 2 * C + wd, 2 * C);
+                            copy_means(sm[n.buf] + o, wide[n.buf], im + 2 * C, 2 * C + wd, wd);
+                        }
+                        entropy_params(d, pn, in, part + 1, &prm, mc ? im : nullptr, 2 * C + wd);
+                        arena.top = m2;
+                    } else {
+                        prm = entropy_params(d, pn, suffix, part + 1, nullptr, mc ? sm[n.buf] + o : nullptr, wide[n.buf]);
+                    }
+                    code_part(cd, m, 1 - part, prm, ys[m], hs[m], part_off + part * part_syms);
+                    // the local context of what is decoded by now, for the nets that follow: the modality's own after its
+                    // anchor part (hs holds the anchor half only so far), RGB's again after its non-anchor part when a depth net
+                    // follows
+                    if (part && (m || nm == 1)) continue;
+                    const int lb = d.loc_buf[part ? 2 : m], ls = part ? kLocR : kLocR + m;
+                    const Act loc = seg(lb, ls);
+                    const std::string ln = d.prefix[m] + ((part ? "local_context_anchor_with_nonanchor." : "local_context.") + si);
+                    if (!part && d.anchor_taps) conv_anchor_in(ln, hs[m], 2, loc);
+                    else conv(ln, hs[m], 1, 2, Epi(), &loc);
+                    if (d.mean_cache) means_of(loc, sm[lb] + off[lb][ls], wide[lb]);
+                }
             part_off += 2 * part_syms;
             c0 += C;
             arena.top = mark;
@@ -2260,68 +2343,6 @@ struct rgbd_elic {
         *hr = r;
         *hd = d;
     }
-    // elic_united_R2D.py:149-326.  RGB context buffer [r_loc 2C | hyper_r 2M | ch_r 2C]: anchor reads the suffix, non-anchor
-    // the whole.  Depth context buffer as in ELIC_united: [r_loc 2C | d_loc 2C | hyper_r | hyper_d | ch_r | ch_d].
-    void bicee_r2d(Coding& cd, const Act* y_r, const Act* y_d, const Act& hyp_r, const Act& hyp_d, const Act& yhat_r,
-                   const Act& yhat_d)
-    {
-        yhat_base[0] = yhat_r.p;
-        yhat_base[1] = yhat_d.p;
-        int c0 = 0;
-        int64_t part_off = 0;
-        const int h = hyp_r.h, w = hyp_r.w, HC = hyp_r.c;
-        for (size_t i = 0; i < slice_ch.size(); ++i) {
-            const int C = slice_ch[i];
-            const size_t mark = arena.top;
-            const std::string si = std::to_string(i);
-            const int wide_r = 2 * C + HC + (i ? 2 * C : 0);
-            const int wide_d = 4 * C + 2 * HC + (i ? 4 * C : 0);
-            Act cr = alloc(hyp_r.n, h, w, wide_r), cdx = alloc(hyp_r.n, h, w, wide_d);
-            copy_ch(hyp_r, view(cr, 2 * C, HC));
-            copy_ch(hyp_r, view(cdx, 4 * C, HC));
-            copy_ch(hyp_d, view(cdx, 4 * C + HC, HC));
-            if (i) {
-                const Act chr_ = view(cdx, 4 * C + 2 * HC, 2 * C), chd = view(cdx, 6 * C + 2 * HC, 2 * C);
-                const std::string cn[2] = {"rgb_channel_context." + si, "depth_channel_context." + si};
-                const Act cx[2] = {view(yhat_r, 0, c0), view(yhat_d, 0, c0)};
-                const Act cdst[2] = {chr_, chd};
-                for (int m = 0; m < 2; ++m) channel_context2(1, cn + m, cx + m, cdst + m);
-                copy_ch(chr_, view(cr, 2 * C + HC, 2 * C));
-            }
-            const Act yr = y_r ? view(*y_r, c0, C) : Act();
-            const Act yd = y_d ? view(*y_d, c0, C) : Act();
-            const Act hr = view(yhat_r, c0, C), hd = view(yhat_d, c0, C);
-            const int64_t part_syms = (int64_t)C * h * (w / 2);
-            const Act r_loc = view(cr, 0, 2 * C), r_loc_d = view(cdx, 0, 2 * C), d_loc = view(cdx, 2 * C, 2 * C);
-            // rgb anchor: [hyper_r, ch_r]
-            Act p_ra = entropy_params("rgb_entropy_parameters_anchor." + si, view(cr, 2 * C, wide_r - 2 * C), 1);
-            code_part(cd, 0, 1, p_ra, yr, hr, part_off);
-            conv("rgb_local_context." + si, hr, 1, 2, Epi(), &r_loc);
-            // depth anchor: [r_loc, hyper_r, hyper_d, ch_r, ch_d] (gathered: d_loc's slot sits in between)
-            Act p_da = alloc(hyp_r.n, h, w, 2 * C);
-            {
-                const size_t m2 = arena.top;
-                Act in = alloc(hyp_r.n, h, w, wide_d - 2 * C);
-                copy_ch(r_loc, view(in, 0, 2 * C));
-                copy_ch(view(cdx, 4 * C, wide_d - 4 * C), view(in, 2 * C, wide_d - 4 * C));
-                entropy_params("depth_entropy_parameters_anchor." + si, in, 1, &p_da);
-                arena.top = m2;
-            }
-            code_part(cd, 1, 1, p_da, yd, hd, part_off);
-            conv("depth_local_context." + si, hd, 1, 2, Epi(), &d_loc);
-            // rgb non-anchor: [r_loc, hyper_r, ch_r]
-            Act p_rn = entropy_params("rgb_entropy_parameters_nonanchor." + si, cr, 2);
-            code_part(cd, 0, 0, p_rn, yr, hr, part_off + part_syms);
-            conv("rgb_local_context_anchor_with_nonanchor." + si, hr, 1, 2, Epi(), &r_loc_d);
-            // depth non-anchor: the whole depth buffer
-            Act p_dn = entropy_params("depth_entropy_parameters_nonanchor." + si, cdx, 2);
-            code_part(cd, 1, 0, p_dn, yd, hd, part_off + part_syms);
-            part_off += 2 * part_syms;
-            c0 += C;
-            arena.top = mark;
-        }
-    }
-
     // ---- single-modal ELIC (models/elic.py:15-57; BASELINE config 1) ------------------------------------------
     // analysis.py:29-52 / synthesis.py:32-70: the same blocks as above without the cross-modal fusion stages
     Act g_a1(const Act& x)
@@ -2353,57 +2374,6 @@ struct rgbd_elic {
         Act t = conv("h_s.increase.0", zhat, 2, 2, relu);
         t = conv("h_s.increase.2", t, 2, 2, relu);
         return conv("h_s.increase.4", t, 1, 1, Epi(), dst);
-    }
-    // entropy.py:7-29: three 1x1 convolutions
-    // `part` as in entropy_params(): 1x1 convolutions do not mix positions, so the whole net runs on one half only
-    Act entropy_params1(const std::string& p, const Act& ctx, int part)
-    {
-        Epi relu, lin;
-        relu.act = ACT_RELU;
-        relu.ckbd = lin.ckbd = g_ckbd_conv ? part : 0;
-        const PackedConv* last = conv_of(p + ".fusion.4.weight");
-        if (!last) return Act();
-        Act out = alloc(ctx.n, ctx.h, ctx.w, last->cout);
-        const size_t mark = arena.top;
-        Act t = conv(p + ".fusion.0", ctx, 1, 0, relu);
-        t = conv(p + ".fusion.2", t, 1, 0, relu);
-        conv(p + ".fusion.4", t, 1, 0, lin, &out);
-        arena.top = mark;
-        return out;
-    }
-    // elic.py:180-251 / 268-316.  Context buffer of a slice: [local 2C | channel 2C (i > 0) | hyper 2M]; the anchor
-    // net reads the suffix behind the local-context slot, the non-anchor net the whole buffer.
-    void bicee1(Coding& cd, const Act* y, const Act& hyper, const Act& yhat)
-    {
-        yhat_base[0] = yhat.p;
-        int c0 = 0;
-        int64_t part_off = 0;
-        const int h = hyper.h, w = hyper.w, HC = hyper.c;
-        for (size_t i = 0; i < slice_ch.size(); ++i) {
-            const int C = slice_ch[i];
-            const size_t mark = arena.top;
-            const std::string si = std::to_string(i);
-            const int wide = 2 * C + (i ? 2 * C : 0) + HC;
-            Act ctx = alloc(hyper.n, h, w, wide);
-            copy_ch(hyper, view(ctx, wide - HC, HC));
-            if (i) {
-                const std::string cn = "channel_context." + si;
-                const Act cx = view(yhat, 0, c0), cc = view(ctx, 2 * C, 2 * C);
-                channel_context2(1, &cn, &cx, &cc);
-            }
-            const Act ys = y ? view(*y, c0, C) : Act();
-            const Act hs = view(yhat, c0, C);
-            const int64_t part_syms = (int64_t)C * h * (w / 2);
-            Act pa = entropy_params1("entropy_parameters_anchor." + si, view(ctx, 2 * C, wide - 2 * C), 1);
-            code_part(cd, 0, 1, pa, ys, hs, part_off);
-            const Act loc = view(ctx, 0, 2 * C);
-            conv("local_context." + si, hs, 1, 2, Epi(), &loc);
-            Act pn = entropy_params1("entropy_parameters_nonanchor." + si, ctx, 2);
-            code_part(cd, 0, 0, pn, ys, hs, part_off + part_syms);
-            part_off += 2 * part_syms;
-            c0 += C;
-            arena.top = mark;
-        }
     }
     // ---- single-modal STF (models/stf.py:408-816): the Swin transforms without the cross-modal fusion, and the channel-slice
     // entropy model: 12 raster slices of 32 channels, two hyper-synthesis nets, per slice two parameter nets and latent
@@ -2580,29 +2550,9 @@ struct rgbd_elic {
         a.gamma = gamma;
         a.inverse = inverse ? 1 : 0;
         hipEvent_t e1 = nullptr;
-        if (profile) {
-            if (ev_used + 2 > ev_pool.size()) {
-                for (int i = 0; i < 256; ++i) {
-                    hipEvent_t e;
-                    if (hipEventCreate(&e) != hipSuccess) {
-                        fail(RGBD_EHIP);
-                        return y;
-                    }
-                    ev_pool.push_back(e);
-                }
-            }
-            (void)hipEventRecord(ev_pool[ev_used++], s);
-            e1 = ev_pool[ev_used++];
-        }
+        if (profile && !prof_begin(&e1)) return y;
         const int r = launch_gdn(a, s);
-        if (profile) {
-            (void)hipEventRecord(e1, s);
-            const double fl = 2.0 * (double)a.npix * x.c * x.c;
-            prof_flops += fl;
-            prof_flops_exec += fl;
-            ++prof_launches;
-            ev_names.push_back({name, fl, fl});
-        }
+        if (profile) prof_end(e1, name, 2.0 * (double)a.npix * x.c * x.c, 2.0 * (double)a.npix * x.c * x.c);
         if (r) fail(r);
         return y;
     }
@@ -2721,18 +2671,8 @@ struct rgbd_elic {
         e.ckbd = 2;
         ConvPlan cp = conv_plan("context_prediction", yhat, 1, 2, e, &dst);
         if (!dry() && cp.ok && cp.a.nphase == 1) {
-            TapTable& t = cp.a.taps;
-            int n = 0;
-            for (int k = 0; k < t.n[0]; ++k) {
-                if (!((t.dy[0][k] + t.dx[0][k]) & 1)) continue;
-                t.dy[0][n] = t.dy[0][k];
-                t.dx[0][n] = t.dx[0][k];
-                t.wt[0][n] = t.wt[0][k];
-                ++n;
-            }
-            cp.flops_exec = cp.flops * 0.5 * n / std::max(1, (int)t.n[0]);
-            for (int k = n; k < 25; ++k) t.dy[0][k] = t.dx[0][k] = t.wt[0][k] = 0;
-            t.n[0] = (int8_t)n;
+            const int all = cp.a.taps.n[0], n = keep_taps(cp.a.taps, 1);
+            cp.flops_exec = cp.flops * 0.5 * n / std::max(1, all);
         }
         conv_issue(cp);
     }

@@ -360,13 +360,13 @@ void rgbd_elic::g_s_family(const Act yhat[2], Act xhat[2])
 // The latent stage: everything between z_hat and y_hat -- the family's buffers, its hyper synthesis, its debug tensors and its
 // coding loop (symbols when cd.encode, from the streams when not, likelihoods into cd.lik[m] when cd.estimate).  y: the
 // latents (null when decoding); hyp: the hyper tensors when the caller has them already (the Latents path; zhat is null then).
-//   ELIC: y_hat = round(y - mean) + mean slice by slice through the two-part checkerboard loop (elic.py:180-251 / 268-316).
+//   ELIC: y_hat = round(y - mean) + mean slice by slice through the checkerboard slice loop (elic.py:180-251 / 268-316).
 //   STF: the y stream is ONE stream for all slices of all images of the call (per-image streams: one per image), coded after
 //     the last slice; the decoder resumes its rANS state slice by slice.  A batch decompresses as the inverse of compress()
 //     (the reference's decompress handles one image only, stf.py:799).
 //   Checkerboard: both halves of all images of the call go into ONE y stream, anchor half first (per-image streams: one per
 //     image, each with its own two halves); the decoder resumes its rANS state between the halves.
-//   The two-modality codecs: hyper synthesis and the Bi-CEE loop over both modalities (elic_united.py:265-348).
+//   The two-modality codecs: hyper synthesis and the same slice loop over both modalities (Bi-CEE, elic_united.py:265-348).
 void rgbd_elic::latent_family(Coding& cd, int B, int h, int w, const Act* y, const Act* zhat, const Act* hyp, Act yhat[2])
 {
     const Modes mo = modes();
@@ -376,7 +376,7 @@ void rgbd_elic::latent_family(Coding& cd, int B, int h, int w, const Act* y, con
         named["hyper"] = hyper;
         yhat[0] = alloc(B, h, w, M);
         if (cd.estimate) cd.lik[0] = alloc(B, h, w, M);
-        bicee1(cd, y, hyper, yhat[0]);
+        slice_loop_ckbd(cd, slice_loop_family(), 1, y, &hyper, yhat);
         break;
     }
     case 4: {
@@ -464,8 +464,7 @@ void rgbd_elic::latent_family(Coding& cd, int B, int h, int w, const Act* y, con
         }
         if (cd.estimate)
             for (int m = 0; m < 2; ++m) cd.lik[m] = alloc(B, h, w, M);
-        if (variant == 3) bicee_r2d(cd, y, y ? y + 1 : nullptr, hy[0], hy[1], yhat[0], yhat[1]);
-        else bicee(cd, y, y ? y + 1 : nullptr, hy[0], hy[1], yhat[0], yhat[1]);
+        slice_loop_ckbd(cd, slice_loop_family(), 2, y, hy, yhat);
     }
     }
     name(mo, "yhat", yhat);
