@@ -361,6 +361,25 @@ int rgbd_elic_create_ckbd(int32_t N, int32_t in_ch, rgbd_elic** out);
  * (not clamped), likelihoods of y [B,M,H/16,W/16] and of z [B,N,H/64,W/64] ("y_likelihoods" / "z_likelihoods"). */
 int rgbd_elic_forward_single(rgbd_elic* m, const float* x_dev, int32_t B, int32_t H, int32_t W, float* xhat_dev, float* lik_y,
                              float* lik_z, void* stream);
+/* ELIC(return_mid=True) (models/elic.py:159-170 forward, :318-329 decompress; modules/transform/synthesis.py:54-67): the two
+ * calls above for a handle of rgbd_elic_create_single, which also hand back the outputs of the first three transposed
+ * convolutions of g_s: up1 [B,N,H/8,W/8], up2 [B,N,H/4,W/4], up3 [B,N,H/2,W/2], NCHW fp32, none NULL.  x_hat and the
+ * likelihoods are those of the calls above, bit for bit. */
+int rgbd_elic_decompress_single_mid(rgbd_elic* m, const uint8_t* const* y, const int64_t* y_len, int32_t n_y,
+                                    const uint8_t* const* z, const int64_t* z_len, int32_t B, int32_t zh, int32_t zw,
+                                    float* x_dev, float* up1, float* up2, float* up3, void* stream);
+int rgbd_elic_forward_single_mid(rgbd_elic* m, const float* x_dev, int32_t B, int32_t H, int32_t W, float* xhat_dev, float* lik_y,
+                                 float* lik_z, float* up1, float* up2, float* up3, void* stream);
+/* Spatial_aligner alone (modules/transform/spatialAligner.py:341-390; the block SynthesisTransformPlus inserts behind up1..up3,
+ * synthesis.py:74-110): two 2x2 stride-2 patch embeddings to 96 channels, two Swin blocks whose attention takes the query from
+ * x and key / value from guided (rgbd_guided_window_attention; shift 0, then 2), a 2x2 stride-2 transposed convolution to
+ * out_ch.  Life cycle of the codec handles: set_tensor with the reference's names (patch_embeding1/2, blocks.K.*, recovery;
+ * Linear weights as [out][in][1][1]), finalize, clone_shared, destroy; no tables.  x, guided: [B,in_ch,H,W] NCHW fp32; out:
+ * [B,out_ch,H,W]; H % 8 == 0, W % 8 == 0.  The codec calls on an aligner handle, and rgbd_aligner_forward on a handle of
+ * another family, return RGBD_EINVAL. */
+int rgbd_aligner_create(int32_t in_ch, int32_t out_ch, rgbd_elic** out);
+int rgbd_aligner_forward(rgbd_elic* m, const float* x_dev, const float* guided_dev, int32_t B, int32_t H, int32_t W,
+                         float* out_dev, void* stream);
 
 /*
  * STF_united (BASELINE config 5): replaces models/stf_united.py: SymmetricalTransFormerUnited :605-678 with
@@ -542,6 +561,15 @@ int rgbd_layernorm2(const float* x, int64_t ntok, int32_t C, int32_t xcs, const 
 int rgbd_window_attention(const float* qkv, int32_t B, int32_t H, int32_t W, int32_t C, int32_t qcs, int32_t heads, int32_t shift,
                           const float* rpb, float* out, int32_t ocs, const float* qkv1, const float* rpb1, float* out1,
                           void* stream);
+/* rgbd_guided_window_attention: the cross attention of Spatial_aligner's Swin blocks (modules/transform/spatialAligner.py:
+ * WindowAttention.forward :138-170 with the partition / roll / mask of SwinTransformerBlock.forward :279-331 and create_mask
+ * :249-277): 4x4 windows, head_dim 32, softmax((q * 32^-0.5) k^T + bias + mask) v.  q: [B][H][W][qcs], channel head * 32 + d
+ * (qkv1, :130,147); kv: [B][H][W][kvcs], channel which * C + head * 32 + d, which 0 = k, 1 = v (qkv2, :131,148-149); rpb:
+ * [49][heads]; out: [B][H][W][ocs], channels C .. ocs - 1 untouched.  H and W are those of the token grid.  Returns RGBD_EINVAL
+ * and writes nothing unless H % 4 == 0, W % 4 == 0, C == 32 * heads, 0 <= shift < 4, qcs >= C, kvcs >= 2 C, ocs >= C,
+ * qcs % 4 == 0, kvcs % 4 == 0, q and kv 16-byte aligned, B * (H/4) * (W/4) * heads <= 0x7fffffff, no pointer NULL. */
+int rgbd_guided_window_attention(const float* q, int32_t qcs, const float* kv, int32_t kvcs, int32_t B, int32_t H, int32_t W,
+                                 int32_t C, int32_t heads, int32_t shift, const float* rpb, float* out, int32_t ocs, void* stream);
 int rgbd_patch_merge_gather(const float* x, int32_t B, int32_t H, int32_t W, int32_t C, int32_t xcs, float* y, int32_t ycs,
                             void* stream);
 int rgbd_pixel_shuffle2(const float* x, int32_t B, int32_t H, int32_t W, int32_t Co, int32_t xcs, float* y, int32_t ycs,

@@ -25,6 +25,7 @@ modelZoo["STF"] = SymmetricalTransFormer  # after "STF_united": the testers matc
 from .ckbd import Cheng2020AnchorwithCheckerboard  # noqa: F401,E402
 
 modelZoo["ckbd"] = Cheng2020AnchorwithCheckerboard  # last: no zoo name contains "ckbd" and "ckbd" contains none of them
+from .aligner import Spatial_aligner  # noqa: F401,E402
 from .pool import CodecPool  # noqa: F401,E402
 from . import datautils, ioutils, metrics, tester  # noqa: F401,E402
 from .tester import TesterSingle, TesterUnited  # noqa: F401,E402

@@ -168,6 +168,12 @@ def lib():
         "rgbd_elic_compress_single": (ctypes.c_int, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp]),
         "rgbd_elic_forward_single": (ctypes.c_int, [c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
         "rgbd_elic_decompress_single": (ctypes.c_int, [c_vp, u8pp, i64p, c_i32, u8pp, i64p, c_i32, c_i32, c_i32, c_vp, c_vp]),
+        "rgbd_elic_forward_single_mid": (ctypes.c_int, [c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+        "rgbd_elic_decompress_single_mid": (ctypes.c_int, [c_vp, u8pp, i64p, c_i32, u8pp, i64p, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp,
+                                                          c_vp, c_vp]),
+        "rgbd_aligner_create": (ctypes.c_int, [c_i32, c_i32, ctypes.POINTER(c_vp)]),
+        "rgbd_aligner_forward": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp]),
+        "rgbd_guided_window_attention": (ctypes.c_int, [c_vp, c_i32, c_vp, c_i32] + [c_i32] * 6 + [c_vp, c_vp, c_i32, c_vp]),
         "rgbd_elic_debug_tensor": (ctypes.c_int, [c_vp, ctypes.c_char_p, f32p, c_i64, i32p]),
         "rgbd_elic_debug_symbols": (ctypes.c_int, [c_vp, c_i32, i32p, i32p, c_i64, i64p]),
         "rgbd_elic_set_profile": (ctypes.c_int, [c_vp, c_i32]),
@@ -223,7 +229,9 @@ EXPORTS = ["rgbd_abi_version", "rgbd_set_blocking_sync", "rgbd_get_blocking_sync
            "rgbd_elic_profile_read", "rgbd_elic_profile_read_executed", "rgbd_debug_force_splitk", "rgbd_debug_force_fuse", "rgbd_debug_force_subpix", "rgbd_debug_force_pair", "rgbd_debug_fail_captures", "rgbd_debug_force_ckbd", "rgbd_debug_force_blocked", "rgbd_debug_bench_streams", "rgbd_elic_set_tile_mode", "rgbd_debug_force_tile", "rgbd_debug_conv_log", "rgbd_debug_conv_log_read", "rgbd_debug_tile_override", "rgbd_debug_tile_list", "rgbd_conv_bench",
            "rgbd_elic_profile_dump", "rgbd_elic_create_stf_single", "rgbd_slice_quant_index", "rgbd_slice_dequant", "rgbd_lrp_update",
            "rgbd_ckbd_estimate_part", "rgbd_slice_estimate", "rgbd_ckbd_part", "rgbd_z_quant", "rgbd_z_dequant", "rgbd_eb_forward",
-           "rgbd_elic_create_ckbd", "rgbd_gdn_nchw", "rgbd_gdn_parametrize", "rgbd_debug_force_gdn_tile", "rgbd_gdn_bench"]
+           "rgbd_elic_create_ckbd", "rgbd_gdn_nchw", "rgbd_gdn_parametrize", "rgbd_debug_force_gdn_tile", "rgbd_gdn_bench",
+           "rgbd_guided_window_attention", "rgbd_aligner_create", "rgbd_aligner_forward", "rgbd_elic_decompress_single_mid",
+           "rgbd_elic_forward_single_mid"]
 
 
 _BS_HOLDERS = 0

@@ -528,6 +528,34 @@ def stf_entries(channel: int = 3) -> "OrderedDict[str, Entry]":
     return b.entries
 
 
+ALIGNER_EMBED, ALIGNER_HEADS = 96, 3  # modules/transform/spatialAligner.py:344-348 (window 4, patch 2)
+
+
+def spatial_aligner_entries(in_ch: int = 192, out_ch: int = 192, prefix: str = "") -> "OrderedDict[str, Entry]":
+    """Every state_dict entry of Spatial_aligner (reference: modules/transform/spatialAligner.py:341-374), in the reference's
+    order: two 2x2 stride-2 patch embeddings, two Swin blocks with a cross attention (qkv1 for the query, qkv2 for key and
+    value, :130-132) and the 2x2 stride-2 transposed convolution `recovery`.  prefix: "" or the block's name inside a model
+    (e.g. "g_s.sp1")."""
+    b = _Builder()
+    p = f"{prefix}." if prefix else ""
+    E = ALIGNER_EMBED
+    b.conv(f"{p}patch_embeding1", in_ch, E, 2)
+    b.conv(f"{p}patch_embeding2", in_ch, E, 2)
+    for k in range(2):
+        n = f"{p}blocks.{k}"
+        b.layernorm(f"{n}.norm1", E)
+        b.entries[f"{n}.attn.relative_position_bias_table"] = Entry((49, ALIGNER_HEADS), "rpb_table")
+        b.buffer(f"{n}.attn.relative_position_index", (16, 16), "int64")
+        b.linear(f"{n}.attn.qkv1", E, E)
+        b.linear(f"{n}.attn.qkv2", E, 2 * E)
+        b.linear(f"{n}.attn.proj", E, E)
+        b.layernorm(f"{n}.norm2", E)
+        b.linear(f"{n}.mlp.fc1", E, 4 * E)
+        b.linear(f"{n}.mlp.fc2", 4 * E, E)
+    b.deconv(f"{p}recovery", E, out_ch, 2)
+    return b.entries
+
+
 def ckbd_config(N: int = 192) -> Config:
     """Cheng2020 anchor model with the checkerboard context (models/Cheng2020withCKBD.py:46-50): M = N, one slice."""
     cfg = model_config()

@@ -243,6 +243,9 @@ int launch_layernorm(const float* x, size_t ntok, int C, int xcs, const float* w
 int launch_window_attention(const float* qkv, int B, int H, int W, int C, int qcs, int heads, int shift, const float* rpb,
                             float* out, int ocs, hipStream_t s, const float* qkv1 = nullptr, const float* rpb1 = nullptr,
                             float* out1 = nullptr);
+// guided (cross) window attention of Spatial_aligner: q [B,H,W,qcs], kv [B,H,W,kvcs] (k | v), head_dim 32; checks its arguments
+int launch_guided_window_attention(const float* q, int qcs, const float* kv, int kvcs, int B, int H, int W, int C, int heads,
+                                   int shift, const float* rpb, float* out, int ocs, hipStream_t s);
 int launch_patch_merge_gather(const float* x, int B, int H, int W, int C, int xcs, float* y, int ycs, hipStream_t s);
 int launch_pixel_shuffle2(const float* x, int B, int H, int W, int Co, int xcs, float* y, int ycs, hipStream_t s);
 

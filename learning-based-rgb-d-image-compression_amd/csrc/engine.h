@@ -412,9 +412,11 @@ struct rgbd_elic {
     int N = 192, M = 320;
     int tile_mode = 0;  // rgbd_elic_set_tile_mode: 0 latency tiles (isolated launches), 1 throughput tiles (shared chip)
     int variant = 0;  // 0: ELIC_united (RGB + depth), 1: single-modal ELIC (models/elic.py), 2: STF_united, 3: ELIC_united_R2D,
-                      // 4: single-modal STF (models/stf.py), 5: checkerboard Cheng2020 (models/Cheng2020withCKBD.py)
+                      // 4: single-modal STF (models/stf.py), 5: checkerboard Cheng2020 (models/Cheng2020withCKBD.py),
+                      // 6: Spatial_aligner alone (modules/transform/spatialAligner.py): no codec, rgbd_aligner_forward only
     bool single() const { return variant == 1 || variant == 4 || variant == 5; }
-    int in_ch = 3;    // image channels of the single-modal variant
+    int in_ch = 3;    // image channels of the single-modal variant (variant 6: channels of x and guided)
+    int out_ch = 0;   // variant 6: output channels
     // what the call paths (engine.hip) need to know about one versus two modalities; arrays are read at [0, nm)
     struct Modes {
         int nm;
@@ -1668,6 +1670,8 @@ struct rgbd_elic {
         bool grouped;  // the branches of a stage go as one grouped launch (conv2(2, ...)), not one after the other
         bool ends;     // the stage loop alternates the workspace ends (ends_begin / ends_stage / ends_finish)
         bool leads;    // an "rb" stage hands the next block's .branch.0 to its fused tail (next_lead)
+        const Act* mids = nullptr;  // kSyn15 with return_mid: buffers the outputs of stages 1, 5 and 10 (up1..up3,
+                                    // synthesis.py:54-67) are copied into
     };
     static constexpr const char* kAna18[18] = {"conv", "rb", "rb", "rb", "spf", "conv", "rb", "rb", "rb",
                                                "attn", "spf", "conv", "rb", "rb", "rb", "spf", "conv", "attn"};
@@ -1721,6 +1725,7 @@ struct rgbd_elic {
                 else attention2(g, names + m, x + m, dsts + m, o + m);
             }
             for (int m = 0; m < nm; ++m) x[m] = dsts[m] ? cat[m] : o[m];
+            if (sd.mids && (i == 1 || i == 5 || i == 10)) copy_ch(x[0], sd.mids[i == 1 ? 0 : (i == 5 ? 1 : 2)]);
         }
         if (sd.ends) ends_finish(ends);
         for (int m = 0; m < nm; ++m) out[m] = x[m];
@@ -2188,6 +2193,46 @@ struct rgbd_elic {
         conv2(nm, n, hdn, 1, 0, e2, odst, o);
         arena.top = mark;
     }
+    // Spatial_aligner (modules/transform/spatialAligner.py:341-390): patch embeddings of x and guided, two Swin blocks whose
+    // attention reads q from x and k, v from guided (:279-338; norm1 on both, guided itself never updated: :290-291, 383-384),
+    // and the 2x2 stride-2 transposed convolution `recovery`, whose taps do not overlap: a 1x1 convolution to 4 * out channels
+    // (repacked in finalize) and a pixel shuffle.  prefix: "" (the stand-alone variant) or the block's name, e.g. "g_s.sp1".
+    Act spatial_aligner(const std::string& prefix, const Act& x, const Act& guided)
+    {
+        const std::string p = prefix.empty() ? std::string() : prefix + ".";
+        Act ex = conv(p + "patch_embeding1", x, 2, 0);
+        const Act eg = conv(p + "patch_embeding2", guided, 2, 0);
+        const int heads = 3;  // :346; embed_dim 96 = 3 * 32
+        for (int k = 0; k < 2; ++k) {
+            const std::string pb = p + "blocks." + std::to_string(k);
+            const Act out = alloc(ex.n, ex.h, ex.w, ex.c);
+            const size_t mark = arena.top;
+            const Act t = layernorm(pb + ".norm1", ex);
+            const Act tg = layernorm(pb + ".norm1", eg);
+            const Act q = conv(pb + ".attn.qkv1", t, 1, 0);
+            const Act kv = conv(pb + ".attn.qkv2", tg, 1, 0);
+            const Act a = alloc(ex.n, ex.h, ex.w, ex.c);
+            float* rpb = dense_of(pb + ".attn.relative_position_bias_table");
+            if (!dry() && !rc && rpb) {
+                const int r = launch_guided_window_attention(q.p, q.cs, kv.p, kv.cs, ex.n, ex.h, ex.w, ex.c, heads, k ? 2 : 0, rpb,
+                                                             a.p, a.cs, s);
+                if (r) fail(r);
+            }
+            Epi e1;
+            e1.res1 = &ex;
+            const Act x1 = conv(pb + ".attn.proj", a, 1, 0, e1);
+            const Act t2 = layernorm(pb + ".norm2", x1);
+            Epi g;
+            g.act = ACT_GELU;
+            const Act hdn = conv(pb + ".mlp.fc1", t2, 1, 0, g);
+            Epi e2;
+            e2.res1 = &x1;
+            conv(pb + ".mlp.fc2", hdn, 1, 0, e2, &out);
+            arena.top = mark;
+            ex = out;
+        }
+        return pixel_shuffle(conv(p + "recovery", ex, 1, 0));
+    }
     // stf_united.py:270-366 for both modalities; down: 0 none, 1 PatchMerging (:217-249), 2 PatchSplit (:252-267)
     void basic_layer2(int nm, const std::string p[2], const Act x_in[2], int depth, int heads, int down, Act out[2])
     {
@@ -2354,9 +2399,10 @@ struct rgbd_elic {
     Act g_s1(const Act& yhat)
     {
         Act xhat[2];
-        stages({kSyn15, 15, 1, {"g_s.synthesis_transform.", ""}, kNoFusion, false, false, false}, &yhat, xhat);
+        stages({kSyn15, 15, 1, {"g_s.synthesis_transform.", ""}, kNoFusion, false, false, false, mid_dst}, &yhat, xhat);
         return xhat[0];
     }
+    const Act* mid_dst = nullptr;  // set around g_s_family by a return_mid call (run_forward / run_decompress)
     // analysis.py:207-216
     Act h_a1(const Act& y)
     {
@@ -2758,9 +2804,15 @@ struct rgbd_elic {
     using In2 = std::array<const float*, 2>;
     using Out2 = std::array<float*, 2>;
     int run_compress(int nm, In2 x_dev, int B, int H, int W, int per_image, const Latents* lat = nullptr);
-    int run_forward(int nm, In2 x_dev, int B, int H, int W, Out2 xhat_dev, Out2 ly, Out2 lz);
+    // up: NULL, or (single-modal ELIC only) the three NCHW tensors of return_mid: [B,N,H/8,W/8], [B,N,H/4,W/4], [B,N,H/2,W/2]
+    using Mid3 = std::array<float*, 3>;
+    int run_forward(int nm, In2 x_dev, int B, int H, int W, Out2 xhat_dev, Out2 ly, Out2 lz, const Mid3* up = nullptr);
     int run_decompress(int nm, const uint8_t* const* ys[2], const int64_t* ylen[2], int n_y, const uint8_t* const* zs[2],
-                       const int64_t* zlen[2], int B, int h, int w, Out2 xhat_dev, const Latents* lat = nullptr);
+                       const int64_t* zlen[2], int B, int h, int w, Out2 xhat_dev, const Latents* lat = nullptr,
+                       const Mid3* up = nullptr);
+    void mids_begin(int B, int H, int W, Act mid[3]);  // workspace of up1..up3; g_s1 fills it while mid_dst points at it
+    int mids_out(const Act mid[3], int B, int H, int W, const Mid3& up);
+    int run_aligner(const float* x_dev, const float* guided_dev, int B, int H, int W, float* out_dev);
     int ensure_arena(size_t bytes);
 };
 

@@ -549,10 +549,11 @@ int rgbd_elic::run_compress(int nm, In2 x_dev, int B, int H, int W, int per_imag
 // eval-mode forward(): elic_united.py:234-263 with quant == "ste" (round in eval), elic.py:60-161, stf.py:618-678,
 // Cheng2020withCKBD.py:52-71; likelihoods as in entropy_models.py:391-428 (factorised prior) and :534-558 (Gaussian
 // conditional) instead of symbols
-int rgbd_elic::run_forward(int nm, In2 x_dev, int B, int H, int W, Out2 xhat_dev, Out2 ly, Out2 lz)
+int rgbd_elic::run_forward(int nm, In2 x_dev, int B, int H, int W, Out2 xhat_dev, Out2 ly, Out2 lz, const Mid3* up)
 {
     const Modes mo = modes();
     if (nm != mo.nm) return RGBD_ESTATE;
+    if (up && variant != 1) return RGBD_EINVAL;
     const int h = H / 16, w = W / 16, zh = H / 64, zw = W / 64;
     begin_call(B, true);  // forward() is one reference call on the whole batch
     Act x[2];
@@ -565,6 +566,7 @@ int rgbd_elic::run_forward(int nm, In2 x_dev, int B, int H, int W, Out2 xhat_dev
     // ==== body: captured into / replayed from a HIP graph per call shape (the prologue above reads the caller's pointers,
     // the epilogue below writes them) ====
     Act out[3][2];  // x_hat, likelihoods of y, likelihoods of z: cur_ge->out[2 * k + m]
+    Act mid[3];     // return_mid (one modality): cur_ge->out[1], [3], [5]
     if (body_begin()) {
         Act y[2], z[2], zhat[2], yhat[2];
         for (int m = 0; m < nm; ++m) y[m] = alloc(B, h, w, M);
@@ -581,14 +583,19 @@ int rgbd_elic::run_forward(int nm, In2 x_dev, int B, int H, int W, Out2 xhat_dev
         Coding cd;
         cd.estimate = true;
         latent_family(cd, B, h, w, y, zhat, nullptr, yhat);
+        if (up) mids_begin(B, H, W, mid);
         g_s_family(yhat, out[0]);
+        mid_dst = nullptr;
         for (int m = 0; m < nm; ++m) out[1][m] = cd.lik[m];
-        if (cur_ge && !dry())
+        if (cur_ge && !dry()) {
             for (int k = 0; k < 3; ++k)
                 for (int m = 0; m < nm; ++m) cur_ge->out[2 * k + m] = out[k][m];
+            for (int k = 0; k < 3 && up; ++k) cur_ge->out[2 * k + 1] = mid[k];
+        }
     } else {
         for (int k = 0; k < 3; ++k)
             for (int m = 0; m < nm; ++m) out[k][m] = cur_ge->out[2 * k + m];
+        for (int k = 0; k < 3 && up; ++k) mid[k] = cur_ge->out[2 * k + 1];
     }
     if (const int r = finish_body()) return r;
     if (dry()) return RGBD_OK;
@@ -597,16 +604,61 @@ int rgbd_elic::run_forward(int nm, In2 x_dev, int B, int H, int W, Out2 xhat_dev
         r = launch_nhwc_to_nchw_clamp(out[0][m].p, B, mo.img_ch[m], H, W, out[0][m].cs, xhat_dev[m], 0, s);
     for (int m = 0; m < nm && !r; ++m) r = launch_nhwc_to_nchw_clamp(out[1][m].p, B, M, h, w, out[1][m].cs, ly[m], 0, s, perm());
     for (int m = 0; m < nm && !r; ++m) r = launch_nhwc_to_nchw_clamp(out[2][m].p, B, N, zh, zw, out[2][m].cs, lz[m], 0, s, perm());
+    if (!r && up) r = mids_out(mid, B, H, W, *up);
+    if (!r) r = wait_stream();
+    return r;
+}
+
+// return_mid (models/elic.py:159-170, 318-329): up1..up3 are the outputs of g_s's first three transposed convolutions.  The body
+// copies them into workspace of the call that lives until its end (the addresses a captured graph replays); like x_hat they go
+// to the caller's NCHW tensors in the epilogue, which is never captured: a replay must not write to the tensors of the call
+// that was captured.
+void rgbd_elic::mids_begin(int B, int H, int W, Act mid[3])
+{
+    for (int k = 0; k < 3; ++k) mid[k] = alloc(B, H >> (3 - k), W >> (3 - k), N);
+    mid_dst = mid;
+}
+
+int rgbd_elic::mids_out(const Act mid[3], int B, int H, int W, const Mid3& up)
+{
+    int r = 0;
+    for (int k = 0; k < 3 && !r; ++k)
+        r = launch_nhwc_to_nchw_clamp(mid[k].p, B, N, H >> (3 - k), W >> (3 - k), mid[k].cs, up[k], 0, s, perm());
+    return r;
+}
+
+// Spatial_aligner alone (variant 6): x, guided [B,in_ch,H,W] -> out [B,out_ch,H,W]
+int rgbd_elic::run_aligner(const float* x_dev, const float* guided_dev, int B, int H, int W, float* out_dev)
+{
+    begin_call(B, true);
+    const Act x = alloc(B, H, W, in_ch), g = alloc(B, H, W, in_ch);
+    if (!dry()) {
+        int r = launch_nchw_to_nhwc16(x_dev, B, in_ch, H, W, x.p, x.cs, s);
+        if (!r) r = launch_nchw_to_nhwc16(guided_dev, B, in_ch, H, W, g.p, g.cs, s);
+        if (r) return r;
+    }
+    // ==== body: captured into / replayed from a HIP graph per call shape ====
+    Act out;
+    if (body_begin()) {
+        out = spatial_aligner("", x, g);
+        if (cur_ge && !dry()) cur_ge->out[0] = out;
+    } else {
+        out = cur_ge->out[0];
+    }
+    if (const int r = finish_body()) return r;
+    if (dry()) return RGBD_OK;
+    int r = launch_nhwc_to_nchw_clamp(out.p, B, out_ch, H, W, out.cs, out_dev, 0, s);
     if (!r) r = wait_stream();
     return r;
 }
 
 // decompress: elic_united.py:462-578, elic.py:255-325, stf.py:766-816, Cheng2020withCKBD.py:138-174; h x w: the latent grid
 int rgbd_elic::run_decompress(int nm, const uint8_t* const* ys[2], const int64_t* ylen[2], int n_y, const uint8_t* const* zs[2],
-                              const int64_t* zlen[2], int B, int h, int w, Out2 xhat_dev, const Latents* lat)
+                              const int64_t* zlen[2], int B, int h, int w, Out2 xhat_dev, const Latents* lat, const Mid3* up)
 {
     const Modes mo = modes();
     if (nm != mo.nm) return RGBD_ESTATE;
+    if (up && (variant != 1 || lat)) return RGBD_EINVAL;
     const int zh = lat ? 1 : h / 4, zw = lat ? 1 : w / 4, H = h * 16, W = w * 16;
     const int64_t T = (int64_t)M * h * w, Tz = (int64_t)N * zh * zw;
     const int per_image = (n_y == B && !(B == 1)) ? 1 : (n_y == 1 ? (B == 1 ? 1 : 0) : -1);
@@ -629,6 +681,7 @@ int rgbd_elic::run_decompress(int nm, const uint8_t* const* ys[2], const int64_t
 
     // ==== body: captured into / replayed from a HIP graph per call shape ================================================
     Act out[2];  // what the epilogue hands back: x_hat (or y_hat for decompress_united) per modality: cur_ge->out[m]
+    Act mid[3];  // return_mid (one modality): cur_ge->out[1], [3], [5]
     if (body_begin()) {
         Act zhat[2], yhat[2];
         if (!lat) {
@@ -640,11 +693,18 @@ int rgbd_elic::run_decompress(int nm, const uint8_t* const* ys[2], const int64_t
         latent_family(cd, B, h, w, nullptr, lat ? nullptr : zhat, lat ? hyp : nullptr, yhat);
         if (lat)  // decompress_united ends here: y_hat back to the caller
             for (int m = 0; m < nm; ++m) out[m] = yhat[m];
-        else g_s_family(yhat, out);
-        if (cur_ge && !dry())
+        else {
+            if (up) mids_begin(B, H, W, mid);
+            g_s_family(yhat, out);
+            mid_dst = nullptr;
+        }
+        if (cur_ge && !dry()) {
             for (int m = 0; m < nm; ++m) cur_ge->out[m] = out[m];
+            for (int k = 0; k < 3 && up; ++k) cur_ge->out[2 * k + 1] = mid[k];
+        }
     } else {
         for (int m = 0; m < nm; ++m) out[m] = cur_ge->out[m];
+        for (int k = 0; k < 3 && up; ++k) mid[k] = cur_ge->out[2 * k + 1];
     }
     if (const int r = finish_body()) return r;
     if (dry()) return RGBD_OK;
@@ -654,5 +714,6 @@ int rgbd_elic::run_decompress(int nm, const uint8_t* const* ys[2], const int64_t
     for (int m = 0; m < nm && !r; ++m)
         r = lat ? launch_nhwc_to_nchw_clamp(out[m].p, B, M, h, w, out[m].cs, lat->yhat[m], 0, s, perm())
                 : launch_nhwc_to_nchw_clamp(out[m].p, B, mo.img_ch[m], H, W, out[m].cs, xhat_dev[m], mo.clamp, s);
+    if (!r && up) r = mids_out(mid, B, H, W, *up);
     return r;
 }

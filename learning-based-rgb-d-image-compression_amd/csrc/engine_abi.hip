@@ -928,6 +928,68 @@ int rgbd_elic_decompress_single(rgbd_elic* m, const uint8_t* const* y, const int
     return r;
 }
 
+// return_mid (models/elic.py:159-170, 318-329): the two calls above plus up1..up3; call shapes of their own in the graph cache
+// (their bodies hold three more copies)
+int rgbd_elic_forward_single_mid(rgbd_elic* m, const float* x_dev, int32_t B, int32_t H, int32_t W, float* xhat_dev, float* lik_y,
+                                 float* lik_z, float* up1, float* up2, float* up3, void* stream)
+{
+    int r = check_ready(m);
+    if (r) return r;
+    if (m->variant != 1 || !x_dev || !xhat_dev || !lik_y || !lik_z || !up1 || !up2 || !up3 || B <= 0 || H <= 0 || W <= 0 ||
+        H % 64 || W % 64)
+        return RGBD_EINVAL;
+    if (const int ur = m->use_stream(stream)) return ur;
+    const rgbd_elic::Mid3 up = {up1, up2, up3};
+    char key[96];
+    snprintf(key, sizeof(key), "f1m|%d|%d|%d", B, H, W);
+    return run_sized(m, key, [&]() { return m->run_forward(1, {x_dev}, B, H, W, {xhat_dev}, {lik_y}, {lik_z}, &up); });
+}
+
+int rgbd_elic_decompress_single_mid(rgbd_elic* m, const uint8_t* const* y, const int64_t* y_len, int32_t n_y,
+                                    const uint8_t* const* z, const int64_t* z_len, int32_t B, int32_t zh, int32_t zw,
+                                    float* x_dev, float* up1, float* up2, float* up3, void* stream)
+{
+    int r = check_ready(m);
+    if (r) return r;
+    if (m->variant != 1 || !y || !y_len || !z || !z_len || !x_dev || !up1 || !up2 || !up3 || B <= 0 || zh <= 0 || zw <= 0)
+        return RGBD_EINVAL;
+    if (n_y != 1 && n_y != B) return RGBD_EINVAL;
+    if (const int ur = m->use_stream(stream)) return ur;
+    const rgbd_elic::Mid3 up = {up1, up2, up3};
+    char key[96];
+    snprintf(key, sizeof(key), "d1m|%d|%d|%d|%d", B, zh, zw, n_y);
+    r = run_sized(m, key, [&]() { return m->run_decompress(1, &y, &y_len, n_y, &z, &z_len, B, zh * 4, zw * 4, {x_dev}, nullptr, &up); });
+    if (!r) r = m->wait_stream();
+    if (m->profile && !r) m->profile_collect();
+    return r;
+}
+
+// Spatial_aligner alone (modules/transform/spatialAligner.py:341-390): embed_dim 96, 3 heads, 4x4 windows
+int rgbd_aligner_create(int32_t in_ch, int32_t out_ch, rgbd_elic** out)
+{
+    if (!out || in_ch < 1 || in_ch > 1024 || out_ch < 1 || out_ch > 1024) return RGBD_EINVAL;
+    const int32_t slice = 96;
+    const int r = rgbd_elic_create(96, 96, &slice, 1, out);
+    if (r) return r;
+    (*out)->variant = 6;
+    (*out)->in_ch = in_ch;
+    (*out)->out_ch = out_ch;
+    (*out)->refnum = false;  // (a float block behind the entropy decoder: the single-chain arithmetic of the Swin path)
+    return RGBD_OK;
+}
+
+int rgbd_aligner_forward(rgbd_elic* m, const float* x_dev, const float* guided_dev, int32_t B, int32_t H, int32_t W,
+                         float* out_dev, void* stream)
+{
+    if (!m || m->variant != 6) return RGBD_EINVAL;
+    if (!m->finalized) return RGBD_ESTATE;
+    if (!x_dev || !guided_dev || !out_dev || B <= 0 || H <= 0 || W <= 0 || H % 8 || W % 8) return RGBD_EINVAL;
+    if (const int ur = m->use_stream(stream)) return ur;
+    char key[96];
+    snprintf(key, sizeof(key), "al|%d|%d|%d", B, H, W);
+    return run_sized(m, key, [&]() { return m->run_aligner(x_dev, guided_dev, B, H, W, out_dev); });
+}
+
 int rgbd_elic_clone_shared(const rgbd_elic* src, rgbd_elic** out)
 {
     if (!src || !out || !src->finalized) return RGBD_EINVAL;
@@ -937,6 +999,7 @@ int rgbd_elic_clone_shared(const rgbd_elic* src, rgbd_elic** out)
     m->slice_ch = src->slice_ch;
     m->variant = src->variant;
     m->in_ch = src->in_ch;
+    m->out_ch = src->out_ch;
     m->refnum = src->refnum;
     m->ref_threads = src->ref_threads;
     m->ref_tab = src->ref_tab;
@@ -1087,7 +1150,29 @@ int rgbd_elic_finalize(rgbd_elic* m)
     for (auto& kv : m->raw) {
         const std::string& name = kv.first;
         const HostTensor& t = kv.second;
-        if (ends_with(name, ".weight") && t.shape.size() == 4) {
+        if (ends_with(name, "recovery.weight") && t.shape.size() == 4 && t.shape[2] == 2 && t.shape[3] == 2) {
+            // Spatial_aligner.recovery = ConvTranspose2d(96, out, 2, 2) (spatialAligner.py:372-374): its taps do not overlap, so
+            // it is a 1x1 convolution to output channel co * 4 + dy * 2 + dx followed by a pixel shuffle (spatial_aligner()).
+            // Packed in plain channel order: the aligner runs the single-chain arithmetic.
+            const int ci_n = (int)t.shape[0], co_n = (int)t.shape[1];
+            HostTensor w1, b1;
+            w1.shape = {4 * co_n, ci_n, 1, 1};
+            w1.v.resize((size_t)4 * co_n * ci_n);
+            for (int ci = 0; ci < ci_n; ++ci)
+                for (int co = 0; co < co_n; ++co)
+                    for (int tap = 0; tap < 4; ++tap) w1.v[(size_t)(co * 4 + tap) * ci_n + ci] = t.v[((size_t)ci * co_n + co) * 4 + tap];
+            auto bit = m->raw.find(name.substr(0, name.size() - 6) + "bias");
+            if (bit != m->raw.end()) {
+                if ((int)bit->second.v.size() != co_n) return RGBD_EINVAL;
+                b1.shape = {4 * co_n};
+                b1.v.resize((size_t)4 * co_n);
+                for (int i = 0; i < 4 * co_n; ++i) b1.v[i] = bit->second.v[i / 4];
+            }
+            PackedConv pc;
+            const int r = pack_conv(w1, bit == m->raw.end() ? nullptr : &b1, false, &pc, gen.get(), 0, 0);
+            if (r) return r;
+            convs[name] = pc;
+        } else if (ends_with(name, ".weight") && t.shape.size() == 4) {
             // ConvTranspose2d layers of this model: g_s stages 1/6/12/17 and the h_s deconvs
             // (single-modal ELIC: g_s stages 1/5/10/14 and h_s.increase.*; stage numbers that are not a bare
             //  "<stage>.weight" in the other variant belong to blocks with sub-names, so the union is unambiguous)
@@ -1236,6 +1321,7 @@ int rgbd_elic_finalize(rgbd_elic* m)
 
 static int check_ready(const rgbd_elic* m)
 {
+    if (m && m->variant == 6) return RGBD_EINVAL;  // a Spatial_aligner handle has no codec calls
     if (!m || !m->finalized || !m->scale_table) return RGBD_ESTATE;
     for (int i = 0; i < 4; ++i)
         if (!m->tables[i].ready && !(m->single() && (i & 1))) return RGBD_ESTATE;  // single-modal: slots 0 and 2

@@ -323,6 +323,148 @@ int launch_window_attention(const float* qkv, int B, int H, int W, int C, int qc
 }
 
 // ---------------------------------------------------------------------------------------------
+// Guided (cross) window attention of Spatial_aligner (modules/transform/spatialAligner.py:138-170, 279-331): the query comes
+// from one token map, key and value from another ("guided"), head_dim 32.  q: [B,H,W,qcs] with channel = head*32 + d
+// (nn.Linear(dim, dim)); kv: [B,H,W,kvcs] with channel = which*C + head*32 + d, which 0 = k, 1 = v (nn.Linear(dim, 2*dim));
+// out: [B,H,W,ocs], channels [0, C).  The same form as window_attention_kernel -- one wavefront walks GWA_PAIRS (window,
+// head) pairs, v_mfma_f32_16x16x4_f32, the same operand layouts, bias / mask rule and softmax tree -- with
+//   S:  eight k-steps: A = (q * 32^-0.5)[token i = l % 16][d = 4 s + l / 16], B = k[token j = l % 16][d = 4 s + l / 16]; every
+//       score is one fused chain over d = 0 .. 31 in order, from 0.  q is scaled before the product as the reference does
+//       (:151): 32^-0.5 is no power of two, so scaling the score instead would round differently;
+//   O:  two 16x16 tiles (dims 0-15 and 16-31), four k-steps each over j = 0 .. 15 in order; A = P[i][j] from LDS for both,
+//       B = v[token j = 4 s + l / 16][dim l % 16 (+ 16)] straight from kv.
+#define GWA_PAIRS 4
+__global__ __launch_bounds__(256) void guided_window_attention_kernel(const float* __restrict__ qp, int qcs,
+                                                                      const float* __restrict__ kvp, int kvcs,
+                                                                      const float* __restrict__ rpb, float* __restrict__ out,
+                                                                      int ocs, int H, int W, int C, int heads, int shift, int npairs)
+{
+    __shared__ float sq[4][16][33], sk[4][16][33], sp[4][16][17];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int l15 = lane & 15, q = lane >> 4;
+    const int nwx = W / 4, nwy = H / 4;
+    for (int it = 0; it < GWA_PAIRS; ++it) {
+        const long long pair64 = ((long long)blockIdx.x * 4 + wv) * GWA_PAIRS + it;  // wave-uniform
+        if (pair64 >= npairs) break;
+        const int pair = (int)pair64;
+        const int head = pair % heads;
+        const int win = pair / heads;
+        const int wj = win % nwx, wi = (win / nwx) % nwy, b = win / (nwx * nwy);
+        const size_t img = (size_t)b * H * W;
+        // stage q (scaled) and k of this pair: lane loads token t = lane / 4, dims 8 (lane % 4) .. + 7 (128-byte rows)
+        {
+            const int t = lane >> 2, d0 = (lane & 3) * 8;
+            const int ys = wi * 4 + (t >> 2), xs = wj * 4 + (t & 3);
+            const int y = (ys + shift) % H, x = (xs + shift) % W;
+            const size_t pix = img + (size_t)y * W + x;
+            const float* pq = qp + pix * qcs + head * 32 + d0;
+            const float* pk = kvp + pix * kvcs + head * 32 + d0;
+            const f32x4 qa = *reinterpret_cast<const f32x4*>(pq), qb = *reinterpret_cast<const f32x4*>(pq + 4);
+            const f32x4 ka = *reinterpret_cast<const f32x4*>(pk), kb = *reinterpret_cast<const f32x4*>(pk + 4);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                sq[wv][t][d0 + e] = qa[e] * 0.17677669529663687f;  // head_dim ** -0.5, head_dim = 32
+                sq[wv][t][d0 + 4 + e] = qb[e] * 0.17677669529663687f;
+                sk[wv][t][d0 + e] = ka[e];
+                sk[wv][t][d0 + 4 + e] = kb[e];
+            }
+        }
+        // v operands straight from memory: lane (q, c = l15), tile h, k-step s: v[token 4 s + q][dim 16 h + c]
+        float vb[2][4];
+#pragma unroll
+        for (int sstep = 0; sstep < 4; ++sstep) {
+            const int t = 4 * sstep + q;
+            const int ys = wi * 4 + (t >> 2), xs = wj * 4 + (t & 3);
+            const int y = (ys + shift) % H, x = (xs + shift) % W;
+            const float* pv = kvp + (img + (size_t)y * W + x) * kvcs + C + head * 32 + l15;
+            vb[0][sstep] = pv[0];
+            vb[1][sstep] = pv[16];
+        }
+        __builtin_amdgcn_wave_barrier();
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // this wave's LDS writes have landed (its own region only)
+        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int sstep = 0; sstep < 8; ++sstep)
+            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(sq[wv][l15][4 * sstep + q], sk[wv][l15][4 * sstep + q], acc, 0, 0, 0);
+        // acc[r] = S[i = 4 q + r][j = l15]
+        const int j = l15, jy = j >> 2, jx = j & 3;
+        int reg_j = 0;
+        if (shift > 0) {
+            const int ys = wi * 4 + jy, xs = wj * 4 + jx;
+            reg_j = (ys < H - 4 ? 0 : (ys < H - shift ? 1 : 2)) * 3 + (xs < W - 4 ? 0 : (xs < W - shift ? 1 : 2));
+        }
+        float pr[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int i = 4 * q + r, iy = i >> 2, ix = i & 3;
+            float sc = acc[r] + rpb[((iy - jy + 3) * 7 + (ix - jx + 3)) * heads + head];  // relative_position_index, spatialAligner.py:118-128
+            if (shift > 0) {  // create_mask, spatialAligner.py:249-277
+                const int ys = wi * 4 + iy, xs = wj * 4 + ix;
+                const int reg_i = (ys < H - 4 ? 0 : (ys < H - shift ? 1 : 2)) * 3 + (xs < W - 4 ? 0 : (xs < W - shift ? 1 : 2));
+                if (reg_j != reg_i) sc += -100.0f;
+            }
+            // softmax over the row, the tree of window_attention_kernel
+            float mx = sc;
+            mx = fmaxf(mx, __shfl_xor(mx, 1));
+            mx = fmaxf(mx, __shfl_xor(mx, 2));
+            mx = fmaxf(mx, __shfl_xor(mx, 4));
+            mx = fmaxf(mx, __shfl_xor(mx, 8));
+            const float ex = expf(sc - mx);
+            float sum = ex + __shfl_down(ex, 1);
+            sum += __shfl_down(ex, 2);
+            sum += __shfl_down(ex, 3);
+            sum = __shfl(sum, lane & ~3);
+            sum += __shfl_xor(sum, 4);
+            sum += __shfl_xor(sum, 8);
+            pr[r] = ex / sum;
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) sp[wv][4 * q + r][l15] = pr[r];
+        __builtin_amdgcn_wave_barrier();
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        f32x4 o0 = {0.f, 0.f, 0.f, 0.f}, o1 = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int sstep = 0; sstep < 4; ++sstep) {
+            const float a = sp[wv][l15][4 * sstep + q];
+            o0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a, vb[0][sstep], o0, 0, 0, 0);
+            o1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a, vb[1][sstep], o1, 0, 0, 0);
+        }
+        // o0[r] / o1[r] = O[token 4 q + r][dim l15 / 16 + l15]: 64-byte rows per store instruction
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int t = 4 * q + r;
+            const int ys = wi * 4 + (t >> 2), xs = wj * 4 + (t & 3);
+            const int y = (ys + shift) % H, x = (xs + shift) % W;
+            float* po = out + (img + (size_t)y * W + x) * ocs + head * 32 + l15;
+            po[0] = o0[r];
+            po[16] = o1[r];
+        }
+        __builtin_amdgcn_wave_barrier();  // the next pair overwrites this wave's LDS region
+    }
+}
+
+// Everything the kernel assumes is checked here (the engine and the operator boundary both come through): window 4,
+// head_dim 32, 16-byte vector loads of q and kv.  Nothing is written on a refusal.
+int launch_guided_window_attention(const float* q, int qcs, const float* kv, int kvcs, int B, int H, int W, int C, int heads,
+                                   int shift, const float* rpb, float* out, int ocs, hipStream_t s)
+{
+    if (!q || !kv || !rpb || !out || B <= 0 || H <= 0 || W <= 0 || heads <= 0) return RGBD_EINVAL;
+    if (H % 4 || W % 4 || C != heads * 32 || shift < 0 || shift >= 4 || qcs < C || kvcs < 2 * C || ocs < C) return RGBD_EINVAL;
+    if (qcs % 4 || kvcs % 4 || ((uintptr_t)q & 15) || ((uintptr_t)kv & 15)) return RGBD_EINVAL;
+    size_t pairs = (size_t)(H / 4) * (W / 4);  // (checked factor by factor: the product of four ints can pass 2^64)
+    if (pairs > 0x7fffffffu) return RGBD_EINVAL;
+    pairs *= (size_t)B;
+    if (pairs > 0x7fffffffu) return RGBD_EINVAL;
+    pairs *= (size_t)heads;
+    if (pairs > 0x7fffffffu) return RGBD_EINVAL;
+    const size_t blocks = (pairs + 4 * GWA_PAIRS - 1) / (4 * GWA_PAIRS);
+    hipLaunchKernelGGL(guided_window_attention_kernel, dim3((unsigned)blocks), dim3(256), 0, s, q, qcs, kv, kvcs, rpb, out, ocs, H, W,
+                       C, heads, shift, (int)pairs);
+    HIP_TRY(hipGetLastError());
+    return RGBD_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
 // PatchMerging gather (stf_united.py:240-245): y[b,h,w] = cat(x[2h,2w], x[2h+1,2w], x[2h,2w+1], x[2h+1,2w+1]) on channels
 __global__ void patch_merge_gather_kernel(const float* __restrict__ x, int B, int H, int W, int C, int xcs,
                                           float* __restrict__ y, int ycs)
@@ -398,6 +540,13 @@ extern "C" int rgbd_window_attention(const float* qkv, int32_t B, int32_t H, int
     if (pair && !wa_set_ok(qkv1, rpb1, out1)) return RGBD_EINVAL;
     return launch_window_attention(qkv, B, H, W, C, qcs, heads, shift, rpb, out, ocs, (hipStream_t)stream, pair ? qkv1 : nullptr,
                                    pair ? rpb1 : nullptr, pair ? out1 : nullptr);
+}
+
+extern "C" int rgbd_guided_window_attention(const float* q, int32_t qcs, const float* kv, int32_t kvcs, int32_t B, int32_t H,
+                                            int32_t W, int32_t C, int32_t heads, int32_t shift, const float* rpb, float* out,
+                                            int32_t ocs, void* stream)
+{
+    return launch_guided_window_attention(q, qcs, kv, kvcs, B, H, W, C, heads, shift, rpb, out, ocs, (hipStream_t)stream);
 }
 
 extern "C" int rgbd_patch_merge_gather(const float* x, int32_t B, int32_t H, int32_t W, int32_t C, int32_t xcs, float* y,

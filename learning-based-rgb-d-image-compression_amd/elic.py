@@ -5,6 +5,10 @@
     out = net.compress(x)                              -> {"strings": [[y], [z]*B], "shape": (H/64, W/64)}
     rec = net.decompress(out["strings"], out["shape"]) -> {"x_hat": [B,C,H,W] (not clamped, as in the reference), "cost_time"}
 
+ELIC(config, channel, return_mid=True) (the aux network of the reference's TesterMaster / trainer_master): decompress() and
+forward() also return "up1", "up2", "up3", the outputs of the first three transposed convolutions of g_s
+(modules/transform/synthesis.py:54-67): [B,N,H/8,W/8], [B,N,H/4,W/4], [B,N,H/2,W/2].
+
 Same engine, kernels and rules as ELIC_united (no CPU path); only the layer graph differs (no cross-modal fusion, one
 entropy bottleneck, EntropyParameters = three 1x1 convolutions).
 """
@@ -21,10 +25,10 @@ from .entropy_models import EntropyBottleneck, GaussianConditional, get_scale_ta
 
 class ELIC(ELIC_united):
     _MODEL = "ELIC"
+    return_mid = False  # (class default: the subclasses that build themselves without this __init__ never return them)
 
     def __init__(self, config=None, channel=3, return_mid=False, init_seed=0, **kwargs):
-        if return_mid:
-            raise NotImplementedError("return_mid (intermediate up-sampling outputs) is not part of the inference path")
+        self.return_mid = bool(return_mid)  # models/elic.py:17,44
         self.config = model_config() if config is None else config
         self.channel = channel
         self.N, self.M = int(self.config["N"]), int(self.config["M"])
@@ -99,11 +103,23 @@ class ELIC(ELIC_united):
         out = torch.empty((B, self.channel, zh * 64, zw * 64), dtype=torch.float32, device=self._device)
         k1, py, ly = self._pack_strings(ys)
         k2, pz, lz = self._pack_strings(zs)
-        check(lib().rgbd_elic_decompress_single(self._h, py, ly, len(ys), pz, lz, B, zh, zw, ctypes.c_void_p(out.data_ptr()),
-                                                self._stream_ptr()), "decompress")
+        if self.return_mid:  # models/elic.py:318-329
+            ups = self._mid_tensors(B, zh * 64, zw * 64)
+            check(lib().rgbd_elic_decompress_single_mid(self._h, py, ly, len(ys), pz, lz, B, zh, zw, ctypes.c_void_p(out.data_ptr()),
+                                                        *[ctypes.c_void_p(u.data_ptr()) for u in ups], self._stream_ptr()),
+                  "decompress")
+        else:
+            check(lib().rgbd_elic_decompress_single(self._h, py, ly, len(ys), pz, lz, B, zh, zw, ctypes.c_void_p(out.data_ptr()),
+                                                    self._stream_ptr()), "decompress")
         torch.cuda.current_stream().synchronize()
         del k1, k2
-        return {"x_hat": out, "cost_time": time.process_time() - t0}
+        rec = {"x_hat": out, "cost_time": time.process_time() - t0}
+        if self.return_mid:
+            rec.update(up1=ups[0], up2=ups[1], up3=ups[2])
+        return rec
+
+    def _mid_tensors(self, B, H, W):
+        return [torch.empty((B, self.N, H >> k, W >> k), dtype=torch.float32, device=self._device) for k in (3, 2, 1)]
 
     def forward(self, x):  # models/elic.py:60-161 (eval mode, quant = "ste")
         """Eval-mode forward(): {"x_hat", "likelihoods": {"y_likelihoods", "z_likelihoods"}} like the reference (x_hat is not
@@ -122,6 +138,13 @@ class ELIC(ELIC_united):
         xh = torch.empty((B, self.channel, H, W), dtype=torch.float32, device=self._device)
         ly = torch.empty((B, self.M, H // 16, W // 16), dtype=torch.float32, device=self._device)
         lz = torch.empty((B, self.N, H // 64, W // 64), dtype=torch.float32, device=self._device)
+        if self.return_mid:  # models/elic.py:159-170
+            ups = self._mid_tensors(B, H, W)
+            check(lib().rgbd_elic_forward_single_mid(self._h, ctypes.c_void_p(x.data_ptr()), B, H, W, ctypes.c_void_p(xh.data_ptr()),
+                                                     ctypes.c_void_p(ly.data_ptr()), ctypes.c_void_p(lz.data_ptr()),
+                                                     *[ctypes.c_void_p(u.data_ptr()) for u in ups], self._stream_ptr()), "forward")
+            return {"x_hat": xh, "likelihoods": {"y_likelihoods": ly, "z_likelihoods": lz}, "up1": ups[0], "up2": ups[1],
+                    "up3": ups[2]}
         check(lib().rgbd_elic_forward_single(self._h, ctypes.c_void_p(x.data_ptr()), B, H, W, ctypes.c_void_p(xh.data_ptr()),
                                              ctypes.c_void_p(ly.data_ptr()), ctypes.c_void_p(lz.data_ptr()),
                                              self._stream_ptr()), "forward")

@@ -13,7 +13,7 @@ from collections import OrderedDict
 
 import numpy as np
 
-from .arch import (STF_SLICES, Entry, ckbd_config, ckbd_entries, elic_entries, elic_united_entries, elic_united_r2d_entries, model_config, stf_config,
+from .arch import (STF_SLICES, Entry, spatial_aligner_entries, ckbd_config, ckbd_entries, elic_entries, elic_united_entries, elic_united_r2d_entries, model_config, stf_config,
                    stf_entries, stf_single_config, stf_united_entries)
 
 _IH_STD = math.sqrt(4.0 * (65536.0**2 - 1.0) / 12.0)  # std of the sum of four uniform 16-bit ints
@@ -119,7 +119,8 @@ def make_tensor(name: str, e: Entry, seed: int) -> np.ndarray:
 
 
 def synthetic_state_dict(seed: int = 0, config=None, stress: bool = True, as_torch: bool = True,
-                         model: str = "ELIC_united", channel: int = 3, recipe: str = None, N: int = 192):
+                         model: str = "ELIC_united", channel: int = 3, recipe: str = None, N: int = 192,
+                         in_channel: int = 192, out_channel: int = 192):
     """Full state_dict (parameters + buffers) of ELIC_united (default), ELIC_united_R2D, STF_united, the single-modal STF
     (model="STF": recipes "stress" and "plain"), the checkerboard Cheng2020 model (model="ckbd", width N, the same two recipes)
     or the single-modal ELIC with deterministic synthetic values.  `recipe`: "stress" (= stress=True, the default: ~22 bpp, wide CDF rows, 17 % escapes -- the worst
@@ -127,7 +128,18 @@ def synthetic_state_dict(seed: int = 0, config=None, stress: bool = True, as_tor
     bottom of the scale table, ~1 bpp per modality like a trained q=2_2 model -- the coder's realistic operating point),
     "high_rate" (ELIC_united only: latents of tens to hundreds, predicted scales of 10 ... 100 -- scale-table rows of 300 ...
     3000 entries, what a high-quality checkpoint makes the decoder search) or "plain" (default initialisation, everything
-    quantises to zero)."""
+    quantises to zero).  model="Spatial_aligner" (in_channel, out_channel): the guided-attention block alone, always with its
+    stress recipe (_apply_stress_aligner)."""
+    if model == "Spatial_aligner":
+        sd = OrderedDict()
+        for name, e in spatial_aligner_entries(in_channel, out_channel).items():
+            sd[name] = make_tensor(name, e, seed)
+        _apply_stress_aligner(sd, seed)
+        if as_torch:
+            import torch
+
+            return OrderedDict((k, torch.from_numpy(np.ascontiguousarray(v))) for k, v in sd.items())
+        return sd
     if recipe is not None:
         if recipe not in ("stress", "trained_like", "high_rate", "plain"):
             raise ValueError(f"unknown recipe {recipe}")
@@ -176,6 +188,26 @@ def synthetic_state_dict(seed: int = 0, config=None, stress: bool = True, as_tor
 
 
 STF_Y_GAIN = 12.0
+ALIGNER_QK_GAIN = 3.5
+
+
+def _apply_stress_aligner(sd, seed):
+    """Spatial_aligner: what makes a wrong attention visible.  Relative position biases of order 1 (std 1), LayerNorm weights
+    in [0.5, 1.5], and the query and key projections scaled so that the scores (std ~0.3 with the default initialisation on
+    normalised tokens) reach |S| >= 10: a softmax that is far from uniform, so shift, mask, bias and the q / k / v roles
+    all move the output."""
+    for k in range(2):
+        p = f"blocks.{k}"
+        sd[f"{p}.attn.relative_position_bias_table"] = (sd[f"{p}.attn.relative_position_bias_table"] / np.float32(0.3)).astype(np.float32)
+        for n in ("norm1", "norm2"):
+            name = f"{p}.{n}.weight"
+            sd[name] = (1.0 + uniform_like(name + "#stress", seed, sd[name].shape, -0.5, 0.5)).astype(np.float32)
+        g = np.float32(ALIGNER_QK_GAIN)
+        sd[f"{p}.attn.qkv1.weight"] = sd[f"{p}.attn.qkv1.weight"] * g
+        sd[f"{p}.attn.qkv1.bias"] = sd[f"{p}.attn.qkv1.bias"] * g
+        E = sd[f"{p}.attn.qkv1.weight"].shape[0]
+        sd[f"{p}.attn.qkv2.weight"][:E] *= g  # the key half; the value half keeps its scale
+        sd[f"{p}.attn.qkv2.bias"][:E] *= g
 
 
 def _apply_stress(sd, cfg, transforms=True):

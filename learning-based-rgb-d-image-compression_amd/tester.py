@@ -447,7 +447,7 @@ class TesterSingle(TesterUnited):
         return float(filesize(fn)) * 8 / (H * W), enc_time
 
     # tester_single.py:144-170
-    def decompress_one_image(self, stream_path, img_name, mode="reflect0"):
+    def decompress_one_image(self, stream_path, img_name, mode="reflect0", return_mid=False):
         with Path(os.path.join(stream_path, img_name)).open("rb") as f:
             original_size = read_uints(f, 2)
             strings, shape = read_body(f)
@@ -456,6 +456,8 @@ class TesterSingle(TesterUnited):
         out = self.net.decompress(strings, shape)
         torch.cuda.synchronize()
         dec_time = time.time() - start
+        if return_mid:  # tester_single.py:148-149: the padded x_hat and the whole result (x_hat, up1, up2, up3), not cropped
+            return out["x_hat"], dec_time, out
         cropper = crop0 if mode.find("0") != -1 else crop1
         return cropper(out["x_hat"], original_size), dec_time
 
