@@ -1,4 +1,5 @@
-"""Single-modal `ELIC` on MI355X: the reference's model API (models/elic.py) over the HIP engine.
+"""Single-modal `ELIC` on MI355X: the reference's model API (models/elic.py) over the HIP engine -- and `SingleCodec`, the
+base it shares with the other one-tensor models (stf.py, ckbd.py).
 
     net = ELIC(config=model_config(), channel=3).eval()
     net.load_state_dict(checkpoint["state_dict"]); net.update(force=True); net = net.to("cuda")
@@ -12,83 +13,40 @@ forward() also return "up1", "up2", "up3", the outputs of the first three transp
 Same engine, kernels and rules as ELIC_united (no CPU path); only the layer graph differs (no cross-modal fusion, one
 entropy bottleneck, EntropyParameters = three 1x1 convolutions).
 """
-import ctypes
 import time
 
 import torch
 
 from ._lib import check, lib
 from .arch import elic_entries, model_config
-from .elic_united import ELIC_united, _LazyStore
-from .entropy_models import EntropyBottleneck, GaussianConditional, get_scale_table
+from .elic_united import Codec
 
 
-class ELIC(ELIC_united):
-    _MODEL = "ELIC"
-    return_mid = False  # (class default: the subclasses that build themselves without this __init__ never return them)
+class SingleCodec(Codec):
+    """One tensor per call: compress(x) / decompress(strings, shape) / forward(x) over the engine's *_single entry points."""
+    _MODALITIES = (("", 0, 2),)
+    _LIKELIHOOD_KEYS = ("y", "z")  # of forward()["likelihoods"]
 
-    def __init__(self, config=None, channel=3, return_mid=False, init_seed=0, **kwargs):
-        self.return_mid = bool(return_mid)  # models/elic.py:17,44
-        self.config = model_config() if config is None else config
-        self.channel = channel
-        self.N, self.M = int(self.config["N"]), int(self.config["M"])
-        self.slice_ch = list(self.config["slice_ch"])
-        self.slice_num = len(self.slice_ch)
-        self.quant = self.config.get("quant", "ste") if hasattr(self.config, "get") else "ste"
-        self.training = False
-        self.per_image_streams = False
-        self._entries = elic_entries(self.config, channel)
-        self._init_seed = init_seed
-        self._params = None
-        self.gaussian_conditional = GaussianConditional(None)
-        self._store = _LazyStore(self)
-        self.entropy_bottleneck = EntropyBottleneck(self._store, "entropy_bottleneck")
-        self._h = None
-        self._device = None
-        self._dirty = True
-        self._gen = 0
-        self._parent = None
+    def _synth_args(self):
+        return {**super()._synth_args(), "channel": self.channel}
 
-    def _materialize(self):
-        if self._params is None:
-            from . import synth
+    def _mid_tensors(self, B, H, W):
+        """Tensors for what a call returns besides x_hat (none: the *_mid entry points belong to ELIC(return_mid=True))."""
+        return []
 
-            self._params = synth.synthetic_state_dict(self._init_seed, self.config, stress=False, model="ELIC",
-                                                      channel=self.channel)
-        return self._params
-
-    def _holders(self):
-        return {"gaussian_conditional": self.gaussian_conditional, "entropy_bottleneck": self.entropy_bottleneck}
-
-    def _table_slots(self):
-        return [(0, self.gaussian_conditional), (2, self.entropy_bottleneck)]
-
-    def _create_engine(self):
-        h = ctypes.c_void_p()
-        sl = (ctypes.c_int32 * len(self.slice_ch))(*self.slice_ch)
-        check(lib().rgbd_elic_create_single(self.N, self.M, sl, len(self.slice_ch), int(self.channel), ctypes.byref(h)),
-              "elic_create_single")
-        return h
-
-    def update(self, scale_table=None, force=False):  # models/elic.py:327-332
-        self._materialize()
-        if scale_table is None:
-            scale_table = get_scale_table()
-        updated = self.gaussian_conditional.update_scale_table(scale_table, force=force)
-        updated |= bool(self.entropy_bottleneck.update(force=force))
-        self._dirty = True
-        return updated
+    def _check_image(self, x):
+        if x.dim() != 4 or x.size(1) != self.channel:
+            raise ValueError(f"expected x [B,{self.channel},H,W]")
+        if x.shape[2] % 64 or x.shape[3] % 64:
+            raise ValueError("H and W must be multiples of 64 (pad first: dataset/utils.py:58-67)")
+        return x.shape[0], x.shape[2], x.shape[3]
 
     def compress(self, x):  # models/elic.py:161-253
         self._ready()
-        if x.dim() != 4 or x.size(1) != self.channel:
-            raise ValueError(f"expected x [B,{self.channel},H,W]")
-        B, _, H, W = x.shape
-        if H % 64 or W % 64:
-            raise ValueError("H and W must be multiples of 64 (pad first: dataset/utils.py:58-67)")
+        B, H, W = self._check_image(x)
         x = x.to(self._device, torch.float32).contiguous()
-        check(lib().rgbd_elic_compress_single(self._h, ctypes.c_void_p(x.data_ptr()), B, H, W,
-                                              1 if self.per_image_streams else 0, self._stream_ptr()), "compress")
+        check(lib().rgbd_elic_compress_single(self._h, self._ptr(x), B, H, W, 1 if self.per_image_streams else 0,
+                                              self._stream_ptr()), "compress")
         return {"strings": [self._fetch_streams(0, 0), self._fetch_streams(0, 1)], "shape": torch.Size((H // 64, W // 64))}
 
     def decompress(self, strings, shape):  # models/elic.py:255-325
@@ -103,56 +61,51 @@ class ELIC(ELIC_united):
         out = torch.empty((B, self.channel, zh * 64, zw * 64), dtype=torch.float32, device=self._device)
         k1, py, ly = self._pack_strings(ys)
         k2, pz, lz = self._pack_strings(zs)
-        if self.return_mid:  # models/elic.py:318-329
-            ups = self._mid_tensors(B, zh * 64, zw * 64)
-            check(lib().rgbd_elic_decompress_single_mid(self._h, py, ly, len(ys), pz, lz, B, zh, zw, ctypes.c_void_p(out.data_ptr()),
-                                                        *[ctypes.c_void_p(u.data_ptr()) for u in ups], self._stream_ptr()),
-                  "decompress")
-        else:
-            check(lib().rgbd_elic_decompress_single(self._h, py, ly, len(ys), pz, lz, B, zh, zw, ctypes.c_void_p(out.data_ptr()),
-                                                    self._stream_ptr()), "decompress")
+        ups = self._mid_tensors(B, zh * 64, zw * 64)  # models/elic.py:318-329
+        fn = lib().rgbd_elic_decompress_single_mid if ups else lib().rgbd_elic_decompress_single
+        check(fn(self._h, py, ly, len(ys), pz, lz, B, zh, zw, self._ptr(out), *map(self._ptr, ups), self._stream_ptr()),
+              "decompress")
         torch.cuda.current_stream().synchronize()
         del k1, k2
-        rec = {"x_hat": out, "cost_time": time.process_time() - t0}
-        if self.return_mid:
-            rec.update(up1=ups[0], up2=ups[1], up3=ups[2])
-        return rec
+        return {"x_hat": out, "cost_time": time.process_time() - t0, **dict(zip(("up1", "up2", "up3"), ups))}
 
-    def _mid_tensors(self, B, H, W):
-        return [torch.empty((B, self.N, H >> k, W >> k), dtype=torch.float32, device=self._device) for k in (3, 2, 1)]
-
-    def forward(self, x):  # models/elic.py:60-161 (eval mode, quant = "ste")
-        """Eval-mode forward(): {"x_hat", "likelihoods": {"y_likelihoods", "z_likelihoods"}} like the reference (x_hat is not
-        clamped; y_hat = round(y - mean) + mean slice by slice, Gaussian / factorised-prior likelihoods)."""
+    def forward(self, x):  # models/elic.py:60-161, stf.py:618-678, Cheng2020withCKBD.py:52-71 (eval mode, quant = "ste")
+        """Eval-mode forward(): {"x_hat", "likelihoods": {y key, z key}} like the reference (x_hat is not clamped; Gaussian /
+        factorised-prior likelihoods).  ELIC: y_hat = round(y - mean) + mean slice by slice, keys "y_likelihoods" /
+        "z_likelihoods".  STF, ckbd: keys "y" / "z"; ckbd: y_hat = round(y), one parameter pass over the context with its
+        anchor outputs zeroed."""
         self._ready()
         if self.training:
             raise RuntimeError("forward() is built for eval mode (inference path); call .eval() first")
         if self.quant != "ste":  # models/elic.py:84-99: any other setting rounds without the mean (and adds noise in training)
             raise NotImplementedError(f"forward() implements config quant = 'ste' (the reference's model_config); got {self.quant!r}")
-        if x.dim() != 4 or x.size(1) != self.channel:
-            raise ValueError(f"expected x [B,{self.channel},H,W]")
-        B, _, H, W = x.shape
-        if H % 64 or W % 64:
-            raise ValueError("H and W must be multiples of 64 (pad first: dataset/utils.py:58-67)")
+        B, H, W = self._check_image(x)
         x = x.to(self._device, torch.float32).contiguous()
         xh = torch.empty((B, self.channel, H, W), dtype=torch.float32, device=self._device)
         ly = torch.empty((B, self.M, H // 16, W // 16), dtype=torch.float32, device=self._device)
         lz = torch.empty((B, self.N, H // 64, W // 64), dtype=torch.float32, device=self._device)
-        if self.return_mid:  # models/elic.py:159-170
-            ups = self._mid_tensors(B, H, W)
-            check(lib().rgbd_elic_forward_single_mid(self._h, ctypes.c_void_p(x.data_ptr()), B, H, W, ctypes.c_void_p(xh.data_ptr()),
-                                                     ctypes.c_void_p(ly.data_ptr()), ctypes.c_void_p(lz.data_ptr()),
-                                                     *[ctypes.c_void_p(u.data_ptr()) for u in ups], self._stream_ptr()), "forward")
-            return {"x_hat": xh, "likelihoods": {"y_likelihoods": ly, "z_likelihoods": lz}, "up1": ups[0], "up2": ups[1],
-                    "up3": ups[2]}
-        check(lib().rgbd_elic_forward_single(self._h, ctypes.c_void_p(x.data_ptr()), B, H, W, ctypes.c_void_p(xh.data_ptr()),
-                                             ctypes.c_void_p(ly.data_ptr()), ctypes.c_void_p(lz.data_ptr()),
-                                             self._stream_ptr()), "forward")
-        return {"x_hat": xh, "likelihoods": {"y_likelihoods": ly, "z_likelihoods": lz}}
+        ups = self._mid_tensors(B, H, W)  # models/elic.py:159-170
+        fn = lib().rgbd_elic_forward_single_mid if ups else lib().rgbd_elic_forward_single
+        check(fn(self._h, self._ptr(x), B, H, W, self._ptr(xh), self._ptr(ly), self._ptr(lz), *map(self._ptr, ups),
+                 self._stream_ptr()), "forward")
+        return {"x_hat": xh, "likelihoods": dict(zip(self._LIKELIHOOD_KEYS, (ly, lz))), **dict(zip(("up1", "up2", "up3"), ups))}
 
     __call__ = forward
 
-    def compress_united(self, *a, **k):
-        raise NotImplementedError("ELIC is single-modal")
 
-    decompress_united = compress_united
+class ELIC(SingleCodec):
+    _MODEL = "ELIC"
+    _LIKELIHOOD_KEYS = ("y_likelihoods", "z_likelihoods")
+
+    def __init__(self, config=None, channel=3, return_mid=False, init_seed=0, **kwargs):
+        config = model_config() if config is None else config
+        super().__init__(elic_entries(config, channel), config, channel, init_seed)
+        self.return_mid = bool(return_mid)  # models/elic.py:17,44
+
+    def _create_engine(self):
+        return self._create("rgbd_elic_create_single", self.N, self.M, self.slice_ch, self.channel)
+
+    def _mid_tensors(self, B, H, W):
+        if not self.return_mid:
+            return []
+        return [torch.empty((B, self.N, H >> k, W >> k), dtype=torch.float32, device=self._device) for k in (3, 2, 1)]

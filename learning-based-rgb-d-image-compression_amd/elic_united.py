@@ -1,4 +1,5 @@
-"""`ELIC_united` on MI355X: the reference's model API (models/elic_united.py) over the HIP engine.
+"""`ELIC_united` on MI355X: the reference's model API (models/elic_united.py) over the HIP engine -- and `Codec`, the base of
+every entropy-coding model of this package (engine_module.py has the class tree).
 
 Drop-in surface for testing/tester.py:55-108 and testing/tester_united.py:141-195:
     net = ELIC_united(config=model_config(), channel=4).eval()
@@ -7,7 +8,7 @@ Drop-in surface for testing/tester.py:55-108 and testing/tester_united.py:141-19
     rec = net.decompress(out["r_strings"], out["d_strings"], out["shape"])  -> {"x_hat": {"r","d"}, "cost_time"}
 
 The network, the checkerboard entropy model and the rANS coder all run inside librgbd_amd.so (hand-written gfx950
-kernels); this class only holds the checkpoint, builds the integer tables once (update()) and marshals pointers.
+kernels); these classes only hold the checkpoint, build the integer tables once (update()) and marshal pointers.
 There is no CPU execution path: compress()/decompress() raise if the HIP library or a GPU is missing.
 """
 import ctypes
@@ -18,82 +19,49 @@ from collections import OrderedDict
 import numpy as np
 import torch
 
-from . import synth
-from ._lib import RgbdError, check, lib
+from ._lib import check, lib
 from .arch import elic_united_entries, model_config
+from .engine_module import EngineModule
 from .entropy_models import EntropyBottleneck, GaussianConditional, get_scale_table
 
 _TABLE_KEYS = ("_offset", "_quantized_cdf", "_cdf_length")
 _log = logging.getLogger("rgbd_amd")
 
 
-class ELIC_united:
-    def __init__(self, config=None, channel=4, init_seed=0, **kwargs):
-        self.config = model_config() if config is None else config
+class Codec(EngineModule):
+    """An engine with entropy tables: the table holders, state_dict / load_state_dict / update(), the streams of the last
+    compress(), and the debug / profile hooks.  A subclass names its modalities and writes compress / decompress / forward."""
+    _CALLS = "compress()/decompress()"
+    _MODALITIES = ()  # (state_dict prefix, engine table slot of the Gaussian conditional, slot of the entropy bottleneck)
+    _tile_mode = None
+
+    def __init__(self, entries, config, channel, init_seed=0):
+        super().__init__(entries, init_seed)
+        self.config = config
         self.channel = channel
-        self.N, self.M = int(self.config["N"]), int(self.config["M"])
-        self.slice_ch = list(self.config["slice_ch"])
+        self.N, self.M = int(config["N"]), int(config["M"])
+        self.slice_ch = list(config["slice_ch"])
         self.slice_num = len(self.slice_ch)
-        self.quant = self.config.get("quant", "ste") if hasattr(self.config, "get") else "ste"
+        self.quant = config.get("quant", "ste") if hasattr(config, "get") else "ste"
         self.training = False
         self.per_image_streams = False  # False = reference format: one y-stream per modality for the whole batch
-        self._entries = elic_united_entries(self.config)
-        self._init_seed = init_seed
-        self._params = None  # name -> torch CPU tensor (parameters and float buffers)
-        self.rgb_gaussian_conditional = GaussianConditional(None)
-        self.depth_gaussian_conditional = GaussianConditional(None)
         self._store = _LazyStore(self)
-        self.rgb_entropy_bottleneck = EntropyBottleneck(self._store, "rgb_entropy_bottleneck")
-        self.depth_entropy_bottleneck = EntropyBottleneck(self._store, "depth_entropy_bottleneck")
-        self._h = None
-        self._device = None
-        self._dirty = True
-        self._gen = 0        # bumped by every upload of weights / tables to the GPU
-        self._parent = None  # set on shared-weight clones (clone_shared)
+        for prefix, _, _ in self._MODALITIES:
+            setattr(self, prefix + "gaussian_conditional", GaussianConditional(None))
+            setattr(self, prefix + "entropy_bottleneck", EntropyBottleneck(self._store, prefix + "entropy_bottleneck"))
 
-    # ---- torch.nn.Module-like surface ------------------------------------------------------------------
-    _MODEL = "ELIC_united"
-
-    def _materialize(self):
-        if self._params is None:
-            self._params = synth.synthetic_state_dict(self._init_seed, self.config, stress=False, model=self._MODEL)
-        return self._params
+    def _synth_args(self):
+        return {"config": self.config, "stress": False}
 
     def _holders(self):
         """state_dict prefix -> table holder."""
-        return {"rgb_gaussian_conditional": self.rgb_gaussian_conditional,
-                "depth_gaussian_conditional": self.depth_gaussian_conditional,
-                "rgb_entropy_bottleneck": self.rgb_entropy_bottleneck,
-                "depth_entropy_bottleneck": self.depth_entropy_bottleneck}
+        return {p + kind: getattr(self, p + kind) for kind in ("gaussian_conditional", "entropy_bottleneck")
+                for p, _, _ in self._MODALITIES}
 
     def _table_slots(self):
-        """(engine table slot, holder): 0/1 gaussian rgb/depth, 2/3 bottleneck rgb/depth."""
-        return [(0, self.rgb_gaussian_conditional), (1, self.depth_gaussian_conditional),
-                (2, self.rgb_entropy_bottleneck), (3, self.depth_entropy_bottleneck)]
-
-    def _create_engine(self):
-        h = ctypes.c_void_p()
-        sl = (ctypes.c_int32 * len(self.slice_ch))(*self.slice_ch)
-        check(lib().rgbd_elic_create(self.N, self.M, sl, len(self.slice_ch), ctypes.byref(h)), "elic_create")
-        return h
-
-    def eval(self):
-        self.training = False
-        return self
-
-    def train(self, mode=True):
-        if mode:
-            raise NotImplementedError("the MI355X path is inference-only (training is out of scope, DESIGN.md)")
-        return self
-
-    def parameters(self):
-        p = self._materialize()
-        for name, e in self._entries.items():
-            if e.is_param:
-                yield p[name]
-
-    def count_parameters(self, only_trainable=False):
-        return sum(p.numel() for p in self.parameters())
+        """(engine table slot, holder), the Gaussian conditionals first: 0/1 gaussian rgb/depth, 2/3 bottleneck rgb/depth."""
+        return [(g, getattr(self, p + "gaussian_conditional")) for p, g, _ in self._MODALITIES] + \
+               [(b, getattr(self, p + "entropy_bottleneck")) for p, _, b in self._MODALITIES]
 
     def state_dict(self):
         p = self._materialize()
@@ -154,114 +122,37 @@ class ELIC_united:
         return None
 
     def update(self, scale_table=None, force=False):
-        """models/elic_united.py:580-586 + compressai/models/priors.py:73-92."""
+        """models/elic_united.py:580-586, models/elic.py:327-332 + compressai/models/priors.py:73-92."""
         self._require_owner("update")
         self._materialize()
         if scale_table is None:
             scale_table = get_scale_table()
-        r = self.rgb_gaussian_conditional.update_scale_table(scale_table, force=force)
-        d = self.depth_gaussian_conditional.update_scale_table(scale_table, force=force)
-        eb = False
-        for m in (self.rgb_entropy_bottleneck, self.depth_entropy_bottleneck):
-            eb |= bool(m.update(force=force))
+        slots = self._table_slots()
+        gc = [h.update_scale_table(scale_table, force=force) for which, h in slots if which < 2]
+        eb = [bool(h.update(force=force)) for which, h in slots if which >= 2]
         self._dirty = True
-        return (r & d) | eb
-
-    def to(self, device):
-        dev = torch.device(device)
-        if dev.type != "cuda":
-            raise RgbdError("ELIC_united (rgbd_amd) runs on the GPU only: use .to('cuda'); there is no CPU path")
-        if not torch.cuda.is_available():
-            raise RgbdError("no HIP device visible to torch")
-        self._device = torch.device("cuda", torch.cuda.current_device() if dev.index is None else dev.index)
-        self._upload()
-        return self
-
-    def cuda(self, device=None):
-        return self.to("cuda" if device is None else f"cuda:{int(device)}")
+        return all(gc) | any(eb)
 
     # ---- engine ------------------------------------------------------------------------------------
-    def _upload(self):
-        L = lib()
-        torch.cuda.set_device(self._device)
-        if self._h is None:
-            self._h = self._create_engine()
-        p = self._materialize()
-        for name, e in self._entries.items():
-            if not e.is_param:
-                continue
-            t = p[name].detach().float().contiguous()
-            a = t.numpy()
-            if e.kind == "linear_w" and ".fc." not in name:  # nn.Linear of the Swin blocks -> 1x1 convolution
-                a = a.reshape(a.shape[0], a.shape[1], 1, 1)
-            shape = (ctypes.c_int64 * a.ndim)(*a.shape)
-            check(L.rgbd_elic_set_tensor(self._h, name.encode(), a.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), shape,
-                                         a.ndim), f"set_tensor({name})")
+    def _upload_extras(self, L):
         for which, holder in self._table_slots():
             cdf, sizes, offs = holder.numpy_tables()  # raises "Uninitialized CDFs. Run update() first"
             i32p = ctypes.POINTER(ctypes.c_int32)
             check(L.rgbd_elic_set_tables(self._h, which, cdf.ctypes.data_as(i32p), int(cdf.shape[1]),
                                          sizes.ctypes.data_as(i32p), offs.ctypes.data_as(i32p), int(cdf.shape[0])),
                   f"set_tables({which})")
-        st = self._table_slots()[0][1].scale_table.float().contiguous().numpy()
+        st = self.scale_table_numpy()
         check(L.rgbd_elic_set_scale_table(self._h, st.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), int(st.shape[0])),
               "set_scale_table")
         from . import refarith
 
         refarith.push(L, self._h, check)  # the reference's accumulation blocks per layer shape (DESIGN.md 4a)
-        check(L.rgbd_elic_finalize(self._h), "finalize")
-        self._dirty = False
-        self._gen += 1
-
-    def _require_owner(self, what):
-        if self._parent is not None:
-            raise RgbdError(f"{what}() on a shared-weight clone: call it on the parent engine (clones follow it)")
 
     def _ready(self):
-        if self._h is None or self._device is None:
-            raise RgbdError("call .to('cuda') before compress()/decompress()")
-        if self._parent is not None:
-            # shared-weight clone: follow the parent.  If the parent has re-uploaded weights or tables since this clone
-            # was made (update() / load_state_dict()), take a fresh clone of it -- the old device buffers stay valid
-            # until then (they are reference-counted in the library), they are merely stale.
-            par = self._parent
-            par._ready()
-            if par._gen != self._gen:
-                L = lib()
-                h = ctypes.c_void_p()
-                check(L.rgbd_elic_clone_shared(par._h, ctypes.byref(h)), "clone_shared")
-                L.rgbd_elic_destroy(self._h)
-                self._h = h
-                self._gen = par._gen
-                self._params = par._params
-                if getattr(self, "_tile_mode", None):
-                    check(L.rgbd_elic_set_tile_mode(self._h, {"latency": 0, "throughput": 1}[self._tile_mode]), "tile_mode")
-            torch.cuda.set_device(self._device)
-            return
-        if self._dirty:
-            self._upload()
-        torch.cuda.set_device(self._device)
-
-    @staticmethod
-    def _stream_ptr():
-        return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-    def compress(self, rgb, depth):
-        self._ready()
-        if rgb.dim() != 4 or depth.dim() != 4 or rgb.size(1) != 3 or depth.size(1) != 1:
-            raise ValueError("expected rgb [B,3,H,W] and depth [B,1,H,W]")
-        B, _, H, W = rgb.shape
-        if depth.shape[0] != B or depth.shape[-2:] != rgb.shape[-2:]:
-            raise ValueError("rgb and depth must have the same batch and spatial size")
-        if H % 64 or W % 64:
-            raise ValueError("H and W must be multiples of 64 (pad first: dataset/utils.py:58-67)")
-        rgb = rgb.to(self._device, torch.float32).contiguous()
-        depth = depth.to(self._device, torch.float32).contiguous()
-        L = lib()
-        check(L.rgbd_elic_compress(self._h, ctypes.c_void_p(rgb.data_ptr()), ctypes.c_void_p(depth.data_ptr()), B, H, W,
-                                   1 if self.per_image_streams else 0, self._stream_ptr()), "compress")
-        out = [[self._fetch_streams(mod, kind) for kind in (0, 1)] for mod in (0, 1)]
-        return {"r_strings": out[0], "d_strings": out[1], "shape": torch.Size((H // 64, W // 64))}
+        gen = self._gen
+        super()._ready()
+        if self._parent is not None and self._gen != gen and self._tile_mode:  # a fresh clone: its handle has the default tiles
+            check(lib().rgbd_elic_set_tile_mode(self._h, {"latency": 0, "throughput": 1}[self._tile_mode]), "tile_mode")
 
     def _fetch_streams(self, mod, kind):
         L = lib()
@@ -280,106 +171,6 @@ class ELIC_united:
         ptrs = (u8p * len(bufs))(*[b.ctypes.data_as(u8p) for b in bufs])
         lens = (ctypes.c_int64 * len(bufs))(*[int(b.shape[0]) for b in bufs])
         return bufs, ptrs, lens
-
-    # ---- the Bi-CEE stage alone (models/elic_united.py:350-401, 543-578) ------------------------------------
-    def _check_latents(self, y, hyper, what):
-        if y is not None and (y.dim() != 4 or y.size(1) != self.M):
-            raise ValueError(f"{what} y: expected [B,{self.M},h,w]")
-        if hyper.dim() != 4 or hyper.size(1) != 2 * self.M:
-            raise ValueError(f"{what} hyper parameters: expected [B,{2 * self.M},h,w]")
-        if y is not None and (y.shape[0] != hyper.shape[0] or y.shape[-2:] != hyper.shape[-2:]):
-            raise ValueError(f"{what}: y and hyper parameters disagree in batch or spatial size")
-        if hyper.shape[-1] % 2:
-            raise ValueError("latent width must be even (checkerboard packing, utils/ckbd.py:51-64)")
-
-    def compress_united(self, rgb_y, rgb_hyper_params, depth_y, depth_hyper_params):
-        """Latents + hyper parameters -> (rgb_y_strings, depth_y_strings), each a list of byte strings (one for the whole
-        batch like the reference, or one per image when per_image_streams is set)."""
-        self._ready()
-        self._check_latents(rgb_y, rgb_hyper_params, "rgb")
-        self._check_latents(depth_y, depth_hyper_params, "depth")
-        if rgb_y.shape != depth_y.shape:
-            raise ValueError("rgb and depth latents must have the same shape")
-        t = [x.to(self._device, torch.float32).contiguous() for x in (rgb_y, rgb_hyper_params, depth_y, depth_hyper_params)]
-        B, _, h, w = t[0].shape
-        p = lambda x: ctypes.c_void_p(x.data_ptr())  # noqa: E731
-        check(lib().rgbd_elic_compress_united(self._h, p(t[0]), p(t[1]), p(t[2]), p(t[3]), B, h, w,
-                                              1 if self.per_image_streams else 0, self._stream_ptr()), "compress_united")
-        return self._fetch_streams(0, 0), self._fetch_streams(1, 0)
-
-    def decompress_united(self, rgb_y_strings, rgb_hyper_params, depth_y_strings, depth_hyper_params):
-        """(y strings, hyper parameters) per modality -> (rgb_y_hat, depth_y_hat).  A string argument may be one bytes
-        object (what the reference passes: strings[0][0]) or a list of them (one per image)."""
-        self._ready()
-        self._check_latents(None, rgb_hyper_params, "rgb")
-        self._check_latents(None, depth_hyper_params, "depth")
-        y_r = [rgb_y_strings] if isinstance(rgb_y_strings, (bytes, bytearray)) else list(rgb_y_strings)
-        y_d = [depth_y_strings] if isinstance(depth_y_strings, (bytes, bytearray)) else list(depth_y_strings)
-        hr = rgb_hyper_params.to(self._device, torch.float32).contiguous()
-        hd = depth_hyper_params.to(self._device, torch.float32).contiguous()
-        B, _, h, w = hr.shape
-        if hd.shape != hr.shape or len(y_r) != len(y_d) or len(y_r) not in (1, B):
-            raise ValueError("Invalid strings parameters")
-        out_r = torch.empty((B, self.M, h, w), dtype=torch.float32, device=self._device)
-        out_d = torch.empty_like(out_r)
-        k1, pyr, lyr = self._pack_strings(y_r)
-        k2, pyd, lyd = self._pack_strings(y_d)
-        p = lambda x: ctypes.c_void_p(x.data_ptr())  # noqa: E731
-        check(lib().rgbd_elic_decompress_united(self._h, pyr, lyr, len(y_r), pyd, lyd, p(hr), p(hd), B, h, w, p(out_r),
-                                                p(out_d), self._stream_ptr()), "decompress_united")
-        torch.cuda.current_stream().synchronize()
-        del k1, k2
-        return out_r, out_d
-
-    def decompress(self, rgb_strings, depth_strings, shape):
-        self._ready()
-        # the reference brackets decompress() with torch.cuda.synchronize() (elic_united.py:431,449); here only the
-        # calling stream is waited for, so engine instances on other streams (CodecPool) are not dragged into it
-        torch.cuda.current_stream().synchronize()
-        t0 = time.process_time()
-        y_r, z_r = list(rgb_strings[0]), list(rgb_strings[1])
-        y_d, z_d = list(depth_strings[0]), list(depth_strings[1])
-        B = len(z_r)
-        if len(z_d) != B or len(y_r) != len(y_d) or len(y_r) not in (1, B):
-            raise ValueError("Invalid strings parameters")
-        zh, zw = int(shape[0]), int(shape[1])
-        xr = torch.empty((B, 3, zh * 64, zw * 64), dtype=torch.float32, device=self._device)
-        xd = torch.empty((B, 1, zh * 64, zw * 64), dtype=torch.float32, device=self._device)
-
-        pack = self._pack_strings
-        k1, pyr, lyr = pack(y_r)
-        k2, pyd, lyd = pack(y_d)
-        k3, pzr, lzr = pack(z_r)
-        k4, pzd, lzd = pack(z_d)
-        check(lib().rgbd_elic_decompress(self._h, pyr, lyr, len(y_r), pyd, lyd, pzr, lzr, pzd, lzd, B, zh, zw,
-                                         ctypes.c_void_p(xr.data_ptr()), ctypes.c_void_p(xd.data_ptr()),
-                                         self._stream_ptr()), "decompress")
-        torch.cuda.current_stream().synchronize()
-        del k1, k2, k3, k4
-        return {"x_hat": {"r": xr, "d": xd}, "cost_time": time.process_time() - t0}
-
-    def forward(self, rgb, depth):
-        """Eval-mode forward (models/elic_united.py:234-263): x_hat without entropy coding plus the likelihoods."""
-        if self.training:
-            raise NotImplementedError("training-mode forward (noise / STE gradients) is out of scope")
-        self._ready()
-        B, _, H, W = rgb.shape
-        if H % 64 or W % 64:
-            raise ValueError("H and W must be multiples of 64")
-        rgb = rgb.to(self._device, torch.float32).contiguous()
-        depth = depth.to(self._device, torch.float32).contiguous()
-        dev = self._device
-        xr = torch.empty((B, 3, H, W), device=dev)
-        xd = torch.empty((B, 1, H, W), device=dev)
-        ly = [torch.empty((B, self.M, H // 16, W // 16), device=dev) for _ in range(2)]
-        lz = [torch.empty((B, self.N, H // 64, W // 64), device=dev) for _ in range(2)]
-        p = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
-        check(lib().rgbd_elic_forward(self._h, p(rgb), p(depth), B, H, W, p(xr), p(xd), p(ly[0]), p(ly[1]), p(lz[0]), p(lz[1]),
-                                      self._stream_ptr()), "forward")
-        return {"x_hat": {"r": xr, "d": xd}, "r_likelihoods": {"y": ly[0], "z": lz[0]},
-                "d_likelihoods": {"y": ly[1], "z": lz[1]}}
-
-    __call__ = forward
 
     # ---- parity hooks --------------------------------------------------------------------------------
     def debug_tensor(self, name: str) -> np.ndarray:
@@ -435,20 +226,6 @@ class ELIC_united:
         check(lib().rgbd_elic_set_forced_symbols(self._h, modality, ys.ctypes.data_as(i32p), ys.size, zs.ctypes.data_as(i32p),
                                                  zs.size), "set_forced_symbols")
 
-    def clone_shared(self):
-        """Another engine instance on the same GPU that borrows this one's device weights and tables (own workspace and
-        stream).  The clone keeps a reference to its parent so the weights outlive it."""
-        self._ready()
-        other = type(self).__new__(type(self))
-        other.__dict__.update({k: v for k, v in self.__dict__.items() if k != "_h"})
-        h = ctypes.c_void_p()
-        check(lib().rgbd_elic_clone_shared(self._h, ctypes.byref(h)), "clone_shared")
-        other._h = h
-        other._parent = self
-        other._gen = self._gen
-        other._dirty = False
-        return other
-
     def set_tile_mode(self, mode: str):
         """Convolution tile tables: "latency" (default; winners of isolated launches) or "throughput" (winners with the
         chip shared between several engine instances -- what `CodecPool` / `test_model(workers > 1)` select).  The outputs
@@ -475,13 +252,134 @@ class ELIC_united:
         check(lib().rgbd_elic_profile_read_executed(self._h, ctypes.byref(fx)), "profile_read_executed")
         return {"conv_ms": ms.value, "launches": n.value, "flops": fl.value, "flops_executed": fx.value}
 
-    def __del__(self):
-        try:
-            if self._h is not None:
-                lib().rgbd_elic_destroy(self._h)
-                self._h = None
-        except Exception:
-            pass
+
+class ELIC_united(Codec):
+    _MODEL = "ELIC_united"
+    _MODALITIES = (("rgb_", 0, 2), ("depth_", 1, 3))
+    _ENTRIES = staticmethod(elic_united_entries)
+
+    def __init__(self, config=None, channel=4, init_seed=0, **kwargs):
+        config = model_config() if config is None else config
+        super().__init__(self._ENTRIES(config), config, channel, init_seed)
+
+    def _create_engine(self):
+        return self._create("rgbd_elic_create", self.N, self.M, self.slice_ch)
+
+    def compress(self, rgb, depth):
+        self._ready()
+        if rgb.dim() != 4 or depth.dim() != 4 or rgb.size(1) != 3 or depth.size(1) != 1:
+            raise ValueError("expected rgb [B,3,H,W] and depth [B,1,H,W]")
+        B, _, H, W = rgb.shape
+        if depth.shape[0] != B or depth.shape[-2:] != rgb.shape[-2:]:
+            raise ValueError("rgb and depth must have the same batch and spatial size")
+        if H % 64 or W % 64:
+            raise ValueError("H and W must be multiples of 64 (pad first: dataset/utils.py:58-67)")
+        rgb = rgb.to(self._device, torch.float32).contiguous()
+        depth = depth.to(self._device, torch.float32).contiguous()
+        L = lib()
+        check(L.rgbd_elic_compress(self._h, self._ptr(rgb), self._ptr(depth), B, H, W,
+                                   1 if self.per_image_streams else 0, self._stream_ptr()), "compress")
+        out = [[self._fetch_streams(mod, kind) for kind in (0, 1)] for mod in (0, 1)]
+        return {"r_strings": out[0], "d_strings": out[1], "shape": torch.Size((H // 64, W // 64))}
+
+    # ---- the Bi-CEE stage alone (models/elic_united.py:350-401, 543-578) ------------------------------------
+    def _check_latents(self, y, hyper, what):
+        if y is not None and (y.dim() != 4 or y.size(1) != self.M):
+            raise ValueError(f"{what} y: expected [B,{self.M},h,w]")
+        if hyper.dim() != 4 or hyper.size(1) != 2 * self.M:
+            raise ValueError(f"{what} hyper parameters: expected [B,{2 * self.M},h,w]")
+        if y is not None and (y.shape[0] != hyper.shape[0] or y.shape[-2:] != hyper.shape[-2:]):
+            raise ValueError(f"{what}: y and hyper parameters disagree in batch or spatial size")
+        if hyper.shape[-1] % 2:
+            raise ValueError("latent width must be even (checkerboard packing, utils/ckbd.py:51-64)")
+
+    def compress_united(self, rgb_y, rgb_hyper_params, depth_y, depth_hyper_params):
+        """Latents + hyper parameters -> (rgb_y_strings, depth_y_strings), each a list of byte strings (one for the whole
+        batch like the reference, or one per image when per_image_streams is set)."""
+        self._ready()
+        self._check_latents(rgb_y, rgb_hyper_params, "rgb")
+        self._check_latents(depth_y, depth_hyper_params, "depth")
+        if rgb_y.shape != depth_y.shape:
+            raise ValueError("rgb and depth latents must have the same shape")
+        t = [x.to(self._device, torch.float32).contiguous() for x in (rgb_y, rgb_hyper_params, depth_y, depth_hyper_params)]
+        B, _, h, w = t[0].shape
+        p = self._ptr
+        check(lib().rgbd_elic_compress_united(self._h, p(t[0]), p(t[1]), p(t[2]), p(t[3]), B, h, w,
+                                              1 if self.per_image_streams else 0, self._stream_ptr()), "compress_united")
+        return self._fetch_streams(0, 0), self._fetch_streams(1, 0)
+
+    def decompress_united(self, rgb_y_strings, rgb_hyper_params, depth_y_strings, depth_hyper_params):
+        """(y strings, hyper parameters) per modality -> (rgb_y_hat, depth_y_hat).  A string argument may be one bytes
+        object (what the reference passes: strings[0][0]) or a list of them (one per image)."""
+        self._ready()
+        self._check_latents(None, rgb_hyper_params, "rgb")
+        self._check_latents(None, depth_hyper_params, "depth")
+        y_r = [rgb_y_strings] if isinstance(rgb_y_strings, (bytes, bytearray)) else list(rgb_y_strings)
+        y_d = [depth_y_strings] if isinstance(depth_y_strings, (bytes, bytearray)) else list(depth_y_strings)
+        hr = rgb_hyper_params.to(self._device, torch.float32).contiguous()
+        hd = depth_hyper_params.to(self._device, torch.float32).contiguous()
+        B, _, h, w = hr.shape
+        if hd.shape != hr.shape or len(y_r) != len(y_d) or len(y_r) not in (1, B):
+            raise ValueError("Invalid strings parameters")
+        out_r = torch.empty((B, self.M, h, w), dtype=torch.float32, device=self._device)
+        out_d = torch.empty_like(out_r)
+        k1, pyr, lyr = self._pack_strings(y_r)
+        k2, pyd, lyd = self._pack_strings(y_d)
+        p = self._ptr
+        check(lib().rgbd_elic_decompress_united(self._h, pyr, lyr, len(y_r), pyd, lyd, p(hr), p(hd), B, h, w, p(out_r),
+                                                p(out_d), self._stream_ptr()), "decompress_united")
+        torch.cuda.current_stream().synchronize()
+        del k1, k2
+        return out_r, out_d
+
+    def decompress(self, rgb_strings, depth_strings, shape):
+        self._ready()
+        # the reference brackets decompress() with torch.cuda.synchronize() (elic_united.py:431,449); here only the
+        # calling stream is waited for, so engine instances on other streams (CodecPool) are not dragged into it
+        torch.cuda.current_stream().synchronize()
+        t0 = time.process_time()
+        y_r, z_r = list(rgb_strings[0]), list(rgb_strings[1])
+        y_d, z_d = list(depth_strings[0]), list(depth_strings[1])
+        B = len(z_r)
+        if len(z_d) != B or len(y_r) != len(y_d) or len(y_r) not in (1, B):
+            raise ValueError("Invalid strings parameters")
+        zh, zw = int(shape[0]), int(shape[1])
+        xr = torch.empty((B, 3, zh * 64, zw * 64), dtype=torch.float32, device=self._device)
+        xd = torch.empty((B, 1, zh * 64, zw * 64), dtype=torch.float32, device=self._device)
+
+        pack = self._pack_strings
+        k1, pyr, lyr = pack(y_r)
+        k2, pyd, lyd = pack(y_d)
+        k3, pzr, lzr = pack(z_r)
+        k4, pzd, lzd = pack(z_d)
+        check(lib().rgbd_elic_decompress(self._h, pyr, lyr, len(y_r), pyd, lyd, pzr, lzr, pzd, lzd, B, zh, zw,
+                                         self._ptr(xr), self._ptr(xd), self._stream_ptr()), "decompress")
+        torch.cuda.current_stream().synchronize()
+        del k1, k2, k3, k4
+        return {"x_hat": {"r": xr, "d": xd}, "cost_time": time.process_time() - t0}
+
+    def forward(self, rgb, depth):
+        """Eval-mode forward (models/elic_united.py:234-263): x_hat without entropy coding plus the likelihoods."""
+        if self.training:
+            raise NotImplementedError("training-mode forward (noise / STE gradients) is out of scope")
+        self._ready()
+        B, _, H, W = rgb.shape
+        if H % 64 or W % 64:
+            raise ValueError("H and W must be multiples of 64")
+        rgb = rgb.to(self._device, torch.float32).contiguous()
+        depth = depth.to(self._device, torch.float32).contiguous()
+        dev = self._device
+        xr = torch.empty((B, 3, H, W), device=dev)
+        xd = torch.empty((B, 1, H, W), device=dev)
+        ly = [torch.empty((B, self.M, H // 16, W // 16), device=dev) for _ in range(2)]
+        lz = [torch.empty((B, self.N, H // 64, W // 64), device=dev) for _ in range(2)]
+        p = self._ptr
+        check(lib().rgbd_elic_forward(self._h, p(rgb), p(depth), B, H, W, p(xr), p(xd), p(ly[0]), p(ly[1]), p(lz[0]), p(lz[1]),
+                                      self._stream_ptr()), "forward")
+        return {"x_hat": {"r": xr, "d": xd}, "r_likelihoods": {"y": ly[0], "z": lz[0]},
+                "d_likelihoods": {"y": ly[1], "z": lz[1]}}
+
+    __call__ = forward
 
 
 class _LazyStore:
@@ -492,6 +390,3 @@ class _LazyStore:
 
     def __getitem__(self, k):
         return self._o._materialize()[k]
-
-
-modelZoo = {"ELIC_united": ELIC_united}  # models/__init__.py:11-20; rgbd_amd/__init__.py adds "ELIC"

@@ -1,0 +1,169 @@
+"""`EngineModule`: what every Python class over a librgbd_amd.so engine handle shares -- the checkpoint on the host, the handle
+and its device, uploads, and shared-weight clones.  Nothing here knows about entropy coding.
+
+    EngineModule                      handle lifecycle
+    ├── Spatial_aligner               aligner.py
+    └── Codec                         elic_united.py: entropy-table holders, streams, debug / profile hooks
+        ├── ELIC_united               elic_united.py (ELIC_united_R2D, SymmetricalTransFormerUnited under it)
+        └── SingleCodec               elic.py (ELIC, SymmetricalTransFormer, Cheng2020AnchorwithCheckerboard under it)
+
+A subclass fills in: `_MODEL` (its name in messages and in synth.synthetic_state_dict), `_synth_args()` (the other keyword
+arguments of synth.synthetic_state_dict), `_create_engine()` (one `self._create(...)` line) and, where it sends more than
+tensors, `_upload_extras(L)`.  There is no CPU execution path: every call raises if the HIP library or a GPU is missing.
+"""
+import ctypes
+from collections import OrderedDict
+
+import torch
+
+from . import synth
+from ._lib import RgbdError, check, lib
+
+
+class EngineModule:
+    _MODEL = ""
+    _CALLS = "the forward pass"  # what _ready() names in its message
+
+    def __init__(self, entries, init_seed=0):
+        self._entries = entries  # name -> arch.Entry, in state_dict order
+        self._init_seed = init_seed
+        self._params = None  # name -> torch CPU tensor (parameters and float buffers)
+        self._h = None
+        self._device = None
+        self._dirty = True
+        self._gen = 0        # bumped by every upload of weights / tables to the GPU
+        self._parent = None  # set on shared-weight clones (clone_shared)
+
+    # ---- per-class hooks ---------------------------------------------------------------------------------
+    def _synth_args(self):
+        return {}
+
+    def _create_engine(self):
+        raise NotImplementedError
+
+    def _upload_extras(self, L):
+        pass
+
+    # ---- torch.nn.Module-like surface ------------------------------------------------------------------
+    def _materialize(self):
+        if self._params is None:
+            self._params = synth.synthetic_state_dict(self._init_seed, model=self._MODEL, **self._synth_args())
+        return self._params
+
+    def eval(self):
+        return self  # (inference only: `training`, where a class has it, is never True)
+
+    def train(self, mode=True):
+        if mode:
+            raise NotImplementedError("the MI355X path is inference-only (training is out of scope, DESIGN.md)")
+        return self
+
+    def parameters(self):
+        p = self._materialize()
+        for name, e in self._entries.items():
+            if e.is_param:
+                yield p[name]
+
+    def count_parameters(self, only_trainable=False):
+        return sum(p.numel() for p in self.parameters())
+
+    def state_dict(self):
+        p = self._materialize()
+        return OrderedDict((name, p[name]) for name in self._entries)
+
+    def to(self, device):
+        dev = torch.device(device)
+        if dev.type != "cuda":
+            raise RgbdError(f"{self._MODEL} (rgbd_amd) runs on the GPU only: use .to('cuda'); there is no CPU path")
+        if not torch.cuda.is_available():
+            raise RgbdError("no HIP device visible to torch")
+        self._device = torch.device("cuda", torch.cuda.current_device() if dev.index is None else dev.index)
+        self._upload()
+        return self
+
+    def cuda(self, device=None):
+        return self.to("cuda" if device is None else f"cuda:{int(device)}")
+
+    # ---- engine ------------------------------------------------------------------------------------
+    @staticmethod
+    def _create(fn, *args):
+        """Call the exported creation function `fn`; a list among its integer arguments goes as (int32 array, length)."""
+        h, cargs = ctypes.c_void_p(), []
+        for a in args:
+            cargs += [(ctypes.c_int32 * len(a))(*a), len(a)] if isinstance(a, list) else [int(a)]
+        check(getattr(lib(), fn)(*cargs, ctypes.byref(h)), fn[len("rgbd_"):])
+        return h
+
+    def _upload(self):
+        L = lib()
+        torch.cuda.set_device(self._device)
+        if self._h is None:
+            self._h = self._create_engine()
+        p = self._materialize()
+        for name, e in self._entries.items():
+            if not e.is_param:
+                continue
+            a = p[name].detach().float().contiguous().numpy()
+            if e.kind == "linear_w" and ".fc." not in name:  # nn.Linear of the Swin blocks -> 1x1 convolution
+                a = a.reshape(a.shape[0], a.shape[1], 1, 1)
+            shape = (ctypes.c_int64 * a.ndim)(*a.shape)
+            check(L.rgbd_elic_set_tensor(self._h, name.encode(), a.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), shape,
+                                         a.ndim), f"set_tensor({name})")
+        self._upload_extras(L)
+        check(L.rgbd_elic_finalize(self._h), "finalize")
+        self._dirty = False
+        self._gen += 1
+
+    def _require_owner(self, what):
+        if self._parent is not None:
+            raise RgbdError(f"{what}() on a shared-weight clone: call it on the parent engine (clones follow it)")
+
+    def _clone_handle(self, parent):
+        h = ctypes.c_void_p()
+        check(lib().rgbd_elic_clone_shared(parent._h, ctypes.byref(h)), "clone_shared")
+        self._h = h
+        self._gen = parent._gen
+        self._params = parent._params
+
+    def _ready(self):
+        if self._h is None or self._device is None:
+            raise RgbdError(f"call .to('cuda') before {self._CALLS}")
+        if self._parent is not None:
+            # shared-weight clone: follow the parent.  If the parent has re-uploaded weights or tables since this clone
+            # was made (update() / load_state_dict()), take a fresh clone of it -- the old device buffers stay valid
+            # until then (they are reference-counted in the library), they are merely stale.
+            self._parent._ready()
+            if self._parent._gen != self._gen:
+                old = self._h
+                self._clone_handle(self._parent)
+                lib().rgbd_elic_destroy(old)
+        elif self._dirty:
+            self._upload()
+        torch.cuda.set_device(self._device)
+
+    def clone_shared(self):
+        """Another engine instance on the same GPU that borrows this one's device weights and tables (own workspace and
+        stream).  The clone keeps a reference to its parent so the weights outlive it, and follows its re-uploads."""
+        self._ready()
+        other = type(self).__new__(type(self))
+        other.__dict__.update({k: v for k, v in self.__dict__.items() if k != "_h"})
+        other._clone_handle(self)
+        other._parent = self
+        other._dirty = False
+        return other
+
+    @staticmethod
+    def _stream_ptr():
+        return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+    @staticmethod
+    def _ptr(t):
+        return ctypes.c_void_p(t.data_ptr())
+
+    def __del__(self):
+        try:
+            if self._h is not None:
+                lib().rgbd_elic_destroy(self._h)
+                self._h = None
+        except Exception:
+            pass

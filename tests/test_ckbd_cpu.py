@@ -134,40 +134,6 @@ def test_zoo_resolution_through_the_tester(tmp_path):
     assert isinstance(t.net, rgbd_amd.Cheng2020AnchorwithCheckerboard) and t.net.N == 192 and t.net.channel == 3
 
 
-def test_host_side_errors():
-    import rgbd_amd
-
-    m = rgbd_amd.modelZoo["ckbd"](config=rgbd_amd.model_config(), channel=3).eval()
-    with pytest.raises(rgbd_amd.RgbdError):
-        m.to("cpu")
-    if not torch.cuda.is_available():
-        with pytest.raises(rgbd_amd.RgbdError):
-            m.to("cuda")
-    with pytest.raises(rgbd_amd.RgbdError):
-        m.compress(torch.zeros(1, 3, 64, 64))  # before .to("cuda")
-    with pytest.raises(NotImplementedError):
-        m.validate(torch.zeros(1, 3, 64, 64))
-    with pytest.raises(NotImplementedError):
-        m.train()
-    # the size check comes before any device work
-    m._ready = lambda: None
-    m._device = torch.device("cpu")
-    for shape in ((1, 3, 100, 128), (1, 3, 128, 100)):
-        with pytest.raises(ValueError):
-            m.compress(torch.zeros(shape))
-        with pytest.raises(ValueError):
-            m.forward(torch.zeros(shape))
-    with pytest.raises(ValueError):
-        m.compress(torch.zeros(1, 1, 128, 128))  # channel mismatch
-    # the C ABI rejects widths / channel counts the model does not have before it creates anything
-    from rgbd_amd import _lib
-
-    h = ctypes.c_void_p()
-    for N, ch in ((160, 3), (192, 2), (0, 3), (192, 0)):
-        assert _lib.lib().rgbd_elic_create_ckbd(N, ch, ctypes.byref(h)) == -22 and not h.value
-    assert _lib.lib().rgbd_elic_create_ckbd(192, 3, None) == -22
-
-
 @pytest.mark.parametrize("is_beta", [1, 0])
 def test_host_parametrizer_equals_torch_bit_for_bit(is_beta):
     """rgbd_gdn_parametrize (what packs beta / gamma for the kernel) against NonNegativeParametrizer.forward in torch fp32."""

@@ -88,3 +88,21 @@ def test_aligner_refusals(nets):
     assert L.rgbd_aligner_forward(net._h, p(x), p(x), 1, 64, 64, p(out), s) == EINVAL
     torch.cuda.synchronize()
     assert (out == 7.0).all()
+
+
+def test_aligner_clone_follows_its_parent():
+    """A clone made before the parent's load_state_dict() computes with the parent's NEW weights afterwards, like a codec clone
+    (the generation counter of EngineModule).  Before Spatial_aligner stood on that base its clone kept the device buffers it
+    was made with: there the first assertion below fails (out_c equals out0, the stale weights)."""
+    from rgbd_amd import Spatial_aligner, synth
+
+    require_gpu()
+    x, g = (t.cuda() for t in ac.case_inputs("a_1x192_8x8"))
+    parent = Spatial_aligner(in_channel=192, out_channel=192, init_seed=0).to("cuda")
+    clone = parent.clone_shared()
+    out0 = clone(x, g)
+    parent.load_state_dict(synth.synthetic_state_dict(1, model="Spatial_aligner", in_channel=192, out_channel=192))
+    out_p = parent(x, g)
+    out_c = clone(x, g)
+    assert torch.equal(out_c, out_p)
+    assert not torch.equal(out_c, out0)

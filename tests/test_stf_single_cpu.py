@@ -123,29 +123,6 @@ def test_zoo_order_and_tester_name_resolution(tmp_path):
     assert isinstance(t.net, rgbd_amd.SymmetricalTransFormer)
 
 
-def test_host_side_errors():
-    import rgbd_amd
-
-    m = rgbd_amd.modelZoo["STF"](config=rgbd_amd.model_config(), channel=3).eval()
-    with pytest.raises(rgbd_amd.RgbdError):
-        m.to("cpu")
-    if not torch.cuda.is_available():
-        with pytest.raises(rgbd_amd.RgbdError):
-            m.to("cuda")
-    with pytest.raises(rgbd_amd.RgbdError):
-        m.compress(torch.zeros(1, 3, 64, 64))  # before .to("cuda")
-    # the size check comes before any device work
-    m._ready = lambda: None
-    m._device = torch.device("cpu")
-    for shape in ((1, 3, 100, 128), (1, 3, 128, 100)):
-        with pytest.raises(ValueError):
-            m.compress(torch.zeros(shape))
-        with pytest.raises(ValueError):
-            m.forward(torch.zeros(shape))
-    with pytest.raises(ValueError):
-        m.compress(torch.zeros(1, 1, 128, 128))  # channel mismatch
-
-
 @pytest.mark.parametrize("name", CASES)
 def test_integer_stage_from_the_reference_symbols(name):
     """Machine independent: tables + coder of the restatement on the reference's own symbols / indexes."""
