@@ -465,9 +465,65 @@ int rgbd_debug_tile_override(const char* csv);
 /* The pointwise operators of Bi-SPF / ESA / SE_Block alone (test hook; NCHW device tensors in and out, host weights):
  * op 0 = F.max_pool2d(kernel 7, stride 3) (attention.py:87), 1 = F.interpolate(bilinear, align_corners=False) to (oh, ow)
  * (attention.py:91), 2 = SE_Block x * gate (attention.py:52-67; w0 = fc.0.weight [c/16][c], w1 = fc.2.weight [c][c/16]),
- * 3 = x + x * gate as the entropy-parameter nets use it (entropy.py:75). */
+ * 3 = x + x * gate as the entropy-parameter nets use it (entropy.py:75).
+ * Every operator runs in its reference-arithmetic form with permuted channels, and stages its tensors through the layout
+ * kernels.  The single-chain forms (STF_united, the single-modal STF, the checkerboard Cheng2020 model, the aligner) and the
+ * layout kernels themselves are reached through the rgbd_pw_* hooks below. */
 int rgbd_pointwise_nchw(int32_t op, const float* x_dev, int32_t n, int32_t c, int32_t h, int32_t w, int32_t oh, int32_t ow,
                         const float* w0, const float* w1, float* y_dev, void* stream);
+
+/* The single-chain pointwise kernels and the two layout kernels alone, on the engine's own layout (test hooks:
+ * tests/test_gpu_pointwise_forms.py).  Tensors are NHWC fp32 on the device, [N][pixels][channel stride], with the caller's
+ * channel strides; nothing is staged or converted, so pad channels and neighbouring memory stay visible to the caller.  Each
+ * call checks its arguments on the host and returns -22 before any launch on a NULL required pointer, a non-positive extent,
+ * N > 65535, a channel stride smaller than the channels it has to hold or no multiple of 4, a vector stride (mstride, sstride)
+ * smaller than C or no multiple of 4, a pointer its kernel reads or writes in 16-byte vectors that is not 16-byte aligned, one
+ * half of an operand pair (x1 without y1), perm / mode / clamp01 outside {0, 1}, or N * stride * pixels >= 2^31 for any
+ * tensor; then it calls the launcher the engine calls.  Asynchronous on `stream` unless stated.
+ *
+ * rgbd_pw_channel_mean: mean_dev[n * mstride + c] = mean over the HW pixels of channel c < C (SE_Block's x.mean((2, 3)),
+ *   attention.py:63).  Fixed order: chain r = 0..3 adds pixels r, r + 4, ... one after the other from 0; the total is
+ *   (chain0 + chain1) + (chain2 + chain3), divided by float(HW).  Only those N x C floats are written.
+ * rgbd_pw_se_gate: gate_dev[n * C + pos] = sigmoid(fc.2 . relu(fc.0 . mean)) (attention.py:64-66); w0 = fc.0.weight
+ *   [C/16][C], w1 = fc.2.weight [C][C/16] (HOST; w1 is transposed as rgbd_elic_finalize does it), mean_dev[n * mstride + pos].
+ *   perm != 0: channel c sits at position (c & ~15) | (c & 3) << 2 | (c >> 2) & 3 of the mean and gate vectors, and the
+ *   sigmoid is the reference-arithmetic one; perm == 0: pos = c, 1 / (1 + expf(-s)).  C % 16 == 0.  Synchronous.
+ * rgbd_pw_bilinear: F.interpolate(bilinear, align_corners=False) from (h, w) to (H, W) over all cs channel positions
+ *   (attention.py:91).  ref_channels == 0: the single-chain form (source index = scale * (dst + 0.5) - 0.5 as a multiply
+ *   and a subtract, taps combined as ly0 * (lx0 * v00 + lx1 * v01) + ly1 * (lx0 * v10 + lx1 * v11), every step rounded);
+ *   ref_channels = C > 0: the reference-arithmetic form for a tensor of C permuted channels.  x1_dev / y1_dev: NULL, or a
+ *   second operand pair of the same shape in the same launch.
+ * rgbd_pw_maxpool7s3: F.max_pool2d(kernel 7, stride 3) (attention.py:87) over all cs channel positions, H, W >= 7,
+ *   y [N][(H - 7) / 3 + 1][(W - 7) / 3 + 1][cs]; x1_dev / y1_dev as above.
+ * rgbd_pw_channel_scale: y[n][p][c] = x * s (mode 0) or x + x * s (mode 1; two roundings), s = scale_dev[n * sstride + c],
+ *   c < C, C % 4 == 0; x / y with strides xcs / ycs.  scale_dev and y_dev may point into wider buffers (the gate and the
+ *   destination of one half of a concatenation); channels C .. ycs - 1 of y are not written.
+ * rgbd_pw_copy_channels: dst[p][c] = src[p][c], c < C, C % 4 == 0, npix pixels with strides scs / dcs.
+ * rgbd_pw_im2col5s2: the packed input of the image-consuming Conv2d(C <= 3, k 5, stride 2, pad 2): y [N][(H + 1) / 2]
+ *   [(W + 1) / 2][KP]; term = tap * C + c (tap = ky * 5 + kx) = j * 16 + e * 4 + q sits at packed index j * 16 + q * 4 + e;
+ *   taps outside the image and the terms 25 C .. KP - 1 are 0.  KP % 16 == 0, 25 C <= KP, C <= cs.
+ * rgbd_pw_fill_zero: n floats at p_dev become 0.
+ * rgbd_pw_nchw_to_nhwc: src [N][C][H][W] -> dst [N][H][W][cs]; position p holds channel p (perm 0) or the channel whose
+ *   permuted position is p (perm 1, cs % 16 == 0); positions that hold no channel < C are written as 0.
+ * rgbd_pw_nhwc_to_nchw: the inverse, dst [N][C][H][W]; clamp01: fminf(fmaxf(v, 0), 1) on the way. */
+int rgbd_pw_channel_mean(const float* x_dev, int32_t N, int32_t HW, int32_t cs, int32_t C, float* mean_dev, int32_t mstride,
+                         void* stream);
+int rgbd_pw_se_gate(const float* mean_dev, int32_t N, int32_t C, const float* w0, const float* w1, int32_t mstride, int32_t perm,
+                    float* gate_dev, void* stream);
+int rgbd_pw_bilinear(const float* x_dev, int32_t N, int32_t h, int32_t w, int32_t cs, float* y_dev, int32_t H, int32_t W,
+                     const float* x1_dev, float* y1_dev, int32_t ref_channels, void* stream);
+int rgbd_pw_maxpool7s3(const float* x_dev, int32_t N, int32_t H, int32_t W, int32_t cs, float* y_dev, const float* x1_dev,
+                       float* y1_dev, void* stream);
+int rgbd_pw_channel_scale(const float* x_dev, int32_t N, int32_t HW, int32_t xcs, int32_t C, const float* scale_dev, int32_t sstride,
+                          int32_t mode, float* y_dev, int32_t ycs, void* stream);
+int rgbd_pw_copy_channels(const float* src_dev, int32_t scs, float* dst_dev, int32_t dcs, int32_t npix, int32_t C, void* stream);
+int rgbd_pw_im2col5s2(const float* x_dev, int32_t N, int32_t H, int32_t W, int32_t cs, int32_t C, float* y_dev, int32_t KP,
+                      void* stream);
+int rgbd_pw_fill_zero(float* p_dev, int64_t n, void* stream);
+int rgbd_pw_nchw_to_nhwc(const float* src_dev, int32_t N, int32_t C, int32_t H, int32_t W, float* dst_dev, int32_t cs, int32_t perm,
+                         void* stream);
+int rgbd_pw_nhwc_to_nchw(const float* src_dev, int32_t N, int32_t C, int32_t H, int32_t W, int32_t cs, float* dst_dev,
+                         int32_t clamp01, int32_t perm, void* stream);
 
 /* The reference-arithmetic pointwise kernels alone (test hooks; tests/test_gpu_refpointwise.py compares each with
  * oracle/cpu_arith.c bit for bit).  Device tensors are logical NCHW fp32 / vectors in logical channel order, weights and

@@ -116,6 +116,16 @@ def lib():
                                                 c_i32, c_i32, c_vp, c_vp, c_vp, i32p, c_i32, c_i32, c_i32]),
         "rgbd_conv_forms_nchw": (ctypes.c_int, [ctypes.POINTER(ConvFormsDesc), c_vp]),
         "rgbd_pointwise_nchw": (ctypes.c_int, [c_i32, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, f32p, f32p, c_vp, c_vp]),
+        "rgbd_pw_channel_mean": (ctypes.c_int, [c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_i32, c_vp]),
+        "rgbd_pw_se_gate": (ctypes.c_int, [c_vp, c_i32, c_i32, f32p, f32p, c_i32, c_i32, c_vp, c_vp]),
+        "rgbd_pw_bilinear": (ctypes.c_int, [c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_i32, c_i32, c_vp, c_vp, c_i32, c_vp]),
+        "rgbd_pw_maxpool7s3": (ctypes.c_int, [c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
+        "rgbd_pw_channel_scale": (ctypes.c_int, [c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_i32, c_i32, c_vp, c_i32, c_vp]),
+        "rgbd_pw_copy_channels": (ctypes.c_int, [c_vp, c_i32, c_vp, c_i32, c_i32, c_i32, c_vp]),
+        "rgbd_pw_im2col5s2": (ctypes.c_int, [c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_i32, c_vp]),
+        "rgbd_pw_fill_zero": (ctypes.c_int, [c_vp, c_i64, c_vp]),
+        "rgbd_pw_nchw_to_nhwc": (ctypes.c_int, [c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_i32, c_i32, c_vp]),
+        "rgbd_pw_nhwc_to_nchw": (ctypes.c_int, [c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_i32, c_i32, c_vp]),
         "rgbd_ref_channel_mean": (ctypes.c_int, [c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_i32, c_vp]),
         "rgbd_ref_linear": (ctypes.c_int, [f32p, c_vp, c_i32, c_i32, c_i32, i32p, c_i32, c_i32, c_i32, c_vp, c_vp]),
         "rgbd_ref_sigmoid_gate": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp]),
@@ -231,7 +241,9 @@ EXPORTS = ["rgbd_abi_version", "rgbd_set_blocking_sync", "rgbd_get_blocking_sync
            "rgbd_ckbd_estimate_part", "rgbd_slice_estimate", "rgbd_ckbd_part", "rgbd_z_quant", "rgbd_z_dequant", "rgbd_eb_forward",
            "rgbd_elic_create_ckbd", "rgbd_gdn_nchw", "rgbd_gdn_parametrize", "rgbd_debug_force_gdn_tile", "rgbd_gdn_bench",
            "rgbd_guided_window_attention", "rgbd_aligner_create", "rgbd_aligner_forward", "rgbd_elic_decompress_single_mid",
-           "rgbd_elic_forward_single_mid"]
+           "rgbd_elic_forward_single_mid", "rgbd_pw_channel_mean", "rgbd_pw_se_gate", "rgbd_pw_bilinear", "rgbd_pw_maxpool7s3",
+           "rgbd_pw_channel_scale", "rgbd_pw_copy_channels", "rgbd_pw_im2col5s2", "rgbd_pw_fill_zero", "rgbd_pw_nchw_to_nhwc",
+           "rgbd_pw_nhwc_to_nchw"]
 
 
 _BS_HOLDERS = 0

@@ -85,6 +85,14 @@ inline int pack_conv(const HostTensor& w, const HostTensor* b, bool transposed, 
     return RGBD_OK;
 }
 
+// SE_Block's fc.2.weight ([C][hidden]) as launch_se_fc reads it: transposed to [hidden][C], so that the gate kernel's
+// consecutive lanes read consecutive addresses.  w1t must not alias w1.
+inline void se_pack_fc2(const float* w1, size_t C, size_t Hd, float* w1t)
+{
+    for (size_t c = 0; c < C; ++c)
+        for (size_t j = 0; j < Hd; ++j) w1t[j * C + c] = w1[c * Hd + j];
+}
+
 // ConvTranspose2d(cin -> cout <= 4, k = 5, stride 2, pad 2, output_padding 1) as ONE stride-1 3x3 conv over the input grid
 // with 16 output channels = 4 output phases x 4: the per-phase form pads the couts to 16 for each of its 25 taps, this one
 // runs 9 taps for all phases together (2.8x fewer MFMAs).  Output phase (ry, rx) at input offset (dy, dx) uses kernel

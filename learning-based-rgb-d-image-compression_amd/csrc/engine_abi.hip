@@ -413,6 +413,121 @@ int rgbd_ref_deconv_s2_nchw(const float* x_dev, int32_t n, int32_t cin, int32_t 
     return rc;
 }
 
+// ---- the single-chain pointwise and layout kernels alone (test hooks: tests/test_gpu_pointwise_forms.py) ---------------------
+// Operator boundaries on the engine's own layout, like the entropy and Swin hooks: NHWC fp32 device pointers with the caller's
+// channel strides, nothing staged, nothing converted.  Each checks on the host what its kernel assumes, then calls the
+// launcher the engine calls.  Asynchronous on `stream` (rgbd_pw_se_gate, which uploads its weights, returns when done).
+namespace {
+inline bool pw_al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+// [n][pix][cs] holding c channels: positive extents, n within a grid's y range, a stride that holds c and keeps 16-byte
+// vectors aligned, fewer than 2^31 elements
+inline bool pw_tensor_ok(int64_t n, int64_t pix, int64_t c, int64_t cs)
+{
+    return n > 0 && n <= 65535 && pix > 0 && pix < ((int64_t)1 << 31) && c > 0 && cs >= c && cs % 4 == 0 && cs <= (1 << 20) &&
+           n * pix * cs < ((int64_t)1 << 31);
+}
+inline bool pw_hw_ok(int64_t h, int64_t w) { return h > 0 && w > 0 && h <= 65536 && w <= 65536; }
+}  // namespace
+
+int rgbd_pw_channel_mean(const float* x_dev, int32_t N, int32_t HW, int32_t cs, int32_t C, float* mean_dev, int32_t mstride,
+                         void* stream)
+{
+    if (!x_dev || !mean_dev || !pw_tensor_ok(N, HW, C, cs) || mstride < C || mstride % 4 || mstride > (1 << 20)) return RGBD_EINVAL;
+    return launch_channel_mean_strided(x_dev, N, HW, cs, C, mean_dev, mstride, (hipStream_t)stream);
+}
+
+int rgbd_pw_se_gate(const float* mean_dev, int32_t N, int32_t C, const float* w0, const float* w1, int32_t mstride, int32_t perm,
+                    float* gate_dev, void* stream)
+{
+    std::unique_lock<std::shared_mutex> cap_lk(g_capture_mu);  // frees / synchronous copies: not while a stream captures
+    if (!mean_dev || !w0 || !w1 || !gate_dev || N <= 0 || N > 65535 || C <= 0 || C % 16 || C > 65536 || mstride < C || mstride % 4 ||
+        mstride > (1 << 20) || perm < 0 || perm > 1)
+        return RGBD_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    const int hidden = C / 16;
+    const size_t wf = (size_t)C * hidden;
+    std::vector<float> w1t(wf);
+    se_pack_fc2(w1, (size_t)C, (size_t)hidden, w1t.data());
+    DevBufs b;
+    float *dw0 = b.get(wf), *dw1 = b.get(wf), *hid = b.get((size_t)N * hidden);
+    if (!dw0 || !dw1 || !hid) return RGBD_ENOMEM;
+    HIP_TRY(hipMemcpy(dw0, w0, wf * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(dw1, w1t.data(), wf * sizeof(float), hipMemcpyHostToDevice));
+    int rc = launch_se_fc(mean_dev, N, C, hidden, dw0, dw1, hid, gate_dev, s, mstride, perm);
+    const hipError_t e = hipStreamSynchronize(s);
+    if (!rc && e != hipSuccess) rc = RGBD_EHIP;
+    return rc;
+}
+
+int rgbd_pw_bilinear(const float* x_dev, int32_t N, int32_t h, int32_t w, int32_t cs, float* y_dev, int32_t H, int32_t W,
+                     const float* x1_dev, float* y1_dev, int32_t ref_channels, void* stream)
+{
+    if (!x_dev || !y_dev || !pw_hw_ok(h, w) || !pw_hw_ok(H, W) || !pw_tensor_ok(N, (int64_t)h * w, cs, cs) ||
+        !pw_tensor_ok(N, (int64_t)H * W, cs, cs) || ref_channels < 0 || ref_channels > cs || !x1_dev != !y1_dev || !pw_al16(x_dev) ||
+        !pw_al16(y_dev) || !pw_al16(x1_dev) || !pw_al16(y1_dev))
+        return RGBD_EINVAL;
+    return launch_bilinear(x_dev, N, h, w, cs, y_dev, H, W, (hipStream_t)stream, x1_dev, y1_dev, ref_channels);
+}
+
+int rgbd_pw_maxpool7s3(const float* x_dev, int32_t N, int32_t H, int32_t W, int32_t cs, float* y_dev, const float* x1_dev,
+                       float* y1_dev, void* stream)
+{
+    if (!x_dev || !y_dev || !pw_hw_ok(H, W) || H < 7 || W < 7 || !pw_tensor_ok(N, (int64_t)H * W, cs, cs) || !x1_dev != !y1_dev ||
+        !pw_al16(x_dev) || !pw_al16(y_dev) || !pw_al16(x1_dev) || !pw_al16(y1_dev))
+        return RGBD_EINVAL;
+    return launch_maxpool7s3(x_dev, N, H, W, cs, y_dev, (H - 7) / 3 + 1, (W - 7) / 3 + 1, (hipStream_t)stream, x1_dev, y1_dev);
+}
+
+int rgbd_pw_channel_scale(const float* x_dev, int32_t N, int32_t HW, int32_t xcs, int32_t C, const float* scale_dev, int32_t sstride,
+                          int32_t mode, float* y_dev, int32_t ycs, void* stream)
+{
+    if (!x_dev || !scale_dev || !y_dev || !pw_tensor_ok(N, HW, C, xcs) || !pw_tensor_ok(N, HW, C, ycs) || C % 4 || sstride < C ||
+        sstride % 4 || sstride > (1 << 20) || mode < 0 || mode > 1 || !pw_al16(x_dev) || !pw_al16(scale_dev) || !pw_al16(y_dev))
+        return RGBD_EINVAL;
+    return launch_channel_scale_to_strided(x_dev, N, HW, xcs, C, scale_dev, sstride, mode, y_dev, ycs, (hipStream_t)stream);
+}
+
+int rgbd_pw_copy_channels(const float* src_dev, int32_t scs, float* dst_dev, int32_t dcs, int32_t npix, int32_t C, void* stream)
+{
+    if (!src_dev || !dst_dev || !pw_tensor_ok(1, npix, C, scs) || !pw_tensor_ok(1, npix, C, dcs) || C % 4 || !pw_al16(src_dev) ||
+        !pw_al16(dst_dev))
+        return RGBD_EINVAL;
+    return launch_copy_channels(src_dev, scs, dst_dev, dcs, npix, C, (hipStream_t)stream);
+}
+
+int rgbd_pw_im2col5s2(const float* x_dev, int32_t N, int32_t H, int32_t W, int32_t cs, int32_t C, float* y_dev, int32_t KP,
+                      void* stream)
+{
+    if (!x_dev || !y_dev || !pw_hw_ok(H, W) || !pw_tensor_ok(N, (int64_t)H * W, C, cs) || KP <= 0 || KP % 16 || 25 * (int64_t)C > KP ||
+        !pw_tensor_ok(N, (int64_t)((H + 1) / 2) * ((W + 1) / 2), KP, KP) || !pw_al16(y_dev))
+        return RGBD_EINVAL;
+    return launch_im2col5s2(x_dev, N, H, W, cs, C, y_dev, (H + 1) / 2, (W + 1) / 2, KP, (hipStream_t)stream);
+}
+
+int rgbd_pw_fill_zero(float* p_dev, int64_t n, void* stream)
+{
+    if (!p_dev || n <= 0 || n >= ((int64_t)1 << 31)) return RGBD_EINVAL;
+    return launch_fill_zero(p_dev, (size_t)n, (hipStream_t)stream);
+}
+
+int rgbd_pw_nchw_to_nhwc(const float* src_dev, int32_t N, int32_t C, int32_t H, int32_t W, float* dst_dev, int32_t cs, int32_t perm,
+                         void* stream)
+{
+    if (!src_dev || !dst_dev || !pw_hw_ok(H, W) || !pw_tensor_ok(N, (int64_t)H * W, C, cs) || perm < 0 || perm > 1 ||
+        (perm && cs % 16) || !pw_al16(dst_dev))
+        return RGBD_EINVAL;
+    return launch_nchw_to_nhwc16(src_dev, N, C, H, W, dst_dev, cs, (hipStream_t)stream, perm);
+}
+
+int rgbd_pw_nhwc_to_nchw(const float* src_dev, int32_t N, int32_t C, int32_t H, int32_t W, int32_t cs, float* dst_dev, int32_t clamp01,
+                         int32_t perm, void* stream)
+{
+    if (!src_dev || !dst_dev || !pw_hw_ok(H, W) || !pw_tensor_ok(N, (int64_t)H * W, C, cs) || perm < 0 || perm > 1 ||
+        (perm && cs % 16) || clamp01 < 0 || clamp01 > 1)
+        return RGBD_EINVAL;
+    return launch_nhwc_to_nchw_clamp(src_dev, N, C, H, W, cs, dst_dev, clamp01, (hipStream_t)stream, perm);
+}
+
 // ---- the conv launchers in every form the engine issues (test hook: tests/test_gpu_convforms.py; include/rgbd_amd.h) ---------
 // conv2d_nchw_impl above always builds the plainest ConvArgs.  This one builds, from the helpers the engine's planner builds
 // its launches from (conv_args.h), every other form -- fused tail, lead layer, gate / skip operands, second destination,
@@ -1260,11 +1375,7 @@ int rgbd_elic_finalize(rgbd_elic* m)
                     dense[name + ".rowclass"] = dcls;
                 }
             }
-            if (ends_with(name, ".fc.2.weight") && !m->refnum) {
-                const size_t C = (size_t)t.shape[0], Hd = (size_t)t.shape[1];
-                for (size_t c = 0; c < C; ++c)
-                    for (size_t j = 0; j < Hd; ++j) hv[j * C + c] = t.v[c * Hd + j];
-            }
+            if (ends_with(name, ".fc.2.weight") && !m->refnum) se_pack_fc2(t.v.data(), (size_t)t.shape[0], (size_t)t.shape[1], hv.data());
             float* d = nullptr;
             if (const int r = dev_copy(hv.data(), hv.size(), &d)) return r;
             dense[name] = d;

@@ -396,3 +396,73 @@ def test_ckbd_quant_index_vs_oracle(n, c, h, w, kat):
         prev = back
     assert lib().rgbd_ckbd_quant_index(_vp(yd), _vp(md), _vp(sd), n, c, h, w + 1, 1, tb.ctypes.data_as(f32p), _vp(sym), _vp(idx),
                                        _vp(yhat), None) == -22  # odd width: the reference's squeeze needs w even
+
+
+@pytest.mark.parametrize("misaligned", ["all", "y", "means", "scales", "yhat"])
+@pytest.mark.parametrize("n,c,h,w", [(1, 5, 3, 2), (2, 16, 8, 10)])
+def test_ckbd_quant_index_misaligned_vs_oracle(n, c, h, w, misaligned, kat):
+    """The scalar (VEC = false) instantiations of ckbd_nchw_kernel: test_ckbd_quant_index_vs_oracle's comparison with y, means,
+    scales and y_hat each a view that starts one float into a larger allocation (4-byte, not 8-byte aligned), and then with
+    only one of the four so placed -- the launcher's choice of the vectorised form is all-or-nothing.  Same oracle, same
+    bit-for-bit assertions, for rgbd_ckbd_quant_index and rgbd_ckbd_dequant."""
+    dev = require_gpu()
+    import ctypes
+
+    import torch
+
+    from oracle import elic_oracle as eo
+    from rgbd_amd._lib import check, lib
+
+    g = torch.Generator().manual_seed(n * 1000 + c)
+    table = eo.scale_table()
+    y = torch.randn(n, c, h, w, generator=g) * 6
+    means = torch.randn(n, c, h, w, generator=g)
+    scales = torch.exp(torch.randn(n, c, h, w, generator=g) * 2 - 0.5)
+    scales.view(-1)[::7] = table[torch.randint(0, 64, ((scales.numel() + 6) // 7,), generator=g)]  # exactly on table entries
+    scales.view(-1)[3::11] = 0.05                                                                   # under the bound
+    scales.view(-1)[5::13] = -1.0
+    y.view(-1)[::5] = (means.view(-1)[::5] + torch.randint(-4, 5, ((y.numel() + 4) // 5,), generator=g).float() + 0.5)  # ties
+    tb = np.ascontiguousarray(table.numpy(), np.float32)
+    f32p = ctypes.POINTER(ctypes.c_float)
+    numel = n * c * h * w
+    GUARD = 54321.0
+
+    def place(t, name):
+        """t on the device: a fresh allocation, or elements 1 .. numel of one with a guard float on either side."""
+        if misaligned not in ("all", name):
+            out = t.to(dev).contiguous()
+            assert out.data_ptr() % 8 == 0
+            return out, None
+        base = torch.full((numel + 2,), GUARD, device=dev)
+        view = base[1:1 + numel].view(n, c, h, w)
+        view.copy_(t)
+        assert view.data_ptr() % 8 == 4
+        return view, base
+
+    yd, _ = place(y, "y")
+    md, _ = place(means, "means")
+    sd, _ = place(scales, "scales")
+    yhat, yhat_base = place(torch.full((n, c, h, w), 7.0), "yhat")  # (the anchor half defines every position: the 7s must go)
+    m = n * c * h * (w // 2)
+    want_hat = torch.zeros(n, c, h, w)
+    for anchor in (1, 0):
+        sym = torch.zeros(m, dtype=torch.int32, device=dev)
+        idx = torch.zeros(m, dtype=torch.int32, device=dev)
+        check(lib().rgbd_ckbd_quant_index(_vp(yd), _vp(md), _vp(sd), n, c, h, w, anchor, tb.ctypes.data_as(f32p), _vp(sym), _vp(idx),
+                                          _vp(yhat), None), "ckbd_quant_index")
+        ws = eo.quantize_symbols(eo.pack(y, bool(anchor)), eo.pack(means, bool(anchor)))
+        wi = eo.scale_indexes(eo.pack(scales, bool(anchor)), table)
+        assert np.array_equal(sym.cpu().numpy(), ws.reshape(-1).numpy()), f"symbols, anchor={anchor}"
+        assert np.array_equal(idx.cpu().numpy(), wi.reshape(-1).numpy()), f"indexes, anchor={anchor}"
+        want_hat = want_hat + eo.unpack(ws.float() + eo.pack(means, bool(anchor)), bool(anchor))
+        assert np.array_equal(yhat.cpu().numpy(), want_hat.numpy()), f"y_hat, anchor={anchor}"
+        # the decoder's half of the step rebuilds the same y_hat from the symbols
+        if anchor:
+            back, back_base = place(torch.full((n, c, h, w), 7.0), "yhat")
+        else:
+            back, back_base = place(prev.cpu(), "yhat")
+        check(lib().rgbd_ckbd_dequant(_vp(sym), _vp(md), n, c, h, w, anchor, _vp(back), None), "ckbd_dequant")
+        assert np.array_equal(back.cpu().numpy(), want_hat.numpy())
+        prev = back
+        for base in (yhat_base, back_base):  # the floats on either side of a misplaced y_hat are not the kernel's
+            assert base is None or (float(base[0]) == GUARD and float(base[-1]) == GUARD)
