@@ -604,8 +604,10 @@ int rgbd_layernorm2(const float* x, int64_t ntok, int32_t C, int32_t xcs, const 
  * (models/stf_united.py:48-114, 162-203).  qkv: [B][H][W][qcs], channel which * C + head * 16 + d (which = q, k, v);
  * rpb: [49][heads] relative position bias table; out: [B][H][W][ocs].  Requires H % 4 == 0, W % 4 == 0, C == 16 * heads,
  * 0 <= shift < 4 (shift > 0: roll by -shift, the -100 mask between the regions of the rolled frame, roll back),
- * qcs >= 3 C, qcs % 4 == 0, ocs >= C, qkv 16-byte aligned.  qkv1 / rpb1 / out1: NULL, or a second operand set of the same
- * shape run in the same launch.  Pad channels C .. ocs - 1 of out are not written.
+ * qcs >= 3 C, qcs % 4 == 0, ocs >= C, qkv 16-byte aligned, B * (H/4) * (W/4) * heads <= 0x7fffffff - 16.  qkv1 / rpb1 /
+ * out1: all NULL, or a second operand set of the same shape run in the same launch.  Pad channels C .. ocs - 1 of out are
+ * not written.  (The same kernel as rgbd_guided_window_attention, csrc/swin.hip: window_attention_kernel<head_dim>, behind
+ * the same checks.)
  *
  * rgbd_patch_merge_gather: PatchMerging's 2x2 gather (stf_united.py:240-245), y[b][h][w] = cat(x[2h][2w], x[2h+1][2w],
  * x[2h][2w+1], x[2h+1][2w+1]) over the first C channels; x: [B][H][W][xcs], y: [B][H/2][W/2][ycs].  H, W even, C % 4 == 0,
@@ -623,7 +625,7 @@ int rgbd_window_attention(const float* qkv, int32_t B, int32_t H, int32_t W, int
  * (qkv1, :130,147); kv: [B][H][W][kvcs], channel which * C + head * 32 + d, which 0 = k, 1 = v (qkv2, :131,148-149); rpb:
  * [49][heads]; out: [B][H][W][ocs], channels C .. ocs - 1 untouched.  H and W are those of the token grid.  Returns RGBD_EINVAL
  * and writes nothing unless H % 4 == 0, W % 4 == 0, C == 32 * heads, 0 <= shift < 4, qcs >= C, kvcs >= 2 C, ocs >= C,
- * qcs % 4 == 0, kvcs % 4 == 0, q and kv 16-byte aligned, B * (H/4) * (W/4) * heads <= 0x7fffffff, no pointer NULL. */
+ * qcs % 4 == 0, kvcs % 4 == 0, q and kv 16-byte aligned, B * (H/4) * (W/4) * heads <= 0x7fffffff - 16, no pointer NULL. */
 int rgbd_guided_window_attention(const float* q, int32_t qcs, const float* kv, int32_t kvcs, int32_t B, int32_t H, int32_t W,
                                  int32_t C, int32_t heads, int32_t shift, const float* rpb, float* out, int32_t ocs, void* stream);
 int rgbd_patch_merge_gather(const float* x, int32_t B, int32_t H, int32_t W, int32_t C, int32_t xcs, float* y, int32_t ycs,

@@ -2126,6 +2126,18 @@ struct rgbd_elic {
     // window attention one launch over both tensors -- half the launches of a model whose launches are too small to fill the
     // chip (35 us on average at one 512x512 pair).  Each output keeps its arithmetic: bit-identical to the one-by-one form.
     // nm == 1 (the single-modal STF, models/stf.py): the same blocks on one tensor; arrays are read at [0, nm) only.
+    // A kernel with two operand sets (LayerNorm, window attention) over in[m] -> out[m] of nm modalities: one launch with
+    // the second set when g_pair and the two modalities agree in shape and in both channel strides, else one launch each.
+    // launch(m, pair): set m alone, or (pair) sets 0 and 1.
+    template <class F>
+    void pair_or_each(int nm, const Act in[2], const Act out[2], F launch)
+    {
+        const bool same = nm == 2 && g_pair && in[0].n == in[1].n && in[0].h == in[1].h && in[0].w == in[1].w &&
+                          in[0].c == in[1].c && in[0].cs == in[1].cs && out[0].cs == out[1].cs;
+        int r = launch(0, same);
+        if (!r && nm == 2 && !same) r = launch(1, false);
+        if (r) fail(r);
+    }
     void layernorm2(int nm, const std::string p[2], const Act x[2], Act y[2])
     {
         float *w[2] = {}, *b[2] = {};
@@ -2135,53 +2147,20 @@ struct rgbd_elic {
             b[m] = dense_of(p[m] + ".bias");
         }
         if (dry() || rc || !w[0] || !b[0] || !w[nm - 1] || !b[nm - 1]) return;
-        if (nm == 1) {
-            const int r = launch_layernorm(x[0].p, (size_t)x[0].n * x[0].h * x[0].w, x[0].c, x[0].cs, w[0], b[0], y[0].p, y[0].cs, s);
-            if (r) fail(r);
-            return;
-        }
-        const bool same = g_pair && x[0].n == x[1].n && x[0].h == x[1].h && x[0].w == x[1].w && x[0].c == x[1].c &&
-                          x[0].cs == x[1].cs && y[0].cs == y[1].cs;
-        const size_t ntok = (size_t)x[0].n * x[0].h * x[0].w;
-        int r = launch_layernorm(x[0].p, ntok, x[0].c, x[0].cs, w[0], b[0], y[0].p, y[0].cs, s, same ? x[1].p : nullptr,
-                                 same ? w[1] : nullptr, same ? b[1] : nullptr, same ? y[1].p : nullptr);
-        if (!r && !same)
-            r = launch_layernorm(x[1].p, (size_t)x[1].n * x[1].h * x[1].w, x[1].c, x[1].cs, w[1], b[1], y[1].p, y[1].cs, s);
-        if (r) fail(r);
+        pair_or_each(nm, x, y, [&](int m, bool pair) {
+            return launch_layernorm(x[m].p, (size_t)x[m].n * x[m].h * x[m].w, x[m].c, x[m].cs, w[m], b[m], y[m].p, y[m].cs, s,
+                                    pair ? x[1].p : nullptr, pair ? w[1] : nullptr, pair ? b[1] : nullptr, pair ? y[1].p : nullptr);
+        });
     }
-    void swin_block2(int nm, const std::string p[2], const Act x[2], int shift, int heads, Act out[2])
+    // the Swin block after its attention: x + attn.proj(a), then + mlp(norm2(.)) into out (allocated by the caller, before
+    // its arena mark); allocates x1, t2 and the hidden layer, in that order
+    void swin_block_tail2(int nm, const std::string p[2], const Act x[2], const Act a[2], const Act out[2])
     {
-        for (int m = 0; m < nm; ++m) out[m] = alloc(x[m].n, x[m].h, x[m].w, x[m].c);
-        const size_t mark = arena.top;
         auto names = [&](const char* suf, std::string n[2]) {
             for (int m = 0; m < nm; ++m) n[m] = p[m] + suf;
         };
         std::string n[2];
-        const Epi none[2];
-        Act t[2], qkv[2], a[2], x1[2], t2[2], hdn[2], o[2];
-        names(".norm1", n);
-        layernorm2(nm, n, x, t);
-        names(".attn.qkv", n);
-        conv2(nm, n, t, 1, 0, none, nullptr, qkv);
-        float* rpb[2] = {};
-        for (int m = 0; m < nm; ++m) {
-            a[m] = alloc(x[m].n, x[m].h, x[m].w, x[m].c);
-            rpb[m] = dense_of(p[m] + ".attn.relative_position_bias_table");
-        }
-        if (!dry() && !rc && rpb[0] && nm == 1) {
-            const int r = launch_window_attention(qkv[0].p, x[0].n, x[0].h, x[0].w, x[0].c, qkv[0].cs, heads, shift, rpb[0], a[0].p,
-                                                  a[0].cs, s);
-            if (r) fail(r);
-        } else if (!dry() && !rc && rpb[0] && rpb[1]) {
-            const bool same = g_pair && x[0].n == x[1].n && x[0].h == x[1].h && x[0].w == x[1].w && x[0].c == x[1].c &&
-                              qkv[0].cs == qkv[1].cs && a[0].cs == a[1].cs;
-            int r = launch_window_attention(qkv[0].p, x[0].n, x[0].h, x[0].w, x[0].c, qkv[0].cs, heads, shift, rpb[0], a[0].p, a[0].cs,
-                                            s, same ? qkv[1].p : nullptr, same ? rpb[1] : nullptr, same ? a[1].p : nullptr);
-            if (!r && !same)
-                r = launch_window_attention(qkv[1].p, x[1].n, x[1].h, x[1].w, x[1].c, qkv[1].cs, heads, shift, rpb[1], a[1].p,
-                                            a[1].cs, s);
-            if (r) fail(r);
-        }
+        Act x1[2], t2[2], hdn[2], o[2];
         Epi e1[2];
         e1[0].res1 = &x[0];
         e1[1].res1 = &x[1];
@@ -2199,6 +2178,28 @@ struct rgbd_elic {
         const Act* odst[2] = {&out[0], &out[1]};
         names(".mlp.fc2", n);
         conv2(nm, n, hdn, 1, 0, e2, odst, o);
+    }
+    void swin_block2(int nm, const std::string p[2], const Act x[2], int shift, int heads, Act out[2])
+    {
+        for (int m = 0; m < nm; ++m) out[m] = alloc(x[m].n, x[m].h, x[m].w, x[m].c);
+        const size_t mark = arena.top;
+        const std::string n1[2] = {p[0] + ".norm1", p[nm - 1] + ".norm1"}, nq[2] = {p[0] + ".attn.qkv", p[nm - 1] + ".attn.qkv"};
+        const Epi none[2];
+        Act t[2], qkv[2], a[2];
+        layernorm2(nm, n1, x, t);
+        conv2(nm, nq, t, 1, 0, none, nullptr, qkv);
+        float* rpb[2] = {};
+        for (int m = 0; m < nm; ++m) {
+            a[m] = alloc(x[m].n, x[m].h, x[m].w, x[m].c);
+            rpb[m] = dense_of(p[m] + ".attn.relative_position_bias_table");
+        }
+        if (!dry() && !rc && rpb[0] && rpb[nm - 1])
+            pair_or_each(nm, qkv, a, [&](int m, bool pair) {
+                return launch_window_attention(qkv[m].p, x[m].n, x[m].h, x[m].w, x[m].c, qkv[m].cs, heads, shift, rpb[m], a[m].p,
+                                               a[m].cs, s, pair ? qkv[1].p : nullptr, pair ? rpb[1] : nullptr,
+                                               pair ? a[1].p : nullptr);
+            });
+        swin_block_tail2(nm, p, x, a, out);
         arena.top = mark;
     }
     // Spatial_aligner (modules/transform/spatialAligner.py:341-390): patch embeddings of x and guided, two Swin blocks whose
@@ -2226,16 +2227,7 @@ struct rgbd_elic {
                                                              a.p, a.cs, s);
                 if (r) fail(r);
             }
-            Epi e1;
-            e1.res1 = &ex;
-            const Act x1 = conv(pb + ".attn.proj", a, 1, 0, e1);
-            const Act t2 = layernorm(pb + ".norm2", x1);
-            Epi g;
-            g.act = ACT_GELU;
-            const Act hdn = conv(pb + ".mlp.fc1", t2, 1, 0, g);
-            Epi e2;
-            e2.res1 = &x1;
-            conv(pb + ".mlp.fc2", hdn, 1, 0, e2, &out);
+            swin_block_tail2(1, &pb, &ex, &a, &out);  // (nm == 1: arrays of one)
             arena.top = mark;
             ex = out;
         }

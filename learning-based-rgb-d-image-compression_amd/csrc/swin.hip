@@ -184,36 +184,57 @@ extern "C" int rgbd_layernorm(const float* x, int64_t ntok, int32_t C, int32_t x
 }
 
 // ---------------------------------------------------------------------------------------------
-// WindowAttention + the window partition / cyclic shift around it (stf_united.py:48-114, 177-203, 329-352) on the matrix
-// cores.  qkv: [B,H,W,3C] with channel = which*C + head*16 + d (the layout nn.Linear(dim, 3*dim) produces); out: [B,H,W,C].
-// A 4x4 window with head_dim 16 is two 16x16x16 products per (window, head): S = (q * 0.25) k^T and O = softmax(S + bias
-// [+ mask]) v -- four v_mfma_f32_16x16x4_f32 each.  One wavefront walks WA_PAIRS (window, head) pairs, four wavefronts per
+// Window attention + the window partition / cyclic shift around it on the matrix cores, for a head_dim HD of 16 or 32:
+//   * WindowAttention of STF_united / STF (stf_united.py:48-114, 177-203, 329-352), HD = 16: q, k and v in one tensor
+//     qkv [B,H,W,3C] with channel = which*C + head*16 + d (the layout nn.Linear(dim, 3*dim) produces);
+//   * the guided (cross) attention of Spatial_aligner (modules/transform/spatialAligner.py:138-170, 279-331), HD = 32: the
+//     query from one token map, q [B,H,W,qcs] with channel = head*32 + d (nn.Linear(dim, dim)), key and value from another
+//     ("guided"), kv [B,H,W,kvcs] with channel = which*C + head*32 + d, which 0 = k, 1 = v (nn.Linear(dim, 2*dim)).
+// Both are operands of the same kernel: the q tensor and the k/v tensor of a set (WaSet), their channel strides and the
+// channels koff / voff where k and v start in the k/v tensor (C and 2C of qkv; 0 and C of kv).  out: [B,H,W,ocs], channels
+// [0, C).
+// A 4x4 window is two products per (window, head): S = (q * HD^-0.5) k^T (16 x 16 x HD) and O = softmax(S + bias [+ mask]) v
+// (16 x HD x 16), in v_mfma_f32_16x16x4_f32.  One wavefront walks WA_PAIRS (window, head) pairs, four wavefronts per
 // workgroup.  Operand layouts of the instruction (A: lane l = row l % 16, k = l / 16; B: col l % 16, k = l / 16; D: rows
 // 4 (l / 16) + r in register r, col l % 16):
-//   S:  A = q[token i = l % 16][d = 4 s + l / 16], B = k[token j = l % 16][d = 4 s + l / 16]  (k-step s = 0..3), so every score
-//       is ONE fused-multiply-add chain over d = 0 .. 15 in order, starting from 0;
-//   O:  A = P[i][j = 4 s + l / 16] (P goes through LDS: it comes out of the first product in the D layout), B = v[token
-//       j = 4 s + l / 16][dim l % 16] read straight from qkv; the chain over j = 0 .. 15 in order.
-// The relative position bias and the shifted-window mask (-100 between different regions of the rolled frame) are added to
-// the accumulator registers, the softmax runs over the 16 lanes that hold a row (sum: four consecutive columns in order,
-// then the groups pairwise -- a fixed tree).  Against the vector-ALU form of rounds 1-3 (one wavefront per pair; the
-// compiler had turned its dot products into packed multiplies followed by separate adds, two roundings per term) the
-// results differ in the last bits -- fewer roundings here; same-box A/B on the STF golden: |dPSNR| vs the reference 1.05e-4 /
-// 2.4e-5 dB before, 2.7e-5 / 8.1e-5 dB now.
+//   S:  HD / 4 k-steps s: A = (q * HD^-0.5)[token i = l % 16][d = 4 s + l / 16], B = k[token j = l % 16][d = 4 s + l / 16], so
+//       every score is ONE fused-multiply-add chain over d = 0 .. HD - 1 in order, starting from 0.  q is scaled before the
+//       product as the reference does (spatialAligner.py:151): 32^-0.5 is no power of two, so scaling the score instead
+//       would round differently;
+//   O:  HD / 16 tiles of 16 dims, each its own accumulator, four k-steps each: A = P[i][j = 4 s + l / 16] for every tile (P
+//       goes through LDS: it comes out of the first product in the D layout), B = v[token j = 4 s + l / 16][dim 16 n + l % 16]
+//       read straight from memory; the chain over j = 0 .. 15 in order.
+// The relative position bias and then the shifted-window mask (-100 between different regions of the rolled frame;
+// create_mask, spatialAligner.py:249-277) are added to the accumulator registers, the softmax runs over the 16 lanes that
+// hold a row (sum: four consecutive columns in order, then the groups pairwise -- a fixed tree).  Against the vector-ALU form
+// of rounds 1-3 (one wavefront per pair; the compiler had turned its dot products into packed multiplies followed by
+// separate adds, two roundings per term) the results differ in the last bits -- fewer roundings here; same-box A/B on the
+// STF golden: |dPSNR| vs the reference 1.05e-4 / 2.4e-5 dB before, 2.7e-5 / 8.1e-5 dB now.
 // shift > 0: the window lives in the rolled frame (token (ys,xs) is pixel ((ys+shift)%H, (xs+shift)%W)).
 // blockIdx.y == 1: the second operand set (the other modality).
+// The (window, head) pair index is 32-bit (a 64-bit one costs the HD = 16 instance two VGPRs and one wave of occupancy);
+// launch_wa() refuses pair counts within one workgroup's 16 of INT_MAX, so the index of a wave past the end cannot wrap.
 #define WA_PAIRS 4
 struct WaSet {
-    const float* qkv;
+    const float* q;    // [B,H,W,qcs]
+    const float* kv;   // [B,H,W,kvcs]; k / v of a token: kv[koff / voff + head * HD + d]
     const float* rpb;  // [49][heads]
     float* out;
 };
-__global__ __launch_bounds__(256) void window_attention_kernel(WaSet s0, WaSet s1, int B, int H, int W, int C, int qcs, int heads,
-                                                               int shift, int ocs, int npairs)
+// (qcs, kvcs, koff, voff hold for both sets, so they are passed once: with them inside the sets every launch measured
+// 0.1 - 0.4 us slower than the two kernels this one replaces; passed once, the launches of a step's Swin stages sum to the
+// same time as before)
+template <int HD>
+__global__ __launch_bounds__(256) void window_attention_kernel(WaSet s0, WaSet s1, int qcs, int kvcs, size_t koff, size_t voff, int H,
+                                                               int W, int heads, int shift, int ocs, int npairs)
 {
-    __shared__ float sq[4][16][17], sk[4][16][17], sp[4][16][17];
+    constexpr int NT = HD / 16;                                       // output tiles = f32x4 loads per staging lane
+    constexpr float scale = HD == 16 ? 0.25f : 0.17677669529663687f;  // head_dim ** -0.5
+    __shared__ float sq[4][16][HD + 1], sk[4][16][HD + 1], sp[4][16][17];
     const WaSet st = blockIdx.y ? s1 : s0;
-    const float* __restrict__ qkv = st.qkv;
+    const float* __restrict__ qp = st.q;
+    const float* __restrict__ kp = st.kv + koff;
+    const float* __restrict__ vp = st.kv + voff;
     const float* __restrict__ rpb = st.rpb;
     float* __restrict__ out = st.out;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -226,34 +247,45 @@ __global__ __launch_bounds__(256) void window_attention_kernel(WaSet s0, WaSet s
         const int win = pair / heads;
         const int wj = win % nwx, wi = (win / nwx) % nwy, b = win / (nwx * nwy);
         const size_t img = (size_t)b * H * W;
-        // stage q (scaled) and k of this pair: lane loads token t = lane / 4, dims 4 (lane % 4) .. + 3 (64-byte rows)
+        // stage q (scaled) and k of this pair: lane loads token t = lane / 4, dims (HD / 4) (lane % 4) .. + HD / 4 - 1
         {
-            const int t = lane >> 2, d0 = (lane & 3) * 4;
+            const int t = lane >> 2, d0 = (lane & 3) * (HD / 4);
             const int ys = wi * 4 + (t >> 2), xs = wj * 4 + (t & 3);
             const int y = (ys + shift) % H, x = (xs + shift) % W;
-            const float* p = qkv + (img + (size_t)y * W + x) * qcs + head * 16 + d0;
-            const f32x4 qv = *reinterpret_cast<const f32x4*>(p);
-            const f32x4 kv = *reinterpret_cast<const f32x4*>(p + C);
+            const size_t pix = img + (size_t)y * W + x;
+            const int hd0 = head * HD + d0;
+            const float* pq = qp + (pix * qcs + hd0);
+            const float* pk = kp + (pix * kvcs + hd0);
+            f32x4 qv[NT], kv[NT];
 #pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                sq[wv][t][d0 + e] = qv[e] * 0.25f;  // head_dim ** -0.5, head_dim = 16
-                sk[wv][t][d0 + e] = kv[e];
+            for (int n = 0; n < NT; ++n) {
+                qv[n] = *reinterpret_cast<const f32x4*>(pq + 4 * n);
+                kv[n] = *reinterpret_cast<const f32x4*>(pk + 4 * n);
             }
+#pragma unroll
+            for (int n = 0; n < NT; ++n)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    sq[wv][t][d0 + 4 * n + e] = qv[n][e] * scale;
+                    sk[wv][t][d0 + 4 * n + e] = kv[n][e];
+                }
         }
-        // v operands straight from memory: lane (q, c = l15), k-step s: v[token 4 s + q][dim c]
-        float vb[4];
+        // v operands straight from memory: lane (q, c = l15), tile n, k-step s: v[token 4 s + q][dim 16 n + c]
+        float vb[NT][4];
 #pragma unroll
         for (int sstep = 0; sstep < 4; ++sstep) {
             const int t = 4 * sstep + q;
             const int ys = wi * 4 + (t >> 2), xs = wj * 4 + (t & 3);
             const int y = (ys + shift) % H, x = (xs + shift) % W;
-            vb[sstep] = qkv[(img + (size_t)y * W + x) * qcs + 2 * C + head * 16 + l15];
+            const float* pv = vp + (img + (size_t)y * W + x) * kvcs + head * HD + l15;
+#pragma unroll
+            for (int n = 0; n < NT; ++n) vb[n][sstep] = pv[16 * n];
         }
         __builtin_amdgcn_wave_barrier();
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // this wave's LDS writes have landed (its own region only)
         f32x4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-        for (int sstep = 0; sstep < 4; ++sstep)
+        for (int sstep = 0; sstep < HD / 4; ++sstep)
             acc = __builtin_amdgcn_mfma_f32_16x16x4f32(sq[wv][l15][4 * sstep + q], sk[wv][l15][4 * sstep + q], acc, 0, 0, 0);
         // acc[r] = S[i = 4 q + r][j = l15]
         const int j = l15, jy = j >> 2, jx = j & 3;
@@ -292,176 +324,71 @@ __global__ __launch_bounds__(256) void window_attention_kernel(WaSet s0, WaSet s
         for (int r = 0; r < 4; ++r) sp[wv][4 * q + r][l15] = pr[r];
         __builtin_amdgcn_wave_barrier();
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        f32x4 o = {0.f, 0.f, 0.f, 0.f};
+        f32x4 o[NT];
 #pragma unroll
-        for (int sstep = 0; sstep < 4; ++sstep)
-            o = __builtin_amdgcn_mfma_f32_16x16x4f32(sp[wv][l15][4 * sstep + q], vb[sstep], o, 0, 0, 0);
-        // o[r] = O[token 4 q + r][dim l15]: 64-byte rows per store instruction
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int t = 4 * q + r;
-            const int ys = wi * 4 + (t >> 2), xs = wj * 4 + (t & 3);
-            const int y = (ys + shift) % H, x = (xs + shift) % W;
-            out[(img + (size_t)y * W + x) * ocs + head * 16 + l15] = o[r];
-        }
-        __builtin_amdgcn_wave_barrier();  // the next pair overwrites this wave's LDS region
-    }
-}
-
-int launch_window_attention(const float* qkv, int B, int H, int W, int C, int qcs, int heads, int shift, const float* rpb,
-                            float* out, int ocs, hipStream_t s, const float* qkv1, const float* rpb1, float* out1)
-{
-    if (H % 4 || W % 4 || C != heads * 16 || shift < 0 || shift >= 4) return RGBD_EINVAL;  // window 4, head_dim 16
-    const size_t pairs = (size_t)B * (H / 4) * (W / 4) * heads;
-    if (pairs > 0x7fffffffu) return RGBD_EINVAL;
-    const size_t blocks = (pairs + 4 * WA_PAIRS - 1) / (4 * WA_PAIRS);
-    const WaSet s0{qkv, rpb, out}, s1{qkv1, rpb1, out1};
-    hipLaunchKernelGGL(window_attention_kernel, dim3((unsigned)blocks, qkv1 ? 2 : 1), dim3(256), 0, s, s0, s1, B, H, W, C, qcs, heads,
-                       shift, ocs, (int)pairs);
-    HIP_TRY(hipGetLastError());
-    return RGBD_OK;
-}
-
-// ---------------------------------------------------------------------------------------------
-// Guided (cross) window attention of Spatial_aligner (modules/transform/spatialAligner.py:138-170, 279-331): the query comes
-// from one token map, key and value from another ("guided"), head_dim 32.  q: [B,H,W,qcs] with channel = head*32 + d
-// (nn.Linear(dim, dim)); kv: [B,H,W,kvcs] with channel = which*C + head*32 + d, which 0 = k, 1 = v (nn.Linear(dim, 2*dim));
-// out: [B,H,W,ocs], channels [0, C).  The same form as window_attention_kernel -- one wavefront walks GWA_PAIRS (window,
-// head) pairs, v_mfma_f32_16x16x4_f32, the same operand layouts, bias / mask rule and softmax tree -- with
-//   S:  eight k-steps: A = (q * 32^-0.5)[token i = l % 16][d = 4 s + l / 16], B = k[token j = l % 16][d = 4 s + l / 16]; every
-//       score is one fused chain over d = 0 .. 31 in order, from 0.  q is scaled before the product as the reference does
-//       (:151): 32^-0.5 is no power of two, so scaling the score instead would round differently;
-//   O:  two 16x16 tiles (dims 0-15 and 16-31), four k-steps each over j = 0 .. 15 in order; A = P[i][j] from LDS for both,
-//       B = v[token j = 4 s + l / 16][dim l % 16 (+ 16)] straight from kv.
-#define GWA_PAIRS 4
-__global__ __launch_bounds__(256) void guided_window_attention_kernel(const float* __restrict__ qp, int qcs,
-                                                                      const float* __restrict__ kvp, int kvcs,
-                                                                      const float* __restrict__ rpb, float* __restrict__ out,
-                                                                      int ocs, int H, int W, int C, int heads, int shift, int npairs)
-{
-    __shared__ float sq[4][16][33], sk[4][16][33], sp[4][16][17];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int l15 = lane & 15, q = lane >> 4;
-    const int nwx = W / 4, nwy = H / 4;
-    for (int it = 0; it < GWA_PAIRS; ++it) {
-        const long long pair64 = ((long long)blockIdx.x * 4 + wv) * GWA_PAIRS + it;  // wave-uniform
-        if (pair64 >= npairs) break;
-        const int pair = (int)pair64;
-        const int head = pair % heads;
-        const int win = pair / heads;
-        const int wj = win % nwx, wi = (win / nwx) % nwy, b = win / (nwx * nwy);
-        const size_t img = (size_t)b * H * W;
-        // stage q (scaled) and k of this pair: lane loads token t = lane / 4, dims 8 (lane % 4) .. + 7 (128-byte rows)
-        {
-            const int t = lane >> 2, d0 = (lane & 3) * 8;
-            const int ys = wi * 4 + (t >> 2), xs = wj * 4 + (t & 3);
-            const int y = (ys + shift) % H, x = (xs + shift) % W;
-            const size_t pix = img + (size_t)y * W + x;
-            const float* pq = qp + pix * qcs + head * 32 + d0;
-            const float* pk = kvp + pix * kvcs + head * 32 + d0;
-            const f32x4 qa = *reinterpret_cast<const f32x4*>(pq), qb = *reinterpret_cast<const f32x4*>(pq + 4);
-            const f32x4 ka = *reinterpret_cast<const f32x4*>(pk), kb = *reinterpret_cast<const f32x4*>(pk + 4);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                sq[wv][t][d0 + e] = qa[e] * 0.17677669529663687f;  // head_dim ** -0.5, head_dim = 32
-                sq[wv][t][d0 + 4 + e] = qb[e] * 0.17677669529663687f;
-                sk[wv][t][d0 + e] = ka[e];
-                sk[wv][t][d0 + 4 + e] = kb[e];
-            }
-        }
-        // v operands straight from memory: lane (q, c = l15), tile h, k-step s: v[token 4 s + q][dim 16 h + c]
-        float vb[2][4];
-#pragma unroll
-        for (int sstep = 0; sstep < 4; ++sstep) {
-            const int t = 4 * sstep + q;
-            const int ys = wi * 4 + (t >> 2), xs = wj * 4 + (t & 3);
-            const int y = (ys + shift) % H, x = (xs + shift) % W;
-            const float* pv = kvp + (img + (size_t)y * W + x) * kvcs + C + head * 32 + l15;
-            vb[0][sstep] = pv[0];
-            vb[1][sstep] = pv[16];
-        }
-        __builtin_amdgcn_wave_barrier();
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // this wave's LDS writes have landed (its own region only)
-        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int sstep = 0; sstep < 8; ++sstep)
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(sq[wv][l15][4 * sstep + q], sk[wv][l15][4 * sstep + q], acc, 0, 0, 0);
-        // acc[r] = S[i = 4 q + r][j = l15]
-        const int j = l15, jy = j >> 2, jx = j & 3;
-        int reg_j = 0;
-        if (shift > 0) {
-            const int ys = wi * 4 + jy, xs = wj * 4 + jx;
-            reg_j = (ys < H - 4 ? 0 : (ys < H - shift ? 1 : 2)) * 3 + (xs < W - 4 ? 0 : (xs < W - shift ? 1 : 2));
-        }
-        float pr[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int i = 4 * q + r, iy = i >> 2, ix = i & 3;
-            float sc = acc[r] + rpb[((iy - jy + 3) * 7 + (ix - jx + 3)) * heads + head];  // relative_position_index, spatialAligner.py:118-128
-            if (shift > 0) {  // create_mask, spatialAligner.py:249-277
-                const int ys = wi * 4 + iy, xs = wj * 4 + ix;
-                const int reg_i = (ys < H - 4 ? 0 : (ys < H - shift ? 1 : 2)) * 3 + (xs < W - 4 ? 0 : (xs < W - shift ? 1 : 2));
-                if (reg_j != reg_i) sc += -100.0f;
-            }
-            // softmax over the row, the tree of window_attention_kernel
-            float mx = sc;
-            mx = fmaxf(mx, __shfl_xor(mx, 1));
-            mx = fmaxf(mx, __shfl_xor(mx, 2));
-            mx = fmaxf(mx, __shfl_xor(mx, 4));
-            mx = fmaxf(mx, __shfl_xor(mx, 8));
-            const float ex = expf(sc - mx);
-            float sum = ex + __shfl_down(ex, 1);
-            sum += __shfl_down(ex, 2);
-            sum += __shfl_down(ex, 3);
-            sum = __shfl(sum, lane & ~3);
-            sum += __shfl_xor(sum, 4);
-            sum += __shfl_xor(sum, 8);
-            pr[r] = ex / sum;
-        }
-#pragma unroll
-        for (int r = 0; r < 4; ++r) sp[wv][4 * q + r][l15] = pr[r];
-        __builtin_amdgcn_wave_barrier();
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        f32x4 o0 = {0.f, 0.f, 0.f, 0.f}, o1 = {0.f, 0.f, 0.f, 0.f};
+        for (int n = 0; n < NT; ++n) o[n] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int sstep = 0; sstep < 4; ++sstep) {
             const float a = sp[wv][l15][4 * sstep + q];
-            o0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a, vb[0][sstep], o0, 0, 0, 0);
-            o1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a, vb[1][sstep], o1, 0, 0, 0);
+#pragma unroll
+            for (int n = 0; n < NT; ++n) o[n] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, vb[n][sstep], o[n], 0, 0, 0);
         }
-        // o0[r] / o1[r] = O[token 4 q + r][dim l15 / 16 + l15]: 64-byte rows per store instruction
+        // o[n][r] = O[token 4 q + r][dim 16 n + l15]: 64-byte rows per store instruction
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int t = 4 * q + r;
             const int ys = wi * 4 + (t >> 2), xs = wj * 4 + (t & 3);
             const int y = (ys + shift) % H, x = (xs + shift) % W;
-            float* po = out + (img + (size_t)y * W + x) * ocs + head * 32 + l15;
-            po[0] = o0[r];
-            po[16] = o1[r];
+            float* po = out + (img + (size_t)y * W + x) * ocs + head * HD + l15;
+#pragma unroll
+            for (int n = 0; n < NT; ++n) po[16 * n] = o[n][r];
         }
         __builtin_amdgcn_wave_barrier();  // the next pair overwrites this wave's LDS region
     }
 }
 
-// Everything the kernel assumes is checked here (the engine and the operator boundary both come through): window 4,
-// head_dim 32, 16-byte vector loads of q and kv.  Nothing is written on a refusal.
+// Everything the kernel assumes is checked here (the engine and the operator boundaries both come through): window 4,
+// head_dim HD, 16-byte vector loads of q and k, a pair index that fits an int.  s1: all of its pointers or none.  Nothing
+// is written on a refusal.
+template <int HD>
+static int launch_wa(const WaSet& s0, const WaSet& s1, int qcs, int kvcs, size_t koff, size_t voff, int B, int H, int W, int C,
+                     int heads, int shift, int ocs, hipStream_t s)
+{
+    const auto set_ok = [](const WaSet& t) {
+        return t.q && t.kv && t.rpb && t.out && ((uintptr_t)t.q & 15) == 0 && ((uintptr_t)t.kv & 15) == 0;
+    };
+    const bool pair = s1.q || s1.kv || s1.rpb || s1.out;
+    if (B <= 0 || H <= 0 || W <= 0 || heads <= 0 || H % 4 || W % 4 || heads > INT_MAX / HD || C != heads * HD || shift < 0 ||
+        shift >= 4 || ocs < C || !set_ok(s0) || (pair && !set_ok(s1)))
+        return RGBD_EINVAL;
+    if (qcs < C || kvcs <= 0 || (size_t)kvcs < std::max(koff, voff) + (size_t)C || qcs % 4 || kvcs % 4 || koff % 4) return RGBD_EINVAL;
+    const size_t lim = (size_t)INT_MAX - 4 * WA_PAIRS;  // (checked factor by factor: the product of four ints can pass 2^64)
+    size_t pairs = (size_t)(H / 4) * (W / 4);
+    if (pairs > lim) return RGBD_EINVAL;
+    pairs *= (size_t)B;
+    if (pairs > lim) return RGBD_EINVAL;
+    pairs *= (size_t)heads;
+    if (pairs > lim) return RGBD_EINVAL;
+    const size_t blocks = (pairs + 4 * WA_PAIRS - 1) / (4 * WA_PAIRS);
+    hipLaunchKernelGGL(window_attention_kernel<HD>, dim3((unsigned)blocks, pair ? 2 : 1), dim3(256), 0, s, s0, s1, qcs, kvcs, koff, voff, H,
+                       W, heads, shift, ocs, (int)pairs);
+    HIP_TRY(hipGetLastError());
+    return RGBD_OK;
+}
+
+// self-attention, head_dim 16: q, k, v at channels 0, C, 2C of qkv ([B,H,W,qcs]); qkv1 / rpb1 / out1: the second set
+int launch_window_attention(const float* qkv, int B, int H, int W, int C, int qcs, int heads, int shift, const float* rpb,
+                            float* out, int ocs, hipStream_t s, const float* qkv1, const float* rpb1, float* out1)
+{
+    return launch_wa<16>(WaSet{qkv, qkv, rpb, out}, WaSet{qkv1, qkv1, rpb1, out1}, qcs, qcs, (size_t)C, 2 * (size_t)C, B, H, W, C, heads,
+                         shift, ocs, s);
+}
+
+// guided attention, head_dim 32: q from its own tensor, k, v at channels 0, C of kv
 int launch_guided_window_attention(const float* q, int qcs, const float* kv, int kvcs, int B, int H, int W, int C, int heads,
                                    int shift, const float* rpb, float* out, int ocs, hipStream_t s)
 {
-    if (!q || !kv || !rpb || !out || B <= 0 || H <= 0 || W <= 0 || heads <= 0) return RGBD_EINVAL;
-    if (H % 4 || W % 4 || C != heads * 32 || shift < 0 || shift >= 4 || qcs < C || kvcs < 2 * C || ocs < C) return RGBD_EINVAL;
-    if (qcs % 4 || kvcs % 4 || ((uintptr_t)q & 15) || ((uintptr_t)kv & 15)) return RGBD_EINVAL;
-    size_t pairs = (size_t)(H / 4) * (W / 4);  // (checked factor by factor: the product of four ints can pass 2^64)
-    if (pairs > 0x7fffffffu) return RGBD_EINVAL;
-    pairs *= (size_t)B;
-    if (pairs > 0x7fffffffu) return RGBD_EINVAL;
-    pairs *= (size_t)heads;
-    if (pairs > 0x7fffffffu) return RGBD_EINVAL;
-    const size_t blocks = (pairs + 4 * GWA_PAIRS - 1) / (4 * GWA_PAIRS);
-    hipLaunchKernelGGL(guided_window_attention_kernel, dim3((unsigned)blocks), dim3(256), 0, s, q, qcs, kv, kvcs, rpb, out, ocs, H, W,
-                       C, heads, shift, (int)pairs);
-    HIP_TRY(hipGetLastError());
-    return RGBD_OK;
+    return launch_wa<32>(WaSet{q, kv, rpb, out}, WaSet{}, qcs, kvcs, 0, (size_t)C, B, H, W, C, heads, shift, ocs, s);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -523,23 +450,13 @@ int launch_pixel_shuffle2(const float* x, int B, int H, int W, int Co, int xcs, 
 
 // ---------------------------------------------------------------------------------------------
 // Operator boundaries of the kernels above for the tests (include/rgbd_amd.h).  The engine calls the launch_* functions
-// directly; these only check what the kernels assume before launching them.
-static bool wa_set_ok(const float* qkv, const float* rpb, const float* out)
-{
-    return qkv && rpb && out && ((uintptr_t)qkv & 15) == 0;
-}
-
+// directly; these only check what the kernels assume before launching them (the two attention launchers check for
+// themselves).
 extern "C" int rgbd_window_attention(const float* qkv, int32_t B, int32_t H, int32_t W, int32_t C, int32_t qcs, int32_t heads,
                                      int32_t shift, const float* rpb, float* out, int32_t ocs, const float* qkv1,
                                      const float* rpb1, float* out1, void* stream)
 {
-    if (B <= 0 || H <= 0 || W <= 0 || heads <= 0 || H % 4 || W % 4 || C != 16 * heads || shift < 0 || shift >= 4 ||
-        qcs < 3 * C || qcs % 4 || ocs < C || !wa_set_ok(qkv, rpb, out))
-        return RGBD_EINVAL;
-    const bool pair = qkv1 || rpb1 || out1;
-    if (pair && !wa_set_ok(qkv1, rpb1, out1)) return RGBD_EINVAL;
-    return launch_window_attention(qkv, B, H, W, C, qcs, heads, shift, rpb, out, ocs, (hipStream_t)stream, pair ? qkv1 : nullptr,
-                                   pair ? rpb1 : nullptr, pair ? out1 : nullptr);
+    return launch_window_attention(qkv, B, H, W, C, qcs, heads, shift, rpb, out, ocs, (hipStream_t)stream, qkv1, rpb1, out1);
 }
 
 extern "C" int rgbd_guided_window_attention(const float* q, int32_t qcs, const float* kv, int32_t kvcs, int32_t B, int32_t H,

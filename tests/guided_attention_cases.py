@@ -1,4 +1,4 @@
-"""Guided (cross) window attention of Spatial_aligner (csrc/swin.hip: guided_window_attention_kernel): the cases, a float64
+"""Guided (cross) window attention of Spatial_aligner (csrc/swin.hip: window_attention_kernel<32>): the cases, a float64
 statement of the published operation written out here, and the acceptance function -- shared by the CPU test of this file's
 own logic (test_guided_attention_cases.py) and the GPU test of the kernel (test_gpu_guided_attention.py).
 

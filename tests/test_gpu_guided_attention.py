@@ -1,4 +1,4 @@
-"""The guided window attention kernel (csrc/swin.hip: guided_window_attention_kernel) alone, through its C entry
+"""The guided window attention kernel (csrc/swin.hip: window_attention_kernel<32>) alone, through its C entry
 rgbd_guided_window_attention, against the float64 statement of tests/guided_attention_cases.py (which
 tests/test_guided_attention_cases.py pins to the reference's way of computing it).
 

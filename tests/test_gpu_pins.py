@@ -44,6 +44,24 @@ def _cases():
                                     torch.cuda.current_stream().cuda_stream) == 0
         torch.cuda.synchronize()
         out[f"layernorm_{C}"] = _sha(y)
+    # the two window-attention ops (csrc/swin.hip), whose op tests are tolerance tests: (B, H, W, heads, shift), padded
+    # strides at B == 2.  All nine mask regions with a partly filled last workgroup, the C = 384 stage, an odd shift, and a
+    # paired launch (both sets' outputs); guided: the same, and one window row with one head.
+    import guided_attention_cases as gc
+    from test_gpu_guided_attention import _gpu as _gwa_gpu
+    from test_gpu_swin import _wa_gpu, _wa_inputs
+
+    L = lib()
+    for n, (B, H, W, heads, shift) in enumerate([(2, 8, 12, 3, 2), (1, 12, 8, 24, 0), (1, 8, 12, 3, 3)]):
+        qkv, rpb, _, ocs = _wa_inputs(B, H, W, heads, 2.6, B == 2, seed=9100 + n)
+        out[f"window_attention_{B}x{H}x{W}_h{heads}_s{shift}"] = _sha(_wa_gpu(L, qkv, rpb, heads, shift, ocs))
+    qa, ra, _, ocs = _wa_inputs(2, 12, 8, 3, 2.6, True, seed=9110)
+    qb, rb, _, _ = _wa_inputs(2, 12, 8, 3, 2.6, True, seed=9111)
+    pa, pb = _wa_gpu(L, qa, ra, 3, 2, ocs, pair=(qb, rb))
+    out["window_attention_pair_2x12x8_h3_s2_set0"], out["window_attention_pair_2x12x8_h3_s2_set1"] = _sha(pa), _sha(pb)
+    for n, (B, H, W, heads, shift) in enumerate([(2, 8, 12, 3, 2), (1, 12, 8, 3, 0), (1, 4, 20, 1, 2), (1, 8, 12, 3, 3)]):
+        q, kv, rpb, _, _, ocs = gc.inputs(B, H, W, heads, B == 2, 9200 + n)
+        out[f"guided_attention_{B}x{H}x{W}_h{heads}_s{shift}"] = _sha(_gwa_gpu(L, q, kv, rpb, heads, shift, ocs))
     # round-4 review, item 3: the kernels behind a decision or a reported number that are not convolutions -- the factorised
     # prior (eb_forward, entropy_models.py:391-428), the Gaussian likelihoods of the checkerboard parts (ckbd_estimate,
     # entropy_models.py:534-558; its quantiser is ckbd_part's), x_hat of the eval forward, and the metric kernel
