@@ -380,6 +380,25 @@ int rgbd_elic_forward_single_mid(rgbd_elic* m, const float* x_dev, int32_t B, in
 int rgbd_aligner_create(int32_t in_ch, int32_t out_ch, rgbd_elic** out);
 int rgbd_aligner_forward(rgbd_elic* m, const float* x_dev, const float* guided_dev, int32_t B, int32_t H, int32_t W,
                          float* out_dev, void* stream);
+/* The three attention contexts of MLIC++ alone (modules/transform/context.py; MLICPlusPlus builds them with slice_ch 32,
+ * config/config.py:15-18).  Handles of the aligner's kind: set_tensor under the reference's state-dict names (Linear weights
+ * as [out][in][1][1], depthwise weights as [C][1][3][3]), finalize, clone_shared, destroy; no tables; the codec calls on such
+ * a handle, and a forward call on a handle of another family, return RGBD_EINVAL.  All tensors NCHW fp32 on the device.
+ * rgbd_local_context_*: LocalContext(dim) (:33-137): norm1, qkv_proj, rgbd_local_ckbd_attention (5x5 window, 2 heads of 16,
+ *   with `fusion`), proj, x + mlp(norm2(x)).  dim must be 32.  x [B,dim,H,W] -> out [B,2 dim,H,W], any H, W >= 1.
+ * rgbd_linear_inter_*: LinearGlobalInterContext(dim, out_dim, heads) (:216-262): keys / queries / values = 1x1 + depthwise 3x3
+ *   of x1, rgbd_linear_attention mode 0, 5x5 reprojection to 3/2 out_dim, skip(a) + mlp(a).  dim / heads in {16, 32},
+ *   out_dim % 32 == 0.  x1 [B,dim,H,W] -> out [B,out_dim,H,W].
+ * rgbd_linear_intra_*: LinearGlobalIntraContext(dim, heads) (:163-213): keys from the anchor half of x1 ((row + col) odd,
+ *   utils/ckbd.py:37-48), queries from the other half, values from x2, rgbd_linear_attention mode 1, 5x5 reprojection to
+ *   2 dim, a + mlp(a).  dim / heads in {16, 32}, W even.  x1, x2 [B,dim,H,W] -> out [B,2 dim,H,W]. */
+int rgbd_local_context_create(int32_t dim, rgbd_elic** out);
+int rgbd_local_context_forward(rgbd_elic* m, const float* x_dev, int32_t B, int32_t H, int32_t W, float* out_dev, void* stream);
+int rgbd_linear_inter_create(int32_t dim, int32_t out_dim, int32_t heads, rgbd_elic** out);
+int rgbd_linear_inter_forward(rgbd_elic* m, const float* x1_dev, int32_t B, int32_t H, int32_t W, float* out_dev, void* stream);
+int rgbd_linear_intra_create(int32_t dim, int32_t heads, rgbd_elic** out);
+int rgbd_linear_intra_forward(rgbd_elic* m, const float* x1_dev, const float* x2_dev, int32_t B, int32_t H, int32_t W,
+                              float* out_dev, void* stream);
 
 /*
  * STF_united (BASELINE config 5): replaces models/stf_united.py: SymmetricalTransFormerUnited :605-678 with
@@ -628,6 +647,38 @@ int rgbd_window_attention(const float* qkv, int32_t B, int32_t H, int32_t W, int
  * qcs % 4 == 0, kvcs % 4 == 0, q and kv 16-byte aligned, B * (H/4) * (W/4) * heads <= 0x7fffffff - 16, no pointer NULL. */
 int rgbd_guided_window_attention(const float* q, int32_t qcs, const float* kv, int32_t kvcs, int32_t B, int32_t H, int32_t W,
                                  int32_t C, int32_t heads, int32_t shift, const float* rpb, float* out, int32_t ocs, void* stream);
+/* The kernels of MLIC++'s attention contexts alone (csrc/context_attn.hip; modules/transform/context.py).  fp32, single-chain
+ * sums in a fixed order: the same bits on every call, and image b of a batch as it is alone.  Each returns RGBD_EINVAL and
+ * writes nothing when a condition below fails or a pointer is NULL.  Inputs and outputs must not overlap.
+ * rgbd_local_ckbd_attention: LocalContext.forward :93-133.  qkv: [B][H][W][qcs], channel which * C + c, which 0 / 1 / 2 =
+ *   q / k / v, c = d * heads + h (head fast, :102-110); table: relative_position_table [81][heads]; fusion_w: [2C][C][5][5],
+ *   fusion_b: [2C]; out: [B][H][W][ocs], channels 0 .. 2C - 1 written (input channel of fusion: h * 16 + d, :127-132),
+ *   channels 2C .. ocs - 1 untouched.  Around every position a 5x5 window (zeros outside the map, which still take part in
+ *   the softmax); per head softmax_j((q_i / 4) k_j + table[(iy - jy + 4) * 9 + ix - jx + 4][h] + mask[i][j]) v_j with
+ *   mask 0 where window positions i and j are both inside the map with (row + col) odd and -100 (a finite addend)
+ *   otherwise (:67-78); then fusion over the 25 * C values.  Conditions: C == 32, heads == 2, qcs >= 3C, qcs % 4 == 0,
+ *   ocs >= 2C, qkv and fusion_w 16-byte aligned, B <= 65535, H <= 131070, B * H * W <= 0x7fffffff.
+ * rgbd_linear_attention: :198-208 (mode 1) and :250-259 (mode 0).  k, q, v, out: [B][H][W][kcs / qcs / vcs / ocs], channel
+ *   head * head_dim + d; out channels 0 .. heads * head_dim - 1 written, the others untouched.  Per image and head:
+ *   Ks = softmax over the tokens of each key channel, Qs = softmax over the head's channels at each token,
+ *   ctx[d1][d2] = sum_n Ks[d1][n] v[d2][n], out[d2][n] = sum_d1 ctx[d1][d2] Qs[d1][n].  mode 0: every position is a token of
+ *   all three.  mode 1: the tokens of k and v are the anchor positions ((row + col) odd), those of q the others; out is
+ *   written at the query positions and is 0.0f at the anchor positions.  ws: scratch of ws_floats floats, at least
+ *   rgbd_linear_attention_ws_floats(...) (which returns RGBD_EINVAL for a shape the kernel refuses).  Conditions: head_dim
+ *   16 or 32, mode 0 or 1, W even in mode 1, strides >= heads * head_dim and % 4 == 0, k, q, v, out 16-byte aligned,
+ *   B, heads <= 65535, B * H * W <= 0x7fffffff.
+ * rgbd_dwconv3x3: nn.Conv2d(C, C, 3, 1, 1, groups = C) (+ nn.GELU(), erf form, when gelu == 1).  x: [B][H][W][xcs],
+ *   w: [C][1][3][3], bias: [C], y: [B][H][W][ycs], channels C .. ycs - 1 untouched.  Conditions: xcs >= C, ycs >= C,
+ *   gelu 0 or 1, x != y, B * H * W <= 0x7fffffff. */
+int rgbd_local_ckbd_attention(const float* qkv, int32_t qcs, int32_t B, int32_t H, int32_t W, int32_t C, int32_t heads,
+                              const float* table, const float* fusion_w, const float* fusion_b, float* out, int32_t ocs,
+                              void* stream);
+int64_t rgbd_linear_attention_ws_floats(int32_t B, int32_t H, int32_t W, int32_t heads, int32_t head_dim, int32_t mode);
+int rgbd_linear_attention(const float* k, int32_t kcs, const float* q, int32_t qcs, const float* v, int32_t vcs, int32_t B,
+                          int32_t H, int32_t W, int32_t heads, int32_t head_dim, int32_t mode, float* out, int32_t ocs, float* ws,
+                          int64_t ws_floats, void* stream);
+int rgbd_dwconv3x3(const float* x, int32_t B, int32_t H, int32_t W, int32_t C, int32_t xcs, const float* w, const float* bias,
+                   int32_t gelu, float* y, int32_t ycs, void* stream);
 int rgbd_patch_merge_gather(const float* x, int32_t B, int32_t H, int32_t W, int32_t C, int32_t xcs, float* y, int32_t ycs,
                             void* stream);
 int rgbd_pixel_shuffle2(const float* x, int32_t B, int32_t H, int32_t W, int32_t Co, int32_t xcs, float* y, int32_t ycs,

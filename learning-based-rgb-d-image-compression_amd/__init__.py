@@ -22,6 +22,7 @@ modelZoo = {"ELIC_united_R2D": ELIC_united_R2D, "ELIC_united": ELIC_united, "ELI
             "STF_united": SymmetricalTransFormerUnited, "STF": SymmetricalTransFormer, "ckbd": Cheng2020AnchorwithCheckerboard}
 elic_united.modelZoo = modelZoo  # (`from rgbd_amd.elic_united import modelZoo`, the name's first home, is this dict)
 from .aligner import Spatial_aligner  # noqa: F401,E402
+from .mlic_context import LinearGlobalInterContext, LinearGlobalIntraContext, LocalContext  # noqa: F401,E402
 from .pool import CodecPool  # noqa: F401,E402
 from . import datautils, ioutils, metrics, tester  # noqa: F401,E402
 from .tester import TesterSingle, TesterUnited  # noqa: F401,E402

@@ -9,7 +9,7 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _SO = os.path.join(_HERE, "librgbd_amd.so")
 _SO = os.environ.get("RGBD_AMD_LIB", _SO)  # A/B builds: point at another librgbd_amd.so
-_SRCS = ["conv_mfma.hip", "conv_mfma_blk.hip", "pointwise.hip", "swin.hip", "entropy.hip", "metrics.hip", "coder_abi.hip", "gdn.hip", "engine.hip", "engine_abi.hip"]
+_SRCS = ["conv_mfma.hip", "conv_mfma_blk.hip", "pointwise.hip", "swin.hip", "entropy.hip", "metrics.hip", "coder_abi.hip", "gdn.hip", "context_attn.hip", "engine.hip", "engine_abi.hip"]
 _LIB = None
 
 ERRORS = {-22: "invalid argument", -12: "out of memory", -5: "HIP runtime error", -28: "buffer too small",
@@ -184,6 +184,16 @@ def lib():
         "rgbd_aligner_create": (ctypes.c_int, [c_i32, c_i32, ctypes.POINTER(c_vp)]),
         "rgbd_aligner_forward": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp]),
         "rgbd_guided_window_attention": (ctypes.c_int, [c_vp, c_i32, c_vp, c_i32] + [c_i32] * 6 + [c_vp, c_vp, c_i32, c_vp]),
+        "rgbd_local_context_create": (ctypes.c_int, [c_i32, ctypes.POINTER(c_vp)]),
+        "rgbd_local_context_forward": (ctypes.c_int, [c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp]),
+        "rgbd_linear_inter_create": (ctypes.c_int, [c_i32, c_i32, c_i32, ctypes.POINTER(c_vp)]),
+        "rgbd_linear_inter_forward": (ctypes.c_int, [c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp]),
+        "rgbd_linear_intra_create": (ctypes.c_int, [c_i32, c_i32, ctypes.POINTER(c_vp)]),
+        "rgbd_linear_intra_forward": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp]),
+        "rgbd_local_ckbd_attention": (ctypes.c_int, [c_vp] + [c_i32] * 6 + [c_vp, c_vp, c_vp, c_vp, c_i32, c_vp]),
+        "rgbd_linear_attention_ws_floats": (c_i64, [c_i32] * 6),
+        "rgbd_linear_attention": (ctypes.c_int, [c_vp, c_i32, c_vp, c_i32, c_vp, c_i32] + [c_i32] * 6 + [c_vp, c_i32, c_vp, c_i64, c_vp]),
+        "rgbd_dwconv3x3": (ctypes.c_int, [c_vp] + [c_i32] * 5 + [c_vp, c_vp, c_i32, c_vp, c_i32, c_vp]),
         "rgbd_elic_debug_tensor": (ctypes.c_int, [c_vp, ctypes.c_char_p, f32p, c_i64, i32p]),
         "rgbd_elic_debug_symbols": (ctypes.c_int, [c_vp, c_i32, i32p, i32p, c_i64, i64p]),
         "rgbd_elic_set_profile": (ctypes.c_int, [c_vp, c_i32]),
@@ -243,7 +253,9 @@ EXPORTS = ["rgbd_abi_version", "rgbd_set_blocking_sync", "rgbd_get_blocking_sync
            "rgbd_guided_window_attention", "rgbd_aligner_create", "rgbd_aligner_forward", "rgbd_elic_decompress_single_mid",
            "rgbd_elic_forward_single_mid", "rgbd_pw_channel_mean", "rgbd_pw_se_gate", "rgbd_pw_bilinear", "rgbd_pw_maxpool7s3",
            "rgbd_pw_channel_scale", "rgbd_pw_copy_channels", "rgbd_pw_im2col5s2", "rgbd_pw_fill_zero", "rgbd_pw_nchw_to_nhwc",
-           "rgbd_pw_nhwc_to_nchw"]
+           "rgbd_pw_nhwc_to_nchw", "rgbd_local_context_create", "rgbd_local_context_forward", "rgbd_linear_inter_create",
+           "rgbd_linear_inter_forward", "rgbd_linear_intra_create", "rgbd_linear_intra_forward", "rgbd_local_ckbd_attention",
+           "rgbd_linear_attention_ws_floats", "rgbd_linear_attention", "rgbd_dwconv3x3"]
 
 
 _BS_HOLDERS = 0

@@ -11,9 +11,6 @@ takes the query from x and key / value from guided, and a 2x2 stride-2 transpose
 reference's (patch_embeding1/2, blocks.K.{norm1,attn.{qkv1,qkv2,proj,relative_position_bias_table,relative_position_index},
 norm2,mlp.{fc1,fc2}}, recovery); the index buffer is accepted and ignored.  No CPU path.
 """
-from collections import OrderedDict
-
-import numpy as np
 import torch
 
 from ._lib import check, lib
@@ -34,24 +31,6 @@ class Spatial_aligner(EngineModule):
 
     def _create_engine(self):
         return self._create("rgbd_aligner_create", self.in_channel, self.out_channel)
-
-    def load_state_dict(self, state_dict, strict=True):
-        self._require_owner("load_state_dict")
-        missing = [k for k, e in self._entries.items() if k not in state_dict and (e.is_param or strict)]
-        unexpected = [k for k in state_dict if k not in self._entries]
-        if strict and (missing or unexpected):
-            raise RuntimeError(f"Error(s) in loading state_dict for Spatial_aligner: missing {missing[:5]}, unexpected {unexpected[:5]}")
-        params = OrderedDict(self._materialize()) if missing else OrderedDict()
-        for name, e in self._entries.items():
-            if name not in state_dict:
-                continue
-            v = state_dict[name]
-            v = v.detach().cpu() if isinstance(v, torch.Tensor) else torch.as_tensor(np.asarray(v))
-            if tuple(v.shape) != tuple(e.shape):
-                raise RuntimeError(f"size mismatch for {name}: checkpoint {tuple(v.shape)} vs model {tuple(e.shape)}")
-            params[name] = v.float().contiguous().clone() if e.is_param else v.clone()
-        self._params = params
-        self._dirty = True
 
     def forward(self, x, guided):  # spatialAligner.py:376-390
         self._ready()

@@ -556,6 +556,53 @@ def spatial_aligner_entries(in_ch: int = 192, out_ch: int = 192, prefix: str = "
     return b.entries
 
 
+def local_context_entries(dim: int = 32, window_size: int = 5, mlp_ratio: float = 2.0, num_heads: int = 2,
+                          qkv_bias: bool = True) -> "OrderedDict[str, Entry]":
+    """Every state_dict entry of MLIC++'s LocalContext (reference: modules/transform/context.py:33-56), in the reference's
+    order: the module's own table and index buffer, then qkv_proj, proj, mlp, the two LayerNorms and the window-sized `fusion`."""
+    b = _Builder()
+    b.entries["relative_position_table"] = Entry(((2 * window_size - 1) ** 2, num_heads), "rpb_table")
+    b.buffer("relative_position_index", (window_size ** 2, window_size ** 2), "int64")
+    b.linear("qkv_proj", dim, 3 * dim, qkv_bias)
+    b.linear("proj", 2 * dim, 2 * dim)
+    b.linear("mlp.fc1", 2 * dim, int(2 * dim * mlp_ratio))
+    b.linear("mlp.fc2", int(2 * dim * mlp_ratio), 2 * dim)
+    b.layernorm("norm1", dim)
+    b.layernorm("norm2", 2 * dim)
+    b.conv("fusion", dim, 2 * dim, window_size)
+    return b.entries
+
+
+def _linear_context_entries(dim: int, mid: int, hidden: int, out: int, skip: bool) -> "OrderedDict[str, Entry]":
+    b = _Builder()
+
+    def dw(name, c):  # nn.Conv2d(c, c, 3, 1, 1, groups=c): weight [c][1][3][3]
+        b.conv(name, 1, c, 3)
+
+    for n in ("keys", "queries", "values"):
+        b.conv(f"{n}.0", dim, dim, 1)
+        dw(f"{n}.1", dim)
+    b.conv("reprojection", dim, mid, 5)
+    b.conv("mlp.0", mid, hidden, 1)
+    dw("mlp.2", hidden)
+    b.conv("mlp.4", hidden, out, 1)
+    if skip:
+        b.conv("skip", mid, out, 1)
+    return b.entries
+
+
+def linear_global_intra_entries(dim: int = 32) -> "OrderedDict[str, Entry]":
+    """LinearGlobalIntraContext (context.py:163-187): keys / queries / values = 1x1 + depthwise 3x3, a 5x5 reprojection to
+    2 dim and the 1x1 / depthwise / 1x1 mlp."""
+    return _linear_context_entries(dim, 2 * dim, 4 * dim, 2 * dim, False)
+
+
+def linear_global_inter_entries(dim: int = 32, out_dim: int = 64) -> "OrderedDict[str, Entry]":
+    """LinearGlobalInterContext (context.py:216-241): as the intra context with a reprojection to 3/2 out_dim, an mlp over
+    2 out_dim and the 1x1 `skip`."""
+    return _linear_context_entries(dim, out_dim * 3 // 2, 2 * out_dim, out_dim, True)
+
+
 def ckbd_config(N: int = 192) -> Config:
     """Cheng2020 anchor model with the checkerboard context (models/Cheng2020withCKBD.py:46-50): M = N, one slice."""
     cfg = model_config()

@@ -249,6 +249,20 @@ int launch_guided_window_attention(const float* q, int qcs, const float* kv, int
 int launch_patch_merge_gather(const float* x, int B, int H, int W, int C, int xcs, float* y, int ycs, hipStream_t s);
 int launch_pixel_shuffle2(const float* x, int B, int H, int W, int Co, int xcs, float* y, int ycs, hipStream_t s);
 
+// ---- MLIC++ context operators (context_attn.hip; modules/transform/context.py); all check their arguments ----
+// 5x5 window attention with the checkerboard mask and the `fusion` product: qkv [B,H,W,qcs] (q | k | v, head fast) -> [B,H,W,ocs]
+int launch_local_ckbd_attention(const float* qkv, int qcs, int B, int H, int W, int C, int heads, const float* table,
+                                const float* fusion_w, const float* fusion_b, float* out, int ocs, hipStream_t s);
+// linear attention; mode 0: all positions, 1: keys / values at anchor, queries at non-anchor positions.  ws: ws_floats floats
+int64_t linear_attention_ws_floats(int B, int H, int W, int heads, int head_dim, int mode);
+int launch_linear_attention(const float* k, int kcs, const float* q, int qcs, const float* v, int vcs, int B, int H, int W,
+                            int heads, int head_dim, int mode, float* out, int ocs, float* ws, int64_t ws_floats, hipStream_t s);
+// depthwise 3x3, stride 1, pad 1; w: [C][9], gelu: 0 / 1
+int launch_dwconv3x3(const float* x, int B, int H, int W, int C, int xcs, const float* w, const float* bias, int gelu, float* y,
+                     int ycs, hipStream_t s);
+// xa = x at the anchor positions and 0 elsewhere, xn the other half (utils/ckbd.py:37-48); all three with channel stride cs
+int launch_ckbd_split(const float* x, int B, int H, int W, int cs, float* xa, float* xn, hipStream_t s);
+
 // ---- GDN / IGDN (gdn.hip) -----------------------------------------------------------------------
 // out = x * f(beta + gamma * x^2) (+ res) per pixel; f = 1 / sqrt, or sqrt when inverse (gdn.py:52-67)
 struct GdnArgs {

@@ -421,10 +421,13 @@ struct rgbd_elic {
     int tile_mode = 0;  // rgbd_elic_set_tile_mode: 0 latency tiles (isolated launches), 1 throughput tiles (shared chip)
     int variant = 0;  // 0: ELIC_united (RGB + depth), 1: single-modal ELIC (models/elic.py), 2: STF_united, 3: ELIC_united_R2D,
                       // 4: single-modal STF (models/stf.py), 5: checkerboard Cheng2020 (models/Cheng2020withCKBD.py),
-                      // 6: Spatial_aligner alone (modules/transform/spatialAligner.py): no codec, rgbd_aligner_forward only
+                      // 6: Spatial_aligner alone (modules/transform/spatialAligner.py): no codec, rgbd_aligner_forward only,
+                      // 7 / 8 / 9: LocalContext / LinearGlobalInterContext / LinearGlobalIntraContext of MLIC++ alone
+                      // (modules/transform/context.py): no codec, rgbd_local_context_forward / rgbd_linear_*_forward only
     bool single() const { return variant == 1 || variant == 4 || variant == 5; }
-    int in_ch = 3;    // image channels of the single-modal variant (variant 6: channels of x and guided)
-    int out_ch = 0;   // variant 6: output channels
+    int in_ch = 3;    // image channels of the single-modal variant (variant 6: channels of x and guided; 7-9: dim)
+    int out_ch = 0;   // variants 6-9: output channels
+    int ctx_heads = 0;  // variants 7-9: num_heads
     // what the call paths (engine.hip) need to know about one versus two modalities; arrays are read at [0, nm)
     struct Modes {
         int nm;
@@ -2233,6 +2236,72 @@ struct rgbd_elic {
         }
         return pixel_shuffle(conv(p + "recovery", ex, 1, 0));
     }
+    // ---- the attention contexts of MLIC++ (modules/transform/context.py), each a block of its own (variants 7-9) -------
+    // nn.Conv2d(C, C, 3, 1, 1, groups = C) (+ nn.GELU()): weight [C][1][3][3] and bias as plain arrays (finalize)
+    Act dwconv(const std::string& name, const Act& x, bool gelu)
+    {
+        const Act y = alloc(x.n, x.h, x.w, x.c);
+        float* w = dense_of(name + ".weight");
+        float* b = dense_of(name + ".bias");
+        if (dry() || rc || !w || !b) return y;
+        const int r = launch_dwconv3x3(x.p, x.n, x.h, x.w, x.c, x.cs, w, b, gelu ? 1 : 0, y.p, y.cs, s);
+        if (r) fail(r);
+        return y;
+    }
+    // LocalContext.forward (:82-137): norm1, qkv_proj, the 5x5 window attention with `fusion` (one launch), proj, and
+    // x + mlp(norm2(x)); the Linear layers are 1x1 convolutions, GELU and the add their epilogues
+    Act local_context(const Act& x)
+    {
+        const Act t = layernorm("norm1", x);
+        const Act qkv = conv("qkv_proj", t, 1, 0);
+        const Act a = alloc(x.n, x.h, x.w, 2 * x.c);
+        float* tab = dense_of("relative_position_table");
+        float* fw = dense_of("fusion.weight");
+        float* fb = dense_of("fusion.bias");
+        if (!dry() && !rc && tab && fw && fb) {
+            const int r = launch_local_ckbd_attention(qkv.p, qkv.cs, x.n, x.h, x.w, x.c, ctx_heads, tab, fw, fb, a.p, a.cs, s);
+            if (r) fail(r);
+        }
+        const Act x1 = conv("proj", a, 1, 0);
+        const Act t2 = layernorm("norm2", x1);
+        Epi g;
+        g.act = ACT_GELU;
+        const Act hdn = conv("mlp.fc1", t2, 1, 0, g);
+        Epi e;
+        e.res1 = &x1;
+        return conv("mlp.fc2", hdn, 1, 0, e);
+    }
+    // LinearGlobalInterContext.forward (:243-262; xk = xq = xv = x1, mode 0, with `skip`) and LinearGlobalIntraContext.forward
+    // (:189-213; xk = anchor half of x1, xq = the other half, xv = x2, mode 1, no `skip`): three 1x1 + depthwise branches, the
+    // linear attention, the 5x5 reprojection, and skip(a) (or a) + mlp(a)
+    Act linear_context(const Act& xk, const Act& xq, const Act& xv, int mode, bool skip)
+    {
+        const Act k = dwconv("keys.1", conv("keys.0", xk, 1, 0), false);
+        const Act q = dwconv("queries.1", conv("queries.0", xq, 1, 0), false);
+        const Act v = dwconv("values.1", conv("values.0", xv, 1, 0), false);
+        const Act a = alloc(k.n, k.h, k.w, k.c);
+        const int hd = k.c / ctx_heads;
+        const int64_t wsf = linear_attention_ws_floats(k.n, k.h, k.w, ctx_heads, hd, mode);
+        if (wsf <= 0) {
+            fail(RGBD_EINVAL);
+            return a;
+        }
+        float* ws = (float*)arena.take((size_t)wsf * sizeof(float));
+        if (!dry() && !rc) {
+            const int r = launch_linear_attention(k.p, k.cs, q.p, q.cs, v.p, v.cs, k.n, k.h, k.w, ctx_heads, hd, mode, a.p, a.cs, ws,
+                                                  wsf, s);
+            if (r) fail(r);
+        }
+        const Act att = conv("reprojection", a, 1, 2);
+        Epi g;
+        g.act = ACT_GELU;
+        const Act h1 = conv("mlp.0", att, 1, 0, g);
+        const Act h2 = dwconv("mlp.2", h1, true);
+        const Act sk = skip ? conv("skip", att, 1, 0) : att;
+        Epi e;
+        e.res1 = &sk;
+        return conv("mlp.4", h2, 1, 0, e);
+    }
     // stf_united.py:270-366 for both modalities; down: 0 none, 1 PatchMerging (:217-249), 2 PatchSplit (:252-267)
     void basic_layer2(int nm, const std::string p[2], const Act x_in[2], int depth, int heads, int down, Act out[2])
     {
@@ -2813,6 +2882,8 @@ struct rgbd_elic {
     void mids_begin(int B, int H, int W, Act mid[3]);  // workspace of up1..up3; g_s1 fills it while mid_dst points at it
     int mids_out(const Act mid[3], int B, int H, int W, const Mid3& up);
     int run_aligner(const float* x_dev, const float* guided_dev, int B, int H, int W, float* out_dev);
+    // variants 7-9: x1 (and, variant 9, x2) [B,in_ch,H,W] -> out [B,out_ch,H,W]
+    int run_context(const float* x1_dev, const float* x2_dev, int B, int H, int W, float* out_dev);
     int ensure_arena(size_t bytes);
 };
 

@@ -652,6 +652,42 @@ int rgbd_elic::run_aligner(const float* x_dev, const float* guided_dev, int B, i
     return r;
 }
 
+// An attention context of MLIC++ alone (variants 7-9): x1 (and x2 of LinearGlobalIntraContext) [B,in_ch,H,W] -> [B,out_ch,H,W]
+int rgbd_elic::run_context(const float* x1_dev, const float* x2_dev, int B, int H, int W, float* out_dev)
+{
+    begin_call(B, true);
+    const Act x1 = alloc(B, H, W, in_ch), x2 = variant == 9 ? alloc(B, H, W, in_ch) : Act();
+    if (!dry()) {
+        int r = launch_nchw_to_nhwc16(x1_dev, B, in_ch, H, W, x1.p, x1.cs, s);
+        if (!r && variant == 9) r = launch_nchw_to_nhwc16(x2_dev, B, in_ch, H, W, x2.p, x2.cs, s);
+        if (r) return r;
+    }
+    // ==== body: captured into / replayed from a HIP graph per call shape ====
+    Act out;
+    if (body_begin()) {
+        if (variant == 7) {
+            out = local_context(x1);
+        } else if (variant == 8) {
+            out = linear_context(x1, x1, x1, 0, true);
+        } else {
+            const Act xa = alloc(B, H, W, in_ch), xn = alloc(B, H, W, in_ch);  // ckbd_anchor(x1), ckbd_nonanchor(x1): :191-192
+            if (!dry() && !rc) {
+                const int r = launch_ckbd_split(x1.p, B, H, W, x1.cs, xa.p, xn.p, s);
+                if (r) fail(r);
+            }
+            out = linear_context(xa, xn, x2, 1, false);
+        }
+        if (cur_ge && !dry()) cur_ge->out[0] = out;
+    } else {
+        out = cur_ge->out[0];
+    }
+    if (const int r = finish_body()) return r;
+    if (dry()) return RGBD_OK;
+    int r = launch_nhwc_to_nchw_clamp(out.p, B, out_ch, H, W, out.cs, out_dev, 0, s);
+    if (!r) r = wait_stream();
+    return r;
+}
+
 // decompress: elic_united.py:462-578, elic.py:255-325, stf.py:766-816, Cheng2020withCKBD.py:138-174; h x w: the latent grid
 int rgbd_elic::run_decompress(int nm, const uint8_t* const* ys[2], const int64_t* ylen[2], int n_y, const uint8_t* const* zs[2],
                               const int64_t* zlen[2], int B, int h, int w, Out2 xhat_dev, const Latents* lat, const Mid3* up)

@@ -1105,6 +1105,70 @@ int rgbd_aligner_forward(rgbd_elic* m, const float* x_dev, const float* guided_d
     return run_sized(m, key, [&]() { return m->run_aligner(x_dev, guided_dev, B, H, W, out_dev); });
 }
 
+// The attention contexts of MLIC++ alone (modules/transform/context.py): handles of the aligner's kind (no codec, no tables)
+static int context_create(int variant, int32_t dim, int32_t out_ch, int32_t heads, rgbd_elic** out)
+{
+    const int32_t slice = 96;
+    const int r = rgbd_elic_create(96, 96, &slice, 1, out);
+    if (r) return r;
+    (*out)->variant = variant;
+    (*out)->in_ch = dim;
+    (*out)->out_ch = out_ch;
+    (*out)->ctx_heads = heads;
+    (*out)->refnum = false;  // the single-chain arithmetic of the Swin path
+    return RGBD_OK;
+}
+
+int rgbd_local_context_create(int32_t dim, rgbd_elic** out)
+{
+    if (!out || dim != 32) return RGBD_EINVAL;  // window 5, 2 heads of 16: the one form MLIC++ builds (context_attn.hip)
+    return context_create(7, dim, 2 * dim, 2, out);
+}
+
+int rgbd_linear_inter_create(int32_t dim, int32_t out_dim, int32_t heads, rgbd_elic** out)
+{
+    if (!out || heads < 1 || dim < 1 || dim > 1024 || dim % heads || (dim / heads != 16 && dim / heads != 32) || out_dim < 32 ||
+        out_dim > 1024 || out_dim % 32)
+        return RGBD_EINVAL;
+    return context_create(8, dim, out_dim, heads, out);
+}
+
+int rgbd_linear_intra_create(int32_t dim, int32_t heads, rgbd_elic** out)
+{
+    if (!out || heads < 1 || dim < 1 || dim > 1024 || dim % heads || (dim / heads != 16 && dim / heads != 32)) return RGBD_EINVAL;
+    return context_create(9, dim, 2 * dim, heads, out);
+}
+
+static int context_forward(rgbd_elic* m, int variant, const float* x1_dev, const float* x2_dev, int32_t B, int32_t H, int32_t W,
+                           float* out_dev, void* stream)
+{
+    if (!m || m->variant != variant) return RGBD_EINVAL;
+    if (!m->finalized) return RGBD_ESTATE;
+    if (!x1_dev || (variant == 9 && !x2_dev) || !out_dev || B <= 0 || H <= 0 || W <= 0 || (variant == 9 && (W & 1)) ||
+        (int64_t)B * H * W > 0x7fffffff)
+        return RGBD_EINVAL;
+    if (const int ur = m->use_stream(stream)) return ur;
+    char key[96];
+    snprintf(key, sizeof(key), "cx%d|%d|%d|%d", variant, B, H, W);
+    return run_sized(m, key, [&]() { return m->run_context(x1_dev, x2_dev, B, H, W, out_dev); });
+}
+
+int rgbd_local_context_forward(rgbd_elic* m, const float* x_dev, int32_t B, int32_t H, int32_t W, float* out_dev, void* stream)
+{
+    return context_forward(m, 7, x_dev, nullptr, B, H, W, out_dev, stream);
+}
+
+int rgbd_linear_inter_forward(rgbd_elic* m, const float* x1_dev, int32_t B, int32_t H, int32_t W, float* out_dev, void* stream)
+{
+    return context_forward(m, 8, x1_dev, nullptr, B, H, W, out_dev, stream);
+}
+
+int rgbd_linear_intra_forward(rgbd_elic* m, const float* x1_dev, const float* x2_dev, int32_t B, int32_t H, int32_t W,
+                              float* out_dev, void* stream)
+{
+    return context_forward(m, 9, x1_dev, x2_dev, B, H, W, out_dev, stream);
+}
+
 int rgbd_elic_clone_shared(const rgbd_elic* src, rgbd_elic** out)
 {
     if (!src || !out || !src->finalized) return RGBD_EINVAL;
@@ -1115,6 +1179,7 @@ int rgbd_elic_clone_shared(const rgbd_elic* src, rgbd_elic** out)
     m->variant = src->variant;
     m->in_ch = src->in_ch;
     m->out_ch = src->out_ch;
+    m->ctx_heads = src->ctx_heads;
     m->refnum = src->refnum;
     m->ref_threads = src->ref_threads;
     m->ref_tab = src->ref_tab;
@@ -1287,6 +1352,17 @@ int rgbd_elic_finalize(rgbd_elic* m)
             const int r = pack_conv(w1, bit == m->raw.end() ? nullptr : &b1, false, &pc, gen.get(), 0, 0);
             if (r) return r;
             convs[name] = pc;
+        } else if (m->variant >= 7 && ends_with(name, ".weight") && t.shape.size() == 4 &&
+                   (name == "fusion.weight" || (t.shape[1] == 1 && t.shape[2] == 3 && t.shape[3] == 3))) {
+            // the contexts of MLIC++: LocalContext.fusion (read by the attention launch in the reference's [2C][C][5][5]
+            // layout) and the depthwise 3x3 layers ([C][1][3][3]) go to the device as they are, with their biases
+            auto bit = m->raw.find(name.substr(0, name.size() - 6) + "bias");
+            if (bit == m->raw.end() || (int64_t)bit->second.v.size() != t.shape[0]) return RGBD_EINVAL;
+            float *dw = nullptr, *db = nullptr;
+            if (const int r = dev_copy(t.v.data(), t.v.size(), &dw)) return r;
+            if (const int r = dev_copy(bit->second.v.data(), bit->second.v.size(), &db)) return r;
+            dense[name] = dw;
+            dense[bit->first] = db;
         } else if (ends_with(name, ".weight") && t.shape.size() == 4) {
             // ConvTranspose2d layers of this model: g_s stages 1/6/12/17 and the h_s deconvs
             // (single-modal ELIC: g_s stages 1/5/10/14 and h_s.increase.*; stage numbers that are not a bare
@@ -1379,8 +1455,8 @@ int rgbd_elic_finalize(rgbd_elic* m)
             float* d = nullptr;
             if (const int r = dev_copy(hv.data(), hv.size(), &d)) return r;
             dense[name] = d;
-        } else if ((t.shape.size() == 1 && (name.find(".norm") != std::string::npos)) ||
-                   ends_with(name, "relative_position_bias_table")) {
+        } else if ((t.shape.size() == 1 && (name.find(".norm") != std::string::npos || (m->variant == 7 && name.rfind("norm", 0) == 0))) ||
+                   ends_with(name, "relative_position_bias_table") || (m->variant == 7 && name == "relative_position_table")) {
             // Swin LayerNorm affine parameters and relative position bias tables: plain device arrays
             float* d = nullptr;
             if (const int r = dev_copy(t.v.data(), t.v.size(), &d)) return r;
@@ -1432,7 +1508,7 @@ int rgbd_elic_finalize(rgbd_elic* m)
 
 static int check_ready(const rgbd_elic* m)
 {
-    if (m && m->variant == 6) return RGBD_EINVAL;  // a Spatial_aligner handle has no codec calls
+    if (m && m->variant >= 6) return RGBD_EINVAL;  // a Spatial_aligner or context handle has no codec calls
     if (!m || !m->finalized || !m->scale_table) return RGBD_ESTATE;
     for (int i = 0; i < 4; ++i)
         if (!m->tables[i].ready && !(m->single() && (i & 1))) return RGBD_ESTATE;  // single-modal: slots 0 and 2

@@ -3,6 +3,7 @@ and its device, uploads, and shared-weight clones.  Nothing here knows about ent
 
     EngineModule                      handle lifecycle
     ├── Spatial_aligner               aligner.py
+    ├── LocalContext, LinearGlobalIntraContext, LinearGlobalInterContext    mlic_context.py
     └── Codec                         elic_united.py: entropy-table holders, streams, debug / profile hooks
         ├── ELIC_united               elic_united.py (ELIC_united_R2D, SymmetricalTransFormerUnited under it)
         └── SingleCodec               elic.py (ELIC, SymmetricalTransFormer, Cheng2020AnchorwithCheckerboard under it)
@@ -14,6 +15,7 @@ tensors, `_upload_extras(L)`.  There is no CPU execution path: every call raises
 import ctypes
 from collections import OrderedDict
 
+import numpy as np
 import torch
 
 from . import synth
@@ -70,6 +72,25 @@ class EngineModule:
     def state_dict(self):
         p = self._materialize()
         return OrderedDict((name, p[name]) for name in self._entries)
+
+    def load_state_dict(self, state_dict, strict=True):
+        """Every parameter must be there (a missing buffer only counts under strict); shapes are checked either way."""
+        self._require_owner("load_state_dict")
+        missing = [k for k, e in self._entries.items() if k not in state_dict and (e.is_param or strict)]
+        unexpected = [k for k in state_dict if k not in self._entries]
+        if strict and (missing or unexpected):
+            raise RuntimeError(f"Error(s) in loading state_dict for {self._MODEL}: missing {missing[:5]}, unexpected {unexpected[:5]}")
+        params = OrderedDict(self._materialize()) if missing else OrderedDict()
+        for name, e in self._entries.items():
+            if name not in state_dict:
+                continue
+            v = state_dict[name]
+            v = v.detach().cpu() if isinstance(v, torch.Tensor) else torch.as_tensor(np.asarray(v))
+            if tuple(v.shape) != tuple(e.shape):
+                raise RuntimeError(f"size mismatch for {name}: checkpoint {tuple(v.shape)} vs model {tuple(e.shape)}")
+            params[name] = v.float().contiguous().clone() if e.is_param else v.clone()
+        self._params = params
+        self._dirty = True
 
     def to(self, device):
         dev = torch.device(device)

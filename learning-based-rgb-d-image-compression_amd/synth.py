@@ -13,7 +13,8 @@ from collections import OrderedDict
 
 import numpy as np
 
-from .arch import (STF_SLICES, Entry, spatial_aligner_entries, ckbd_config, ckbd_entries, elic_entries, elic_united_entries, elic_united_r2d_entries, model_config, stf_config,
+from .arch import (STF_SLICES, Entry, linear_global_inter_entries, linear_global_intra_entries, local_context_entries,
+                   spatial_aligner_entries, ckbd_config, ckbd_entries, elic_entries, elic_united_entries, elic_united_r2d_entries, model_config, stf_config,
                    stf_entries, stf_single_config, stf_united_entries)
 
 _IH_STD = math.sqrt(4.0 * (65536.0**2 - 1.0) / 12.0)  # std of the sum of four uniform 16-bit ints
@@ -120,7 +121,7 @@ def make_tensor(name: str, e: Entry, seed: int) -> np.ndarray:
 
 def synthetic_state_dict(seed: int = 0, config=None, stress: bool = True, as_torch: bool = True,
                          model: str = "ELIC_united", channel: int = 3, recipe: str = None, N: int = 192,
-                         in_channel: int = 192, out_channel: int = 192):
+                         in_channel: int = 192, out_channel: int = 192, dim: int = 32, out_dim: int = 64, num_heads: int = 2):
     """Full state_dict (parameters + buffers) of ELIC_united (default), ELIC_united_R2D, STF_united, the single-modal STF
     (model="STF": recipes "stress" and "plain"), the checkerboard Cheng2020 model (model="ckbd", width N, the same two recipes)
     or the single-modal ELIC with deterministic synthetic values.  `recipe`: "stress" (= stress=True, the default: ~22 bpp, wide CDF rows, 17 % escapes -- the worst
@@ -129,7 +130,18 @@ def synthetic_state_dict(seed: int = 0, config=None, stress: bool = True, as_tor
     "high_rate" (ELIC_united only: latents of tens to hundreds, predicted scales of 10 ... 100 -- scale-table rows of 300 ...
     3000 entries, what a high-quality checkpoint makes the decoder search) or "plain" (default initialisation, everything
     quantises to zero).  model="Spatial_aligner" (in_channel, out_channel): the guided-attention block alone, always with its
-    stress recipe (_apply_stress_aligner)."""
+    stress recipe (_apply_stress_aligner).  model="LocalContext" (dim, num_heads), "LinearGlobalIntraContext" (dim) or
+    "LinearGlobalInterContext" (dim, out_dim): an attention context of MLIC++ alone, always with _apply_stress_context."""
+    if model in ("LocalContext", "LinearGlobalIntraContext", "LinearGlobalInterContext"):
+        entries = (local_context_entries(dim, num_heads=num_heads) if model == "LocalContext" else
+                   linear_global_intra_entries(dim) if model == "LinearGlobalIntraContext" else linear_global_inter_entries(dim, out_dim))
+        sd = OrderedDict((name, make_tensor(name, e, seed)) for name, e in entries.items())
+        _apply_stress_context(sd, seed)
+        if as_torch:
+            import torch
+
+            return OrderedDict((k, torch.from_numpy(np.ascontiguousarray(v))) for k, v in sd.items())
+        return sd
     if model == "Spatial_aligner":
         sd = OrderedDict()
         for name, e in spatial_aligner_entries(in_channel, out_channel).items():
@@ -208,6 +220,31 @@ def _apply_stress_aligner(sd, seed):
         E = sd[f"{p}.attn.qkv1.weight"].shape[0]
         sd[f"{p}.attn.qkv2.weight"][:E] *= g  # the key half; the value half keeps its scale
         sd[f"{p}.attn.qkv2.bias"][:E] *= g
+
+
+LOCAL_QK_GAIN = 3.5
+LINEAR_QK_GAIN = 8.0
+
+
+def _apply_stress_context(sd, seed):
+    """The attention contexts of MLIC++: what makes a wrong attention visible.  LocalContext: relative position biases of
+    order 1, LayerNorm weights in [0.5, 1.5], the query and key rows of qkv_proj scaled so that the scores (std ~0.3 with the
+    default initialisation) reach |S| of 10 to 40 -- far from a uniform softmax, and still well below the mask's 100.  The
+    linear contexts: the depthwise layers behind keys and queries scaled so that both softmaxes (over tokens, over channels)
+    see arguments of order 10."""
+    if "relative_position_table" in sd:
+        sd["relative_position_table"] = (sd["relative_position_table"] / np.float32(0.3)).astype(np.float32)
+        for n in ("norm1", "norm2"):
+            name = f"{n}.weight"
+            sd[name] = (1.0 + uniform_like(name + "#stress", seed, sd[name].shape, -0.5, 0.5)).astype(np.float32)
+        C = sd["qkv_proj.weight"].shape[1]
+        sd["qkv_proj.weight"][:2 * C] *= np.float32(LOCAL_QK_GAIN)  # the query and key rows; the value rows keep their scale
+        if "qkv_proj.bias" in sd:
+            sd["qkv_proj.bias"][:2 * C] *= np.float32(LOCAL_QK_GAIN)
+    else:
+        for n in ("keys.1", "queries.1"):
+            sd[f"{n}.weight"] = sd[f"{n}.weight"] * np.float32(LINEAR_QK_GAIN)
+            sd[f"{n}.bias"] = sd[f"{n}.bias"] * np.float32(LINEAR_QK_GAIN)
 
 
 def _apply_stress(sd, cfg, transforms=True):
