@@ -201,7 +201,10 @@ int rgbd_conv2d_ref_nchw(const float* x_dev, int32_t n, int32_t cin, int32_t h, 
  *
  *   first layer   n, cin, h, w, cout, k <= 5, stride 1 / 2, pad, transposed, act; refmode != 0: the reference's CPU arithmetic
  *                 with blocks / nblocks / bias_mode / flags as in rgbd_conv2d_ref_nchw
- *   plain form    (cout2 == 0)  y = act(conv(x) + bias + res1) * mul + res2, every operand optional; y2: a second copy of y
+ *   plain form    (cout2 == 0)  y = act(conv(x) + bias + res1) * mul + res2, every operand optional; y2: a second copy of y.
+ *                 act 0 none, 1 ReLU, 2 LeakyReLU(0.01), 3 sigmoid, 4 GELU (erf form: 0.5 v (1 + erf(v / sqrt 2))).  GELU is
+ *                 applied by the split-K reducer, as in the engine: the hook books one partial plane for it when the split
+ *                 factor is 1, splitk * n * OH * OW * cout_pad floats in general (Engine::conv_plan's rule).
  *   fused tail    (cout2 > 0)   t = act_mid(conv(x) + bias), y = act(w2 * t + bias2 + res1); w2 [cout2][cout][1][1],
  *                 act_mid 0 / 1, act 0 / 1 / 2.  In refmode the chains of the 1x1 layers start from their bias.
  *   lead layer    (cout3 > 0, with a fused tail)  u = relu(w3 * y + bias3) -> y3; w3 [cout3][cout2][1][1]
@@ -223,9 +226,11 @@ int rgbd_conv2d_ref_nchw(const float* x_dev, int32_t n, int32_t cin, int32_t h, 
  *
  * Every argument is checked on the host before anything is allocated or launched: a NULL required pointer, a bad size or any
  * combination the launchers refuse (fused with stride 2 / k = 5 / a first layer whose padded cout is not 96 / act 3, a lead
- * layer on a cout2 whose padded width is not a multiple of 32, y2 together with split-K, checkerboard output of a strided
- * layer, a grouped call with a twin pointer missing, ...) returns -22.  A forced tile that cannot hold the layer returns -28.
- * Every destination is followed on the device by a guard band of one output row and one pixel; -1 = a launch wrote into it. */
+ * layer on a cout2 whose padded width is not a multiple of 32, y2 together with split-K, act 4 with a fused tail / in refmode /
+ * with y2, act above 4, checkerboard output of a strided layer, a grouped call with a twin pointer missing, ...) returns -22.
+ * A forced tile that cannot hold the layer returns -28.
+ * Every destination, and the partial planes of a split-K / GELU launch, is followed on the device by a guard band of one output
+ * row and one pixel; -1 = a launch wrote into it. */
 typedef struct rgbd_conv_forms_ops {
     const float* x_dev;    /* [n, x_total, h, w] */
     const float* weight;   /* host: Conv2d layout, or ConvTranspose2d layout when transposed != 0 */

@@ -557,9 +557,12 @@ int rgbd_conv_forms_nchw(const rgbd_conv_forms_desc* d, void* stream)
     const int n = d->n, cin = d->cin, h = d->h, w = d->w, cout = d->cout, k = d->k, stride = d->stride, pad = d->pad;
     const bool tr = d->transposed != 0, refmode = d->refmode != 0, fused = d->cout2 > 0, lead = d->cout3 > 0;
     if (!tensor_ok(n, cin, h, w) || cout <= 0 || cout > 65536 || k < 1 || k > 5 || stride < 1 || stride > 2 || pad < 0 || pad > k ||
-        d->act < ACT_NONE || d->act > ACT_SIGMOID || d->cout2 < 0 || d->cout2 > 65536 || d->cout3 < 0 || d->cout3 > 65536 ||
+        d->act < ACT_NONE || d->act > ACT_GELU || d->cout2 < 0 || d->cout2 > 65536 || d->cout3 < 0 || d->cout3 > 65536 ||
         (lead && !fused))
         return RGBD_EINVAL;
+    // GELU is the reducer's (launch_conv): the plain form outside refmode, one destination
+    const bool gelu = d->act == ACT_GELU;
+    if (gelu && (fused || refmode || d->set[0].y2_dev || (d->groups == 2 && d->set[1].y2_dev))) return RGBD_EINVAL;
     if (!tr && (h + 2 * pad < k || w + 2 * pad < k)) return RGBD_EINVAL;
     int OH, OW;
     conv_out_hw(h, w, k, stride, pad, tr, &OH, &OW);
@@ -647,13 +650,14 @@ int rgbd_conv_forms_nchw(const rgbd_conv_forms_desc* d, void* stream)
     int rc = RGBD_OK;
     // every destination is followed by a guard band of one output row and one pixel, checked after the launch: a store predicate
     // that lets a tile run past the last image's last row or pixel is reported (RGBD_ESTATE), not left to land in foreign memory
-    const std::vector<uint32_t> guard_pat((size_t)(OW + 1) * std::max(ycs, std::max(y2cs, y3cs)), 0xC0FFEE42u);
-    auto guard_arm = [&](float* p, int cs) {
-        return hipMemcpy(p + opx * cs, guard_pat.data(), (size_t)(OW + 1) * cs * 4, hipMemcpyHostToDevice) == hipSuccess ? RGBD_OK : RGBD_EHIP;
+    // (the partial planes of a split-K / GELU launch too: `px` pixels of `cs` channels, then the band)
+    const std::vector<uint32_t> guard_pat((size_t)(OW + 1) * std::max(std::max(ycs, cout_pad), std::max(y2cs, y3cs)), 0xC0FFEE42u);
+    auto guard_arm = [&](float* p, int cs, size_t px) {
+        return hipMemcpy(p + px * cs, guard_pat.data(), (size_t)(OW + 1) * cs * 4, hipMemcpyHostToDevice) == hipSuccess ? RGBD_OK : RGBD_EHIP;
     };
-    auto guard_intact = [&](const float* p, int cs) {
+    auto guard_intact = [&](const float* p, int cs, size_t px) {
         std::vector<uint32_t> back((size_t)(OW + 1) * cs);
-        if (hipMemcpy(back.data(), p + opx * cs, back.size() * 4, hipMemcpyDeviceToHost) != hipSuccess) return RGBD_EHIP;
+        if (hipMemcpy(back.data(), p + px * cs, back.size() * 4, hipMemcpyDeviceToHost) != hipSuccess) return RGBD_EHIP;
         return memcmp(back.data(), guard_pat.data(), back.size() * 4) ? RGBD_ESTATE : RGBD_OK;
     };
     for (int g = 0; g < G && !rc; ++g) {
@@ -687,13 +691,15 @@ int rgbd_conv_forms_nchw(const rgbd_conv_forms_desc* d, void* stream)
         if (o.res1_dev) f.r1 = b.get((opx + OW + 1) * cyp);  // (the same slack as behind the destinations: what is read there is not used)
         if (o.mul_dev) f.m = b.get((opx + OW + 1) * cyp);
         if (o.res2_dev) f.r2 = b.get((opx + OW + 1) * cyp);
-        if (a.splitk > 1) f.part = b.get((size_t)a.splitk * opx * cout_pad);
+        const bool planes = a.splitk > 1 || gelu;  // (Engine::conv_plan's partial_bytes: a GELU layer books one plane)
+        if (planes) f.part = b.get(((size_t)a.splitk * opx + OW + 1) * cout_pad);
         if (!f.x || !f.y || (o.y2_dev && !f.y2) || (lead && !f.y3) || (o.res1_dev && !f.r1) || (o.mul_dev && !f.m) || (o.res2_dev && !f.r2) ||
-            (a.splitk > 1 && !f.part))
+            (planes && !f.part))
             return RGBD_ENOMEM;
-        rc = guard_arm(f.y, ycs);
-        if (!rc && f.y2) rc = guard_arm(f.y2, y2cs);
-        if (!rc && f.y3) rc = guard_arm(f.y3, y3cs);
+        rc = guard_arm(f.y, ycs, opx);
+        if (!rc && f.y2) rc = guard_arm(f.y2, y2cs, opx);
+        if (!rc && f.y3) rc = guard_arm(f.y3, y3cs, opx);
+        if (!rc && f.part) rc = guard_arm(f.part, cout_pad, (size_t)a.splitk * opx);
         if (!rc) rc = launch_nchw_to_nhwc16(o.x_dev, n, d->x_total, h, w, f.x, xcs, s, perm);
         if (!rc) rc = launch_nchw_to_nhwc16(o.y_dev, n, d->y_total, OH, OW, f.y, ycs, s, perm);
         if (!rc && f.y2) rc = launch_nchw_to_nhwc16(o.y2_dev, n, d->y2_total, OH, OW, f.y2, y2cs, s, perm);
@@ -734,9 +740,10 @@ int rgbd_conv_forms_nchw(const rgbd_conv_forms_desc* d, void* stream)
     if (!rc && e != hipSuccess) rc = RGBD_EHIP;
     for (int g = 0; g < G && !rc; ++g) {
         const FormsSet& f = fs[g];
-        rc = guard_intact(f.y, ycs);
-        if (!rc && f.y2) rc = guard_intact(f.y2, y2cs);
-        if (!rc && f.y3) rc = guard_intact(f.y3, y3cs);
+        rc = guard_intact(f.y, ycs, opx);
+        if (!rc && f.y2) rc = guard_intact(f.y2, y2cs, opx);
+        if (!rc && f.y3) rc = guard_intact(f.y3, y3cs, opx);
+        if (!rc && f.part) rc = guard_intact(f.part, cout_pad, (size_t)a.splitk * opx);
     }
     return rc;
 }

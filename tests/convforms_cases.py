@@ -18,6 +18,10 @@ Error bound of the fp64 comparisons (no new number: the per-layer rule of tests/
                                                            by the inf-operator-norm (largest row sum of |w|) of each 1x1 behind it
   mul is drawn from (0, 1) (a sigmoid gate in the model)   leaves the bound as it is
   res2                                                     + 2^-23 * max|ref|
+  GELU (family "gelu": the reducer's activation)           1.129 * (the conv rule on the pre-activation v) + max B_act, and, against
+                                                           the launch's own fp32 pre-activation, B_act(v) element by element:
+                                                           B_act(v) = (0.5 |v| (E_ERF + 2) + |gelu(v)|) 2^-24 + 2^-149  (act_bound)
+                                                           E_ERF = 4 x the error of torch's CPU fp32 erf on the cases' arguments
 """
 import zlib
 
@@ -29,6 +33,7 @@ from oracle import cpu_arith as ca
 
 f32 = np.float32
 ACT_NONE, ACT_RELU, ACT_LEAKY, ACT_SIGMOID = 0, 1, 2, 3
+ACT_GELU = 4  # erf form; applied by the split-K reducer (csrc/conv_mfma.hip), with one partial plane when the split factor is 1
 FILL_BITS = 0x4B3C614E  # what the destinations are pre-filled with (a finite float, ~1.2e7: no result of a case comes near it)
 FILL = np.array([FILL_BITS], np.uint32).view(f32)[0]
 X_FILL = (3.5, -1234.5)  # the two values the channels next to a sliced input are filled with
@@ -45,7 +50,7 @@ def case_id(c):
 def _case(cid, family, n, cin, h, w, cout, k, **kw):
     c = dict(id=cid, family=family, n=n, cin=cin, h=h, w=w, cout=cout, k=k, stride=1, pad=k // 2, transposed=0, act=ACT_NONE,
              cout2=0, act_mid=0, cout3=0, res1=False, mul=False, res2=False, y2=False, x_off=0, x_total=cin, y_off=0, y_total=None,
-             y2_off=0, y2_total=None, y3_off=0, y3_total=None, groups=1, blocked=False, splitk=1, ckbd=0)
+             y2_off=0, y2_total=None, y3_off=0, y3_total=None, groups=1, blocked=False, splitk=1, ckbd=0, seed=0)
     assert set(kw) <= set(c), kw
     c.update(kw)
     cy = c["cout2"] or cout
@@ -162,19 +167,30 @@ def _build():
     cs.append(_case("slice-in-out-split4", "slice", 1, 72, 3, 7, 24, 1, splitk=4, x_off=16, x_total=112, y_off=24, y_total=72, mul=True,
                     res2=True, act=S))
     cs.append(_case("slice-grouped", "slice", 2, 40, 3, 4, 24, 3, act=L, x_off=16, x_total=64, y_off=24, y_total=48, groups=2))
-    ids = [c["id"] for c in cs]
+    # ---- GELU: the reducer's activation, over one partial plane (split factor 1) or several.  Each case mirrors a launch of the
+    # engine; maps of at most 400 pixels.
+    G = ACT_GELU
+    cs.append(_case("gelu-k1", "gelu", 2, 48, 5, 9, 192, 1, act=G))                              # Swin mlp.fc1, C -> 4C
+    cs.append(_case("gelu-k1-grouped", "gelu", 1, 32, 3, 11, 128, 1, act=G, groups=2))           # swin_block_tail2: two modalities
+    cs.append(_case("gelu-k1-split3", "gelu", 1, 112, 3, 7, 40, 1, act=G, splitk=3))             # chunks of 3, 3, 1 groups; cout 40 -> 48
+    cs.append(_case("gelu-k3", "gelu", 2, 40, 7, 6, 100, 3, act=G))                              # h_a_stf1, stride 1; pad channels on both sides
+    cs.append(_case("gelu-k3-s2", "gelu", 2, 32, 9, 7, 48, 3, act=G, stride=2, pad=1))           # h_a_stf1, stride 2 (5 x 4 outputs)
+    cs.append(_case("gelu-k3-grouped-split2", "gelu", 1, 64, 4, 6, 128, 3, act=G, groups=2, splitk=2))  # h_s_stf1, sub-pixel layer
+    cs.append(_case("gelu-1x1grid", "gelu", 2, 32, 1, 1, 40, 1, act=G, seed=1))                  # one pixel per image (80 values:
+    # the first draw has none within 0.1 of zero -- test_convforms_cases.py::test_gelu_case_is_not_hollow)
+    ids =[c["id"] for c in cs]
     assert len(set(ids)) == len(ids)
     return cs
 
 
 CASES = _build()
-FAMILIES = ("plain", "fused", "lead", "slice")
+FAMILIES = ("plain", "fused", "lead", "slice", "gelu")
 
 
 # ================================================================================================ inputs
 def inputs(c, g=0, x_fill=X_FILL[0]):
     """Operand set g of case c (float32, NCHW).  x is the whole wide input tensor: the channels next to the slice hold x_fill."""
-    r = _rng(c["id"], g)
+    r = _rng(c["id"], g, c["seed"]) if c["seed"] else _rng(c["id"], g)  # (seed: another draw for a case too small to be sure of its shares)
     n, cin, h, w, cout, k = c["n"], c["cin"], c["h"], c["w"], c["cout"], c["k"]
     oh, ow = out_hw(c)
     cy = y_channels(c)
@@ -184,7 +200,8 @@ def inputs(c, g=0, x_fill=X_FILL[0]):
     d["x"] = x
     ws = (cin, cout, k, k) if c["transposed"] else (cout, cin, k, k)
     d["w"] = (r.standard_normal(ws) / (cin * k * k) ** 0.5).astype(f32)
-    d["b"] = (r.standard_normal(cout) * 0.3).astype(f32)
+    # (gelu: pre-activations of about -8 .. 8, which takes in the region below -3 where 1 + erf cancels)
+    d["b"] = (r.standard_normal(cout) * (2.5 if c["family"] == "gelu" else 0.3)).astype(f32)
     if c["cout2"]:
         d["w2"] = (r.standard_normal((c["cout2"], cout, 1, 1)) / cout ** 0.5).astype(f32)
         d["b2"] = (r.standard_normal(c["cout2"]) * 0.3).astype(f32)
@@ -206,7 +223,8 @@ def x_slice(c, d):
 
 # ================================================================================================ torch references
 def _act_t(v, act):
-    return [lambda t: t, torch.relu, lambda t: F.leaky_relu(t, 0.01), torch.sigmoid][act](v)
+    # (F.gelu with the default approximate="none": the erf form, what the reference's nn.GELU() is -- models/stf.py:16,509-527)
+    return [lambda t: t, torch.relu, lambda t: F.leaky_relu(t, 0.01), torch.sigmoid, F.gelu][act](v)
 
 
 def _conv_t(c, x, w, b):
@@ -216,7 +234,7 @@ def _conv_t(c, x, w, b):
 
 
 def torch_compose(c, d, dtype):
-    """The case in torch CPU arithmetic of `dtype` on the fp32 inputs: {"t", "y0" (before mul / res2), "y", "u"}."""
+    """The case in torch CPU arithmetic of `dtype` on the fp32 inputs: {"t", "v" (before act), "y0" (before mul / res2), "y", "u"}."""
     T = lambda a: torch.from_numpy(a).to(dtype)
     o = {}
     v = _conv_t(c, T(x_slice(c, d)), T(d["w"]), T(d["b"]))
@@ -225,6 +243,7 @@ def torch_compose(c, d, dtype):
         v = F.conv2d(o["t"], T(d["w2"]), T(d["b2"]))
     if c["res1"]:
         v = v + T(d["res1"])
+    o["v"] = v  # (the pre-activation of the last layer)
     o["y0"] = o["y"] = _act_t(v, c["act"])
     if c["mul"]:
         o["y"] = o["y"] * T(d["mul"])
@@ -243,9 +262,63 @@ def _opnorm(w):
     return float(np.abs(w.astype(np.float64)).reshape(w.shape[0], -1).sum(axis=1).max())
 
 
+# ================================================================================================ GELU
+GELU_SLOPE = 1.129  # sup |gelu'| = Phi(sqrt 2) + sqrt 2 * phi(sqrt 2) = 1.12890 (test_convforms_cases.py computes it)
+SQRT1_2 = f32(0.70710678118654752)  # the reducer's constant
+
+
+def gelu64(v):
+    """erf-form GELU of v (any float array) in fp64 -> numpy float64"""
+    return F.gelu(torch.from_numpy(np.ascontiguousarray(v, np.float64))).numpy()
+
+
+def gelu_device_formula(v):
+    """0.5f * v * (1.0f + erff(v * 0.70710678f)) as the reducer writes it, in torch-CPU fp32 on fp32 v: every operation one rounding"""
+    v = torch.from_numpy(np.ascontiguousarray(v, f32))
+    return ((0.5 * v) * (1.0 + torch.erf(v * float(SQRT1_2)))).numpy()
+
+
+def erf32_ulps(t):
+    """error of torch's CPU fp32 erf on the fp32 arguments t, in ulps of the exact result (an ulp of |e| < 1 is at most 2^-24)"""
+    t = torch.from_numpy(np.ascontiguousarray(t, f32))
+    e64 = torch.erf(t.double())
+    ulp = torch.clamp(2.0 ** (torch.floor(torch.log2(e64.abs().clamp_min(2.0 ** -126))) - 23), max=2.0 ** -24)
+    return ((torch.erf(t).double() - e64).abs() / ulp).numpy()
+
+
+def act_bound(v, e_erf=None):
+    """B_act(v): what 0.5f * v * (1.0f + erff(v * c)) may differ by from gelu64(v), element by element, for an erff of e_erf ulps.
+    In units of 2^-24, on 0.5 * |v|: the roundings of v * c and of c move erf by at most 2 * max(t * erf'(t)) = 0.97 (counted as 1),
+    erff itself e_erf, the rounding of 1 + e another 1; 0.5f * v is exact; the last product rounds once (|gelu| * 2^-24, or half
+    a subnormal step)."""
+    v = np.asarray(v, np.float64)
+    return (0.5 * np.abs(v) * ((E_ERF if e_erf is None else e_erf) + 2.0) + np.abs(gelu64(v))) * 2.0 ** -24 + 2.0 ** -149
+
+
+def _measure_erf():
+    """Nobody states an error bound for the device's erff.  Measured instead: torch's CPU fp32 erf against fp64 on the very
+    arguments the GELU cases produce (their fp32 pre-activations times the reducer's constant); the device is granted four
+    times that, the margin for another libm."""
+    worst = 0.0
+    for c in CASES:
+        if c["act"] == ACT_GELU:
+            for g in range(c["groups"]):
+                v = torch_compose(c, inputs(c, g), torch.float32)["v"]
+                worst = max(worst, float(erf32_ulps((v * float(SQRT1_2)).numpy()).max()))
+    return worst
+
+
+E_ERF_CPU = _measure_erf()
+E_ERF = 4.0 * E_ERF_CPU
+
+
 def reference64(c, d):
     """fp64 reference and the derived bounds: {"y", "u" (lead), "bound_y", "bound_u"} (numpy float64 arrays / floats)."""
     o = torch_compose(c, d, torch.float64)
+    if c["act"] == ACT_GELU:  # the conv rule on the pre-activation, carried through gelu, + the activation's own arithmetic
+        assert not (c["cout2"] or c["mul"] or c["res2"])
+        by = GELU_SLOPE * _layer_bound(o["v"]) + float(act_bound(o["v"].numpy()).max())
+        return {"y": o["y"].numpy(), "bound_y": by}
     by = _layer_bound(o["y0"])
     if c["cout2"]:
         by += _layer_bound(o["t"]) * _opnorm(d["w2"])

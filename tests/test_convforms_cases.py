@@ -3,11 +3,13 @@ the blocked reference of a fused chain is the chain of three stand-alone oracle 
 coverage tests/test_gpu_convforms.py relies on -- so that a geometry or channel case cannot be dropped quietly."""
 import numpy as np
 import pytest
+import torch
 
 import convforms_cases as cc
 from oracle import cpu_arith as ca
 
 CASES = cc.CASES
+GELU = [c for c in CASES if c["act"] == cc.ACT_GELU]
 
 
 @pytest.mark.parametrize("c", CASES, ids=cc.case_id)
@@ -151,9 +153,106 @@ def test_coverage_slices_and_placement():
 def test_coverage_grouped():
     for fam in cc.FAMILIES:
         assert any(c["groups"] == 2 for c in CASES if c["family"] == fam), fam
+    for groups in (1, 2):  # the reducer's GELU over one plane and over several, each as a single and as a grouped launch
+        sel = [c for c in GELU if c["groups"] == groups]
+        assert any(c["splitk"] == 1 for c in sel) and any(c["splitk"] > 1 for c in sel), groups
     grouped = [c for c in CASES if c["groups"] == 2]
     assert any(c["splitk"] > 1 and c["res1"] for c in grouped) and any(c["ckbd"] for c in grouped) and any(c["y2"] for c in grouped)
     assert any(c["cout2"] and not c["cout3"] and c["res1"] for c in grouped) and any(c["cout3"] for c in grouped)
     assert any(c["blocked"] and c["cout2"] for c in grouped)
     assert any(c["mul"] and c["res2"] for c in grouped)
     assert all(c["groups"] in (1, 2) for c in CASES)
+
+
+# ================================================================================================ GELU (the reducer's activation)
+def _pre(c, d, dtype):
+    return cc.torch_compose(c, d, dtype)["v"].numpy()
+
+
+def test_gelu_family_is_what_the_engine_launches():
+    assert [c["id"] for c in GELU] == ["gelu-k1", "gelu-k1-grouped", "gelu-k1-split3", "gelu-k3", "gelu-k3-s2", "gelu-k3-grouped-split2",
+                                       "gelu-1x1grid"]
+    for c in GELU:  # the plain form outside the reference's CPU arithmetic, one destination: where launch_conv accepts GELU
+        assert c["family"] == "gelu" and not (c["cout2"] or c["blocked"] or c["y2"] or c["ckbd"] or c["transposed"])
+        oh, ow = cc.out_hw(c)
+        assert c["n"] * oh * ow <= 400
+    assert all(c["act"] == cc.ACT_GELU for c in CASES if c["family"] == "gelu")
+    split3 = next(c for c in GELU if c["splitk"] == 3)  # chunks of 3, 3 and 1 groups of 16 channels
+    n16 = cc.round_up(split3["cin"], 16) // 16
+    assert n16 == 7 and -(-n16 // 3) == 3
+    assert {c["k"] for c in GELU} == {1, 3} and {c["stride"] for c in GELU} == {1, 2} and (1, 1) in {cc.out_hw(c) for c in GELU}
+    assert any(c["cout"] % 16 and c["cin"] % 16 for c in GELU)  # pad channels on both sides
+
+
+def test_gelu_constants():
+    """GELU_SLOPE is sup |gelu'| (at v = sqrt 2, where gelu'' = phi(v) (2 - v^2) changes sign), rounded up; E_ERF is four times a
+    measured figure, not a chosen one."""
+    s = 2.0 ** 0.5
+    Phi = 0.5 * (1.0 + torch.erf(torch.tensor(1.0, dtype=torch.float64)).item())
+    phi = np.exp(-1.0) / (2.0 * np.pi) ** 0.5
+    sup = Phi + s * phi
+    print(f"sup |gelu'| = {sup:.5f}; torch CPU fp32 erf on the cases' arguments: {cc.E_ERF_CPU:.3f} ulp; E_ERF = {cc.E_ERF:.3f}")
+    assert sup <= cc.GELU_SLOPE <= sup + 2e-4
+    v = torch.linspace(-9, 9, 180001, dtype=torch.float64, requires_grad=True)
+    (g,) = torch.autograd.grad(torch.nn.functional.gelu(v).sum(), v)
+    assert g.abs().max().item() <= sup + 1e-12
+    # a faithfully rounded erf errs by less than 1 ulp, a correctly rounded one by up to 0.5: the device is granted 2 to 4
+    assert cc.E_ERF == 4.0 * cc.E_ERF_CPU and 0.4 < cc.E_ERF_CPU <= 1.0
+
+
+def test_gelu_device_formula_meets_the_activation_bound_with_one_ulp():
+    """The reference alone passes: 0.5f * v * (1.0f + erff(v * c)) in torch-CPU fp32 stays within B_act with E_ERF = 1 (torch's
+    erf is within 1 ulp), on 2.4 million values of -9 .. 9 and on every case's own pre-activations."""
+    vs = [torch.linspace(-9, 9, 2400001, dtype=torch.float32).numpy()]
+    vs += [_pre(c, cc.inputs(c, g), torch.float32).ravel() for c in GELU for g in range(c["groups"])]
+    v = np.concatenate(vs)
+    assert float(cc.erf32_ulps(v * cc.SQRT1_2).max()) <= 1.0
+    ratio = np.abs(cc.gelu_device_formula(v).astype(np.float64) - cc.gelu64(v)) / cc.act_bound(v, 1.0)
+    print(f"device formula in torch fp32: worst err / B_act(E_ERF = 1) = {ratio.max():.3f} over {v.size} values")
+    assert ratio.max() <= 1.0
+
+
+@pytest.mark.parametrize("c", GELU, ids=cc.case_id)
+def test_gelu_case_is_not_hollow(c):
+    """Each operand set reaches the region where 1 + erf cancels, the linear region, and the neighbourhood of 0."""
+    for g in range(c["groups"]):
+        v = _pre(c, cc.inputs(c, g), torch.float32)
+        lo, hi, mid = float((v < -3).mean()), float((v > 3).mean()), int((np.abs(v) < 0.1).sum())
+        print(f"{c['id']} set {g}: v in [{v.min():.2f}, {v.max():.2f}], {100 * lo:.1f} % below -3, {100 * hi:.1f} % above 3, {mid} within 0.1 of 0")
+        assert lo >= 0.01 and hi >= 0.01 and mid > 0
+
+
+def _split_chunks(c):
+    n16 = cc.round_up(c["cin"], 16) // 16
+    per = -(-n16 // c["splitk"])  # (csrc/conv_mfma_body.h: per = ceil(n16 / splitk))
+    return [(16 * s * per, min(c["cin"], 16 * min(n16, (s + 1) * per))) for s in range(c["splitk"])]
+
+
+@pytest.mark.parametrize("c", GELU, ids=cc.case_id)
+def test_gelu_mistakes_land_far_from_the_bounds(c):
+    """Another GELU than the erf form, against the element-wise bound (b); GELU at the wrong place of the epilogue, against the
+    operator bound (a): each at least 100 times its bound, on every case it applies to."""
+    F = torch.nn.functional
+    for g in range(c["groups"]):
+        d = cc.inputs(c, g)
+        ref = cc.reference64(c, d)
+        v32 = _pre(c, d, torch.float32)
+        want, bound = cc.gelu64(v32), cc.act_bound(v32)
+        t = torch.from_numpy(v32).double()
+        for name, wrong in (("tanh form", F.gelu(t, approximate="tanh")), ("v * sigmoid(1.702 v)", t * torch.sigmoid(1.702 * t))):
+            ratio = float((np.abs(wrong.numpy() - want) / bound).max())
+            print(f"{c['id']} set {g}: {name}: {ratio:.3g} x B_act")
+            assert ratio >= 100.0, name
+        T = lambda a: torch.from_numpy(a).double()
+        x, w, b = T(cc.x_slice(c, d)), T(d["w"]), T(d["b"])
+        wrongs = [("GELU before the bias", F.gelu(cc._conv_t(c, x, w, None)) + b.view(1, -1, 1, 1))]
+        if c["splitk"] > 1:
+            chunks = _split_chunks(c)
+            assert len(chunks) == c["splitk"] and chunks[-1][1] == c["cin"] and all(lo < hi for lo, hi in chunks)
+            parts = [cc._conv_t(c, x[:, lo:hi], w[:, lo:hi], b if i == 0 else None) for i, (lo, hi) in enumerate(chunks)]
+            assert float((sum(parts) - T(ref["y"] * 0 + _pre(c, d, torch.float64))).abs().max()) < 1e-12  # (the chunks are the conv)
+            wrongs.append(("GELU of each partial, then the sum", sum(F.gelu(p) for p in parts)))
+        for name, wrong in wrongs:
+            ratio = float(np.abs(wrong.numpy() - ref["y"]).max()) / ref["bound_y"]
+            print(f"{c['id']} set {g}: {name}: {ratio:.3g} x bound")
+            assert ratio >= 100.0, name

@@ -35,6 +35,20 @@ Spot checks this file is meant to catch (each makes at least one test here fail;
                                                                (fused epilogue), slice-out-o0 / -o24, slice-grouped (plain epilogue),
                                                                slice-in-out-split4 (reducer)
 (tried on scratch builds of the kernels with each line changed: 74, 10 and 21 tests of this file fail.)
+
+GELU (family "gelu") is the split-K reducer's activation (splitk_reduce_kernel): launch_conv refuses it without a partial plane, so
+the hook books one even with a split factor of 1, as Engine::conv_plan does.  The cases stand for the engine's GELU launches (Swin
+mlp.fc1 single and grouped, h_a_stf1 at stride 1 and 2, h_s_stf1 grouped with split-K).  test_against_reference holds them to the
+fp64 operator under 1.129 * (the conv rule on the pre-activation) + max B_act, and -- element by element -- to gelu64 of the
+launch's own fp32 pre-activation (the same launch with act = 0) under B_act (convforms_cases.act_bound), which a tanh-form GELU
+misses by a factor of 1000.  Spot checks on scratch builds, as above (the tests named fail; the counts are of `-k gelu`):
+  the ACT_GELU branch of splitk_reduce_kernel removed          test_against_reference on all 7 gelu cases (the element-wise bound)
+  `g1 ? a.g1.bias : a.bias` -> `a.bias` in the reducer         test_against_reference and test_grouped_equals_single on gelu-k1-grouped and
+                                                               gelu-k3-grouped-split2 (4 tests)
+  the hook's partial plane one pixel row short                 the hook returns -1 (the guard band behind the planes) in every launch that
+                                                               has a partial plane: 11 tests of the gelu cases, and every split-K case.
+                                                               (Tried with the guard band moved one row forward inside an allocation of
+                                                               the full size, so that no store left it.)
 """
 import contextlib
 import ctypes
@@ -203,6 +217,21 @@ def _slices(c, out):
     return r
 
 
+def _check_gelu(c, got, v, what):
+    """The reducer's GELU against the launch's own pre-activation v (the same launch with act = 0: one plane + bias are the two
+    operands of the kernel's own epilogue add; several planes go through the same reducer), element by element:
+    |got - gelu64(v)| <= B_act(v) (convforms_cases.act_bound).  Where v is a zero, so is the result."""
+    want, bound = cc.gelu64(v), cc.act_bound(v)
+    err = np.abs(got.astype(np.float64) - want)
+    ratio = err / bound
+    i = np.unravel_index(np.argmax(ratio), ratio.shape)
+    print(f"{what}: gelu vs own pre-activation: worst err / B_act = {ratio[i]:.3f} at v = {v[i]!r} (E_ERF = {cc.E_ERF:.3f}; v in "
+          f"[{v.min():.2f}, {v.max():.2f}])")
+    assert (err <= bound).all(), f"{what}: {int((~(err <= bound)).sum())} of {got.size} elements off by more than B_act; worst at {i}: " \
+        f"v {v[i]!r}, got {got[i]!r}, want {want[i]!r}, B_act {bound[i]:.3e}"
+    assert (got[v == 0] == 0).all(), f"{what}: a zero pre-activation did not give a zero"
+
+
 @pytest.mark.parametrize("c", CASES, ids=cc.case_id)
 def test_against_reference(c):
     dev = require_gpu()
@@ -210,6 +239,8 @@ def test_against_reference(c):
     for cls in (CLASSES if c["cout2"] else (None,)):
         sets = _sets(c)
         outs = run(c, sets, dev, cls)
+        # (GELU: the same launch without the activation, under the same switches, is its fp32 pre-activation)
+        pre = run(dict(c, act=cc.ACT_NONE), sets, dev, cls) if c["act"] == cc.ACT_GELU else None
         for g, (ins, out) in enumerate(zip(sets, outs)):
             what = f"{c['id']} set {g} class {cls}"
             check_untouched(c, out, what)
@@ -217,6 +248,8 @@ def test_against_reference(c):
             if c["y2"]:
                 y2 = out["y2"][:, c["y2_off"]:c["y2_off"] + cc.y_channels(c)]
                 assert _same_bits(y2[..., mask], got["y"][..., mask]), _report(y2[..., mask], got["y"][..., mask], what + " y2 vs y")
+            if c["act"] == cc.ACT_GELU:
+                _check_gelu(c, got["y"], pre[g]["y"][:, c["y_off"]:c["y_off"] + cc.y_channels(c)], what)
             if c["blocked"]:
                 want = cc.blocked_reference(c, ins)
                 for key in got:
@@ -294,7 +327,7 @@ def test_sliced_input_ignores_its_neighbours(c):
 
 
 TILE_CASES = ["plain-r1", "plain-mr2-split4", "plain-none-y2", "plain-ckbd1", "plain-grouped-r1", "slice-in-out-split4", "slice-grouped",
-              "fused-slice-o0", "lead-c96-own"]
+              "fused-slice-o0", "lead-c96-own", "gelu-k1-grouped", "gelu-k3-grouped-split2"]
 TILES = ["2,3,8,16,1", "2,2,8,16,0", "1,3,4,16,1", "2,5,4,16,0", "1,1,1,16,1", "2,3,4,64,0", "2,2,4,16,4", "2,3,4,16,4", "2,5,2,16,4",
          "1,3,2,16,4", "1,1,1,16,4", "2,2,8,16,5", "1,3,4,16,5"]  # (test_gpu_conv.py::test_tile_choice_never_changes_a_bit)
 
@@ -331,7 +364,7 @@ def test_tile_choice_never_changes_a_bit(tile):
 
 
 DETERMINISM = ["plain-none", "plain-m-split4", "plain-ckbd1", "slice-out-o24", "fused-3x96x33x1-c90-k3-o177-r1-a2-m1", "fused-blk-k3",
-               "lead-c192-own90", "lead-blk", "fused-grouped"]
+               "lead-c192-own90", "lead-blk", "fused-grouped", "gelu-k1", "gelu-k3-s2"]
 
 
 @pytest.mark.parametrize("cid", DETERMINISM)
@@ -372,6 +405,11 @@ def test_refusals():
     _refused(dict(fused, k=5, pad=2), dev, 1)                                 # fused with k = 5
     _refused(dict(fused, act=cc.ACT_SIGMOID), dev, 1)                         # fused with act = 3
     _refused(dict(fused, act_mid=2), dev, 1)
+    # GELU is the reducer's: only the plain form outside the reference's CPU arithmetic, with one destination
+    _refused(dict(fused, act=cc.ACT_GELU), dev, 1)
+    _refused(dict(BY_ID["plain-blk-r1"], act=cc.ACT_GELU), dev)
+    _refused(dict(BY_ID["plain-none-y2"], act=cc.ACT_GELU), dev)
+    _refused(dict(BY_ID["plain-none"], act=5), dev)
     _refused(dict(lead, cout2=80, y_total=80), dev, 1)                        # lead with cout2_pad % 32 != 0
     _refused(dict(lead, cout3=64, y3_total=64), dev, 1)                       # (the lead layer's couts are the first layer's tile)
     _refused(BY_ID["plain-none-y2"], dev, splitk=4)                           # y2 together with split-K
