@@ -705,11 +705,23 @@ int rgbd_pixel_shuffle2(const float* x, int32_t B, int32_t H, int32_t W, int32_t
  * rgbd_debug_force_gdn_tile: pixels per workgroup, 64 / 32 (one wave per 16 pixels) or 16 (the output channels spread over
  * four waves: small grids), 0 = automatic (default).  Same bits for every tile.
  * rgbd_gdn_bench: kernel-only time of one launch on NHWC scratch buffers, as rgbd_conv_bench (tools/gdn_probe.py).
+ * rgbd_gdn_pack (host only): the raw beta [c] / gamma [c][c] as the kernel's operands, exactly what the engine's finalize
+ * uploads: cs = c rounded up to 16; beta_out [cs] = beta', pad channels 1; gamma_out [cs / 16][cs / 16][64][4] = MFMA A
+ * fragments, [it][g][lane][e] = gamma'[16 it + lane % 16][16 g + 4 (lane / 16) + e], pad 0.  -22 on a NULL or c outside [1, 512].
+ * rgbd_gdn_nhwc: the launch itself on the engine's NHWC device tensors -- the boundary the engine uses: no copies, no layout
+ * passes, no synchronisation (asynchronous on `stream`).  x [npix][xcs], y [npix][ycs], res [npix][rcs] (optional, NULL: rcs
+ * is ignored); channels [0, cs) are computed, cs a multiple of 16 up to 512 with x's pad channels zero; channels past cs of
+ * any tensor are neither read nor written; beta_dev / gamma_dev: rgbd_gdn_pack's output on the device.  inverse: 0 = GDN,
+ * otherwise IGDN.  -22 before anything is launched on a NULL x / y / beta / gamma, npix outside [1, 2^30], cs <= 0, cs % 16,
+ * cs > 512, a stride below cs or no multiple of 4, or a pointer that is not 16-byte aligned.
  * ------------------------------------------------------------------------------------------------------------- */
 int rgbd_gdn_nchw(const float* x_dev, int32_t n, int32_t c, int32_t h, int32_t w, const float* beta, const float* gamma,
                   int32_t inverse, const float* res_dev, float* y_dev, void* stream);
 int rgbd_gdn_parametrize(const float* raw, int64_t n, int32_t is_beta, float* out);
 int rgbd_debug_force_gdn_tile(int32_t pixels);
+int rgbd_gdn_pack(const float* beta_raw, const float* gamma_raw, int32_t c, float* beta_out, float* gamma_out);
+int rgbd_gdn_nhwc(const float* x, int32_t xcs, int64_t npix, int32_t cs, const float* beta_dev, const float* gamma_dev,
+                  int32_t inverse, const float* res, int32_t rcs, float* y, int32_t ycs, void* stream);
 int rgbd_gdn_bench(int32_t n, int32_t c, int32_t h, int32_t w, int32_t inverse, int32_t with_residual, int32_t iters, float* ms_out);
 
 /* Bytes of HBM workspace this engine instance holds (grows with the largest call shape seen, never shrinks); the packed

@@ -175,6 +175,8 @@ def lib():
         "rgbd_gdn_parametrize": (ctypes.c_int, [f32p, c_i64, c_i32, f32p]),
         "rgbd_debug_force_gdn_tile": (ctypes.c_int, [c_i32]),
         "rgbd_gdn_bench": (ctypes.c_int, [c_i32] * 7 + [f32p]),
+        "rgbd_gdn_pack": (ctypes.c_int, [f32p, f32p, c_i32, f32p, f32p]),
+        "rgbd_gdn_nhwc": (ctypes.c_int, [c_vp, c_i32, c_i64, c_i32, c_vp, c_vp, c_i32, c_vp, c_i32, c_vp, c_i32, c_vp]),
         "rgbd_elic_compress_single": (ctypes.c_int, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp]),
         "rgbd_elic_forward_single": (ctypes.c_int, [c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
         "rgbd_elic_decompress_single": (ctypes.c_int, [c_vp, u8pp, i64p, c_i32, u8pp, i64p, c_i32, c_i32, c_i32, c_vp, c_vp]),
@@ -249,7 +251,7 @@ EXPORTS = ["rgbd_abi_version", "rgbd_set_blocking_sync", "rgbd_get_blocking_sync
            "rgbd_elic_profile_read", "rgbd_elic_profile_read_executed", "rgbd_debug_force_splitk", "rgbd_debug_force_fuse", "rgbd_debug_force_subpix", "rgbd_debug_force_pair", "rgbd_debug_fail_captures", "rgbd_debug_force_ckbd", "rgbd_debug_force_blocked", "rgbd_debug_bench_streams", "rgbd_elic_set_tile_mode", "rgbd_debug_force_tile", "rgbd_debug_conv_log", "rgbd_debug_conv_log_read", "rgbd_debug_tile_override", "rgbd_debug_tile_list", "rgbd_conv_bench",
            "rgbd_elic_profile_dump", "rgbd_elic_create_stf_single", "rgbd_slice_quant_index", "rgbd_slice_dequant", "rgbd_lrp_update",
            "rgbd_ckbd_estimate_part", "rgbd_slice_estimate", "rgbd_ckbd_part", "rgbd_z_quant", "rgbd_z_dequant", "rgbd_eb_forward",
-           "rgbd_elic_create_ckbd", "rgbd_gdn_nchw", "rgbd_gdn_parametrize", "rgbd_debug_force_gdn_tile", "rgbd_gdn_bench",
+           "rgbd_elic_create_ckbd", "rgbd_gdn_nchw", "rgbd_gdn_parametrize", "rgbd_debug_force_gdn_tile", "rgbd_gdn_bench", "rgbd_gdn_pack", "rgbd_gdn_nhwc",
            "rgbd_guided_window_attention", "rgbd_aligner_create", "rgbd_aligner_forward", "rgbd_elic_decompress_single_mid",
            "rgbd_elic_forward_single_mid", "rgbd_pw_channel_mean", "rgbd_pw_se_gate", "rgbd_pw_bilinear", "rgbd_pw_maxpool7s3",
            "rgbd_pw_channel_scale", "rgbd_pw_copy_channels", "rgbd_pw_im2col5s2", "rgbd_pw_fill_zero", "rgbd_pw_nchw_to_nhwc",

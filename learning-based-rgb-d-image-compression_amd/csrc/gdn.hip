@@ -196,6 +196,34 @@ int rgbd_debug_force_gdn_tile(int32_t pixels)
     return RGBD_OK;
 }
 
+int rgbd_gdn_pack(const float* beta_raw, const float* gamma_raw, int32_t c, float* beta_out, float* gamma_out)
+{
+    if (!beta_raw || !gamma_raw || !beta_out || !gamma_out || c <= 0 || c > kGdnMaxC) return RGBD_EINVAL;
+    std::vector<float> hb, hg;
+    gdn_pack(beta_raw, gamma_raw, c, &hb, &hg);
+    memcpy(beta_out, hb.data(), hb.size() * sizeof(float));
+    memcpy(gamma_out, hg.data(), hg.size() * sizeof(float));
+    return RGBD_OK;
+}
+
+int rgbd_gdn_nhwc(const float* x, int32_t xcs, int64_t npix, int32_t cs, const float* beta_dev, const float* gamma_dev, int32_t inverse,
+                  const float* res, int32_t rcs, float* y, int32_t ycs, void* stream)
+{
+    GdnArgs a{};
+    a.x = x;
+    a.xcs = xcs;
+    a.y = y;
+    a.ycs = ycs;
+    a.res = res;
+    a.rcs = rcs;
+    a.npix = (long)npix;
+    a.cs = cs;
+    a.beta = beta_dev;
+    a.gamma = gamma_dev;
+    a.inverse = inverse ? 1 : 0;
+    return launch_gdn(a, (hipStream_t)stream);
+}
+
 int rgbd_gdn_nchw(const float* x_dev, int32_t n, int32_t c, int32_t h, int32_t w, const float* beta, const float* gamma,
                   int32_t inverse, const float* res_dev, float* y_dev, void* stream)
 {

@@ -10,13 +10,41 @@ sqrt, divide, multiply), then the residual add rounds the result once:
     |out - ref| <= ((c / 2 + 4) * |x * f(norm)| + |ref|) * 2^-24
 
 The raw gamma is dense with values below the parametrizer's bound (the clamp acts), beta varies per channel, and the inputs
-span 1e-3 ... 1e2 in magnitude with exact zeros."""
+span 1e-3 ... 1e2 in magnitude with exact zeros.
+
+The second half of the file runs the launch in the engine's own layout, through rgbd_gdn_pack + rgbd_gdn_nhwc (the boundary
+Engine::gdn uses: a GdnArgs and launch_gdn, nothing else), on the cases of tests/gdn_cases.py: c up to 512 (one, two and
+three passes of 12 output tiles; four-wave splits with a short or empty last part), pixel counts around every tile boundary,
+each channel stride larger than cs on its own and all three different (NaN behind cs in x / res, a sentinel behind cs in y),
+and maps large enough for the launcher to choose the 32- and 64-pixel tiles itself.  Same bound, through
+gdn_cases.accept; tests/test_gdn_cases.py shows on the CPU that this function rejects ten kinds of wrong kernel.
+
+One-line changes to csrc/gdn.hip tried on scratch builds on the MI355X, each alone ("before" = the 22 tests this file had
+before the second half and the shapes c = 208 / 320 / 512 were added; 113 tests now):
+  * `it0 += kGdnIT` -> the body runs once (`break`): before all pass; 22 fail now -- nhwc_vs_f64[auto-c272-n32773] (the one
+    case whose automatic tile walks 17 output tiles in one wave), same_bits_for_every_tile on all 20 cases with cs > 192
+    (tiles 32 / 64 differ from tile 16), dense_equals_the_public_operator[auto-c272-n32773].
+  * `(part + 1) * per` -> `part * per + per - 1`: this one drops the last output tile of EVERY wave's part, also at
+    NT = 12, so "before" already failed (21 of 22); 102 of 113 fail now.  The mistake of that kind which "before" does not
+    see is `per` rounded down (`max(1, NT / WS)`: the tiles behind 4 * (NT / 4) are dropped): before all pass; 53 fail now --
+    every case and shape with NT % 4 != 0 and NT > 4 (nhwc_vs_f64 17, same_bits 18, dense_equals 13, vs_f64[1x208x3x5] 4,
+    nhwc_bad_arguments' final good call).
+  * `a.res + gp * a.rcs` -> `a.res + gp * a.xcs`: before all pass; 11 fail now -- nhwc_vs_f64 and strided_equals_dense on the
+    5 cases with xcs != rcs, and nhwc_bad_arguments' final good call.
+  * `gp * a.ycs` -> `gp * a.cs`: before all pass; 9 fail now -- the same two tests on the 4 cases with ycs > cs, and
+    nhwc_bad_arguments' final good call.
+  * `gp < a.npix` dropped in the epilogue: run on the new nhwc tests only (their buffers are 64 pixels longer than npix, so
+    the stray rows stay inside them; rgbd_gdn_nchw's internal buffers are not, which is why "before" was not run: from the
+    code it cannot see the mistake, it reads back [0, npix) only): 55 of 59 fail -- every case but npix = 16 and 64 (guard
+    band written; tiles 32 / 64 at npix = 16 are caught by same_bits).
+"""
 import ctypes
 
 import numpy as np
 import pytest
 import torch
 
+import gdn_cases as gc
 from gpu_utils import require_gpu
 
 pytestmark = pytest.mark.gpu
@@ -24,7 +52,8 @@ pytestmark = pytest.mark.gpu
 EINVAL = -22
 SENTINEL = 12345.0
 GUARD = 4096
-SHAPES = [(1, 16, 1, 1), (1, 20, 3, 5), (2, 192, 7, 9), (1, 128, 8, 8), (3, 192, 4, 4)]
+SHAPES = [(1, 16, 1, 1), (1, 20, 3, 5), (2, 192, 7, 9), (1, 128, 8, 8), (3, 192, 4, 4),
+          (1, 208, 3, 5), (1, 320, 3, 5), (1, 512, 3, 5)]  # (the last three: the public operator's upper range, up to three passes)
 ZERO_PIXEL_SHAPE = (2, 192, 7, 9)  # image 1, pixel (3, 4) is all zeros there: norm = beta
 
 
@@ -181,3 +210,140 @@ def test_gdn_bad_arguments_write_nothing():
     assert L.rgbd_gdn_nchw(xd.data_ptr(), n, c, h, w, b, g, 0, rd.data_ptr(), y.data_ptr(), _stream()) == 0
     torch.cuda.synchronize()
     assert (y[:x.numel()] != SENTINEL).all() and (y[x.numel():] == SENTINEL).all()
+
+
+# ================================================================================================ the engine's layout
+_DEV = {}
+
+
+def _dev(cid):
+    """(case, device operands): x / res in their strided buffers, beta / gamma as rgbd_gdn_pack lays them out"""
+    if cid not in _DEV:
+        L = _lib()
+        k = gc.build(cid)
+        cs = k["cs"]
+        hb, hg = np.empty(cs, np.float32), np.empty(cs * cs, np.float32)
+        assert L.rgbd_gdn_pack(_f32p(k["beta"]), _f32p(k["gamma"]), k["c"], _f32p(hb), _f32p(hg)) == 0
+        _DEV[cid] = (k, {"x": torch.tensor(k["xbuf"]).cuda(), "res": torch.tensor(k["rbuf"]).cuda(),
+                         "beta": torch.from_numpy(hb).cuda(), "gamma": torch.from_numpy(hg).cuda()})
+    return _DEV[cid]
+
+
+def _new_y(k):
+    return torch.full(((k["npix"] + gc.TAIL) * k["ycs"],), float(gc.SENTINEL), device="cuda")
+
+
+def _nhwc(L, k, d, inverse, with_res):
+    """One rgbd_gdn_nhwc call into a fresh destination (with its guard band); returns it, on the device."""
+    y = _new_y(k)
+    rc = L.rgbd_gdn_nhwc(d["x"].data_ptr(), k["xcs"], k["npix"], k["cs"], d["beta"].data_ptr(), d["gamma"].data_ptr(), inverse,
+                         d["res"].data_ptr() if with_res else None, k["rcs"] if with_res else 0, y.data_ptr(), k["ycs"], _stream())
+    assert rc == 0, rc
+    torch.cuda.synchronize()
+    return y
+
+
+def _same_bits(a, b):
+    return a.shape == b.shape and torch.equal(a.view(torch.int32), b.view(torch.int32))
+
+
+CASE_IDS = [c["id"] for c in gc.CASES]
+
+
+@pytest.mark.parametrize("cid", CASE_IDS)
+def test_gdn_nhwc_vs_f64(cid):
+    """Every case, GDN / IGDN, with / without the residual, at the tile the launcher chooses: gdn_cases.accept."""
+    L = _lib()
+    k, d = _dev(cid)
+    assert L.rgbd_debug_force_gdn_tile(0) == 0
+    worst, fails = {}, {}
+    for inverse, with_res in gc.COMBOS:
+        stats = {}
+        f = gc.accept(k, _nhwc(L, k, d, inverse, with_res).cpu().numpy(), inverse, with_res, stats)
+        worst[(inverse, with_res)] = round(stats["worst"], 3)
+        if f:
+            fails[(inverse, with_res)] = f
+    print(f"gdn nhwc {cid}: worst |err| / bound per (inverse, res) = {worst}")
+    assert not fails, fails
+
+
+@pytest.mark.parametrize("cid", CASE_IDS)
+def test_gdn_nhwc_same_bits_for_every_tile(cid):
+    """Base: the forced 16-pixel tile (four waves share the output tiles).  A second call, the forced 32- and 64-pixel tiles
+    (one wave walks all output tiles, in passes of 12; 64 pixels at cs = 512 is the largest LDS the launch may ask for) and the
+    automatic choice give the same bits over the whole buffer, sentinels included."""
+    L = _lib()
+    k, d = _dev(cid)
+    try:
+        for inverse, with_res in gc.COMBOS:
+            assert L.rgbd_debug_force_gdn_tile(16) == 0
+            base = _nhwc(L, k, d, inverse, with_res)
+            assert _same_bits(base, _nhwc(L, k, d, inverse, with_res)), "two calls differ"
+            for tile in (32, 64, 0):
+                assert L.rgbd_debug_force_gdn_tile(tile) == 0
+                assert _same_bits(base, _nhwc(L, k, d, inverse, with_res)), f"tile {tile} (0 = automatic) differs from tile 16"
+    finally:
+        L.rgbd_debug_force_gdn_tile(0)
+
+
+@pytest.mark.parametrize("cid", [c["id"] for c in gc.CASES if c["group"] != "stride"])
+def test_gdn_nhwc_dense_equals_the_public_operator(cid):
+    """All three strides = cs: the same bits as rgbd_gdn_nchw on the same data (which packs, lays out and launches itself)."""
+    L = _lib()
+    k, d = _dev(cid)
+    c, npix = k["c"], k["npix"]
+    assert k["xcs"] == k["ycs"] == k["rcs"] == k["cs"]
+    assert L.rgbd_debug_force_gdn_tile(0) == 0
+    x = torch.tensor(k["x"]).t().contiguous().reshape(1, c, 1, npix)
+    res = torch.tensor(k["res"]).t().contiguous().reshape(1, c, 1, npix)
+    for inverse, with_res in gc.COMBOS:
+        y = _nhwc(L, k, d, inverse, with_res).view(npix + gc.TAIL, k["ycs"])[:npix, :c]
+        pub = _run(L, x, torch.tensor(k["beta"]), torch.tensor(k["gamma"]), inverse, res if with_res else None)
+        assert (pub[c * npix:] == SENTINEL).all()
+        assert _same_bits(y.cpu().t().contiguous(), pub[:c * npix].view(c, npix)), (inverse, with_res)
+
+
+@pytest.mark.parametrize("cid", [c["id"] for c in gc.CASES if c["group"] == "stride"])
+def test_gdn_nhwc_strided_equals_dense(cid):
+    """A stride larger than cs moves the rows and nothing else: channels [0, cs) equal the dense form's, bit for bit."""
+    L = _lib()
+    k, d = _dev(cid)
+    kd, dd = _dev(gc.dense_id(k))
+    npix, cs = k["npix"], k["cs"]
+    assert L.rgbd_debug_force_gdn_tile(0) == 0
+    for inverse, with_res in gc.COMBOS:
+        y = _nhwc(L, k, d, inverse, with_res).view(npix + gc.TAIL, k["ycs"])
+        dense = _nhwc(L, kd, dd, inverse, with_res).view(npix + gc.TAIL, cs)
+        assert _same_bits(y[:npix, :cs].contiguous(), dense[:npix].contiguous()), (inverse, with_res)
+        assert (y[:npix, cs:] == float(gc.SENTINEL)).all() and (y[npix:] == float(gc.SENTINEL)).all()
+
+
+def test_gdn_nhwc_bad_arguments_write_nothing():
+    """launch_gdn's own check, reached through the hook: -22, nothing launched, and the same buffers work afterwards."""
+    L = _lib()
+    k, d = _dev("stride-c200-n37-s16.4.36")
+    cs = k["cs"]
+    y = _new_y(k)
+    good = dict(x=d["x"].data_ptr(), xcs=k["xcs"], npix=k["npix"], cs=cs, beta=d["beta"].data_ptr(), gamma=d["gamma"].data_ptr(),
+                inverse=0, res=d["res"].data_ptr(), rcs=k["rcs"], y=y.data_ptr(), ycs=k["ycs"])
+    bad = [("cs % 16", dict(cs=cs - 8)), ("cs > 512", dict(cs=528, xcs=528, ycs=528, rcs=528)), ("cs = 0", dict(cs=0)),
+           ("npix = 0", dict(npix=0)), ("npix < 0", dict(npix=-1))]
+    for s in ("xcs", "ycs", "rcs"):
+        bad += [(f"{s} < cs", {s: cs - 4}), (f"{s} % 4", {s: good[s] + 2})]
+    for p in ("x", "y", "res", "beta", "gamma"):
+        bad.append((f"{p} + 4 bytes", {p: good[p] + 4}))
+    for p in ("x", "y", "beta", "gamma"):
+        bad.append((f"{p} NULL", {p: None}))
+
+    def call(a):
+        return L.rgbd_gdn_nhwc(a["x"], a["xcs"], a["npix"], a["cs"], a["beta"], a["gamma"], a["inverse"], a["res"], a["rcs"], a["y"],
+                               a["ycs"], _stream())
+
+    for what, change in bad:
+        assert call({**good, **change}) == EINVAL, what
+        torch.cuda.synchronize()
+        assert (y == float(gc.SENTINEL)).all(), f"the call refused for '{what}' wrote to the destination"
+    # ... and the same buffers are fine with good arguments
+    assert call(good) == 0
+    torch.cuda.synchronize()
+    assert not gc.accept(k, y.cpu().numpy(), 0, 1)
