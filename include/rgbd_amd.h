@@ -684,6 +684,21 @@ int rgbd_linear_attention(const float* k, int32_t kcs, const float* q, int32_t q
                           int64_t ws_floats, void* stream);
 int rgbd_dwconv3x3(const float* x, int32_t B, int32_t H, int32_t W, int32_t C, int32_t xcs, const float* w, const float* bias,
                    int32_t gelu, float* y, int32_t ycs, void* stream);
+/* The pooled head of Channel_aligner alone (csrc/pooled_head.hip): AdaptiveAvgPool2d(1) of nn.Conv2d(Cin, Cout, 3, 1, 1),
+ * replacing modules/transform/channelAligner.py:30-31 and :35-36 without forming the convolution's output.
+ *   out[b][o] = bias[o] + (1 / (H W)) * sum_c sum_(di,dj) w[o][c][di][dj] * S_c(di, dj),
+ *   S_c(di, dj) = T_c - (di == 0: last row's sum, di == 2: first row's) - (dj == 0: last column's, dj == 2: first column's)
+ *                 + (the corner both took out),
+ * which is the mean over all output positions exactly, H = 1 and W = 1 included.  x: [B][H][W][cs] fp32, channels Cin ..
+ * cs - 1 never read; w: [Cout][Cin][3][3] and bias: [Cout] as the state dict holds them; out: [B][Cout]; ws: scratch of
+ * rgbd_pooled_conv3x3_ws_floats(B, H, W, Cin) floats (which returns RGBD_EINVAL for a shape the kernel refuses).  The map is
+ * read once in chunks of pixels whose size depends on H * W only; partial sums (fp32 runs of at most 1024 terms) go through
+ * ws and are combined in fp64 in a fixed order, no atomics: the same bits on every call, and image b of a batch as it is
+ * alone.  Returns RGBD_EINVAL and writes nothing unless: no pointer NULL; B, H, W >= 1; Cin % 4 == 0, 4 <= Cin <= 1024;
+ * 1 <= Cout <= 65535; cs >= Cin, cs % 4 == 0; x and ws 16-byte aligned; B <= 65535; H * W <= 2^30. */
+int64_t rgbd_pooled_conv3x3_ws_floats(int32_t B, int32_t H, int32_t W, int32_t Cin);
+int rgbd_pooled_conv3x3(const float* x, int32_t cs, int32_t B, int32_t H, int32_t W, int32_t Cin, const float* w,
+                        const float* bias, int32_t Cout, float* out, float* ws, void* stream);
 int rgbd_patch_merge_gather(const float* x, int32_t B, int32_t H, int32_t W, int32_t C, int32_t xcs, float* y, int32_t ycs,
                             void* stream);
 int rgbd_pixel_shuffle2(const float* x, int32_t B, int32_t H, int32_t W, int32_t Co, int32_t xcs, float* y, int32_t ycs,

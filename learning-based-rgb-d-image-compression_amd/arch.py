@@ -603,6 +603,21 @@ def linear_global_inter_entries(dim: int = 32, out_dim: int = 64) -> "OrderedDic
     return _linear_context_entries(dim, out_dim * 3 // 2, 2 * out_dim, out_dim, True)
 
 
+CHALIGN_IN, CHALIGN_MID, CHALIGN_OUT = 64, 256, 64  # modules/transform/channelAligner.py:9-20: constants of the reference
+
+
+def channel_aligner_entries() -> "OrderedDict[str, Entry]":
+    """Every state_dict entry of Channel_aligner (reference: modules/transform/channelAligner.py:5-22), in the reference's
+    order: the trunk conv1 (four 3x3 convolutions 64 -> 256 -> 256 -> 256 -> 256 at indexes 0, 2, 4, 6 of a Sequential, a
+    LeakyReLU behind each) and the two 3x3 heads conv2 (beta) and conv3 (gamma), 256 -> 64.  The pools have no state."""
+    b = _Builder()
+    for i, cin in zip((0, 2, 4, 6), (CHALIGN_IN, CHALIGN_MID, CHALIGN_MID, CHALIGN_MID)):
+        b.conv(f"conv1.{i}", cin, CHALIGN_MID, 3)
+    b.conv("conv2", CHALIGN_MID, CHALIGN_OUT, 3)
+    b.conv("conv3", CHALIGN_MID, CHALIGN_OUT, 3)
+    return b.entries
+
+
 def ckbd_config(N: int = 192) -> Config:
     """Cheng2020 anchor model with the checkerboard context (models/Cheng2020withCKBD.py:46-50): M = N, one slice."""
     cfg = model_config()

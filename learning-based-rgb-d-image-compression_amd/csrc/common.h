@@ -263,6 +263,13 @@ int launch_dwconv3x3(const float* x, int B, int H, int W, int C, int xcs, const 
 // xa = x at the anchor positions and 0 elsewhere, xn the other half (utils/ckbd.py:37-48); all three with channel stride cs
 int launch_ckbd_split(const float* x, int B, int H, int W, int cs, float* xa, float* xn, hipStream_t s);
 
+// ---- Channel_aligner's pooled heads (pooled_head.hip; modules/transform/channelAligner.py); all check their arguments ----
+// AdaptiveAvgPool2d(1) of conv3x3(pad 1) from nine border sums per (image, channel): x [B,H,W,cs], w [Cout][Cin][3][3] as the
+// state dict holds it -> out [B][Cout].  ws: pooled_conv3x3_ws_floats(...) floats (RGBD_EINVAL for a shape the kernel refuses)
+int64_t pooled_conv3x3_ws_floats(int B, int H, int W, int Cin);
+int launch_pooled_conv3x3(const float* x, int cs, int B, int H, int W, int Cin, const float* w, const float* bias, int Cout,
+                          float* out, float* ws, hipStream_t s);
+
 // ---- GDN / IGDN (gdn.hip) -----------------------------------------------------------------------
 // out = x * f(beta + gamma * x^2) (+ res) per pixel; f = 1 / sqrt, or sqrt when inverse (gdn.py:52-67)
 struct GdnArgs {

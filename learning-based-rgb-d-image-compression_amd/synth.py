@@ -13,7 +13,7 @@ from collections import OrderedDict
 
 import numpy as np
 
-from .arch import (STF_SLICES, Entry, linear_global_inter_entries, linear_global_intra_entries, local_context_entries,
+from .arch import (STF_SLICES, Entry, channel_aligner_entries, linear_global_inter_entries, linear_global_intra_entries, local_context_entries,
                    spatial_aligner_entries, ckbd_config, ckbd_entries, elic_entries, elic_united_entries, elic_united_r2d_entries, model_config, stf_config,
                    stf_entries, stf_single_config, stf_united_entries)
 
@@ -131,7 +131,16 @@ def synthetic_state_dict(seed: int = 0, config=None, stress: bool = True, as_tor
     3000 entries, what a high-quality checkpoint makes the decoder search) or "plain" (default initialisation, everything
     quantises to zero).  model="Spatial_aligner" (in_channel, out_channel): the guided-attention block alone, always with its
     stress recipe (_apply_stress_aligner).  model="LocalContext" (dim, num_heads), "LinearGlobalIntraContext" (dim) or
-    "LinearGlobalInterContext" (dim, out_dim): an attention context of MLIC++ alone, always with _apply_stress_context."""
+    "LinearGlobalInterContext" (dim, out_dim): an attention context of MLIC++ alone, always with _apply_stress_context.
+    model="Channel_aligner": the block alone (the reference's constant widths), always with _apply_stress_chalign."""
+    if model == "Channel_aligner":
+        sd = OrderedDict((name, make_tensor(name, e, seed)) for name, e in channel_aligner_entries().items())
+        _apply_stress_chalign(sd)
+        if as_torch:
+            import torch
+
+            return OrderedDict((k, torch.from_numpy(np.ascontiguousarray(v))) for k, v in sd.items())
+        return sd
     if model in ("LocalContext", "LinearGlobalIntraContext", "LinearGlobalInterContext"):
         entries = (local_context_entries(dim, num_heads=num_heads) if model == "LocalContext" else
                    linear_global_intra_entries(dim) if model == "LinearGlobalIntraContext" else linear_global_inter_entries(dim, out_dim))
@@ -245,6 +254,23 @@ def _apply_stress_context(sd, seed):
         for n in ("keys.1", "queries.1"):
             sd[f"{n}.weight"] = sd[f"{n}.weight"] * np.float32(LINEAR_QK_GAIN)
             sd[f"{n}.bias"] = sd[f"{n}.bias"] * np.float32(LINEAR_QK_GAIN)
+
+
+CHALIGN_TRUNK_GAIN = math.sqrt(6.0)
+CHALIGN_HEAD_GAIN = 4.0
+
+
+def _apply_stress_chalign(sd):
+    """Channel_aligner: beta and gamma that are not their heads' biases.  The default initialisation (U(+-1 / sqrt(fan_in)),
+    variance 1 / (3 fan_in)) shrinks a map by about 0.4 per 3x3 + LeakyReLU layer, so that behind four of them the pooled
+    product would be a few per cent of the heads' biases (+-1/48).  The trunk weights are therefore scaled by sqrt(6) -- He's
+    gain for a rectifier, variance 2 / fan_in: the maps keep the scale of the input through the trunk -- and the weights of
+    conv2 / conv3 by 4, their biases left alone: the mean of a LeakyReLU map (about 0.4 of its spread) times the 2304 head
+    weights of an output gives max |beta|, |gamma| of 0.2 ... 5.7 on the fixtures' maps, ten to a few hundred times the bias."""
+    for i in (0, 2, 4, 6):
+        sd[f"conv1.{i}.weight"] = sd[f"conv1.{i}.weight"] * np.float32(CHALIGN_TRUNK_GAIN)
+    for n in ("conv2", "conv3"):
+        sd[f"{n}.weight"] = sd[f"{n}.weight"] * np.float32(CHALIGN_HEAD_GAIN)
 
 
 def _apply_stress(sd, cfg, transforms=True):
