@@ -699,6 +699,20 @@ int rgbd_dwconv3x3(const float* x, int32_t B, int32_t H, int32_t W, int32_t C, i
 int64_t rgbd_pooled_conv3x3_ws_floats(int32_t B, int32_t H, int32_t W, int32_t Cin);
 int rgbd_pooled_conv3x3(const float* x, int32_t cs, int32_t B, int32_t H, int32_t W, int32_t Cin, const float* w,
                         const float* bias, int32_t Cout, float* out, float* ws, void* stream);
+/* The two thin 3x3 layers of Feature_encoder / Feature_decoder (csrc/thin_conv.hip; models/elic_master.py:18,41; DESIGN.md
+ * 5.6): stride 1, zero padding 1, no activation, plain fp32 FMA in a fixed order, no workspace.  w: [Cout][Cin][3][3] on the
+ * device, bias: [Cout] on the device or NULL.  The same bits on every call, and image b of a batch as it is alone.
+ * rgbd_conv3x3_thin_in: x [B][Cin][H][W] planes, Cin in 1..4 -> y [B][H][W][ycs]; Cout % 4 == 0, 4 <= Cout <= 64; ycs >= Cout,
+ * ycs % 4 == 0, y 16-byte aligned; channels Cout .. ycs - 1 of y are not written.
+ * rgbd_conv3x3_thin_out: x [B][H][W][xcs], Cin % 4 == 0, 4 <= Cin <= 64, xcs >= Cin, xcs % 4 == 0, x 16-byte aligned, channels
+ * Cin .. xcs - 1 never loaded -> y [B][Cout][H][W] planes, Cout in 1..4.  w in convolution orientation: for a
+ * ConvTranspose2d(Cin, Cout, 3, 1, 1) weight t [Cin][Cout][3][3] that is w[o][c][ky][kx] = t[c][o][2 - ky][2 - kx].
+ * Both return RGBD_EINVAL and write nothing unless the above holds, x, w, y are not NULL, B, H, W >= 1, B <= 65535 and
+ * H * W <= 2^30. */
+int rgbd_conv3x3_thin_in(const float* x_nchw, int32_t B, int32_t Cin, int32_t H, int32_t W, const float* w, const float* bias,
+                         int32_t Cout, float* y_nhwc, int32_t ycs, void* stream);
+int rgbd_conv3x3_thin_out(const float* x_nhwc, int32_t xcs, int32_t B, int32_t H, int32_t W, int32_t Cin, const float* w,
+                          const float* bias, int32_t Cout, float* y_nchw, void* stream);
 int rgbd_patch_merge_gather(const float* x, int32_t B, int32_t H, int32_t W, int32_t C, int32_t xcs, float* y, int32_t ycs,
                             void* stream);
 int rgbd_pixel_shuffle2(const float* x, int32_t B, int32_t H, int32_t W, int32_t Co, int32_t xcs, float* y, int32_t ycs,

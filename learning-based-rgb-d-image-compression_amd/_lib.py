@@ -9,7 +9,7 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _SO = os.path.join(_HERE, "librgbd_amd.so")
 _SO = os.environ.get("RGBD_AMD_LIB", _SO)  # A/B builds: point at another librgbd_amd.so
-_SRCS = ["conv_mfma.hip", "conv_mfma_blk.hip", "pointwise.hip", "swin.hip", "entropy.hip", "metrics.hip", "coder_abi.hip", "gdn.hip", "context_attn.hip", "pooled_head.hip", "engine.hip", "engine_abi.hip"]
+_SRCS = ["conv_mfma.hip", "conv_mfma_blk.hip", "pointwise.hip", "swin.hip", "entropy.hip", "metrics.hip", "coder_abi.hip", "gdn.hip", "context_attn.hip", "pooled_head.hip", "thin_conv.hip", "engine.hip", "engine_abi.hip"]
 _LIB = None
 
 ERRORS = {-22: "invalid argument", -12: "out of memory", -5: "HIP runtime error", -28: "buffer too small",
@@ -198,6 +198,8 @@ def lib():
         "rgbd_dwconv3x3": (ctypes.c_int, [c_vp] + [c_i32] * 5 + [c_vp, c_vp, c_i32, c_vp, c_i32, c_vp]),
         "rgbd_pooled_conv3x3_ws_floats": (c_i64, [c_i32] * 4),
         "rgbd_pooled_conv3x3": (ctypes.c_int, [c_vp] + [c_i32] * 5 + [c_vp, c_vp, c_i32, c_vp, c_vp, c_vp]),
+        "rgbd_conv3x3_thin_in": (ctypes.c_int, [c_vp] + [c_i32] * 4 + [c_vp, c_vp, c_i32, c_vp, c_i32, c_vp]),
+        "rgbd_conv3x3_thin_out": (ctypes.c_int, [c_vp] + [c_i32] * 5 + [c_vp, c_vp, c_i32, c_vp, c_vp]),
         "rgbd_elic_debug_tensor": (ctypes.c_int, [c_vp, ctypes.c_char_p, f32p, c_i64, i32p]),
         "rgbd_elic_debug_symbols": (ctypes.c_int, [c_vp, c_i32, i32p, i32p, c_i64, i64p]),
         "rgbd_elic_set_profile": (ctypes.c_int, [c_vp, c_i32]),
@@ -260,7 +262,7 @@ EXPORTS = ["rgbd_abi_version", "rgbd_set_blocking_sync", "rgbd_get_blocking_sync
            "rgbd_pw_nhwc_to_nchw", "rgbd_local_context_create", "rgbd_local_context_forward", "rgbd_linear_inter_create",
            "rgbd_linear_inter_forward", "rgbd_linear_intra_create", "rgbd_linear_intra_forward", "rgbd_local_ckbd_attention",
            "rgbd_linear_attention_ws_floats", "rgbd_linear_attention", "rgbd_dwconv3x3", "rgbd_pooled_conv3x3_ws_floats",
-           "rgbd_pooled_conv3x3"]
+           "rgbd_pooled_conv3x3", "rgbd_conv3x3_thin_in", "rgbd_conv3x3_thin_out"]
 
 
 _BS_HOLDERS = 0

@@ -618,6 +618,37 @@ def channel_aligner_entries() -> "OrderedDict[str, Entry]":
     return b.entries
 
 
+FEATURE_CH = 64  # the width Feature_encoder / Feature_decoder hard-code inside (models/elic_master.py:19-21, 38-41)
+
+
+def _feature_resblocks(b: "_Builder", in_ch: int):
+    for i, cin in zip((1, 2, 3), (in_ch, FEATURE_CH, FEATURE_CH)):
+        b.conv(f"resblock{i}.conv1", cin, FEATURE_CH, 3)
+        b.conv(f"resblock{i}.conv2", FEATURE_CH, FEATURE_CH, 3)
+        if cin != FEATURE_CH:  # ResidualBlock.skip exists only where the widths differ (modules/layers/res_blk.py:43-46)
+            b.conv(f"resblock{i}.skip", cin, FEATURE_CH, 1)
+
+
+def feature_encoder_entries(in_ch: int = 3) -> "OrderedDict[str, Entry]":
+    """Every state_dict entry of Feature_encoder (reference: models/elic_master.py:15-21), in the reference's order: conv1
+    (3x3, in_ch -> 64) and three ResidualBlock(64, 64)."""
+    b = _Builder()
+    b.conv("conv1", in_ch, FEATURE_CH, 3)
+    _feature_resblocks(b, FEATURE_CH)
+    return b.entries
+
+
+def feature_decoder_entries(in_ch: int = 64, out_ch: int = 3) -> "OrderedDict[str, Entry]":
+    """Every state_dict entry of Feature_decoder (reference: models/elic_master.py:34-42), in the reference's order:
+    ResidualBlock(in_ch, 64) -- with its 1x1 `skip` unless in_ch is 64 --, two ResidualBlock(64, 64), deconv1
+    (ConvTranspose2d(64, out_ch, 3, 1, 1)) and the 1x1 shortcut `conv` (in_ch -> 64)."""
+    b = _Builder()
+    _feature_resblocks(b, in_ch)
+    b.deconv("deconv1", FEATURE_CH, out_ch, 3)
+    b.conv("conv", in_ch, FEATURE_CH, 1)
+    return b.entries
+
+
 def ckbd_config(N: int = 192) -> Config:
     """Cheng2020 anchor model with the checkerboard context (models/Cheng2020withCKBD.py:46-50): M = N, one slice."""
     cfg = model_config()

@@ -270,6 +270,14 @@ int64_t pooled_conv3x3_ws_floats(int B, int H, int W, int Cin);
 int launch_pooled_conv3x3(const float* x, int cs, int B, int H, int W, int Cin, const float* w, const float* bias, int Cout,
                           float* out, float* ws, hipStream_t s);
 
+// ---- the image-facing 3x3 layers of Feature_encoder / Feature_decoder (thin_conv.hip); both check their arguments ----
+// x [B,Cin,H,W] planes, Cin 1..4 -> y NHWC (channel stride ycs), Cout a multiple of 4 up to 64; w [Cout][Cin][3][3], bias or nullptr
+int launch_conv3x3_thin_in(const float* x, int B, int Cin, int H, int W, const float* w, const float* bias, int Cout, float* y,
+                           int ycs, hipStream_t s);
+// x NHWC (channel stride xcs), Cin a multiple of 4 up to 64 -> y [B,Cout,H,W] planes, Cout 1..4; w in convolution orientation
+int launch_conv3x3_thin_out(const float* x, int xcs, int B, int H, int W, int Cin, const float* w, const float* bias, int Cout,
+                            float* y, hipStream_t s);
+
 // ---- GDN / IGDN (gdn.hip) -----------------------------------------------------------------------
 // out = x * f(beta + gamma * x^2) (+ res) per pixel; f = 1 / sqrt, or sqrt when inverse (gdn.py:52-67)
 struct GdnArgs {

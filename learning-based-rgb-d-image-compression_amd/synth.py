@@ -13,7 +13,7 @@ from collections import OrderedDict
 
 import numpy as np
 
-from .arch import (STF_SLICES, Entry, channel_aligner_entries, linear_global_inter_entries, linear_global_intra_entries, local_context_entries,
+from .arch import (STF_SLICES, Entry, channel_aligner_entries, feature_decoder_entries, feature_encoder_entries, linear_global_inter_entries, linear_global_intra_entries, local_context_entries,
                    spatial_aligner_entries, ckbd_config, ckbd_entries, elic_entries, elic_united_entries, elic_united_r2d_entries, model_config, stf_config,
                    stf_entries, stf_single_config, stf_united_entries)
 
@@ -132,7 +132,18 @@ def synthetic_state_dict(seed: int = 0, config=None, stress: bool = True, as_tor
     quantises to zero).  model="Spatial_aligner" (in_channel, out_channel): the guided-attention block alone, always with its
     stress recipe (_apply_stress_aligner).  model="LocalContext" (dim, num_heads), "LinearGlobalIntraContext" (dim) or
     "LinearGlobalInterContext" (dim, out_dim): an attention context of MLIC++ alone, always with _apply_stress_context.
-    model="Channel_aligner": the block alone (the reference's constant widths), always with _apply_stress_chalign."""
+    model="Channel_aligner": the block alone (the reference's constant widths), always with _apply_stress_chalign.
+    model="Feature_encoder" (in_channel) or "Feature_decoder" (in_channel, out_channel): a feature network of ELIC_master alone,
+    always with _apply_stress_feature."""
+    if model in ("Feature_encoder", "Feature_decoder"):
+        entries = feature_encoder_entries(in_channel) if model == "Feature_encoder" else feature_decoder_entries(in_channel, out_channel)
+        sd = OrderedDict((name, make_tensor(name, e, seed)) for name, e in entries.items())
+        _apply_stress_feature(sd)
+        if as_torch:
+            import torch
+
+            return OrderedDict((k, torch.from_numpy(np.ascontiguousarray(v))) for k, v in sd.items())
+        return sd
     if model == "Channel_aligner":
         sd = OrderedDict((name, make_tensor(name, e, seed)) for name, e in channel_aligner_entries().items())
         _apply_stress_chalign(sd)
@@ -271,6 +282,25 @@ def _apply_stress_chalign(sd):
         sd[f"conv1.{i}.weight"] = sd[f"conv1.{i}.weight"] * np.float32(CHALIGN_TRUNK_GAIN)
     for n in ("conv2", "conv3"):
         sd[f"{n}.weight"] = sd[f"{n}.weight"] * np.float32(CHALIGN_HEAD_GAIN)
+
+
+FEATURE_RELU_GAIN = math.sqrt(6.0)
+FEATURE_LINEAR_GAIN = math.sqrt(3.0)
+
+
+def _apply_stress_feature(sd):
+    """Feature_encoder / Feature_decoder: three residual branches and a shortcut of comparable size.  The default
+    initialisation (variance 1 / (3 fan_in)) shrinks a map by about 0.4 per 3x3 + ReLU layer, so that a block's branch
+    relu(conv2(relu(conv1 x))) would be a sixth of its identity and the sum of the three a fraction of the outer shortcut:
+    a wrong branch would hide behind the shortcut.  The 3x3 weights of the blocks are scaled by sqrt(6) (He's gain for a
+    rectifier: a branch keeps the scale of its input), and the layers without an activation -- the encoder's conv1, the
+    decoder's resblock1.skip and `conv` -- by sqrt(3) (variance 1 / fan_in).  Biases and deconv1 keep theirs (torch's fan_in of
+    a transposed convolution is out_channels * 9, so its default weights are already of order 1 / sqrt(27))."""
+    for name in sd:
+        if not name.endswith(".weight") or name == "deconv1.weight":
+            continue
+        relu = name.startswith("resblock") and ".skip." not in name
+        sd[name] = sd[name] * np.float32(FEATURE_RELU_GAIN if relu else FEATURE_LINEAR_GAIN)
 
 
 def _apply_stress(sd, cfg, transforms=True):
