@@ -294,6 +294,22 @@ int rgbd_elic_set_tables(rgbd_elic* m, int32_t which, const int32_t* cdf, int32_
 int rgbd_elic_set_scale_table(rgbd_elic* m, const float* table, int32_t n);
 /* Packs the weights for the MFMA kernels and uploads everything to the current device. */
 int rgbd_elic_finalize(rgbd_elic* m);
+/* What finalize takes a state-dict entry for, decided by the family, the name and the shape alone (test hook; host only, no
+ * GPU needed).  family: 0 ELIC_united, 1 ELIC, 2 STF_united, 3 ELIC_united_R2D, 4 STF, 5 checkerboard Cheng2020,
+ * 6 Spatial_aligner, 7 LocalContext, 8 LinearGlobalInterContext, 9 LinearGlobalIntraContext.  Returns one of the kinds below,
+ * or RGBD_EINVAL for another family, a NULL pointer, ndim outside 1..4 or an extent < 1. */
+enum {
+    RGBD_KIND_IGNORED = 0,         /* read by no packer of its own: biases, betas, bottleneck matrices, buffers */
+    RGBD_KIND_RECOVERY_DECONV = 1, /* Spatial_aligner.recovery, a 2x2 stride-2 deconv: packed as a 1x1 conv + pixel shuffle */
+    RGBD_KIND_CONTEXT_DENSE = 2,   /* fusion.weight / depthwise [C][1][3][3] of the MLIC++ contexts: plain device arrays */
+    RGBD_KIND_CONV = 3,            /* Conv2d layer, packed for the MFMA kernels */
+    RGBD_KIND_CONV_TRANSPOSED = 4, /* ConvTranspose2d layer, likewise */
+    RGBD_KIND_GDN_GAMMA = 5,       /* square .gamma, packed with its .beta */
+    RGBD_KIND_LINEAR = 6,          /* 2-D .weight (SE_Block) */
+    RGBD_KIND_ARRAY = 7,           /* LayerNorm parameters and relative position tables: plain device arrays */
+    RGBD_KIND_QUANTILES = 8        /* entropy_bottleneck.quantiles: medians and the cumulative's parameters */
+};
+int rgbd_debug_tensor_kind(int32_t family, const char* name, const int64_t* shape, int32_t ndim);
 
 /*
  * compress(): rgb_dev [B,3,H,W], depth_dev [B,1,H,W] fp32 on the device, H and W multiples of 64.

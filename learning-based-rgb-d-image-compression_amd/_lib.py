@@ -9,7 +9,7 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _SO = os.path.join(_HERE, "librgbd_amd.so")
 _SO = os.environ.get("RGBD_AMD_LIB", _SO)  # A/B builds: point at another librgbd_amd.so
-_SRCS = ["conv_mfma.hip", "conv_mfma_blk.hip", "pointwise.hip", "swin.hip", "entropy.hip", "metrics.hip", "coder_abi.hip", "gdn.hip", "context_attn.hip", "pooled_head.hip", "thin_conv.hip", "engine.hip", "engine_abi.hip"]
+_SRCS = ["conv_mfma.hip", "conv_mfma_blk.hip", "pointwise.hip", "swin.hip", "entropy.hip", "metrics.hip", "coder_abi.hip", "gdn.hip", "context_attn.hip", "pooled_head.hip", "thin_conv.hip", "engine.hip", "engine_abi.hip", "hooks_abi.hip"]
 _LIB = None
 
 ERRORS = {-22: "invalid argument", -12: "out of memory", -5: "HIP runtime error", -28: "buffer too small",
@@ -57,7 +57,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
              "conv_mfma_blk.hip": [body, tiles]}
     hdrs.append(os.path.join(csrc, "splitk_table.h"))
     extra["coder_abi.hip"] = extra["gdn.hip"] = [os.path.join(csrc, "engine_internal.h")]
-    extra["engine.hip"] = extra["engine_abi.hip"] = [os.path.join(csrc, "engine_internal.h"), os.path.join(csrc, "engine.h"),
+    extra["engine.hip"] = extra["engine_abi.hip"] = extra["hooks_abi.hip"] = [os.path.join(csrc, "engine_internal.h"), os.path.join(csrc, "engine.h"),
                                                      os.path.join(csrc, "conv_args.h")]
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     os.makedirs(objdir, exist_ok=True)
@@ -142,6 +142,7 @@ def lib():
         "rgbd_elic_set_tables": (ctypes.c_int, [c_vp, c_i32, i32p, c_i32, i32p, i32p, c_i32]),
         "rgbd_elic_set_scale_table": (ctypes.c_int, [c_vp, f32p, c_i32]),
         "rgbd_elic_finalize": (ctypes.c_int, [c_vp]),
+        "rgbd_debug_tensor_kind": (ctypes.c_int, [c_i32, ctypes.c_char_p, i64p, c_i32]),
         "rgbd_elic_compress": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp]),
         "rgbd_elic_forward": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
         "rgbd_elic_stream_count": (ctypes.c_int, [c_vp, c_i32, c_i32]),
@@ -262,7 +263,7 @@ EXPORTS = ["rgbd_abi_version", "rgbd_set_blocking_sync", "rgbd_get_blocking_sync
            "rgbd_pw_nhwc_to_nchw", "rgbd_local_context_create", "rgbd_local_context_forward", "rgbd_linear_inter_create",
            "rgbd_linear_inter_forward", "rgbd_linear_intra_create", "rgbd_linear_intra_forward", "rgbd_local_ckbd_attention",
            "rgbd_linear_attention_ws_floats", "rgbd_linear_attention", "rgbd_dwconv3x3", "rgbd_pooled_conv3x3_ws_floats",
-           "rgbd_pooled_conv3x3", "rgbd_conv3x3_thin_in", "rgbd_conv3x3_thin_out"]
+           "rgbd_pooled_conv3x3", "rgbd_conv3x3_thin_in", "rgbd_conv3x3_thin_out", "rgbd_debug_tensor_kind"]
 
 
 _BS_HOLDERS = 0

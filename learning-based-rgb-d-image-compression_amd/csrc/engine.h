@@ -1,10 +1,11 @@
-// Host runtime of the gfx950 codec engine, part 1 of 3: weight packing, the workspace arena and `struct rgbd_elic` -- the
+// Host runtime of the gfx950 codec engine, part 1 of 4: weight packing, the workspace arena and `struct rgbd_elic` -- the
 // layer graph of the six model variants (ELIC_united, single-modal ELIC, STF_united, ELIC_united_R2D, single-modal STF, checkerboard
 // Cheng2020) as inline methods
 // that plan and issue HIP kernel launches on one stream, the conv planner (tiles, split-K, reference arithmetic) and the
 // per-call-shape HIP-graph cache.  engine.hip holds the call paths (compress / decompress / forward: one per direction for
-// one or two modalities; a family enters them through the four `*_family` hooks), engine_abi.hip the C ABI
-// (include/rgbd_amd.h).  Everything shared between those two translation units is `inline` here
+// one or two modalities; a family enters them through the four `*_family` hooks), engine_abi.hip and hooks_abi.hip the C ABI
+// (include/rgbd_amd.h): the engine's entry points, and the operator hooks and debug switches.  Everything shared between those
+// translation units is `inline` here
 // (one instance).
 #pragma once
 #include <algorithm>
@@ -36,7 +37,7 @@
 #include "engine_internal.h"
 
 
-// (process-wide switches and the helpers below: `inline` -- one instance for engine.hip and engine_abi.hip -- inside a namespace of
+// (process-wide switches and the helpers below: `inline` -- one instance for engine.hip, engine_abi.hip and hooks_abi.hip -- inside a namespace of
 // their own, so that the weak symbols they become cannot collide with a host application's globals)
 namespace rgbd_rt {
 
@@ -416,33 +417,74 @@ inline int small_conv_set_kblocks(SmallConvArgs* a, const int* lens, int n, int 
 }  // namespace rgbd_rt
 using namespace rgbd_rt;
 
+// What an engine handle is: a codec (0-5) or one module alone (6-9: no codec calls, no tables, its own forward entry point).
+// DESIGN.md and the history name the families by these numbers, so the numbers stay.
+enum class Family : int {
+    ELIC_united = 0,      // RGB + depth (models/elic_united.py)
+    ELIC = 1,             // single-modal ELIC (models/elic.py)
+    STF_united = 2,       // models/stf_united.py
+    ELIC_united_R2D = 3,  // models/elic_united_R2D.py
+    STF = 4,              // single-modal STF (models/stf.py)
+    Cheng2020_ckbd = 5,   // checkerboard Cheng2020 (models/Cheng2020withCKBD.py)
+    Spatial_aligner = 6,  // modules/transform/spatialAligner.py: rgbd_aligner_forward only
+    LocalContext = 7,     // the contexts of MLIC++ (modules/transform/context.py): rgbd_local_context_forward /
+    LinearGlobalInterContext = 8,  // rgbd_linear_inter_forward /
+    LinearGlobalIntraContext = 9,  // rgbd_linear_intra_forward only
+};
+constexpr int kFamilies = 10;
+
+struct FamilyRow {
+    const char* name;
+    int nm;        // modalities of a codec call; 0: a module handle
+    bool codec;    // has compress / decompress / forward (check_ready refuses the others)
+    bool refnum;   // default arithmetic: the reference's CPU arithmetic, unless RGBD_LEGACY_NUMERICS is set.  The
+                   // Swin transforms (channel slices that are not 16-aligned), the checkerboard family and the float-only modules
+                   // keep the single-chain arithmetic of rounds 1-4
+    int clamp;     // decompress() clamps x_hat to [0, 1] (elic_united.py, stf.py:815; not elic.py:318-325 nor
+                   // Cheng2020withCKBD.py:167-174); forward() and the Latents epilogue never clamp
+    bool forward_names_z;  // forward() names z and z_hat too: the single-modal paths always did, the two-modality one never
+                           // (it names y and y_hat only); kept so that the debug-tensor key sets stay what they were
+    bool dense4d;  // finalize keeps `fusion.weight` and the depthwise [C][1][3][3] weights as plain device arrays
+};
+constexpr FamilyRow kFamilyTable[kFamilies] = {
+    //  name                        nm codec  refnum clamp names_z dense4d
+    {"ELIC_united",                 2, true,  true,  1, false, false},
+    {"ELIC",                        1, true,  true,  0, true,  false},
+    {"STF_united",                  2, true,  false, 1, false, false},
+    {"ELIC_united_R2D",             2, true,  true,  1, false, false},
+    {"STF",                         1, true,  false, 1, true,  false},
+    {"Cheng2020_ckbd",              1, true,  false, 0, true,  false},
+    {"Spatial_aligner",             0, false, false, 0, false, false},
+    {"LocalContext",                0, false, false, 0, false, true},
+    {"LinearGlobalInterContext",    0, false, false, 0, false, true},
+    {"LinearGlobalIntraContext",    0, false, false, 0, false, true},
+};
+constexpr bool family_ok(int f) { return f >= 0 && f < kFamilies; }
+constexpr const FamilyRow& family_row(Family f) { return kFamilyTable[(int)f]; }
+
 struct rgbd_elic {
     int N = 192, M = 320;
     int tile_mode = 0;  // rgbd_elic_set_tile_mode: 0 latency tiles (isolated launches), 1 throughput tiles (shared chip)
-    int variant = 0;  // 0: ELIC_united (RGB + depth), 1: single-modal ELIC (models/elic.py), 2: STF_united, 3: ELIC_united_R2D,
-                      // 4: single-modal STF (models/stf.py), 5: checkerboard Cheng2020 (models/Cheng2020withCKBD.py),
-                      // 6: Spatial_aligner alone (modules/transform/spatialAligner.py): no codec, rgbd_aligner_forward only,
-                      // 7 / 8 / 9: LocalContext / LinearGlobalInterContext / LinearGlobalIntraContext of MLIC++ alone
-                      // (modules/transform/context.py): no codec, rgbd_local_context_forward / rgbd_linear_*_forward only
-    bool single() const { return variant == 1 || variant == 4 || variant == 5; }
-    int in_ch = 3;    // image channels of the single-modal variant (variant 6: channels of x and guided; 7-9: dim)
-    int out_ch = 0;   // variants 6-9: output channels
-    int ctx_heads = 0;  // variants 7-9: num_heads
+    Family family = Family::ELIC_united;
+    const FamilyRow& row() const { return family_row(family); }
+    bool single() const { return row().nm == 1; }
+    int in_ch = 3;    // image channels of the single-modal codecs (Spatial_aligner: channels of x and guided; contexts: dim)
+    int out_ch = 0;   // module handles: output channels
+    int ctx_heads = 0;  // contexts: num_heads
     // what the call paths (engine.hip) need to know about one versus two modalities; arrays are read at [0, nm)
     struct Modes {
         int nm;
         const char* sfx[2];  // suffix of the debug-tensor names: "y" / "y_r", "y_d"
         const char* eb[2];   // prefix of the entropy bottleneck's tensors
         int img_ch[2];       // image channels
-        int clamp;           // decompress() clamps x_hat to [0, 1] (elic_united.py, stf.py:815; not elic.py:318-325 nor
-                             // Cheng2020withCKBD.py:167-174); forward() and the Latents epilogue never clamp
-        bool forward_names_z;  // forward() names z and z_hat too: the single-modal paths always did, the two-modality one never
-                               // (it names y and y_hat only); kept so that the debug-tensor key sets stay what they were
+        int clamp;           // FamilyRow::clamp
+        bool forward_names_z;  // FamilyRow::forward_names_z
     };
     Modes modes() const
     {
-        if (single()) return {1, {"", ""}, {"", ""}, {in_ch, in_ch}, variant == 4 ? 1 : 0, true};
-        return {2, {"_r", "_d"}, {"rgb_", "depth_"}, {3, 1}, 1, false};
+        const FamilyRow& f = row();
+        if (single()) return {1, {"", ""}, {"", ""}, {in_ch, in_ch}, f.clamp, f.forward_names_z};
+        return {2, {"_r", "_d"}, {"rgb_", "depth_"}, {3, 1}, f.clamp, f.forward_names_z};
     }
     std::vector<int> slice_ch;
     std::map<std::string, HostTensor> raw;
@@ -1879,7 +1921,10 @@ struct rgbd_elic {
     static constexpr SliceLoop kLoopSingle = {{{kLocR, kChR, kHypR, kSegEnd}, {kSegEnd}},
                                               {{{0, kChR, false}, {}}, {{0, kLocR, false}, {}}},
                                               {0, 0, 0}, {"", ""}, false, true, false, false, false};
-    const SliceLoop& slice_loop_family() const { return variant == 1 ? kLoopSingle : variant == 3 ? kLoopR2D : kLoopUnited; }
+    const SliceLoop& slice_loop_family() const
+    {
+        return family == Family::ELIC ? kLoopSingle : family == Family::ELIC_united_R2D ? kLoopR2D : kLoopUnited;
+    }
 
     // The parameter net of one part: [SE rescale,] three convs (1x1 / 3x3 / 5x5 or 1x1 x 3; padding k / 2) with ReLU between.
     // SE writes the rescaled copy the first conv reads (params + se(params), keeping the reference's association); `means`:
@@ -2236,7 +2281,7 @@ struct rgbd_elic {
         }
         return pixel_shuffle(conv(p + "recovery", ex, 1, 0));
     }
-    // ---- the attention contexts of MLIC++ (modules/transform/context.py), each a block of its own (variants 7-9) -------
+    // ---- the attention contexts of MLIC++ (modules/transform/context.py), each a block of its own (families 7-9) -------
     // nn.Conv2d(C, C, 3, 1, 1, groups = C) (+ nn.GELU()): weight [C][1][3][3] and bias as plain arrays (finalize)
     Act dwconv(const std::string& name, const Act& x, bool gelu)
     {
@@ -2851,7 +2896,7 @@ struct rgbd_elic {
         for (int m = 0; m < mo.nm; ++m) named[std::string(base) + mo.sfx[m]] = a[m];
     }
 
-    // A family (variant) enters the call paths through these four hooks, which switch on `variant`; Act arrays are read at
+    // A family enters the call paths through these four hooks, which switch on `family`; Act arrays are read at
     // [0, nm).  latent_family owns everything between z_hat and y_hat: the family's buffers, its hyper synthesis (skipped when
     // the caller hands in `hyp`, the Latents path), its debug tensors and its coding loop.
     void g_a_family(const Act x[2], Act y[2]);
@@ -2882,7 +2927,7 @@ struct rgbd_elic {
     void mids_begin(int B, int H, int W, Act mid[3]);  // workspace of up1..up3; g_s1 fills it while mid_dst points at it
     int mids_out(const Act mid[3], int B, int H, int W, const Mid3& up);
     int run_aligner(const float* x_dev, const float* guided_dev, int B, int H, int W, float* out_dev);
-    // variants 7-9: x1 (and, variant 9, x2) [B,in_ch,H,W] -> out [B,out_ch,H,W]
+    // the contexts: x1 (and, LinearGlobalIntraContext, x2) [B,in_ch,H,W] -> out [B,out_ch,H,W]
     int run_context(const float* x1_dev, const float* x2_dev, int B, int H, int W, float* out_dev);
     int ensure_arena(size_t bytes);
 };

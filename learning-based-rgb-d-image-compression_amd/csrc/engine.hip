@@ -1,4 +1,4 @@
-// Host runtime of the gfx950 codec engine, part 2 of 3: the call paths -- compress(), decompress() and the eval forward, once
+// Host runtime of the gfx950 codec engine, part 2 of 4: the call paths -- compress(), decompress() and the eval forward, once
 // for every family of one or two modalities -- as sequences of kernel launches through the layer graph of engine.h
 // (prologue: workspace of the call and stream geometry; body: captured into / replayed from a HIP graph; epilogue: fetch
 // the finished streams).  Mirrors the call structure of the reference's models/elic_united.py:350-578 but keeps every
@@ -320,39 +320,39 @@ void rgbd_elic::y_encode(int nm, int B, const EncBufs& e)
     if (r) fail(r);
 }
 
-// ---- the family hooks: ELIC_united (variant 0, models/elic_united.py), ELIC (1, models/elic.py), STF_united (2,
+// ---- the family hooks: ELIC_united (family 0, models/elic_united.py), ELIC (1, models/elic.py), STF_united (2,
 // models/stf_united.py), ELIC_united_R2D (3, models/elic_united_R2D.py), STF (4, models/stf.py) and the checkerboard Cheng2020
 // (5, models/Cheng2020withCKBD.py) share one call path per direction; a family enters through the four hooks below ----------
 void rgbd_elic::g_a_family(const Act x[2], Act y[2])
 {
-    switch (variant) {
-    case 1: y[0] = g_a1(x[0]); break;
-    case 2: g_a_stf(x[0], x[1], &y[0], &y[1]); break;
-    case 3: g_a_r2d(x, y); break;
-    case 4: y[0] = g_a_stf1(x[0]); break;
-    case 5: y[0] = g_a_ckbd(x[0]); break;
+    switch (family) {
+    case Family::ELIC: y[0] = g_a1(x[0]); break;
+    case Family::STF_united: g_a_stf(x[0], x[1], &y[0], &y[1]); break;
+    case Family::ELIC_united_R2D: g_a_r2d(x, y); break;
+    case Family::STF: y[0] = g_a_stf1(x[0]); break;
+    case Family::Cheng2020_ckbd: y[0] = g_a_ckbd(x[0]); break;
     default: g_a(x, y);
     }
 }
 
 void rgbd_elic::h_a_family(const Act y[2], Act z[2])
 {
-    switch (variant) {
-    case 1: z[0] = h_a1(y[0]); break;
-    case 4: z[0] = h_a_stf1(y[0]); break;
-    case 5: z[0] = h_a_ckbd(y[0]); break;
+    switch (family) {
+    case Family::ELIC: z[0] = h_a1(y[0]); break;
+    case Family::STF: z[0] = h_a_stf1(y[0]); break;
+    case Family::Cheng2020_ckbd: z[0] = h_a_ckbd(y[0]); break;
     default: h_a(y[0], y[1], &z[0], &z[1]);
     }
 }
 
 void rgbd_elic::g_s_family(const Act yhat[2], Act xhat[2])
 {
-    switch (variant) {
-    case 1: xhat[0] = g_s1(yhat[0]); break;
-    case 2: g_s_stf(yhat[0], yhat[1], &xhat[0], &xhat[1]); break;
-    case 3: g_s_r2d(yhat, xhat); break;
-    case 4: xhat[0] = g_s_stf1(yhat[0]); break;
-    case 5: xhat[0] = g_s_ckbd(yhat[0]); break;
+    switch (family) {
+    case Family::ELIC: xhat[0] = g_s1(yhat[0]); break;
+    case Family::STF_united: g_s_stf(yhat[0], yhat[1], &xhat[0], &xhat[1]); break;
+    case Family::ELIC_united_R2D: g_s_r2d(yhat, xhat); break;
+    case Family::STF: xhat[0] = g_s_stf1(yhat[0]); break;
+    case Family::Cheng2020_ckbd: xhat[0] = g_s_ckbd(yhat[0]); break;
     default: g_s(yhat, xhat);
     }
 }
@@ -370,8 +370,8 @@ void rgbd_elic::g_s_family(const Act yhat[2], Act xhat[2])
 void rgbd_elic::latent_family(Coding& cd, int B, int h, int w, const Act* y, const Act* zhat, const Act* hyp, Act yhat[2])
 {
     const Modes mo = modes();
-    switch (variant) {
-    case 1: {
+    switch (family) {
+    case Family::ELIC: {
         Act hyper = h_s1(zhat[0]);
         named["hyper"] = hyper;
         yhat[0] = alloc(B, h, w, M);
@@ -379,7 +379,7 @@ void rgbd_elic::latent_family(Coding& cd, int B, int h, int w, const Act* y, con
         slice_loop_ckbd(cd, slice_loop_family(), 1, y, &hyper, yhat);
         break;
     }
-    case 4: {
+    case Family::STF: {
         const int wide = M + (kStfSupport + 1) * kStfSliceCh;
         Act ctxm = alloc(B, h, w, wide), ctxs = alloc(B, h, w, wide);
         yhat[0] = alloc(B, h, w, M);
@@ -394,7 +394,7 @@ void rgbd_elic::latent_family(Coding& cd, int B, int h, int w, const Act* y, con
         slice_loop(cd, y, ctxm, ctxs, yhat[0]);
         break;
     }
-    case 5: {
+    case Family::Cheng2020_ckbd: {
         Act cat = alloc(B, h, w, 4 * M), params = alloc(B, h, w, 2 * M);
         yhat[0] = alloc(B, h, w, M);
         named["hyper"] = view(cat, 2 * M, 2 * M);
@@ -450,14 +450,14 @@ void rgbd_elic::latent_family(Coding& cd, int B, int h, int w, const Act* y, con
         if (hyp) {
             hy[0] = hyp[0];
             hy[1] = hyp[1];
-        } else if (variant == 3) {
+        } else if (family == Family::ELIC_united_R2D) {
             h_s_r2d(zhat[0], zhat[1], &hy[0], &hy[1]);
         } else {
             h_s(zhat[0], zhat[1], &hy[0], &hy[1]);
         }
         if (!cd.estimate) name(mo, "hyper", hy);  // (deliberate: forward() of these codecs never named hyper_r / hyper_d; Modes)
         for (int m = 0; m < 2; ++m) yhat[m] = alloc(B, h, w, M);
-        if (variant == 2 && !dry()) {  // 24-wide slices: a 16-channel read chunk may straddle into a slice not coded yet
+        if (family == Family::STF_united && !dry()) {  // 24-wide slices: a 16-channel read chunk may straddle into a slice not coded yet
             int zr = launch_fill_zero(yhat[0].p, yhat[0].elems(), s);
             if (!zr) zr = launch_fill_zero(yhat[1].p, yhat[1].elems(), s);
             if (zr) fail(zr);
@@ -553,7 +553,7 @@ int rgbd_elic::run_forward(int nm, In2 x_dev, int B, int H, int W, Out2 xhat_dev
 {
     const Modes mo = modes();
     if (nm != mo.nm) return RGBD_ESTATE;
-    if (up && variant != 1) return RGBD_EINVAL;
+    if (up && family != Family::ELIC) return RGBD_EINVAL;
     const int h = H / 16, w = W / 16, zh = H / 64, zw = W / 64;
     begin_call(B, true);  // forward() is one reference call on the whole batch
     Act x[2];
@@ -627,7 +627,7 @@ int rgbd_elic::mids_out(const Act mid[3], int B, int H, int W, const Mid3& up)
     return r;
 }
 
-// Spatial_aligner alone (variant 6): x, guided [B,in_ch,H,W] -> out [B,out_ch,H,W]
+// Spatial_aligner alone (family 6): x, guided [B,in_ch,H,W] -> out [B,out_ch,H,W]
 int rgbd_elic::run_aligner(const float* x_dev, const float* guided_dev, int B, int H, int W, float* out_dev)
 {
     begin_call(B, true);
@@ -652,22 +652,22 @@ int rgbd_elic::run_aligner(const float* x_dev, const float* guided_dev, int B, i
     return r;
 }
 
-// An attention context of MLIC++ alone (variants 7-9): x1 (and x2 of LinearGlobalIntraContext) [B,in_ch,H,W] -> [B,out_ch,H,W]
+// An attention context of MLIC++ alone (families 7-9): x1 (and x2 of LinearGlobalIntraContext) [B,in_ch,H,W] -> [B,out_ch,H,W]
 int rgbd_elic::run_context(const float* x1_dev, const float* x2_dev, int B, int H, int W, float* out_dev)
 {
     begin_call(B, true);
-    const Act x1 = alloc(B, H, W, in_ch), x2 = variant == 9 ? alloc(B, H, W, in_ch) : Act();
+    const Act x1 = alloc(B, H, W, in_ch), x2 = family == Family::LinearGlobalIntraContext ? alloc(B, H, W, in_ch) : Act();
     if (!dry()) {
         int r = launch_nchw_to_nhwc16(x1_dev, B, in_ch, H, W, x1.p, x1.cs, s);
-        if (!r && variant == 9) r = launch_nchw_to_nhwc16(x2_dev, B, in_ch, H, W, x2.p, x2.cs, s);
+        if (!r && family == Family::LinearGlobalIntraContext) r = launch_nchw_to_nhwc16(x2_dev, B, in_ch, H, W, x2.p, x2.cs, s);
         if (r) return r;
     }
     // ==== body: captured into / replayed from a HIP graph per call shape ====
     Act out;
     if (body_begin()) {
-        if (variant == 7) {
+        if (family == Family::LocalContext) {
             out = local_context(x1);
-        } else if (variant == 8) {
+        } else if (family == Family::LinearGlobalInterContext) {
             out = linear_context(x1, x1, x1, 0, true);
         } else {
             const Act xa = alloc(B, H, W, in_ch), xn = alloc(B, H, W, in_ch);  // ckbd_anchor(x1), ckbd_nonanchor(x1): :191-192
@@ -694,7 +694,7 @@ int rgbd_elic::run_decompress(int nm, const uint8_t* const* ys[2], const int64_t
 {
     const Modes mo = modes();
     if (nm != mo.nm) return RGBD_ESTATE;
-    if (up && (variant != 1 || lat)) return RGBD_EINVAL;
+    if (up && (family != Family::ELIC || lat)) return RGBD_EINVAL;
     const int zh = lat ? 1 : h / 4, zw = lat ? 1 : w / 4, H = h * 16, W = w * 16;
     const int64_t T = (int64_t)M * h * w, Tz = (int64_t)N * zh * zw;
     const int per_image = (n_y == B && !(B == 1)) ? 1 : (n_y == 1 ? (B == 1 ? 1 : 0) : -1);

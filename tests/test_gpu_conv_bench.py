@@ -1,4 +1,4 @@
-"""rgbd_conv_bench alone (csrc/engine_abi.hip): the entry point every number in csrc/tile_table*.h and csrc/splitk_table.h was
+"""rgbd_conv_bench alone (csrc/hooks_abi.hip): the entry point every number in csrc/tile_table*.h and csrc/splitk_table.h was
 timed through.  Each case is one call with two timed iterations on a tiny shape, under the conv shape log: the call must
 succeed, report a finite positive time, and have launched exactly the shape the arguments and the debug switches describe --
 one warm-up launch plus the timed ones.
