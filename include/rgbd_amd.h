@@ -89,6 +89,43 @@ int rgbd_rans_decode_batch_dev(const rgbd_tables* t, const uint32_t* streams_dev
                                const int32_t* indexes_dev, int32_t* symbols_dev, const int64_t* sym_base_dev, int64_t part_off,
                                int64_t count, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * Wide rANS: an opt-in second stream format for callers who want low latency and do not need CompressAI-compatible
+ * streams.  `lanes` (L = 1, 2, 4, ... 64) interleaved Rans64 states are coded by one wavefront, one lane per state, with
+ * the reference's state arithmetic and escape coding unchanged.  A stream codes a list of at most 32 SEGMENTS; inside a
+ * segment symbol i belongs to lane i mod L and row i div L, rows restart at every segment, and one decode call decodes one
+ * segment.  The stream starts with the L states (lane 0 first, two words each); per row and item round, the lanes that
+ * renormalise take one word each in increasing lane order.  With L = 1 and one segment the stream is the reference's,
+ * byte for byte.  A wide stream is 8 * (L - 1) bytes longer than the serial one (504 bytes at L = 64) plus rounding.
+ * Refused with RGBD_EINVAL before anything is launched: lanes not a power of two in 1 ... 64, nseg outside 1 ... 32, a
+ * negative count, counts that do not sum to n, a stream shorter than 8 * L bytes, a NULL pointer; RGBD_ENOSPC: cap below
+ * rgbd_rans_wide_max_bytes(n, lanes).  A decode that runs into a damaged stream (a read past its end, an escape of more
+ * than 8 nibbles) reads zeros, stays inside its buffers and returns RGBD_EINVAL / raises *err_dev.
+ * ------------------------------------------------------------------------------------------------------------- */
+int64_t rgbd_rans_wide_max_bytes(int64_t n, int32_t lanes); /* RGBD_EINVAL for bad arguments */
+int rgbd_rans_wide_encode(const rgbd_tables* t, const int32_t* symbols, const int32_t* indexes, int64_t n, int32_t lanes,
+                          const int64_t* seg_counts, int32_t nseg, uint8_t* out, int64_t cap, int64_t* out_len);
+typedef struct rgbd_rans_wide_decoder rgbd_rans_wide_decoder;
+int rgbd_rans_wide_decoder_create(rgbd_rans_wide_decoder** out);
+int rgbd_rans_wide_decoder_set_stream(rgbd_rans_wide_decoder* d, const uint8_t* stream, int64_t nbytes, int32_t lanes);
+/* Decodes the next segment: n symbols for the given table indexes. */
+int rgbd_rans_wide_decoder_decode(rgbd_rans_wide_decoder* d, const rgbd_tables* t, const int32_t* indexes, int64_t n,
+                                  int32_t* symbols_out);
+void rgbd_rans_wide_decoder_destroy(rgbd_rans_wide_decoder* d);
+/* The device-resident pair, as rgbd_rans_{encode,decode}_batch_dev.  encode: every stream codes sum(seg_counts) symbols
+ * from sym_base_dev[s] on; streams [0, split) use t0, the others t1; seg_counts is a HOST array, passed to the kernel by
+ * value; cap_words >= 2 * lanes (the kernel checks every store: a slot smaller than rgbd_rans_wide_max_bytes / 4 that
+ * overflows raises *err_dev and nothing is written outside it).  decode: one segment of `count` symbols per call; state_dev
+ * keeps lanes + 1 uint64 per stream between calls; *err_dev (zero it first) is raised on a damaged stream. */
+int rgbd_rans_wide_encode_batch_dev(const rgbd_tables* t0, const rgbd_tables* t1, int32_t split, const int32_t* symbols_dev,
+                                    const int32_t* indexes_dev, const int64_t* sym_base_dev, int32_t nstreams, int32_t lanes,
+                                    const int64_t* seg_counts, int32_t nseg, uint32_t* out_dev, int64_t cap_words,
+                                    int64_t* out_words_dev, int32_t* err_dev, void* stream);
+int rgbd_rans_wide_decode_batch_dev(const rgbd_tables* t, const uint32_t* streams_dev, const int64_t* stream_off_words_dev,
+                                    const int64_t* stream_len_words_dev, int32_t nstreams, int32_t lanes, uint64_t* state_dev,
+                                    int32_t init, const int32_t* indexes_dev, int32_t* symbols_dev, const int64_t* sym_base_dev,
+                                    int64_t part_off, int64_t count, int32_t* err_dev, void* stream);
+
 /* One checkerboard half of one channel slice on the encoder: utils/ckbd.py:83-105 (ckbd_anchor_sequeeze /
  * ckbd_nonanchor_sequeeze of y, means and scales), entropy_models.py:118-146 (quantize(y, "symbols", means)), :561-568
  * (build_indexes(scales)) and the scatter of y_hat = symbol + mean back onto the full grid (ckbd.py:107-125), as ONE pass.
@@ -463,6 +500,15 @@ int rgbd_elic_debug_floats(rgbd_elic* m, int32_t modality, float* x, float* scal
  * context.  n_y = B * M * h * w per modality (n_z = B * N * zh * zw; 0 = this stage is not forced); n_y = n_z = 0 clears. */
 int rgbd_elic_set_forced_symbols(rgbd_elic* m, int32_t modality, const int32_t* y_sym, int64_t n_y, const int32_t* z_sym,
                                  int64_t n_z);
+
+/* The format of the y streams: format 0 = the reference's (default; `lanes` ignored), 1 = wide rANS with `lanes`
+ * interleaved states (1, 2, 4 ... 64; see rgbd_rans_wide_encode above), one segment per checkerboard half of a slice.  The z
+ * streams keep the reference format.  compress() then returns bare wide y streams and decompress() expects them (the
+ * Python models add and check a 4-byte tag); a damaged wide stream fails decompress() with RGBD_EINVAL.  Drops the cached
+ * graphs.  RGBD_EINVAL: NULL engine, format outside 0 ... 1, bad lanes, or format 1 on a family other than ELIC_united and
+ * ELIC (STF_united, ELIC_united_R2D, STF and the checkerboard Cheng2020 keep the reference format and refuse here, before
+ * anything is launched).  RGBD_ESTATE inside a running call of the engine. */
+int rgbd_elic_set_coder(rgbd_elic* m, int32_t format, int32_t lanes);
 
 /* Test hooks: force a split-K factor for rgbd_conv2d_nchw / the codec's entropy-model layers (0 = automatic) and
  * kernel-only timing of one convolution shape on NHWC scratch buffers (tools/conv_sweep.py). */

@@ -9,7 +9,7 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _SO = os.path.join(_HERE, "librgbd_amd.so")
 _SO = os.environ.get("RGBD_AMD_LIB", _SO)  # A/B builds: point at another librgbd_amd.so
-_SRCS = ["conv_mfma.hip", "conv_mfma_blk.hip", "pointwise.hip", "swin.hip", "entropy.hip", "metrics.hip", "coder_abi.hip", "gdn.hip", "context_attn.hip", "pooled_head.hip", "thin_conv.hip", "engine.hip", "engine_abi.hip", "hooks_abi.hip"]
+_SRCS = ["conv_mfma.hip", "conv_mfma_blk.hip", "pointwise.hip", "swin.hip", "entropy.hip", "rans_wide.hip", "metrics.hip", "coder_abi.hip", "gdn.hip", "context_attn.hip", "pooled_head.hip", "thin_conv.hip", "engine.hip", "engine_abi.hip", "hooks_abi.hip"]
 _LIB = None
 
 ERRORS = {-22: "invalid argument", -12: "out of memory", -5: "HIP runtime error", -28: "buffer too small",
@@ -108,6 +108,17 @@ def lib():
         "rgbd_rans_decoder_destroy": (None, [c_vp]),
         "rgbd_rans_encode_batch_dev": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_i64, c_vp, c_vp, c_vp]),
         "rgbd_rans_decode_batch_dev": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_i64, c_i64, c_vp]),
+        "rgbd_rans_wide_max_bytes": (c_i64, [c_i64, c_i32]),
+        "rgbd_rans_wide_encode": (ctypes.c_int, [c_vp, i32p, i32p, c_i64, c_i32, i64p, c_i32, u8p, c_i64, i64p]),
+        "rgbd_rans_wide_decoder_create": (ctypes.c_int, [ctypes.POINTER(c_vp)]),
+        "rgbd_rans_wide_decoder_set_stream": (ctypes.c_int, [c_vp, u8p, c_i64, c_i32]),
+        "rgbd_rans_wide_decoder_decode": (ctypes.c_int, [c_vp, c_vp, i32p, c_i64, i32p]),
+        "rgbd_rans_wide_decoder_destroy": (None, [c_vp]),
+        "rgbd_rans_wide_encode_batch_dev": (ctypes.c_int, [c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_i32, c_i32, i64p, c_i32, c_vp, c_i64,
+                                                           c_vp, c_vp, c_vp]),
+        "rgbd_rans_wide_decode_batch_dev": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_vp, c_i32, c_vp, c_vp, c_vp, c_i64,
+                                                           c_i64, c_vp, c_vp]),
+        "rgbd_elic_set_coder": (ctypes.c_int, [c_vp, c_i32, c_i32]),
         "rgbd_ckbd_quant_index": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, f32p, c_vp, c_vp, c_vp, c_vp]),
         "rgbd_ckbd_dequant": (ctypes.c_int, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp]),
         "rgbd_conv2d_nchw": (ctypes.c_int, [c_vp, c_i32, c_i32, c_i32, c_i32, f32p, f32p, c_i32, c_i32, c_i32, c_i32,
@@ -263,7 +274,10 @@ EXPORTS = ["rgbd_abi_version", "rgbd_set_blocking_sync", "rgbd_get_blocking_sync
            "rgbd_pw_nhwc_to_nchw", "rgbd_local_context_create", "rgbd_local_context_forward", "rgbd_linear_inter_create",
            "rgbd_linear_inter_forward", "rgbd_linear_intra_create", "rgbd_linear_intra_forward", "rgbd_local_ckbd_attention",
            "rgbd_linear_attention_ws_floats", "rgbd_linear_attention", "rgbd_dwconv3x3", "rgbd_pooled_conv3x3_ws_floats",
-           "rgbd_pooled_conv3x3", "rgbd_conv3x3_thin_in", "rgbd_conv3x3_thin_out", "rgbd_debug_tensor_kind"]
+           "rgbd_pooled_conv3x3", "rgbd_conv3x3_thin_in", "rgbd_conv3x3_thin_out", "rgbd_debug_tensor_kind",
+           "rgbd_rans_wide_max_bytes", "rgbd_rans_wide_encode", "rgbd_rans_wide_decoder_create", "rgbd_rans_wide_decoder_set_stream",
+           "rgbd_rans_wide_decoder_decode", "rgbd_rans_wide_decoder_destroy", "rgbd_rans_wide_encode_batch_dev",
+           "rgbd_rans_wide_decode_batch_dev", "rgbd_elic_set_coder"]
 
 
 _BS_HOLDERS = 0

@@ -138,3 +138,68 @@ class RansDecoder:
                 self._h = None
         except Exception:
             pass
+
+
+# ---- wide rANS: the opt-in lane-interleaved format (include/rgbd_amd.h; not a CompressAI format) ---------------------------
+WIDE_LANES = (1, 2, 4, 8, 16, 32, 64)
+
+
+def _check_lanes(lanes) -> int:
+    if lanes not in WIDE_LANES:
+        raise ValueError(f"lanes must be one of {WIDE_LANES}, got {lanes!r}")
+    return int(lanes)
+
+
+class WideRansEncoder:
+    """One wide stream from (symbol, index) pairs: `lanes` interleaved rANS states, one GPU lane each.  `segments` lists
+    the symbol counts the decoder will ask for, call by call (default: one segment with everything); rows of `lanes` symbols
+    restart at every segment.  A stream is 8 * (lanes - 1) bytes longer than RansEncoder's; with lanes = 1 and one segment
+    it is RansEncoder's stream byte for byte."""
+
+    def __init__(self, lanes: int = 64):
+        self.lanes = _check_lanes(lanes)
+
+    def encode_with_indexes(self, symbols, indexes, cdfs, cdfs_sizes, offsets, segments=None) -> bytes:
+        t = Tables.cached(cdfs, cdfs_sizes, offsets)
+        sym, idx = _i32(symbols).reshape(-1), _i32(indexes).reshape(-1)
+        if sym.shape != idx.shape:
+            raise ValueError("symbols and indexes must have the same length")
+        n = int(sym.shape[0])
+        seg = np.ascontiguousarray(np.asarray([n] if segments is None else segments, dtype=np.int64)).reshape(-1)
+        cap = int(lib().rgbd_rans_wide_max_bytes(n, self.lanes))
+        out = np.empty(cap, dtype=np.uint8)
+        ln = ctypes.c_int64(0)
+        check(lib().rgbd_rans_wide_encode(t.handle, _ptr(sym, ctypes.c_int32), _ptr(idx, ctypes.c_int32), n, self.lanes,
+                                          _ptr(seg, ctypes.c_int64), int(seg.shape[0]), _ptr(out, ctypes.c_uint8), cap,
+                                          ctypes.byref(ln)), "rans_wide_encode")
+        return out[: ln.value].tobytes()
+
+
+class WideRansDecoder:
+    """set_stream(), then one decode_stream() per segment, in the encoder's order."""
+
+    def __init__(self, lanes: int = 64):
+        self.lanes = _check_lanes(lanes)
+        self._h = ctypes.c_void_p()
+        check(lib().rgbd_rans_wide_decoder_create(ctypes.byref(self._h)), "wide_decoder_create")
+
+    def set_stream(self, encoded: bytes):
+        buf = np.frombuffer(bytes(encoded), dtype=np.uint8)
+        check(lib().rgbd_rans_wide_decoder_set_stream(self._h, _ptr(buf, ctypes.c_uint8), int(buf.shape[0]), self.lanes),
+              "wide set_stream")
+
+    def decode_stream(self, indexes, cdfs, cdfs_sizes, offsets):
+        t = Tables.cached(cdfs, cdfs_sizes, offsets)
+        idx = _i32(indexes).reshape(-1)
+        out = np.empty(idx.shape[0], dtype=np.int32)
+        check(lib().rgbd_rans_wide_decoder_decode(self._h, t.handle, _ptr(idx, ctypes.c_int32), int(idx.shape[0]),
+                                                  _ptr(out, ctypes.c_int32)), "wide decode_stream")
+        return out.tolist()
+
+    def __del__(self):
+        try:
+            if self._h:
+                lib().rgbd_rans_wide_decoder_destroy(self._h)
+                self._h = None
+        except Exception:
+            pass

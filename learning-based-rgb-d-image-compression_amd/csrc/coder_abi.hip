@@ -500,6 +500,206 @@ int rgbd_rans_decode_batch_dev(const rgbd_tables* t, const uint32_t* streams_dev
                               symbols_dev, sym_base_dev, part_off, count, t->ts.d, (hipStream_t)stream);
 }
 
+// ---- wide rANS (rans_wide.hip): the lane-interleaved format behind the same kinds of entry point -----------------------------
+// Everything a caller can get wrong is refused here, on the host, before anything is launched.
+static int64_t wide_cap_words(int64_t n, int lanes) { return rgbd_enc_cap_words(n) + 2 * (int64_t)(lanes - 1); }
+
+// the segment list of a call: nseg in 1 ... 32, no negative count, counts summing to n
+static int wide_segs(const int64_t* seg_counts, int32_t nseg, int64_t n, WideSegs* out)
+{
+    if (!seg_counts || nseg < 1 || nseg > WIDE_MAX_SEGS || n < 0) return RGBD_EINVAL;
+    int64_t sum = 0;
+    out->n = nseg;
+    for (int k = 0; k < WIDE_MAX_SEGS; ++k) out->count[k] = 0;
+    for (int k = 0; k < nseg; ++k) {
+        if (seg_counts[k] < 0 || seg_counts[k] > n) return RGBD_EINVAL;
+        out->count[k] = seg_counts[k];
+        sum += seg_counts[k];
+    }
+    return sum == n ? RGBD_OK : RGBD_EINVAL;
+}
+
+int64_t rgbd_rans_wide_max_bytes(int64_t n, int32_t lanes)
+{
+    if (n < 0 || wide_lanes_log2(lanes) < 0) return RGBD_EINVAL;
+    return 4 * wide_cap_words(n, lanes);
+}
+
+int rgbd_rans_wide_encode(const rgbd_tables* t, const int32_t* symbols, const int32_t* indexes, int64_t n, int32_t lanes,
+                          const int64_t* seg_counts, int32_t nseg, uint8_t* out, int64_t cap, int64_t* out_len)
+{
+    std::unique_lock<std::shared_mutex> cap_lk(g_capture_mu);  // frees / synchronous copies: not while a stream captures
+    if (!t || !t->ts.ready || n < 0 || !out || !out_len || (n && (!symbols || !indexes))) return RGBD_EINVAL;
+    if (wide_lanes_log2(lanes) < 0) return RGBD_EINVAL;
+    WideSegs segs;
+    if (const int r = wide_segs(seg_counts, nseg, n, &segs)) return r;
+    const int64_t capw = wide_cap_words(n, lanes);
+    if (cap < 4 * capw) return RGBD_ENOSPC;
+    for (int64_t i = 0; i < n; ++i)
+        if (indexes[i] < 0 || indexes[i] >= t->ts.d.nrows) return RGBD_EINVAL;
+    int32_t *dsym = nullptr, *didx = nullptr;
+    uint32_t* dout = nullptr;
+    int64_t* dmeta = nullptr;
+    int* derr = nullptr;
+    int rc = RGBD_OK;
+    auto cleanup = [&]() {
+        (void)hipFree(dsym);
+        (void)hipFree(didx);
+        (void)hipFree(dout);
+        (void)hipFree(dmeta);
+        (void)hipFree(derr);
+    };
+    auto alloc_all = [&]() -> hipError_t {
+        hipError_t e = hipMalloc((void**)&dsym, sizeof(int32_t) * (size_t)(n + 1));
+        if (e == hipSuccess) e = hipMalloc((void**)&didx, sizeof(int32_t) * (size_t)(n + 1));
+        if (e == hipSuccess) e = hipMalloc((void**)&dout, sizeof(uint32_t) * (size_t)capw);
+        if (e == hipSuccess) e = hipMalloc((void**)&dmeta, sizeof(int64_t) * 4);
+        if (e == hipSuccess) e = hipMalloc((void**)&derr, sizeof(int));
+        return e;
+    };
+    const int64_t hmeta[4] = {0, 0, 0, 0};  // [0]: the stream's symbol base, [2]: its word count
+    hipError_t e = alloc_all();
+    if (e == hipSuccess && n) {
+        e = hipMemcpy(dsym, symbols, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(didx, indexes, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice);
+    }
+    if (e == hipSuccess) e = hipMemcpy(dmeta, hmeta, sizeof(hmeta), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemset(derr, 0, sizeof(int));
+    if (e != hipSuccess) {
+        cleanup();
+        return RGBD_EHIP;
+    }
+    rc = launch_rans_wide_encode(dsym, didx, dmeta, segs, lanes, 1, 1, t->ts.d, t->ts.d, dout, capw, dmeta + 2, derr, nullptr);
+    int64_t nw = 0;
+    int herr = 0;
+    if (!rc) {
+        e = hipMemcpy(&nw, dmeta + 2, sizeof(int64_t), hipMemcpyDeviceToHost);
+        if (e == hipSuccess) e = hipMemcpy(&herr, derr, sizeof(int), hipMemcpyDeviceToHost);
+        if (e != hipSuccess) rc = RGBD_EHIP;
+        else if (herr || nw < 0 || nw > capw) rc = RGBD_ENOSPC;
+        else {
+            e = hipMemcpy(out, dout + (capw - nw), (size_t)nw * 4, hipMemcpyDeviceToHost);
+            if (e != hipSuccess) rc = RGBD_EHIP;
+            *out_len = nw * 4;
+        }
+    }
+    cleanup();
+    return rc;
+}
+
+struct rgbd_rans_wide_decoder {
+    uint32_t* words = nullptr;
+    int64_t nwords = 0;
+    int64_t* meta = nullptr;    // [off, len, base]
+    uint64_t* state = nullptr;  // [x_0 ... x_63, pos]
+    int* err = nullptr;
+    int lanes = 0;
+    bool fresh = false;
+};
+
+int rgbd_rans_wide_decoder_create(rgbd_rans_wide_decoder** out)
+{
+    if (!out) return RGBD_EINVAL;
+    std::unique_ptr<rgbd_rans_wide_decoder> d(new rgbd_rans_wide_decoder());
+    HIP_TRY(hipMalloc((void**)&d->meta, sizeof(int64_t) * 4));
+    HIP_TRY(hipMalloc((void**)&d->state, sizeof(uint64_t) * 65));
+    HIP_TRY(hipMalloc((void**)&d->err, sizeof(int)));
+    *out = d.release();
+    return RGBD_OK;
+}
+
+int rgbd_rans_wide_decoder_set_stream(rgbd_rans_wide_decoder* d, const uint8_t* stream, int64_t nbytes, int32_t lanes)
+{
+    std::unique_lock<std::shared_mutex> cap_lk(g_capture_mu);  // frees / synchronous copies: not while a stream captures
+    if (!d || !stream || wide_lanes_log2(lanes) < 0 || nbytes < 8 * (int64_t)lanes || (nbytes & 3)) return RGBD_EINVAL;
+    if (d->words) (void)hipFree(d->words);
+    d->words = nullptr;
+    HIP_TRY(hipMalloc((void**)&d->words, (size_t)nbytes));
+    HIP_TRY(hipMemcpy(d->words, stream, (size_t)nbytes, hipMemcpyHostToDevice));
+    d->nwords = nbytes / 4;
+    d->lanes = lanes;
+    const int64_t hm[4] = {0, d->nwords, 0, 0};
+    HIP_TRY(hipMemcpy(d->meta, hm, sizeof(hm), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemset(d->err, 0, sizeof(int)));
+    d->fresh = true;
+    return RGBD_OK;
+}
+
+int rgbd_rans_wide_decoder_decode(rgbd_rans_wide_decoder* d, const rgbd_tables* t, const int32_t* indexes, int64_t n,
+                                  int32_t* symbols_out)
+{
+    std::unique_lock<std::shared_mutex> cap_lk(g_capture_mu);  // frees / synchronous copies: not while a stream captures
+    if (!d || !d->words || !t || !t->ts.ready || n < 0 || (n && (!indexes || !symbols_out))) return RGBD_EINVAL;
+    if (!n) return RGBD_OK;
+    for (int64_t i = 0; i < n; ++i)
+        if (indexes[i] < 0 || indexes[i] >= t->ts.d.nrows) return RGBD_EINVAL;
+    int32_t *didx = nullptr, *dsym = nullptr;
+    HIP_TRY(hipMalloc((void**)&didx, sizeof(int32_t) * (size_t)n));
+    if (hipMalloc((void**)&dsym, sizeof(int32_t) * (size_t)n) != hipSuccess) {
+        (void)hipFree(didx);
+        return RGBD_EHIP;
+    }
+    int rc = RGBD_OK, herr = 0;
+    if (hipMemcpy(didx, indexes, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice) != hipSuccess) rc = RGBD_EHIP;
+    if (!rc)
+        rc = launch_rans_wide_decode(d->words, d->meta, d->meta + 1, 1, d->lanes, d->state, d->fresh ? 1 : 0, didx, dsym,
+                                     d->meta + 2, 0, n, t->ts.d, d->err, nullptr);
+    if (!rc && hipMemcpy(symbols_out, dsym, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost) != hipSuccess) rc = RGBD_EHIP;
+    if (!rc && hipMemcpy(&herr, d->err, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) rc = RGBD_EHIP;
+    if (!rc) d->fresh = false;
+    if (!rc && herr) rc = RGBD_EINVAL;  // a damaged stream: read past its end, or an escape no encoder writes
+    (void)hipFree(didx);
+    (void)hipFree(dsym);
+    return rc;
+}
+
+void rgbd_rans_wide_decoder_destroy(rgbd_rans_wide_decoder* d)
+{
+    std::unique_lock<std::shared_mutex> cap_lk(g_capture_mu);  // frees / synchronous copies: not while a stream captures
+    if (!d) return;
+    (void)hipFree(d->words);
+    (void)hipFree(d->meta);
+    (void)hipFree(d->state);
+    (void)hipFree(d->err);
+    delete d;
+}
+
+int rgbd_rans_wide_encode_batch_dev(const rgbd_tables* t0, const rgbd_tables* t1, int32_t split, const int32_t* symbols_dev,
+                                    const int32_t* indexes_dev, const int64_t* sym_base_dev, int32_t nstreams, int32_t lanes,
+                                    const int64_t* seg_counts, int32_t nseg, uint32_t* out_dev, int64_t cap_words,
+                                    int64_t* out_words_dev, int32_t* err_dev, void* stream)
+{
+    if (!t0 || !t0->ts.ready || !t1 || !t1->ts.ready || nstreams < 0 || split < 0 || split > nstreams) return RGBD_EINVAL;
+    if (!sym_base_dev || !out_dev || !out_words_dev || !err_dev || wide_lanes_log2(lanes) < 0) return RGBD_EINVAL;
+    if (!seg_counts || nseg < 1 || nseg > WIDE_MAX_SEGS) return RGBD_EINVAL;
+    int64_t n = 0;
+    for (int k = 0; k < nseg; ++k) {
+        if (seg_counts[k] < 0 || seg_counts[k] >= ((int64_t)1 << 40)) return RGBD_EINVAL;
+        n += seg_counts[k];
+    }
+    WideSegs segs;
+    if (const int r = wide_segs(seg_counts, nseg, n, &segs)) return r;
+    if (n && (!symbols_dev || !indexes_dev)) return RGBD_EINVAL;
+    // (a slot smaller than rgbd_rans_wide_max_bytes is the caller's risk: the kernel checks every store and raises *err_dev)
+    if (cap_words < 2 * (int64_t)lanes || cap_words >= ((int64_t)1 << 31)) return RGBD_EINVAL;
+    return launch_rans_wide_encode(symbols_dev, indexes_dev, sym_base_dev, segs, lanes, nstreams, split, t0->ts.d, t1->ts.d, out_dev,
+                                   cap_words, out_words_dev, err_dev, (hipStream_t)stream);
+}
+
+int rgbd_rans_wide_decode_batch_dev(const rgbd_tables* t, const uint32_t* streams_dev, const int64_t* stream_off_words_dev,
+                                    const int64_t* stream_len_words_dev, int32_t nstreams, int32_t lanes, uint64_t* state_dev,
+                                    int32_t init, const int32_t* indexes_dev, int32_t* symbols_dev, const int64_t* sym_base_dev,
+                                    int64_t part_off, int64_t count, int32_t* err_dev, void* stream)
+{
+    if (!t || !t->ts.ready || nstreams < 0 || count < 0 || part_off < 0 || wide_lanes_log2(lanes) < 0) return RGBD_EINVAL;
+    if (!streams_dev || !stream_off_words_dev || !stream_len_words_dev || !state_dev || !indexes_dev || !symbols_dev ||
+        !sym_base_dev || !err_dev)
+        return RGBD_EINVAL;
+    if (!nstreams || !count) return RGBD_OK;
+    return launch_rans_wide_decode(streams_dev, stream_off_words_dev, stream_len_words_dev, nstreams, lanes, state_dev, init ? 1 : 0,
+                                   indexes_dev, symbols_dev, sym_base_dev, part_off, count, t->ts.d, err_dev, (hipStream_t)stream);
+}
+
 // ---- checkerboard quantise / index (ckbd_op above) ----
 
 int rgbd_ckbd_quant_index(const float* y_dev, const float* means_dev, const float* scales_dev, int32_t n, int32_t c, int32_t h,

@@ -399,3 +399,22 @@ int launch_rans_encode(const int32_t* sym, const int32_t* idx, const int64_t* sy
 int launch_rans_decode(const uint32_t* streams, const int64_t* stream_off_words, const int64_t* stream_len_words,
                        int nstreams, uint64_t* state, int init, const int32_t* idx, int32_t* sym,
                        const int64_t* sym_base, int64_t part_off, int64_t count, DevTables t, hipStream_t s);
+
+// Wide rANS (rans_wide.hip): `lanes` interleaved Rans64 states per stream (1, 2, 4 ... 64), one wavefront
+// per stream with one lane per state.  A stream codes a list of segments; rows of `lanes` symbols restart at every segment.
+#define WIDE_MAX_SEGS 32
+struct WideSegs {  // the segment list of an encode launch, by value: a captured graph bakes it with the call shape
+    int n;
+    int64_t count[WIDE_MAX_SEGS];
+};
+int wide_lanes_log2(int lanes);  // -1 unless lanes is a power of two in 1 ... 64
+// All streams code sum(segs.count) symbols starting at sym_base[s]; slot, out_words, err and the table split as in
+// launch_rans_encode (cap_words: any size from 2 * lanes up; an overflow sets *err and writes nothing outside the slot).
+int launch_rans_wide_encode(const int32_t* sym, const int32_t* idx, const int64_t* sym_base, const WideSegs& segs, int lanes,
+                            int nstreams, int split, DevTables t0, DevTables t1, uint32_t* out, int64_t cap_words,
+                            int64_t* out_words, int* err, hipStream_t s);
+// Stateful decode of ONE segment of `count` symbols per stream: state[s * (lanes + 1) ...] = {x_0 ... x_(lanes-1), pos};
+// init=1 loads it from the head of each stream.  A read past a stream's end yields 0 and sets *err.
+int launch_rans_wide_decode(const uint32_t* streams, const int64_t* stream_off_words, const int64_t* stream_len_words,
+                            int nstreams, int lanes, uint64_t* state, int init, const int32_t* idx, int32_t* sym,
+                            const int64_t* sym_base, int64_t part_off, int64_t count, DevTables t, int* err, hipStream_t s);

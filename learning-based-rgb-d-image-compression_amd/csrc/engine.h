@@ -510,6 +510,13 @@ struct rgbd_elic {
     // rgbd_elic_set_debug_floats: the encoder also keeps, per symbol and in stream order, the value it rounded (y - mean)
     // and the scale it indexed -- what the parity bookkeeping compares with the reference's floats at a flipped symbol
     bool debug_floats = false;
+    // rgbd_elic_set_coder: 0 = the reference's stream format, else the lanes of wide rANS for the y streams (rans_wide.hip)
+    int coder_lanes = 0;
+    WideSegs y_segs{};          // the parts of the call in stream order, recorded by code_part while compress runs
+    int64_t y_seg_next = 0;     // where the next part must start (symbols of one stream)
+    bool dec_err_pending = false;  // a wide decompress left its error flag in res_pin's last slot
+    int y_state_words() const { return coder_lanes ? coder_lanes + 1 : 2; }  // 64-bit words of decoder state per y stream
+    int64_t y_cap_words(int64_t n) const { return rgbd_enc_cap_words(n) + (coder_lanes ? 2 * (coder_lanes - 1) : 0); }
     float* dbg_x = nullptr;
     float* dbg_s = nullptr;
 
@@ -1991,7 +1998,8 @@ struct rgbd_elic {
         const uint32_t* words = nullptr;
         const int64_t* stream_off = nullptr;  // device [2][nstreams]
         const int64_t* stream_len = nullptr;
-        uint64_t* state = nullptr;  // device [2][nstreams][2]
+        uint64_t* state = nullptr;  // device [2][nstreams][2] ([lanes + 1] with the wide coder)
+        int* err = nullptr;         // wide coder: the call's error flag
         int nstreams = 0;
         bool first[2] = {true, true};
     };
@@ -2021,13 +2029,28 @@ struct rgbd_elic {
             r = launch_ckbd_encode_part(y_slice.p, y_slice.cs, params.p, params.cs, yhat_slice.p, yhat_slice.cs,
                                         scale_table, g, sym, idx, sb, part_off, s, dbg_x ? dbg_x + mod_off : nullptr,
                                         dbg_s ? dbg_s + mod_off : nullptr);
+            if (!r && coder_lanes && mod == 0) {  // the parts become the wide encoder's segments (the same for every modality)
+                const int64_t count = (int64_t)g.C * g.h * (g.w / 2) * (cd.per_image ? 1 : g.B);
+                const int64_t poff = cd.per_image ? part_off : part_off * g.B;
+                if (poff != y_seg_next) r = RGBD_ESTATE;
+                else if (y_segs.n >= WIDE_MAX_SEGS) r = RGBD_ENOSPC;
+                else {
+                    y_segs.count[y_segs.n++] = count;
+                    y_seg_next += count;
+                }
+            }
             if (!r && cd.force)  // y_hat of this part again, from the forced symbols (symbol + mean, as the decoder forms it)
                 r = launch_ckbd_decode_part(params.p, params.cs, yhat_slice.p, yhat_slice.cs, g, cd.force + mod_off, sb, part_off, s);
         } else {
             r = launch_ckbd_index_part(params.p, params.cs, scale_table, g, idx, sb, part_off, s);
             const int64_t count = (int64_t)g.C * g.h * (g.w / 2) * (cd.per_image ? 1 : g.B);
             const int64_t poff = cd.per_image ? part_off : part_off * g.B;
-            if (!r)
+            if (!r && coder_lanes)
+                r = launch_rans_wide_decode(cd.words, cd.stream_off + (size_t)mod * cd.nstreams,
+                                            cd.stream_len + (size_t)mod * cd.nstreams, cd.nstreams, coder_lanes,
+                                            cd.state + (size_t)mod * cd.nstreams * y_state_words(), cd.first[mod] ? 1 : 0, idx,
+                                            sym, sb, poff, count, tables[mod].d, cd.err, s);
+            else if (!r)
                 r = launch_rans_decode(cd.words, cd.stream_off + (size_t)mod * cd.nstreams,
                                        cd.stream_len + (size_t)mod * cd.nstreams, cd.nstreams,
                                        cd.state + (size_t)mod * cd.nstreams * 2, cd.first[mod] ? 1 : 0, idx, sym, sb, poff,
@@ -2863,13 +2886,15 @@ struct rgbd_elic {
         int* err = nullptr;
         int ny = 0;  // y streams per modality
         int64_t ycap = 0, zcap = 0;
+        int64_t ycount = 0;  // symbols of one y stream
     };
     int enc_streams(int nm, int B, int64_t T, int64_t Tz, int per_image, EncBufs* e);
     int fetch_streams(int nm, int B, bool with_z, const EncBufs& e);
     // workspace of a decompress call with its streams uploaded
     struct DecBufs {
         uint32_t* words = nullptr;  // [y rgb | y depth | z rgb | z depth] slots of the size the encoder may produce
-        uint64_t *state = nullptr, *zstate = nullptr;      // rANS states [nm][ns_y][2] / [nm][ns_z][2]
+        uint64_t *state = nullptr, *zstate = nullptr;      // rANS states [nm][ns_y][2 (wide coder: lanes + 1)] / [nm][ns_z][2]
+        int* err = nullptr;                                // wide coder only: the decoder's error flag
         int32_t *sym = nullptr, *idx = nullptr;            // [nm][B*T]
         int32_t *zsym = nullptr, *zidx = nullptr;          // [nm][B*Tz]
         const int64_t *yoff = nullptr, *ylen = nullptr;    // [nm][ns_y], in words
@@ -2884,7 +2909,7 @@ struct rgbd_elic {
     int finish_body();                                     // body_end(), behind an error recorded inside the body
     int upload_forced(int nm, const std::vector<int32_t>* f, size_t n, int32_t** out);
     static Coding enc_coding(const EncBufs& e, int per_image, int64_t T, const int32_t* force);
-    static Coding dec_coding(const DecBufs& d, int per_image, int64_t T, int nstreams);
+    Coding dec_coding(const DecBufs& d, int per_image, int64_t T, int nstreams);
     // the z stage of modality m; pfx = "", "rgb_" or "depth_"
     void z_encode(int m, const char* pfx, const EncBufs& e, const Act& z, const Act& zhat, const int32_t* fz);
     void z_decode(int m, const char* pfx, const DecBufs& d, const Act& zhat);

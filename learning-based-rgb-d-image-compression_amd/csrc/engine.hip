@@ -39,7 +39,8 @@ int rgbd_elic::enc_streams(int nm, int B, int64_t T, int64_t Tz, int per_image, 
     const int64_t ycount = per_image ? T : T * B;
     const size_t nmeta = (size_t)(8 + 3 * nm) * B + 64;
     e->ny = ny;
-    e->ycap = rgbd_enc_cap_words(ycount);
+    e->ycap = y_cap_words(ycount);
+    e->ycount = ycount;
     e->zcap = rgbd_enc_cap_words(Tz);
     e->meta = (int64_t*)arena.take(sizeof(int64_t) * nmeta);
     e->sym = (int32_t*)arena.take(sizeof(int32_t) * (size_t)(nm * B * T));
@@ -120,15 +121,17 @@ int rgbd_elic::fetch_streams(int nm, int B, bool with_z, const EncBufs& e)
 int rgbd_elic::dec_streams(int nm, const uint8_t* const* ys[2], const int64_t* ylen[2], int ns_y, const uint8_t* const* zs[2],
                            const int64_t* zlen[2], int ns_z, int B, int64_t T, int64_t Tz, int per_image, DecBufs* d)
 {
-    const int64_t ycap = rgbd_enc_cap_words(per_image ? T : T * B), zcap = rgbd_enc_cap_words(Tz);
+    const int64_t ycap = y_cap_words(per_image ? T : T * B), zcap = rgbd_enc_cap_words(Tz);
+    const int64_t ymin = coder_lanes ? 8 * (int64_t)coder_lanes : 8;  // a stream holds at least its states
     // meta64: y off[nm][ns_y], y len[nm][ns_y], z off[nm][ns_z], z len[nm][ns_z], y base[B], z base[B]
     const size_t o_ylen = (size_t)nm * ns_y, o_zoff = 2 * o_ylen, o_zlen = o_zoff + (size_t)nm * ns_z;
     const size_t o_ybase = o_zlen + (size_t)nm * ns_z, nmeta = o_ybase + (size_t)2 * B;
     int64_t* meta64 = (int64_t*)arena.take(sizeof(int64_t) * nmeta);
     const size_t nwords_cap = (size_t)nm * ns_y * ycap + (size_t)nm * ns_z * zcap;
     d->words = (uint32_t*)arena.take(sizeof(uint32_t) * (nwords_cap + 4));
-    d->state = (uint64_t*)arena.take(sizeof(uint64_t) * (size_t)(2 * nm * (ns_y + ns_z)));
-    d->zstate = d->state + (size_t)2 * nm * ns_y;
+    d->state = (uint64_t*)arena.take(sizeof(uint64_t) * ((size_t)y_state_words() * nm * ns_y + (size_t)2 * nm * ns_z));
+    d->zstate = d->state + (size_t)y_state_words() * nm * ns_y;
+    d->err = coder_lanes ? (int*)arena.take(256) : nullptr;
     d->sym = (int32_t*)arena.take(sizeof(int32_t) * (size_t)(nm * B * T));
     d->idx = (int32_t*)arena.take(sizeof(int32_t) * (size_t)(nm * B * T));
     d->zsym = (int32_t*)arena.take(sizeof(int32_t) * (size_t)(nm * B * Tz));
@@ -149,7 +152,7 @@ int rgbd_elic::dec_streams(int nm, const uint8_t* const* ys[2], const int64_t* y
     }
     for (int m = 0; m < nm; ++m) {
         for (int i = 0; i < ns_y; ++i)
-            if (!ys[m] || !ys[m][i] || ylen[m][i] < 8 || (ylen[m][i] & 3) || ylen[m][i] / 4 > ycap) return RGBD_EINVAL;
+            if (!ys[m] || !ys[m][i] || ylen[m][i] < ymin || (ylen[m][i] & 3) || ylen[m][i] / 4 > ycap) return RGBD_EINVAL;
         for (int i = 0; i < ns_z; ++i)
             if (!zs[m] || !zs[m][i] || zlen[m][i] < 8 || (zlen[m][i] & 3) || zlen[m][i] / 4 > zcap) return RGBD_EINVAL;
     }
@@ -198,6 +201,8 @@ void rgbd_elic::begin_call(int ref_batch_of_call, bool forward)
     pre_leads.clear();
     arena.reset();
     rc = 0;
+    y_segs.n = 0;
+    y_seg_next = 0;
     if (forward) {
         dbg_sym = dbg_idx = nullptr;  // forward() keeps no symbols: the last compress()'s are gone with its workspace layout
         dbg_x = dbg_s = nullptr;
@@ -254,6 +259,7 @@ rgbd_elic::Coding rgbd_elic::dec_coding(const DecBufs& d, int per_image, int64_t
     cd.stream_off = d.yoff;
     cd.stream_len = d.ylen;
     cd.state = d.state;
+    cd.err = d.err;
     cd.nstreams = nstreams;
     return cd;
 }
@@ -315,6 +321,14 @@ void rgbd_elic::y_encode(int nm, int B, const EncBufs& e)
 {
     if (dry() || rc) return;
     const int ny = e.ny, ns = nm * ny;
+    if (coder_lanes) {  // wide rANS: the parts code_part recorded are the segments; they must tile the stream
+        int r = y_segs.n > 0 && y_seg_next == e.ycount ? RGBD_OK : RGBD_ESTATE;
+        if (!r)
+            r = launch_rans_wide_encode(e.sym, e.idx, e.meta + 8 * B, y_segs, coder_lanes, ns, ny, tables[0].d, tables[nm - 1].d,
+                                        e.ywords, e.ycap, e.meta + 8 * B + 2 * ns, e.err, s);
+        if (r) fail(r);
+        return;
+    }
     const int r = launch_rans_encode(e.sym, e.idx, e.meta + 8 * B, e.meta + 8 * B + ns, ns, ny, tables[0].d, tables[nm - 1].d,
                                      e.ywords, e.ycap, e.meta + 8 * B + 2 * ns, e.err, s);
     if (r) fail(r);
@@ -719,6 +733,10 @@ int rgbd_elic::run_decompress(int nm, const uint8_t* const* ys[2], const int64_t
     Act out[2];  // what the epilogue hands back: x_hat (or y_hat for decompress_united) per modality: cur_ge->out[m]
     Act mid[3];  // return_mid (one modality): cur_ge->out[1], [3], [5]
     if (body_begin()) {
+        if (d.err && !dry()) {  // wide coder: the decoder's error flag
+            const int zr = launch_fill_zero((float*)d.err, 64, s);
+            if (zr) fail(zr);
+        }
         Act zhat[2], yhat[2];
         if (!lat) {
             for (int m = 0; m < nm; ++m) zhat[m] = alloc(B, zh, zw, N);
@@ -751,5 +769,12 @@ int rgbd_elic::run_decompress(int nm, const uint8_t* const* ys[2], const int64_t
         r = lat ? launch_nhwc_to_nchw_clamp(out[m].p, B, M, h, w, out[m].cs, lat->yhat[m], 0, s, perm())
                 : launch_nhwc_to_nchw_clamp(out[m].p, B, mo.img_ch[m], H, W, out[m].cs, xhat_dev[m], mo.clamp, s);
     if (!r && up) r = mids_out(mid, B, H, W, *up);
+    if (!r && d.err) {  // the caller's wait (run_call) reads the flag: a damaged wide stream fails the call
+        if (!res_pin) HIP_TRY(hipHostMalloc((void**)&res_pin, kResPinBytes, hipHostMallocDefault));
+        int64_t* slot = res_pin + kResPinBytes / sizeof(int64_t) - 1;
+        *slot = 0;
+        HIP_TRY(hipMemcpyAsync(slot, d.err, sizeof(int), hipMemcpyDeviceToHost, s));
+        dec_err_pending = true;
+    }
     return r;
 }

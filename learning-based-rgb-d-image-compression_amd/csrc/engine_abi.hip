@@ -123,6 +123,10 @@ int run_call(rgbd_elic* m, void* stream, const std::string& key, Tail tail, Body
     if (const int ur = m->use_stream(stream)) return ur;
     int r = run_sized(m, key, body);
     if (tail.wait && !r) r = m->wait_stream();
+    if (m->dec_err_pending) {  // a wide-coder decompress: its error flag arrived with the wait
+        m->dec_err_pending = false;
+        if (tail.wait && !r && m->res_pin[rgbd_elic::kResPinBytes / sizeof(int64_t) - 1]) r = RGBD_EINVAL;
+    }
     if (m->profile && (tail.profile == Tail::kAlways || (tail.profile == Tail::kOnSuccess && !r))) m->profile_collect();
     return r;
 }
@@ -890,6 +894,24 @@ int rgbd_elic_set_debug_floats(rgbd_elic* m, int32_t on)
     if (!m) return RGBD_EINVAL;
     if (m->debug_floats != (on != 0)) m->graphs_invalidate();  // the workspace layout changes
     m->debug_floats = on != 0;
+    return RGBD_OK;
+}
+
+// The y streams' format: 0 = the reference's (default), 1 = wide rANS with `lanes` interleaved states (rans_wide.hip).  Like the
+// other switches it takes the capture lock and drops the cached graphs (the workspace layout and the launch list change); inside
+// a running call of the engine it is refused with RGBD_ESTATE.
+int rgbd_elic_set_coder(rgbd_elic* m, int32_t format, int32_t lanes)
+{
+    std::unique_lock<std::shared_mutex> cap_lk(g_capture_mu);
+    if (!m || format < 0 || format > 1) return RGBD_EINVAL;
+    if (format == 1 && wide_lanes_log2(lanes) < 0) return RGBD_EINVAL;
+    // the checkerboard slice loop of ELIC_united and ELIC is the wide coder's producer; the other families keep the reference
+    // format and say so here, before anything is launched
+    if (format == 1 && m->family != Family::ELIC_united && m->family != Family::ELIC) return RGBD_EINVAL;
+    if (m->body_mode || m->dec_err_pending) return RGBD_ESTATE;  // a call of this engine is running
+    const int want = format ? lanes : 0;
+    if (m->coder_lanes != want) m->graphs_invalidate();
+    m->coder_lanes = want;
     return RGBD_OK;
 }
 

@@ -47,13 +47,13 @@ class SingleCodec(Codec):
         x = x.to(self._device, torch.float32).contiguous()
         check(lib().rgbd_elic_compress_single(self._h, self._ptr(x), B, H, W, 1 if self.per_image_streams else 0,
                                               self._stream_ptr()), "compress")
-        return {"strings": [self._fetch_streams(0, 0), self._fetch_streams(0, 1)], "shape": torch.Size((H // 64, W // 64))}
+        return {"strings": [self._tag_y(self._fetch_streams(0, 0)), self._fetch_streams(0, 1)], "shape": torch.Size((H // 64, W // 64))}
 
     def decompress(self, strings, shape):  # models/elic.py:255-325
         self._ready()
         torch.cuda.current_stream().synchronize()
         t0 = time.process_time()
-        ys, zs = list(strings[0]), list(strings[1])
+        ys, zs = self._untag_y(strings[0]), list(strings[1])
         B = len(zs)
         if len(ys) not in (1, B):
             raise ValueError("Invalid strings parameters")

@@ -279,7 +279,7 @@ class ELIC_united(Codec):
         L = lib()
         check(L.rgbd_elic_compress(self._h, self._ptr(rgb), self._ptr(depth), B, H, W,
                                    1 if self.per_image_streams else 0, self._stream_ptr()), "compress")
-        out = [[self._fetch_streams(mod, kind) for kind in (0, 1)] for mod in (0, 1)]
+        out = [[self._tag_y(self._fetch_streams(mod, 0)), self._fetch_streams(mod, 1)] for mod in (0, 1)]
         return {"r_strings": out[0], "d_strings": out[1], "shape": torch.Size((H // 64, W // 64))}
 
     # ---- the Bi-CEE stage alone (models/elic_united.py:350-401, 543-578) ------------------------------------
@@ -306,7 +306,7 @@ class ELIC_united(Codec):
         p = self._ptr
         check(lib().rgbd_elic_compress_united(self._h, p(t[0]), p(t[1]), p(t[2]), p(t[3]), B, h, w,
                                               1 if self.per_image_streams else 0, self._stream_ptr()), "compress_united")
-        return self._fetch_streams(0, 0), self._fetch_streams(1, 0)
+        return self._tag_y(self._fetch_streams(0, 0)), self._tag_y(self._fetch_streams(1, 0))
 
     def decompress_united(self, rgb_y_strings, rgb_hyper_params, depth_y_strings, depth_hyper_params):
         """(y strings, hyper parameters) per modality -> (rgb_y_hat, depth_y_hat).  A string argument may be one bytes
@@ -316,6 +316,7 @@ class ELIC_united(Codec):
         self._check_latents(None, depth_hyper_params, "depth")
         y_r = [rgb_y_strings] if isinstance(rgb_y_strings, (bytes, bytearray)) else list(rgb_y_strings)
         y_d = [depth_y_strings] if isinstance(depth_y_strings, (bytes, bytearray)) else list(depth_y_strings)
+        y_r, y_d = self._untag_y(y_r), self._untag_y(y_d)
         hr = rgb_hyper_params.to(self._device, torch.float32).contiguous()
         hd = depth_hyper_params.to(self._device, torch.float32).contiguous()
         B, _, h, w = hr.shape
@@ -340,6 +341,7 @@ class ELIC_united(Codec):
         t0 = time.process_time()
         y_r, z_r = list(rgb_strings[0]), list(rgb_strings[1])
         y_d, z_d = list(depth_strings[0]), list(depth_strings[1])
+        y_r, y_d = self._untag_y(y_r), self._untag_y(y_d)
         B = len(z_r)
         if len(z_d) != B or len(y_r) != len(y_d) or len(y_r) not in (1, B):
             raise ValueError("Invalid strings parameters")

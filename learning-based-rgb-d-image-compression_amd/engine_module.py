@@ -1,5 +1,5 @@
 """`EngineModule`: what every Python class over a librgbd_amd.so engine handle shares -- the checkpoint on the host, the handle
-and its device, uploads, and shared-weight clones.  Nothing here knows about entropy coding.
+and its device, uploads, and shared-weight clones.  Of entropy coding it knows one thing, the stream-format switch of the codecs (`set_coder`).
 
     EngineModule                      handle lifecycle
     ├── Spatial_aligner               aligner.py
@@ -35,6 +35,8 @@ class EngineModule:
         self._dirty = True
         self._gen = 0        # bumped by every upload of weights / tables to the GPU
         self._parent = None  # set on shared-weight clones (clone_shared)
+        self._coder = ("reference", 64)  # set_coder(): the format of the y streams
+        self._coder_applied = None       # what the current handle was last told
 
     # ---- per-class hooks ---------------------------------------------------------------------------------
     def _synth_args(self):
@@ -143,6 +145,7 @@ class EngineModule:
         h = ctypes.c_void_p()
         check(lib().rgbd_elic_clone_shared(parent._h, ctypes.byref(h)), "clone_shared")
         self._h = h
+        self._coder_applied = None  # (a fresh handle starts in the reference format)
         self._gen = parent._gen
         self._params = parent._params
 
@@ -161,6 +164,68 @@ class EngineModule:
         elif self._dirty:
             self._upload()
         torch.cuda.set_device(self._device)
+        self._apply_coder()
+
+    # ---- stream format of the y strings ------------------------------------------------------------------
+    WIDE_TAG = b"RW\x01"  # + bytes([lanes]): the head of every y string of a "wide" engine
+
+    @property
+    def coder(self):
+        return self.__dict__.get("_coder", ("reference", 64))[0]
+
+    @property
+    def coder_lanes(self):
+        return self.__dict__.get("_coder", ("reference", 64))[1]
+
+    def set_coder(self, coder="reference", lanes=64):
+        """The format of the y strings compress() returns and decompress() expects: "reference" (default; CompressAI's
+        streams byte for byte) or "wide" -- `lanes` (1, 2, 4 ... 64) interleaved rANS states coded by one GPU lane each, for
+        callers who want a short single call and do not need CompressAI-compatible streams.  A wide y string starts with the
+        tag b"RW\x01" + bytes([lanes]) and is 4 + 8 * (lanes - 1) bytes longer; the z strings do not change.  Models whose
+        engine has no wide path (STF, STF_united, ELIC_united_R2D, the checkerboard Cheng2020) refuse "wide" here."""
+        if coder not in ("reference", "wide"):
+            raise ValueError(f"coder must be 'reference' or 'wide', got {coder!r}")
+        if coder == "wide" and lanes not in (1, 2, 4, 8, 16, 32, 64):
+            raise ValueError(f"lanes must be a power of two in 1 ... 64, got {lanes!r}")
+        old = self.__dict__.get("_coder", ("reference", 64))
+        self._coder = (coder, int(lanes) if coder == "wide" else 64)
+        if self._h is not None:
+            try:
+                self._apply_coder()
+            except RgbdError:
+                self._coder = old
+                raise
+        return self
+
+    def _apply_coder(self):
+        want = self.__dict__.get("_coder", ("reference", 64))
+        if self._h is None or self.__dict__.get("_coder_applied") == want:
+            return
+        if want[0] == "reference" and self.__dict__.get("_coder_applied") is None:
+            self._coder_applied = want  # a fresh handle is in the reference format already
+            return
+        check(lib().rgbd_elic_set_coder(self._h, 1 if want[0] == "wide" else 0, want[1]), f"set_coder({want[0]!r})")
+        self._coder_applied = want
+
+    def _tag_y(self, strings):
+        """y strings as compress() hands them out."""
+        if self.coder != "wide":
+            return strings
+        tag = self.WIDE_TAG + bytes([self.coder_lanes])
+        return [tag + s for s in strings]
+
+    def _untag_y(self, strings):
+        """y strings as the engine takes them; checked on the host, before anything is launched."""
+        if self.coder != "wide":
+            return list(strings)
+        strings = [bytes(s) for s in strings]
+        tag = self.WIDE_TAG + bytes([self.coder_lanes])
+        for s in strings:
+            if s[:3] != self.WIDE_TAG:
+                raise ValueError("coder is 'wide' but a y string has no wide-rANS tag (a reference-format stream?)")
+            if s[:4] != tag:
+                raise ValueError(f"y string was coded with {s[3]} lanes, this engine is set to {self.coder_lanes}")
+        return [s[4:] for s in strings]
 
     def clone_shared(self):
         """Another engine instance on the same GPU that borrows this one's device weights and tables (own workspace and
