@@ -333,8 +333,8 @@ int rgbd_elic_set_scale_table(rgbd_elic* m, const float* table, int32_t n);
 int rgbd_elic_finalize(rgbd_elic* m);
 /* What finalize takes a state-dict entry for, decided by the family, the name and the shape alone (test hook; host only, no
  * GPU needed).  family: 0 ELIC_united, 1 ELIC, 2 STF_united, 3 ELIC_united_R2D, 4 STF, 5 checkerboard Cheng2020,
- * 6 Spatial_aligner, 7 LocalContext, 8 LinearGlobalInterContext, 9 LinearGlobalIntraContext.  Returns one of the kinds below,
- * or RGBD_EINVAL for another family, a NULL pointer, ndim outside 1..4 or an extent < 1. */
+ * 6 Spatial_aligner, 7 LocalContext, 8 LinearGlobalInterContext, 9 LinearGlobalIntraContext, 13 SynthesisTransformPlus (10 to 12
+ * are reserved).  Returns one of the kinds below, or RGBD_EINVAL for another family, a NULL pointer, ndim outside 1..4 or an extent < 1. */
 enum {
     RGBD_KIND_IGNORED = 0,         /* read by no packer of its own: biases, betas, bottleneck matrices, buffers */
     RGBD_KIND_RECOVERY_DECONV = 1, /* Spatial_aligner.recovery, a 2x2 stride-2 deconv: packed as a 1x1 conv + pixel shuffle */
@@ -438,6 +438,22 @@ int rgbd_elic_forward_single_mid(rgbd_elic* m, const float* x_dev, int32_t B, in
 int rgbd_aligner_create(int32_t in_ch, int32_t out_ch, rgbd_elic** out);
 int rgbd_aligner_forward(rgbd_elic* m, const float* x_dev, const float* guided_dev, int32_t B, int32_t H, int32_t W,
                          float* out_dev, void* stream);
+/* SynthesisTransformPlus alone (modules/transform/synthesis.py:74-110; the g_s of ELIC_master, models/elic_master.py): the 15
+ * g_s stages of the single-modal ELIC, with x replaced by Spatial_aligner(x, up_k) behind each of the first three transposed
+ * convolutions (stages 1, 5, 10: in front of the bottlenecks of 2, 7, 11 and of the AttentionBlock of 6).  up1..up3 are what
+ * rgbd_elic_decompress_single_mid hands back for the aux image.  A handle of the aligner's kind (set_tensor, finalize,
+ * clone_shared, destroy; no tables; family 13 of rgbd_debug_tensor_kind) under the reference's names: synthesis_transform.K.*
+ * and sp1|sp2|sp3.* (Linear weights as [out][in][1][1]).  N must be 192 (the reference builds sp1..sp3 with 192 channels whatever
+ * N is); out_ch is `ch`: 1 ... 1024.  yhat [B,M,h,w], up1 [B,N,2h,2w], up2 [B,N,4h,4w], up3 [B,N,8h,8w] -> out
+ * [B,out_ch,16h,16w] (not clamped), NCHW fp32; h % 4 == 0, w % 4 == 0.  Single-chain float arithmetic, weights in plain channel
+ * order.  A bad argument, a handle of another family, the codec calls, rgbd_aligner_forward and rgbd_elic_set_coder(m, 1, .)
+ * on this handle return RGBD_EINVAL before any launch. */
+int rgbd_synthesis_plus_create(int32_t N, int32_t M, int32_t out_ch, rgbd_elic** out);
+int rgbd_synthesis_plus_forward(rgbd_elic* m, const float* yhat_dev, const float* up1_dev, const float* up2_dev,
+                                const float* up3_dev, int32_t B, int32_t h, int32_t w, float* out_dev, void* stream);
+/* Timing aid for the call above: on = 0 runs the walk without the three aligners (the guides are converted and not read),
+ * 1 (default) the module.  RGBD_EINVAL on a handle of another family. */
+int rgbd_debug_synthesis_plus_guides(rgbd_elic* m, int32_t on);
 /* The three attention contexts of MLIC++ alone (modules/transform/context.py; MLICPlusPlus builds them with slice_ch 32,
  * config/config.py:15-18).  Handles of the aligner's kind: set_tensor under the reference's state-dict names (Linear weights
  * as [out][in][1][1], depthwise weights as [C][1][3][3]), finalize, clone_shared, destroy; no tables; the codec calls on such

@@ -21,7 +21,7 @@ from .ckbd import Cheng2020AnchorwithCheckerboard  # noqa: F401,E402
 modelZoo = {"ELIC_united_R2D": ELIC_united_R2D, "ELIC_united": ELIC_united, "ELIC": ELIC,
             "STF_united": SymmetricalTransFormerUnited, "STF": SymmetricalTransFormer, "ckbd": Cheng2020AnchorwithCheckerboard}
 elic_united.modelZoo = modelZoo  # (`from rgbd_amd.elic_united import modelZoo`, the name's first home, is this dict)
-from .aligner import Spatial_aligner  # noqa: F401,E402
+from .aligner import Spatial_aligner, SynthesisTransformPlus  # noqa: F401,E402
 from .mlic_context import LinearGlobalInterContext, LinearGlobalIntraContext, LocalContext  # noqa: F401,E402
 from .pool import CodecPool  # noqa: F401,E402
 from . import datautils, ioutils, metrics, tester  # noqa: F401,E402

@@ -197,6 +197,9 @@ def lib():
                                                           c_vp, c_vp]),
         "rgbd_aligner_create": (ctypes.c_int, [c_i32, c_i32, ctypes.POINTER(c_vp)]),
         "rgbd_aligner_forward": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp]),
+        "rgbd_synthesis_plus_create": (ctypes.c_int, [c_i32, c_i32, c_i32, ctypes.POINTER(c_vp)]),
+        "rgbd_synthesis_plus_forward": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp]),
+        "rgbd_debug_synthesis_plus_guides": (ctypes.c_int, [c_vp, c_i32]),
         "rgbd_guided_window_attention": (ctypes.c_int, [c_vp, c_i32, c_vp, c_i32] + [c_i32] * 6 + [c_vp, c_vp, c_i32, c_vp]),
         "rgbd_local_context_create": (ctypes.c_int, [c_i32, ctypes.POINTER(c_vp)]),
         "rgbd_local_context_forward": (ctypes.c_int, [c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp]),
@@ -277,7 +280,8 @@ EXPORTS = ["rgbd_abi_version", "rgbd_set_blocking_sync", "rgbd_get_blocking_sync
            "rgbd_pooled_conv3x3", "rgbd_conv3x3_thin_in", "rgbd_conv3x3_thin_out", "rgbd_debug_tensor_kind",
            "rgbd_rans_wide_max_bytes", "rgbd_rans_wide_encode", "rgbd_rans_wide_decoder_create", "rgbd_rans_wide_decoder_set_stream",
            "rgbd_rans_wide_decoder_decode", "rgbd_rans_wide_decoder_destroy", "rgbd_rans_wide_encode_batch_dev",
-           "rgbd_rans_wide_decode_batch_dev", "rgbd_elic_set_coder"]
+           "rgbd_rans_wide_decode_batch_dev", "rgbd_elic_set_coder", "rgbd_synthesis_plus_create", "rgbd_synthesis_plus_forward",
+           "rgbd_debug_synthesis_plus_guides"]
 
 
 _BS_HOLDERS = 0

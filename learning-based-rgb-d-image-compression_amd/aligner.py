@@ -14,7 +14,7 @@ norm2,mlp.{fc1,fc2}}, recovery); the index buffer is accepted and ignored.  No C
 import torch
 
 from ._lib import check, lib
-from .arch import spatial_aligner_entries
+from .arch import spatial_aligner_entries, synthesis_plus_entries
 from .engine_module import EngineModule
 
 
@@ -44,6 +44,55 @@ class Spatial_aligner(EngineModule):
         out = torch.empty((B, self.out_channel, H, W), dtype=torch.float32, device=self._device)
         check(lib().rgbd_aligner_forward(self._h, self._ptr(x), self._ptr(guided), B, H, W, self._ptr(out), self._stream_ptr()),
               "aligner_forward")
+        return out
+
+    __call__ = forward
+
+
+class SynthesisTransformPlus(EngineModule):
+    """The guided synthesis transform of ELIC_master (modules/transform/synthesis.py:74-110): the 15 g_s stages of ELIC with
+    x replaced by Spatial_aligner(x, up_k) behind each of the first three transposed convolutions.
+
+        gs = SynthesisTransformPlus(N=192, M=320, ch=3)
+        gs.load_state_dict(state_dict); gs = gs.to("cuda")
+        x_hat = gs(y_hat, up1, up2, up3)   # [B,M,h,w], [B,N,2h,2w], [B,N,4h,4w], [B,N,8h,8w] -> [B,ch,16h,16w]
+
+    up1..up3 are what ELIC(return_mid=True) returns for the aux image; tensors that already live on the module's device are
+    read in place.  h and w are multiples of 4.  State-dict names are the reference's (synthesis_transform.K.*, sp1|sp2|sp3.*);
+    N is 192, the width the reference builds sp1..sp3 with whatever N is.  Float arithmetic (single chain); no CPU path."""
+    _MODEL = "SynthesisTransformPlus"
+
+    def __init__(self, N, M, ch=3, act=None, init_seed=0):
+        if not (act is None or act is torch.nn.ReLU or isinstance(act, torch.nn.ReLU)):
+            raise NotImplementedError("SynthesisTransformPlus on MI355X fuses ReLU into its convolutions: act must be nn.ReLU")
+        self.N, self.M, self.ch = int(N), int(M), int(ch)
+        if self.N != 192:
+            raise ValueError("N must be 192: sp1..sp3 are Spatial_aligner() with 192 channels (synthesis.py:94-96)")
+        super().__init__(synthesis_plus_entries(self.N, self.M, self.ch), init_seed)
+
+    def _synth_args(self):
+        return {"N": self.N, "M": self.M, "channel": self.ch}
+
+    def _create_engine(self):
+        return self._create("rgbd_synthesis_plus_create", self.N, self.M, self.ch)
+
+    def forward(self, x, up1, up2, up3):  # synthesis.py:98-110
+        self._ready()
+        if x.dim() != 4 or x.size(1) != self.M:
+            raise ValueError(f"expected x of shape [B,{self.M},h,w]")
+        B, _, h, w = x.shape
+        if h % 4 or w % 4:
+            raise ValueError("h and w must be multiples of 4 (the aligner behind up1 works on 8x8 blocks of the 2h x 2w map)")
+        ups = []
+        for k, u in enumerate((up1, up2, up3)):
+            want = (B, self.N, (2 * h) << k, (2 * w) << k)
+            if tuple(u.shape) != want:
+                raise ValueError(f"expected up{k + 1} of shape {list(want)}, got {list(u.shape)}")
+            ups.append(u.to(self._device, torch.float32).contiguous())
+        x = x.to(self._device, torch.float32).contiguous()
+        out = torch.empty((B, self.ch, 16 * h, 16 * w), dtype=torch.float32, device=self._device)
+        check(lib().rgbd_synthesis_plus_forward(self._h, self._ptr(x), self._ptr(ups[0]), self._ptr(ups[1]), self._ptr(ups[2]),
+                                                B, h, w, self._ptr(out), self._stream_ptr()), "synthesis_plus_forward")
         return out
 
     __call__ = forward

@@ -556,6 +556,21 @@ def spatial_aligner_entries(in_ch: int = 192, out_ch: int = 192, prefix: str = "
     return b.entries
 
 
+def synthesis_plus_entries(N: int = 192, M: int = 320, ch: int = 3) -> "OrderedDict[str, Entry]":
+    """Every state_dict entry of SynthesisTransformPlus (reference: modules/transform/synthesis.py:74-96), in the reference's
+    order: the g_s rows of elic_entries under `synthesis_transform.` (the last transposed convolution to `ch` channels), then
+    sp1, sp2, sp3 -- Spatial_aligner() with its default 192 channels whatever N is, so only N = 192 gives a module that runs."""
+    cfg = model_config()
+    cfg["N"], cfg["M"] = int(N), int(M)
+    p = "g_s.synthesis_transform."
+    rows = [(name, e) for name, e in elic_entries(cfg, channel=int(ch)).items() if name.startswith(p)]
+    rows.sort(key=lambda r: int(r[0][len(p):].split(".")[0]))  # (stable: stage by stage, each stage in its own order)
+    out: "OrderedDict[str, Entry]" = OrderedDict((name[len("g_s."):], e) for name, e in rows)
+    for k in (1, 2, 3):
+        out.update(spatial_aligner_entries(prefix=f"sp{k}"))
+    return out
+
+
 def local_context_entries(dim: int = 32, window_size: int = 5, mlp_ratio: float = 2.0, num_heads: int = 2,
                           qkv_bias: bool = True) -> "OrderedDict[str, Entry]":
     """Every state_dict entry of MLIC++'s LocalContext (reference: modules/transform/context.py:33-56), in the reference's

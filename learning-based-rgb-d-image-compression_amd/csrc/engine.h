@@ -417,8 +417,9 @@ inline int small_conv_set_kblocks(SmallConvArgs* a, const int* lens, int n, int 
 }  // namespace rgbd_rt
 using namespace rgbd_rt;
 
-// What an engine handle is: a codec (0-5) or one module alone (6-9: no codec calls, no tables, its own forward entry point).
-// DESIGN.md and the history name the families by these numbers, so the numbers stay.
+// What an engine handle is: a codec (0-5) or one module alone (6-9, 13: no codec calls, no tables, its own forward entry point).
+// DESIGN.md and the history name the families by these numbers, so the numbers stay; 10-12 are reserved for the held-back
+// modules of ELIC_master and refused everywhere: the table has holes, not a renumbering.
 enum class Family : int {
     ELIC_united = 0,      // RGB + depth (models/elic_united.py)
     ELIC = 1,             // single-modal ELIC (models/elic.py)
@@ -430,8 +431,9 @@ enum class Family : int {
     LocalContext = 7,     // the contexts of MLIC++ (modules/transform/context.py): rgbd_local_context_forward /
     LinearGlobalInterContext = 8,  // rgbd_linear_inter_forward /
     LinearGlobalIntraContext = 9,  // rgbd_linear_intra_forward only
+    SynthesisTransformPlus = 13,   // modules/transform/synthesis.py:74-110: rgbd_synthesis_plus_forward only
 };
-constexpr int kFamilies = 10;
+constexpr int kFamilies = 14;
 
 struct FamilyRow {
     const char* name;
@@ -458,8 +460,12 @@ constexpr FamilyRow kFamilyTable[kFamilies] = {
     {"LocalContext",                0, false, false, 0, false, true},
     {"LinearGlobalInterContext",    0, false, false, 0, false, true},
     {"LinearGlobalIntraContext",    0, false, false, 0, false, true},
+    {nullptr,                       0, false, false, 0, false, false},  // 10-12: reserved
+    {nullptr,                       0, false, false, 0, false, false},
+    {nullptr,                       0, false, false, 0, false, false},
+    {"SynthesisTransformPlus",      0, false, false, 0, false, false},
 };
-constexpr bool family_ok(int f) { return f >= 0 && f < kFamilies; }
+constexpr bool family_ok(int f) { return f >= 0 && f < kFamilies && kFamilyTable[f].name; }
 constexpr const FamilyRow& family_row(Family f) { return kFamilyTable[(int)f]; }
 
 struct rgbd_elic {
@@ -468,7 +474,8 @@ struct rgbd_elic {
     Family family = Family::ELIC_united;
     const FamilyRow& row() const { return family_row(family); }
     bool single() const { return row().nm == 1; }
-    int in_ch = 3;    // image channels of the single-modal codecs (Spatial_aligner: channels of x and guided; contexts: dim)
+    int in_ch = 3;    // image channels of the single-modal codecs (Spatial_aligner: channels of x and guided; contexts: dim;
+                      // SynthesisTransformPlus: M)
     int out_ch = 0;   // module handles: output channels
     int ctx_heads = 0;  // contexts: num_heads
     // what the call paths (engine.hip) need to know about one versus two modalities; arrays are read at [0, nm)
@@ -1732,6 +1739,9 @@ struct rgbd_elic {
         bool leads;    // an "rb" stage hands the next block's .branch.0 to its fused tail (next_lead)
         const Act* mids = nullptr;  // kSyn15 with return_mid: buffers the outputs of stages 1, 5 and 10 (up1..up3,
                                     // synthesis.py:54-67) are copied into
+        const Act* guides = nullptr;  // kSyn15 of SynthesisTransformPlus (synthesis.py:98-110): up1..up3 of the aux decoder; the
+                                      // output of stages 1, 5 and 10 is replaced by spatial_aligner(sp_prefix + "spK", x, guides[K-1])
+        const char* sp_prefix = "";   // name prefix of sp1, sp2, sp3
     };
     static constexpr const char* kAna18[18] = {"conv", "rb", "rb", "rb", "spf", "conv", "rb", "rb", "rb",
                                                "attn", "spf", "conv", "rb", "rb", "rb", "spf", "conv", "attn"};
@@ -1786,6 +1796,10 @@ struct rgbd_elic {
             }
             for (int m = 0; m < nm; ++m) x[m] = dsts[m] ? cat[m] : o[m];
             if (sd.mids && (i == 1 || i == 5 || i == 10)) copy_ch(x[0], sd.mids[i == 1 ? 0 : (i == 5 ? 1 : 2)]);
+            if (sd.guides && (i == 1 || i == 5 || i == 10)) {  // in front of the bottlenecks of 2, 7, 11 and the attention of 6
+                const int k = i == 1 ? 0 : (i == 5 ? 1 : 2);
+                x[0] = spatial_aligner(std::string(sd.sp_prefix) + "sp" + std::to_string(k + 1), x[0], sd.guides[k]);
+            }
         }
         if (sd.ends) ends_finish(ends);
         for (int m = 0; m < nm; ++m) out[m] = x[m];
@@ -2952,6 +2966,9 @@ struct rgbd_elic {
     void mids_begin(int B, int H, int W, Act mid[3]);  // workspace of up1..up3; g_s1 fills it while mid_dst points at it
     int mids_out(const Act mid[3], int B, int H, int W, const Mid3& up);
     int run_aligner(const float* x_dev, const float* guided_dev, int B, int H, int W, float* out_dev);
+    // SynthesisTransformPlus: yhat [B,M,h,w], up[k] [B,N,2h << k,2w << k] -> out [B,out_ch,16h,16w]
+    bool plus_guides = true;  // rgbd_debug_synthesis_plus_guides(m, 0): the same walk without the three aligners (a timing aid)
+    int run_synthesis_plus(const float* yhat_dev, const float* const up_dev[3], int B, int h, int w, float* out_dev);
     // the contexts: x1 (and, LinearGlobalIntraContext, x2) [B,in_ch,H,W] -> out [B,out_ch,H,W]
     int run_context(const float* x1_dev, const float* x2_dev, int B, int H, int W, float* out_dev);
     int ensure_arena(size_t bytes);

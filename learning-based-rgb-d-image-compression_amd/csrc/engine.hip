@@ -666,6 +666,37 @@ int rgbd_elic::run_aligner(const float* x_dev, const float* guided_dev, int B, i
     return r;
 }
 
+// SynthesisTransformPlus alone (family 13; synthesis.py:74-110): the 15 g_s stages of the single-modal ELIC with
+// Spatial_aligner(x, up_k) in place of x behind the first three transposed convolutions.  in_ch is M.
+int rgbd_elic::run_synthesis_plus(const float* yhat_dev, const float* const up_dev[3], int B, int h, int w, float* out_dev)
+{
+    begin_call(B, true);
+    const Act yhat = alloc(B, h, w, in_ch);
+    Act up[3];
+    for (int k = 0; k < 3; ++k) up[k] = alloc(B, (2 * h) << k, (2 * w) << k, N);
+    if (!dry()) {
+        int r = launch_nchw_to_nhwc16(yhat_dev, B, in_ch, h, w, yhat.p, yhat.cs, s);
+        for (int k = 0; k < 3 && !r; ++k) r = launch_nchw_to_nhwc16(up_dev[k], B, N, up[k].h, up[k].w, up[k].p, up[k].cs, s);
+        if (r) return r;
+    }
+    // ==== body: captured into / replayed from a HIP graph per call shape ====
+    Act out;
+    if (body_begin()) {
+        Act xhat[2];
+        stages({kSyn15, 15, 1, {"synthesis_transform.", ""}, kNoFusion, false, false, false, nullptr, plus_guides ? up : nullptr, ""},
+               &yhat, xhat);
+        out = xhat[0];
+        if (cur_ge && !dry()) cur_ge->out[0] = out;
+    } else {
+        out = cur_ge->out[0];
+    }
+    if (const int r = finish_body()) return r;
+    if (dry()) return RGBD_OK;
+    int r = launch_nhwc_to_nchw_clamp(out.p, B, out_ch, 16 * h, 16 * w, out.cs, out_dev, 0, s);
+    if (!r) r = wait_stream();
+    return r;
+}
+
 // An attention context of MLIC++ alone (families 7-9): x1 (and x2 of LinearGlobalIntraContext) [B,in_ch,H,W] -> [B,out_ch,H,W]
 int rgbd_elic::run_context(const float* x1_dev, const float* x2_dev, int B, int H, int W, float* out_dev)
 {

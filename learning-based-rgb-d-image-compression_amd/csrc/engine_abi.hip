@@ -158,6 +158,11 @@ int tensor_kind(Family f, const std::string& name, const int64_t* shape, int ndi
             for (const char* suf : {"_transform.1.weight", "_transform.6.weight", "_transform.12.weight", "_transform.17.weight",
                                     "_transform.5.weight", "_transform.10.weight", "_transform.14.weight"})
                 transposed = transposed || ends_with(name, suf);
+        // SynthesisTransformPlus names its stages without a "g_s." in front: the four bare "<stage>.weight" are its deconvs
+        if (f == Family::SynthesisTransformPlus)
+            for (const char* full : {"synthesis_transform.1.weight", "synthesis_transform.5.weight", "synthesis_transform.10.weight",
+                                     "synthesis_transform.14.weight"})
+                transposed = transposed || name == full;
         return transposed ? RGBD_KIND_CONV_TRANSPOSED : RGBD_KIND_CONV;
     }
     if (ends_with(name, ".gamma") && ndim == 2 && shape[0] == shape[1]) return RGBD_KIND_GDN_GAMMA;
@@ -437,6 +442,15 @@ int rgbd_aligner_create(int32_t in_ch, int32_t out_ch, rgbd_elic** out)
     return module_new(Family::Spatial_aligner, in_ch, out_ch, 0, out);
 }
 
+// SynthesisTransformPlus alone (modules/transform/synthesis.py:74-110).  Its sp1..sp3 are Spatial_aligner() with the default
+// 192 channels whatever N is (:94-96), so N is 192; out_ch is the `ch` of the last transposed convolution
+int rgbd_synthesis_plus_create(int32_t N, int32_t M, int32_t out_ch, rgbd_elic** out)
+{
+    if (!out || N != 192 || M < 16 || M > 1024 || M % 16 || out_ch < 1 || out_ch > 1024) return RGBD_EINVAL;
+    const int32_t slice = M;
+    return engine_new(Family::SynthesisTransformPlus, N, M, &slice, 1, M, out_ch, 0, out);
+}
+
 // The attention contexts of MLIC++ alone (modules/transform/context.py)
 int rgbd_local_context_create(int32_t dim, rgbd_elic** out)
 {
@@ -543,6 +557,29 @@ int rgbd_aligner_forward(rgbd_elic* m, const float* x_dev, const float* guided_d
     if (!x_dev || !guided_dev || !out_dev || B <= 0 || H <= 0 || W <= 0 || H % 8 || W % 8) return RGBD_EINVAL;
     return run_call(m, stream, call_key("al|%d|%d|%d", B, H, W), kForwardTail,
                     [&]() { return m->run_aligner(x_dev, guided_dev, B, H, W, out_dev); });
+}
+
+int rgbd_synthesis_plus_forward(rgbd_elic* m, const float* yhat_dev, const float* up1_dev, const float* up2_dev,
+                                const float* up3_dev, int32_t B, int32_t h, int32_t w, float* out_dev, void* stream)
+{
+    if (const int r = module_ready(m, Family::SynthesisTransformPlus)) return r;
+    // the aligner behind up1 needs multiples of 8 at 2h x 2w; the output has B * out_ch * 256 h w elements
+    if (!yhat_dev || !up1_dev || !up2_dev || !up3_dev || !out_dev || B <= 0 || h <= 0 || w <= 0 || h % 4 || w % 4 ||
+        (int64_t)B * std::max(m->out_ch, m->N) * 256 * h * w > 0x7fffffff)
+        return RGBD_EINVAL;
+    const float* const up[3] = {up1_dev, up2_dev, up3_dev};
+    return run_call(m, stream, call_key("sp|%d|%d|%d|%d", B, h, w, m->plus_guides ? 1 : 0), kForwardTail,
+                    [&]() { return m->run_synthesis_plus(yhat_dev, up, B, h, w, out_dev); });
+}
+
+// A timing aid (tools/synplus_probe.py): 0 = the walk of a SynthesisTransformPlus handle without its three aligners (what
+// SynthesisTransformEX computes from the same weights), 1 = the module.  A call shape of its own in the graph cache.
+int rgbd_debug_synthesis_plus_guides(rgbd_elic* m, int32_t on)
+{
+    if (!m || m->family != Family::SynthesisTransformPlus) return RGBD_EINVAL;
+    if (m->body_mode) return RGBD_ESTATE;  // a call of this engine is running
+    m->plus_guides = on != 0;
+    return RGBD_OK;
 }
 
 static int context_forward(rgbd_elic* m, Family f, const float* x1_dev, const float* x2_dev, int32_t B, int32_t H, int32_t W,

@@ -3,6 +3,7 @@ and its device, uploads, and shared-weight clones.  Of entropy coding it knows o
 
     EngineModule                      handle lifecycle
     ├── Spatial_aligner               aligner.py
+    ├── SynthesisTransformPlus        aligner.py
     ├── LocalContext, LinearGlobalIntraContext, LinearGlobalInterContext    mlic_context.py
     └── Codec                         elic_united.py: entropy-table holders, streams, debug / profile hooks
         ├── ELIC_united               elic_united.py (ELIC_united_R2D, SymmetricalTransFormerUnited under it)

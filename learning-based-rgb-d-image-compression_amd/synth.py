@@ -14,7 +14,7 @@ from collections import OrderedDict
 import numpy as np
 
 from .arch import (STF_SLICES, Entry, channel_aligner_entries, feature_decoder_entries, feature_encoder_entries, linear_global_inter_entries, linear_global_intra_entries, local_context_entries,
-                   spatial_aligner_entries, ckbd_config, ckbd_entries, elic_entries, elic_united_entries, elic_united_r2d_entries, model_config, stf_config,
+                   spatial_aligner_entries, synthesis_plus_entries, ckbd_config, ckbd_entries, elic_entries, elic_united_entries, elic_united_r2d_entries, model_config, stf_config,
                    stf_entries, stf_single_config, stf_united_entries)
 
 _IH_STD = math.sqrt(4.0 * (65536.0**2 - 1.0) / 12.0)  # std of the sum of four uniform 16-bit ints
@@ -121,7 +121,8 @@ def make_tensor(name: str, e: Entry, seed: int) -> np.ndarray:
 
 def synthetic_state_dict(seed: int = 0, config=None, stress: bool = True, as_torch: bool = True,
                          model: str = "ELIC_united", channel: int = 3, recipe: str = None, N: int = 192,
-                         in_channel: int = 192, out_channel: int = 192, dim: int = 32, out_dim: int = 64, num_heads: int = 2):
+                         in_channel: int = 192, out_channel: int = 192, dim: int = 32, out_dim: int = 64, num_heads: int = 2,
+                         M: int = 320):
     """Full state_dict (parameters + buffers) of ELIC_united (default), ELIC_united_R2D, STF_united, the single-modal STF
     (model="STF": recipes "stress" and "plain"), the checkerboard Cheng2020 model (model="ckbd", width N, the same two recipes)
     or the single-modal ELIC with deterministic synthetic values.  `recipe`: "stress" (= stress=True, the default: ~22 bpp, wide CDF rows, 17 % escapes -- the worst
@@ -134,7 +135,8 @@ def synthetic_state_dict(seed: int = 0, config=None, stress: bool = True, as_tor
     "LinearGlobalInterContext" (dim, out_dim): an attention context of MLIC++ alone, always with _apply_stress_context.
     model="Channel_aligner": the block alone (the reference's constant widths), always with _apply_stress_chalign.
     model="Feature_encoder" (in_channel) or "Feature_decoder" (in_channel, out_channel): a feature network of ELIC_master alone,
-    always with _apply_stress_feature."""
+    always with _apply_stress_feature.  model="SynthesisTransformPlus" (N, M, channel = its `ch`): the guided synthesis transform
+    alone, always with _apply_stress_synplus."""
     if model in ("Feature_encoder", "Feature_decoder"):
         entries = feature_encoder_entries(in_channel) if model == "Feature_encoder" else feature_decoder_entries(in_channel, out_channel)
         sd = OrderedDict((name, make_tensor(name, e, seed)) for name, e in entries.items())
@@ -157,6 +159,15 @@ def synthetic_state_dict(seed: int = 0, config=None, stress: bool = True, as_tor
                    linear_global_intra_entries(dim) if model == "LinearGlobalIntraContext" else linear_global_inter_entries(dim, out_dim))
         sd = OrderedDict((name, make_tensor(name, e, seed)) for name, e in entries.items())
         _apply_stress_context(sd, seed)
+        if as_torch:
+            import torch
+
+            return OrderedDict((k, torch.from_numpy(np.ascontiguousarray(v))) for k, v in sd.items())
+        return sd
+    if model == "SynthesisTransformPlus":
+        entries = synthesis_plus_entries(N, M, channel)
+        sd = OrderedDict((name, make_tensor(name, e, seed)) for name, e in entries.items())
+        _apply_stress_synplus(sd, seed)
         if as_torch:
             import torch
 
@@ -223,13 +234,13 @@ STF_Y_GAIN = 12.0
 ALIGNER_QK_GAIN = 3.5
 
 
-def _apply_stress_aligner(sd, seed):
+def _apply_stress_aligner(sd, seed, prefix=""):
     """Spatial_aligner: what makes a wrong attention visible.  Relative position biases of order 1 (std 1), LayerNorm weights
     in [0.5, 1.5], and the query and key projections scaled so that the scores (std ~0.3 with the default initialisation on
     normalised tokens) reach |S| >= 10: a softmax that is far from uniform, so shift, mask, bias and the q / k / v roles
-    all move the output."""
+    all move the output.  prefix: "" or the block's name inside a model with its dot ("sp1.")."""
     for k in range(2):
-        p = f"blocks.{k}"
+        p = f"{prefix}blocks.{k}"
         sd[f"{p}.attn.relative_position_bias_table"] = (sd[f"{p}.attn.relative_position_bias_table"] / np.float32(0.3)).astype(np.float32)
         for n in ("norm1", "norm2"):
             name = f"{p}.{n}.weight"
@@ -240,6 +251,25 @@ def _apply_stress_aligner(sd, seed):
         E = sd[f"{p}.attn.qkv1.weight"].shape[0]
         sd[f"{p}.attn.qkv2.weight"][:E] *= g  # the key half; the value half keeps its scale
         sd[f"{p}.attn.qkv2.bias"][:E] *= g
+
+
+SYNPLUS_DECONV_GAIN = math.sqrt(12.0)
+SYNPLUS_RECOVERY_GAIN = 8.0
+
+
+def _apply_stress_synplus(sd, seed):
+    """SynthesisTransformPlus: the single-modal g_s recipe (which leaves g_s at its default initialisation) plus
+    _apply_stress_aligner on sp1, sp2 and sp3, and two gains that keep the signal alive through three replacements.  A 5x5
+    stride-2 transposed convolution at the default initialisation (variance 1 / (3 * 25 cout), 25 / 4 taps of cin channels per
+    output) shrinks a map by sqrt(12): its weights are scaled back by that.  A Spatial_aligner returns about a tenth of its
+    input's scale (recovery: 96 terms of variance 1 / (3 * 4 * 192)), so that behind the second one the biases of the patch
+    embeddings would outweigh x and an aligner in the wrong place, or fed the wrong x, would barely move the output: the
+    recovery weights are scaled by 8."""
+    for i in (1, 5, 10, 14):
+        sd[f"synthesis_transform.{i}.weight"] = sd[f"synthesis_transform.{i}.weight"] * np.float32(SYNPLUS_DECONV_GAIN)
+    for k in (1, 2, 3):
+        _apply_stress_aligner(sd, seed, prefix=f"sp{k}.")
+        sd[f"sp{k}.recovery.weight"] = sd[f"sp{k}.recovery.weight"] * np.float32(SYNPLUS_RECOVERY_GAIN)
 
 
 LOCAL_QK_GAIN = 3.5
