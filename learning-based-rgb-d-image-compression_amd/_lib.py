@@ -4,13 +4,16 @@ There is no CPU fallback: if the library is missing or a HIP call fails, the ope
 """
 import ctypes
 import os
+import re
 import subprocess
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _SO = os.path.join(_HERE, "librgbd_amd.so")
 _SO = os.environ.get("RGBD_AMD_LIB", _SO)  # A/B builds: point at another librgbd_amd.so
-_SRCS = ["conv_mfma.hip", "conv_mfma_blk.hip", "pointwise.hip", "swin.hip", "entropy.hip", "rans_wide.hip", "metrics.hip", "coder_abi.hip", "gdn.hip", "context_attn.hip", "pooled_head.hip", "thin_conv.hip", "engine.hip", "engine_abi.hip", "hooks_abi.hip"]
+_SRCS = ["conv_mfma.hip", "conv_mfma_blk.hip", "pointwise.hip", "swin.hip", "entropy.hip", "rans_wide.hip", "metrics.hip", "coder_abi.hip", "gdn.hip", "context_attn.hip", "pooled_head.hip", "thin_conv.hip", "engine_pack.hip", "engine_graph.hip", "engine_conv.hip", "engine_elic.hip", "engine_swin.hip",
+         "engine_ckbd.hip", "engine.hip", "engine_abi.hip", "hooks_abi.hip"]
 _LIB = None
+_INCLUDE = re.compile(r'^[ \t]*#[ \t]*include[ \t]+"([^"]+)"', re.M)  # (indented too: conv_mfma.hip includes its tile tables inside an initializer)
 
 ERRORS = {-22: "invalid argument", -12: "out of memory", -5: "HIP runtime error", -28: "buffer too small",
           -1: "wrong call order / missing weights or tables"}
@@ -42,6 +45,20 @@ class ConvFormsDesc(ctypes.Structure):
                [("set", ConvFormsOps * 2)]
 
 
+def source_deps(src: str) -> list:
+    """`src` and every file it pulls in with `#include "..."`, transitively; an include is resolved relative to the file that
+    names it (what the compiler tries first, and the only form the sources use for the project's own headers)."""
+    seen, todo = [], [os.path.normpath(src)]
+    while todo:
+        f = todo.pop()
+        if f in seen:
+            continue
+        seen.append(f)
+        with open(f, errors="replace") as fh:
+            todo += [os.path.normpath(os.path.join(os.path.dirname(f), inc)) for inc in _INCLUDE.findall(fh.read())]
+    return seen
+
+
 def build(force: bool = False, verbose: bool = False) -> str:
     """Compile the HIP sources for gfx950 into librgbd_amd.so (in-tree, next to this file): one object per source
     (only stale ones are recompiled, up to four at a time), then one link."""
@@ -49,23 +66,13 @@ def build(force: bool = False, verbose: bool = False) -> str:
 
     csrc = os.path.join(_HERE, "csrc")
     objdir = os.path.join(csrc, "build")
-    hdrs = [os.path.join(csrc, "common.h"), os.path.join(csrc, "exact_math.h"),
-            os.path.join(os.path.dirname(_HERE), "include", "rgbd_amd.h")]
-    body, tiles = os.path.join(csrc, "conv_mfma_body.h"), os.path.join(csrc, "conv_tiles.h")
-    extra = {"conv_mfma.hip": [body, tiles, os.path.join(csrc, "tile_table.h"), os.path.join(csrc, "tile_table_loaded.h"),
-                               os.path.join(csrc, "tile_table_blk.h"), os.path.join(csrc, "tile_table_blk_loaded.h")],
-             "conv_mfma_blk.hip": [body, tiles]}
-    hdrs.append(os.path.join(csrc, "splitk_table.h"))
-    extra["coder_abi.hip"] = extra["gdn.hip"] = [os.path.join(csrc, "engine_internal.h")]
-    extra["engine.hip"] = extra["engine_abi.hip"] = extra["hooks_abi.hip"] = [os.path.join(csrc, "engine_internal.h"), os.path.join(csrc, "engine.h"),
-                                                     os.path.join(csrc, "conv_args.h")]
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     os.makedirs(objdir, exist_ok=True)
     jobs, objs = [], []
     for name in _SRCS:
         src, obj = os.path.join(csrc, name), os.path.join(objdir, name + ".o")
         objs.append(obj)
-        deps = [src] + hdrs + extra.get(name, [])
+        deps = source_deps(src)
         if force or not os.path.exists(obj) or any(os.path.getmtime(obj) < os.path.getmtime(d) for d in deps):
             # (conv_mfma_blk.hip: MFMA results in VGPRs -- its kernels read them with vector instructions in the main loop)
             flags = ["-mllvm", "-amdgpu-mfma-vgpr-form"] if name == "conv_mfma_blk.hip" else []

@@ -1,9 +1,9 @@
 // The one place where the fields of a ConvArgs (common.h) are decided.  Plain host functions: no engine state, no HIP call,
-// no allocation.  The engine's planner (engine.h: conv_plan / plan_refnum / conv_issue / deconv_s2_ref_run) and the stand-alone
+// no allocation.  The engine's planner (engine_conv.hip: conv_plan / plan_refnum / conv_issue; engine.h: deconv_s2_ref_run) and the stand-alone
 // entry points of the C ABI (hooks_abi.hip: rgbd_conv2d_nchw, rgbd_conv2d_ref_nchw, rgbd_conv_forms_nchw, rgbd_conv_bench) all
 // build their launches from these pieces, so a test of one of them tests the rules of all.  What stays with a caller is
 // policy -- which layer, which split factor, which scratch -- never how a decision becomes fields.
-// A new ConvArgs field needs: the helper here that sets it, a term in rgbd_elic::pairable (engine.h) and, for a pointer with a
+// A new ConvArgs field needs: the helper here that sets it, a term in rgbd_elic::pairable (engine_conv.hip) and, for a pointer with a
 // twin in ConvPtrs, a line in conv_args_group1 and in conv_groups_ok (conv_mfma.hip).
 #pragma once
 #include <algorithm>

@@ -1,5 +1,6 @@
-// Host runtime of the gfx950 codec engine, part 2 of 4: the call paths -- compress(), decompress() and the eval forward, once
-// for every family of one or two modalities -- as sequences of kernel launches through the layer graph of engine.h
+// Host runtime of the gfx950 codec engine: the call paths -- compress(), decompress() and the eval forward, once
+// for every family of one or two modalities -- as sequences of kernel launches through the layer graphs that engine.h declares
+// and engine_elic.hip, engine_swin.hip and engine_ckbd.hip define; the four `*_family` hooks choose among them
 // (prologue: workspace of the call and stream geometry; body: captured into / replayed from a HIP graph; epilogue: fetch
 // the finished streams).  Mirrors the call structure of the reference's models/elic_united.py:350-578 but keeps every
 // tensor, symbol, index and bitstream resident in HBM; the only device->host traffic is the finished streams.

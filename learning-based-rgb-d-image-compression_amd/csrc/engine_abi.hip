@@ -1,6 +1,6 @@
-// Host runtime of the gfx950 codec engine, part 3 of 4: the engine's side of the C ABI of include/rgbd_amd.h -- the wait
+// Host runtime of the gfx950 codec engine: the engine's side of the C ABI of include/rgbd_amd.h -- the wait
 // policy, engine life cycle (create / finalize / clone / destroy), the codec and module entry points and the per-engine
-// debug readers.  The operator-level entry points, test hooks and debug switches live in hooks_abi.hip (part 4), the coder's
+// debug readers.  The operator-level entry points, test hooks and debug switches live in hooks_abi.hip, the coder's
 // stand-alone entry points in coder_abi.hip.
 #include "engine.h"
 

@@ -1,5 +1,6 @@
-// Shared between the translation units of the host runtime (engine.h / engine.hip / engine_abi.hip / hooks_abi.hip: the codec; coder_abi.hip: the stand-alone coder and
-// checkerboard operators of the C ABI).  Not part of the ABI.
+// Shared between the translation units of the host runtime (engine.h and the engine*.hip files that define what it declares,
+// engine_abi.hip, hooks_abi.hip: the codec; coder_abi.hip: the stand-alone coder and checkerboard operators of the C ABI;
+// gdn.hip: the GDN packers).  Not part of the ABI.
 #pragma once
 #include <algorithm>
 #include <memory>

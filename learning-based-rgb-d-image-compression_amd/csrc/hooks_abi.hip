@@ -1,4 +1,4 @@
-// Host runtime of the gfx950 codec engine, part 4 of 4: the C ABI of include/rgbd_amd.h outside the engine's life cycle --
+// Host runtime of the gfx950 codec engine: the C ABI of include/rgbd_amd.h outside the engine's life cycle --
 // the operator-level entry points (conv2d, pointwise ops), the test hooks that put one launcher behind an operator boundary,
 // the process-wide debug switches and the conv benchmark.  None of this is on the codec path.
 #include "engine.h"

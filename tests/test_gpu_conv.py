@@ -126,7 +126,7 @@ def test_split_k_matches_and_is_deterministic(split):
 @pytest.mark.parametrize("split", [0, 4])
 @pytest.mark.parametrize("k,cin,cout,h,w", [(5, 224, 128, 16, 16), (5, 48, 32, 16, 24), (1, 96, 64, 32, 40), (3, 64, 96, 8, 12)])
 def test_conv_checkerboard_output(k, cin, cout, h, w, split):
-    """ConvArgs::ckbd (entropy-parameter nets, engine.hip entropy_params): only one checkerboard half of the output is
+    """ConvArgs::ckbd (entropy-parameter nets, engine_elic.hip entropy_params): only one checkerboard half of the output is
     computed; those values are bit-identical to the full convolution, the other half is left alone (reads 0 here)."""
     dev = require_gpu()
     from rgbd_amd._lib import check, lib

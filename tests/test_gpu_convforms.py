@@ -14,7 +14,7 @@ tests/convforms_cases.py.
   * the forced tiles of test_gpu_conv.py::test_tile_choice_never_changes_a_bit, a second run and batch[1:2] alone change no bit;
   * what the launchers refuse comes back as -22 from the host check, with nothing launched.
 
-Placements are restricted to the ones the engine makes (csrc/engine.h):
+Placements are restricted to the ones the engine makes (csrc/engine_conv.hip, engine_elic.hip, engine_swin.hip):
   Engine::conv_plan        "a channel slice narrower than its 16-padded width inside a wider buffer (STF_united: 24 of 48): stop at
                            the slice end; a buffer of its own gets its pad channels zeroed as usual"
                            a.cout_store = (pcy->cout % 16 && y.cs != round_up(pcy->cout, 16)) ? round_up(pcy->cout, 4) : pcy->cout_pad;

@@ -27,6 +27,48 @@ def test_library_exports_every_declared_symbol():
     assert declared == set(_lib.EXPORTS)
 
 
+def test_build_sources_and_scanned_header_dependencies():
+    """_lib.build() compiles _SRCS and takes an object for stale when a file of _lib.source_deps(source) is newer: every source
+    of csrc/ must be listed, and the scan must find what the hand-written map it replaced knew.
+
+    That map gave every source common.h, exact_math.h, include/rgbd_amd.h and splitk_table.h, and some sources more.  It is
+    restated below; a source's scan has to hold all of its entries except one of the first kind whose name stands in no
+    #include line of any file the scan did reach (searched as plain text here, not with the scanner's pattern): the old map gave
+    exact_math.h and the public header to sources that include neither, directly or indirectly."""
+    from rgbd_amd import _lib
+
+    csrc = os.path.join(os.path.dirname(_lib.__file__), "csrc")
+    on_disk = sorted(f for f in os.listdir(csrc) if f.endswith(".hip"))
+    assert on_disk == sorted(_lib._SRCS) and len(set(_lib._SRCS)) == len(_lib._SRCS)
+    public = os.path.normpath(os.path.join(csrc, "..", "..", "include", "rgbd_amd.h"))
+    h = lambda *names: {os.path.join(csrc, n) for n in names}  # noqa: E731
+    scan = {name: set(_lib.source_deps(os.path.join(csrc, name))) for name in _lib._SRCS}
+    for name, deps in scan.items():
+        assert os.path.join(csrc, name) in deps and all(os.path.isfile(d) for d in deps), name
+
+    assert scan["conv_mfma.hip"] >= h("tile_table.h", "tile_table_loaded.h", "tile_table_blk.h", "tile_table_blk_loaded.h",
+                                      "conv_mfma_body.h", "conv_tiles.h", "common.h")
+    engine = [n for n in _lib._SRCS if n.startswith("engine")] + ["hooks_abi.hip"]
+    assert len(engine) == 9
+    for name in engine:
+        assert scan[name] >= h("engine.h", "engine_internal.h", "conv_args.h", "common.h") | {public}, name
+    for name in ("coder_abi.hip", "gdn.hip"):
+        assert scan[name] >= h("engine_internal.h"), name
+
+    blanket = h("common.h", "exact_math.h", "splitk_table.h") | {public}
+    body_tiles = h("conv_mfma_body.h", "conv_tiles.h")
+    extra = {"conv_mfma.hip": body_tiles | h("tile_table.h", "tile_table_loaded.h", "tile_table_blk.h", "tile_table_blk_loaded.h"),
+             "conv_mfma_blk.hip": body_tiles, "coder_abi.hip": h("engine_internal.h"), "gdn.hip": h("engine_internal.h")}
+    for name in ("engine.hip", "engine_abi.hip", "hooks_abi.hip"):
+        extra[name] = h("engine_internal.h", "engine.h", "conv_args.h")
+    for name, deps in scan.items():
+        assert deps >= extra.get(name, set()), name
+        assert deps >= h("common.h", "splitk_table.h"), name
+        include_lines = [ln for d in deps for ln in open(d, errors="replace").read().splitlines() if "include" in ln]
+        for lost in blanket - deps:
+            assert not any(os.path.basename(lost) in ln and ln.lstrip().startswith("#") for ln in include_lines), (name, lost)
+
+
 def test_abi_argument_errors_without_gpu():
     from rgbd_amd._lib import lib
 
