@@ -333,8 +333,9 @@ int rgbd_elic_set_scale_table(rgbd_elic* m, const float* table, int32_t n);
 int rgbd_elic_finalize(rgbd_elic* m);
 /* What finalize takes a state-dict entry for, decided by the family, the name and the shape alone (test hook; host only, no
  * GPU needed).  family: 0 ELIC_united, 1 ELIC, 2 STF_united, 3 ELIC_united_R2D, 4 STF, 5 checkerboard Cheng2020,
- * 6 Spatial_aligner, 7 LocalContext, 8 LinearGlobalInterContext, 9 LinearGlobalIntraContext, 13 SynthesisTransformPlus (10 to 12
- * are reserved).  Returns one of the kinds below, or RGBD_EINVAL for another family, a NULL pointer, ndim outside 1..4 or an extent < 1. */
+ * 6 Spatial_aligner, 7 LocalContext, 8 LinearGlobalInterContext, 9 LinearGlobalIntraContext, 13 SynthesisTransformPlus,
+ * 15 EntropyParametersMLIC, 16 ChannelContext, 17 LatentResidualPrediction (10 to 12 are reserved, 14 is unused).  Returns one of
+ * the kinds below, or RGBD_EINVAL for another family, a NULL pointer, ndim outside 1..4 or an extent < 1. */
 enum {
     RGBD_KIND_IGNORED = 0,         /* read by no packer of its own: biases, betas, bottleneck matrices, buffers */
     RGBD_KIND_RECOVERY_DECONV = 1, /* Spatial_aligner.recovery, a 2x2 stride-2 deconv: packed as a 1x1 conv + pixel shuffle */
@@ -344,7 +345,8 @@ enum {
     RGBD_KIND_GDN_GAMMA = 5,       /* square .gamma, packed with its .beta */
     RGBD_KIND_LINEAR = 6,          /* 2-D .weight (SE_Block) */
     RGBD_KIND_ARRAY = 7,           /* LayerNorm parameters and relative position tables: plain device arrays */
-    RGBD_KIND_QUANTILES = 8        /* entropy_bottleneck.quantiles: medians and the cumulative's parameters */
+    RGBD_KIND_QUANTILES = 8,       /* entropy_bottleneck.quantiles: medians and the cumulative's parameters */
+    RGBD_KIND_PIXEL_MLP = 9        /* fusion.K.weight of EntropyParametersMLIC: as RGBD_KIND_CONV, and as the lane fragments of rgbd_pixel_mlp4 */
 };
 int rgbd_debug_tensor_kind(int32_t family, const char* name, const int64_t* shape, int32_t ndim);
 
@@ -473,6 +475,48 @@ int rgbd_linear_inter_forward(rgbd_elic* m, const float* x1_dev, int32_t B, int3
 int rgbd_linear_intra_create(int32_t dim, int32_t heads, rgbd_elic** out);
 int rgbd_linear_intra_forward(rgbd_elic* m, const float* x1_dev, const float* x2_dev, int32_t B, int32_t H, int32_t W,
                               float* out_dev, void* stream);
+/* The three networks MLIC++ runs inside its slice loop, alone (MLICPlusPlus builds them per 32-channel slice, models/mlicpp.py).
+ * Handles of the contexts' kind: set_tensor under the reference's state-dict names, finalize, clone_shared, destroy; no tables;
+ * the codec calls and rgbd_elic_set_coder(m, 1, .) on such a handle, and a forward call on a handle of another family, return
+ * RGBD_EINVAL.  All tensors NCHW fp32 on the device.
+ * rgbd_entropy_params_mlic_*: EntropyParametersMLIC(in_dim, out_dim) (modules/transform/entropy.py:31-53): four 1x1
+ *   convolutions in_dim -> 320 -> 256 -> 128 -> out_dim with nn.GELU() (erf form) between them, names fusion.{0,2,4,6}.  in_dim
+ *   16 ... 960, out_dim 16 ... 128, multiples of 16.  The input is the concatenation of n_seg (1 ... 6) tensors
+ *   [B,seg_channels[i],H,W], each a multiple of 16 channels wide and summing to in_dim, which is never formed (the codec's
+ *   torch.cat([...], dim=1)): a layout pass per tensor, then one rgbd_pixel_mlp4 launch.  parity -1: out [B,out_dim,H,W] is
+ *   written; 0 / 1: only its anchor ((row + col) odd) / other pixels are, the rest keeps its values (W even).
+ *   rgbd_entropy_params_mlic_set_fused(m, 0) runs the same layers as four launches of the conv kernels over the written-out
+ *   concatenation instead (the yardstick; default 1); it drops the cached graphs.
+ * rgbd_channel_context_*: ChannelContext(in_dim, out_dim) (modules/transform/context.py:140-160): three 3x3 convolutions
+ *   in_dim -> 192 -> 128 -> 4 out_dim, GELU between them, names fushion.{0,2,4} (the reference's spelling).
+ *   x [B,in_dim,H,W] -> out [B,4 out_dim,H,W].
+ * rgbd_lrp_*: LatentResidualPrediction(in_dim, out_dim) (modules/transform/LRP.py:9-26): four 3x3 convolutions of widths
+ *   in - d / 4, in - d / 2, in - 3 d / 4, out (d = |out - in|, integer division), GELU between them, then 0.5 * tanh; names
+ *   lrp_transform.{0,2,4,6}.  Widths that are no multiples of 16 are padded with zero weights.  x [B,in_dim,H,W] -> out
+ *   [B,out_dim,H,W].
+ * The two 3x3 modules refuse H < 2 or W < 2 with RGBD_EINVAL before any launch. */
+int rgbd_entropy_params_mlic_create(int32_t in_dim, int32_t out_dim, rgbd_elic** out);
+int rgbd_entropy_params_mlic_forward(rgbd_elic* m, const float* const* seg_dev, const int32_t* seg_channels, int32_t n_seg, int32_t B,
+                                     int32_t H, int32_t W, int32_t parity, float* out_dev, void* stream);
+int rgbd_entropy_params_mlic_set_fused(rgbd_elic* m, int32_t on);
+int rgbd_channel_context_create(int32_t in_dim, int32_t out_dim, rgbd_elic** out);
+int rgbd_channel_context_forward(rgbd_elic* m, const float* x_dev, int32_t B, int32_t H, int32_t W, float* out_dev, void* stream);
+int rgbd_lrp_create(int32_t in_dim, int32_t out_dim, rgbd_elic** out);
+int rgbd_lrp_forward(rgbd_elic* m, const float* x_dev, int32_t B, int32_t H, int32_t W, float* out_dev, void* stream);
+/* The 1x1 stack of EntropyParametersMLIC as ONE launch on NHWC device tensors (csrc/pixel_mlp.hip; replaces the four
+ * nn.Conv2d / three nn.GELU calls of entropy.py:35-41 and the torch.cat in front of them): a workgroup stages 16 pixels of the
+ * input in LDS, the three intermediates stay there, only weights stream.  seg_dev[i]: [B][H][W][seg_stride[i]], of which the
+ * first seg_channels[i] channels are read; n_seg 1 ... 6; every channel count a multiple of 16, their sum 16 ... 960; strides
+ * multiples of 4, pointers 16-byte aligned.  w_dev[k]: layer k's weight [cout][cin] after rgbd_pixel_mlp4_pack (a host-side
+ * reordering into MFMA lane fragments, cout * cin floats), bias_dev[k]: [cout]; the hidden widths are 320, 256 and 128,
+ * out_dim 16 ... 128.  out_dev: [B][H][W][out_stride].  parity -1: every pixel; 0: the anchor pixels ((row + col) odd); 1: the
+ * others; what is not selected is neither computed nor written (W even).  Every output is one fp32 chain that starts from the
+ * bias and takes k in increasing order: a pixel's bits depend on nothing but its own input -- not on B, H, W, parity or on how
+ * the channels are cut into segments.  Any other shape: RGBD_EINVAL before anything is launched. */
+int rgbd_pixel_mlp4_pack(const float* w, int32_t cout, int32_t cin, float* out);
+int rgbd_pixel_mlp4(const float* const* seg_dev, const int32_t* seg_channels, const int32_t* seg_stride, int32_t n_seg,
+                    const float* const* w_dev, const float* const* bias_dev, int32_t out_dim, int32_t B, int32_t H, int32_t W,
+                    int32_t parity, float* out_dev, int32_t out_stride, void* stream);
 
 /*
  * STF_united (BASELINE config 5): replaces models/stf_united.py: SymmetricalTransFormerUnited :605-678 with

@@ -23,6 +23,7 @@ modelZoo = {"ELIC_united_R2D": ELIC_united_R2D, "ELIC_united": ELIC_united, "ELI
 elic_united.modelZoo = modelZoo  # (`from rgbd_amd.elic_united import modelZoo`, the name's first home, is this dict)
 from .aligner import Spatial_aligner, SynthesisTransformPlus  # noqa: F401,E402
 from .mlic_context import LinearGlobalInterContext, LinearGlobalIntraContext, LocalContext  # noqa: F401,E402
+from .mlic_slice import ChannelContext, EntropyParametersMLIC, LatentResidualPrediction  # noqa: F401,E402
 from .pool import CodecPool  # noqa: F401,E402
 from . import datautils, ioutils, metrics, tester  # noqa: F401,E402
 from .tester import TesterSingle, TesterUnited  # noqa: F401,E402

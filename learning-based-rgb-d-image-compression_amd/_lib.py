@@ -10,7 +10,7 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _SO = os.path.join(_HERE, "librgbd_amd.so")
 _SO = os.environ.get("RGBD_AMD_LIB", _SO)  # A/B builds: point at another librgbd_amd.so
-_SRCS = ["conv_mfma.hip", "conv_mfma_blk.hip", "pointwise.hip", "swin.hip", "entropy.hip", "rans_wide.hip", "metrics.hip", "coder_abi.hip", "gdn.hip", "context_attn.hip", "pooled_head.hip", "thin_conv.hip", "engine_pack.hip", "engine_graph.hip", "engine_conv.hip", "engine_elic.hip", "engine_swin.hip",
+_SRCS = ["conv_mfma.hip", "conv_mfma_blk.hip", "pointwise.hip", "swin.hip", "entropy.hip", "rans_wide.hip", "metrics.hip", "coder_abi.hip", "gdn.hip", "context_attn.hip", "pooled_head.hip", "thin_conv.hip", "pixel_mlp.hip", "engine_pack.hip", "engine_graph.hip", "engine_conv.hip", "engine_elic.hip", "engine_swin.hip",
          "engine_ckbd.hip", "engine.hip", "engine_abi.hip", "hooks_abi.hip"]
 _LIB = None
 _INCLUDE = re.compile(r'^[ \t]*#[ \t]*include[ \t]+"([^"]+)"', re.M)  # (indented too: conv_mfma.hip includes its tile tables inside an initializer)
@@ -214,6 +214,16 @@ def lib():
         "rgbd_linear_inter_forward": (ctypes.c_int, [c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp]),
         "rgbd_linear_intra_create": (ctypes.c_int, [c_i32, c_i32, ctypes.POINTER(c_vp)]),
         "rgbd_linear_intra_forward": (ctypes.c_int, [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp]),
+        "rgbd_entropy_params_mlic_create": (ctypes.c_int, [c_i32, c_i32, ctypes.POINTER(c_vp)]),
+        "rgbd_entropy_params_mlic_forward": (ctypes.c_int, [c_vp, ctypes.POINTER(c_vp), i32p, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp]),
+        "rgbd_entropy_params_mlic_set_fused": (ctypes.c_int, [c_vp, c_i32]),
+        "rgbd_channel_context_create": (ctypes.c_int, [c_i32, c_i32, ctypes.POINTER(c_vp)]),
+        "rgbd_channel_context_forward": (ctypes.c_int, [c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp]),
+        "rgbd_lrp_create": (ctypes.c_int, [c_i32, c_i32, ctypes.POINTER(c_vp)]),
+        "rgbd_lrp_forward": (ctypes.c_int, [c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp]),
+        "rgbd_pixel_mlp4_pack": (ctypes.c_int, [f32p, c_i32, c_i32, f32p]),
+        "rgbd_pixel_mlp4": (ctypes.c_int, [ctypes.POINTER(c_vp), i32p, i32p, c_i32, ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), c_i32, c_i32,
+                                           c_i32, c_i32, c_i32, c_vp, c_i32, c_vp]),
         "rgbd_local_ckbd_attention": (ctypes.c_int, [c_vp] + [c_i32] * 6 + [c_vp, c_vp, c_vp, c_vp, c_i32, c_vp]),
         "rgbd_linear_attention_ws_floats": (c_i64, [c_i32] * 6),
         "rgbd_linear_attention": (ctypes.c_int, [c_vp, c_i32, c_vp, c_i32, c_vp, c_i32] + [c_i32] * 6 + [c_vp, c_i32, c_vp, c_i64, c_vp]),
@@ -288,7 +298,9 @@ EXPORTS = ["rgbd_abi_version", "rgbd_set_blocking_sync", "rgbd_get_blocking_sync
            "rgbd_rans_wide_max_bytes", "rgbd_rans_wide_encode", "rgbd_rans_wide_decoder_create", "rgbd_rans_wide_decoder_set_stream",
            "rgbd_rans_wide_decoder_decode", "rgbd_rans_wide_decoder_destroy", "rgbd_rans_wide_encode_batch_dev",
            "rgbd_rans_wide_decode_batch_dev", "rgbd_elic_set_coder", "rgbd_synthesis_plus_create", "rgbd_synthesis_plus_forward",
-           "rgbd_debug_synthesis_plus_guides"]
+           "rgbd_debug_synthesis_plus_guides", "rgbd_entropy_params_mlic_create", "rgbd_entropy_params_mlic_forward",
+           "rgbd_entropy_params_mlic_set_fused", "rgbd_channel_context_create", "rgbd_channel_context_forward", "rgbd_lrp_create",
+           "rgbd_lrp_forward", "rgbd_pixel_mlp4_pack", "rgbd_pixel_mlp4"]
 
 
 _BS_HOLDERS = 0

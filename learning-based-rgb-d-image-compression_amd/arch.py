@@ -618,6 +618,45 @@ def linear_global_inter_entries(dim: int = 32, out_dim: int = 64) -> "OrderedDic
     return _linear_context_entries(dim, out_dim * 3 // 2, 2 * out_dim, out_dim, True)
 
 
+MLIC_PARAM_HIDDEN = (320, 256, 128)  # modules/transform/entropy.py:35-41
+MLIC_CHANNEL_HIDDEN = (192, 128)     # modules/transform/context.py:144-148
+
+
+def entropy_params_mlic_entries(in_dim: int = 640, out_dim: int = 64) -> "OrderedDict[str, Entry]":
+    """EntropyParametersMLIC (reference: modules/transform/entropy.py:31-41): four 1x1 convolutions, `fusion.{0,2,4,6}`."""
+    b = _Builder()
+    widths = (in_dim,) + MLIC_PARAM_HIDDEN + (out_dim,)
+    for i in range(4):
+        b.conv(f"fusion.{2 * i}", widths[i], widths[i + 1], 1)
+    return b.entries
+
+
+def channel_context_entries(in_dim: int = 32, out_dim: int = 32) -> "OrderedDict[str, Entry]":
+    """MLIC++'s ChannelContext (context.py:140-150): three 3x3 convolutions to 4 out_dim channels, `fushion.{0,2,4}` (the
+    reference's spelling)."""
+    b = _Builder()
+    widths = (in_dim,) + MLIC_CHANNEL_HIDDEN + (4 * out_dim,)
+    for i in range(3):
+        b.conv(f"fushion.{2 * i}", widths[i], widths[i + 1], 3)
+    return b.entries
+
+
+def lrp_widths(in_dim: int, out_dim: int) -> List[int]:
+    """Channel counts of LatentResidualPrediction (modules/transform/LRP.py:12-21), input first: the reference's integer
+    divisions as it writes them (diff * 3 // 4, not 3 * (diff // 4))."""
+    diff = abs(out_dim - in_dim)
+    return [in_dim, in_dim - diff // 4, in_dim - diff // 2, in_dim - diff * 3 // 4, out_dim]
+
+
+def lrp_entries(in_dim: int = 352, out_dim: int = 32) -> "OrderedDict[str, Entry]":
+    """LatentResidualPrediction (LRP.py:9-21): four 3x3 convolutions, `lrp_transform.{0,2,4,6}`."""
+    b = _Builder()
+    widths = lrp_widths(in_dim, out_dim)
+    for i in range(4):
+        b.conv(f"lrp_transform.{2 * i}", widths[i], widths[i + 1], 3)
+    return b.entries
+
+
 CHALIGN_IN, CHALIGN_MID, CHALIGN_OUT = 64, 256, 64  # modules/transform/channelAligner.py:9-20: constants of the reference
 
 

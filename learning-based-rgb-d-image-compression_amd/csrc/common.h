@@ -233,6 +233,8 @@ int launch_gather_wslabs(const float* wp, int cout_pad, int ntaps_total, int cin
 int launch_scatter_phase(const float* src, int B, int h, int jw, int scs, int j0, int py, int px, float* dst, int OW, int dcs,
                          int C, hipStream_t s);
 int launch_fill_zero(float* p, size_t n, hipStream_t s);
+// y = 0.5 * tanh(x) over the first C channels (a multiple of 4) of npix NHWC pixels; x == y is allowed
+int launch_half_tanh(const float* x, int xcs, float* y, int ycs, size_t npix, int C, hipStream_t s);
 // packed input of the first analysis conv: y[n][oy][ox][KP], see im2col5s2_kernel
 int launch_im2col5s2(const float* x, int N, int H, int W, int cs, int C, float* y, int OH, int OW, int KP, hipStream_t s);
 // swin.hip (STF_united)
@@ -262,6 +264,27 @@ int launch_dwconv3x3(const float* x, int B, int H, int W, int C, int xcs, const 
                      int ycs, hipStream_t s);
 // xa = x at the anchor positions and 0 elsewhere, xn the other half (utils/ckbd.py:37-48); all three with channel stride cs
 int launch_ckbd_split(const float* x, int B, int H, int W, int cs, float* xa, float* xn, hipStream_t s);
+
+// ---- the 1x1 stack of MLIC++'s EntropyParametersMLIC as one launch (pixel_mlp.hip; modules/transform/entropy.py:31-53) ----
+// in_dim (the sum of the segments' channels, 16 ... 960) -> 320 -> 256 -> 128 -> out_dim (16 ... 128), erf GELU between the
+// layers; every channel count a multiple of 16.  The input is the concatenation of nseg NHWC tensors that is never formed.
+// parity: -1 all pixels, 0 the anchor pixels ((row + col) odd), 1 the others (W even); the other pixels of y are left alone.
+#define PIXEL_MLP_MAX_SEGS 6
+struct PixelMlp4 {
+    const float* seg[PIXEL_MLP_MAX_SEGS];  // [B][H][W][seg_cs[i]], the first seg_c[i] channels are read
+    int seg_c[PIXEL_MLP_MAX_SEGS];
+    int seg_cs[PIXEL_MLP_MAX_SEGS];
+    int nseg;
+    const float* w[4];     // pixel_mlp4_pack of each layer's [cout][cin] weight
+    const float* bias[4];  // [cout]
+    int out_dim;
+    int B, H, W, parity;
+    float* y;  // [B][H][W][ycs]
+    int ycs;
+};
+// w [cout][cin] (host) -> out, cout * cin floats (host): MFMA lane fragments [cout / 16][cin / 16][64][4]
+int pixel_mlp4_pack(const float* w, int cout, int cin, float* out);
+int launch_pixel_mlp4(const PixelMlp4& d, hipStream_t s);  // checks its arguments; RGBD_EINVAL before any launch
 
 // ---- Channel_aligner's pooled heads (pooled_head.hip; modules/transform/channelAligner.py); all check their arguments ----
 // AdaptiveAvgPool2d(1) of conv3x3(pad 1) from nine border sums per (image, channel): x [B,H,W,cs], w [Cout][Cin][3][3] as the

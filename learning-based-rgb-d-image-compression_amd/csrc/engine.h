@@ -6,7 +6,7 @@
 //   engine_graph.hip  HangWatch, the stream, the per-call-shape HIP-graph cache, waits, pinned staging, workspace ends, profiler events
 //   engine_conv.hip   the conv planner (tiles, split-K, reference arithmetic), issue, fusion decisions, SE gates
 //   engine_elic.hip   the blocks of nm modalities, the ELIC-type transforms and the checkerboard slice loop
-//   engine_swin.hip   Swin blocks, Spatial_aligner, the MLIC++ contexts, the STF transforms and their slice loop
+//   engine_swin.hip   Swin blocks, Spatial_aligner, the MLIC++ contexts and per-slice networks, the STF transforms and their slice loop
 //   engine_ckbd.hip   the checkerboard Cheng2020 family
 //   engine.hip        the call paths (compress / decompress / forward: one per direction for one or two modalities; a family
 //                     enters them through the four `*_family` hooks)
@@ -249,9 +249,10 @@ int small_conv_set_kblocks(SmallConvArgs* a, const int* lens, int n, int Kt);
 }  // namespace rgbd_rt
 using namespace rgbd_rt;
 
-// What an engine handle is: a codec (0-5) or one module alone (6-9, 13: no codec calls, no tables, its own forward entry point).
-// DESIGN.md and the history name the families by these numbers, so the numbers stay; 10-12 are reserved for the held-back
-// modules of ELIC_master and refused everywhere: the table has holes, not a renumbering.
+// What an engine handle is: a codec (0-5) or one module alone (6-9, 13, 15-17: no codec calls, no tables, its own forward entry
+// point).  DESIGN.md and the history name the families by these numbers, so the numbers stay; 10-12 are reserved for the
+// held-back modules of ELIC_master and refused everywhere, and so is 14, which nothing has claimed
+// (tests/test_synplus_kinds_cpu.py holds it refused): the table has holes, not a renumbering.
 enum class Family : int {
     ELIC_united = 0,      // RGB + depth (models/elic_united.py)
     ELIC = 1,             // single-modal ELIC (models/elic.py)
@@ -264,8 +265,11 @@ enum class Family : int {
     LinearGlobalInterContext = 8,  // rgbd_linear_inter_forward /
     LinearGlobalIntraContext = 9,  // rgbd_linear_intra_forward only
     SynthesisTransformPlus = 13,   // modules/transform/synthesis.py:74-110: rgbd_synthesis_plus_forward only
+    EntropyParametersMLIC = 15,    // the per-slice networks of MLIC++: modules/transform/entropy.py:31-53, rgbd_entropy_params_mlic_forward /
+    ChannelContext = 16,           // modules/transform/context.py:140-160, rgbd_channel_context_forward /
+    LatentResidualPrediction = 17, // modules/transform/LRP.py:9-26, rgbd_lrp_forward only
 };
-constexpr int kFamilies = 14;
+constexpr int kFamilies = 18;
 
 struct FamilyRow {
     const char* name;
@@ -296,6 +300,10 @@ constexpr FamilyRow kFamilyTable[kFamilies] = {
     {nullptr,                       0, false, false, 0, false, false},
     {nullptr,                       0, false, false, 0, false, false},
     {"SynthesisTransformPlus",      0, false, false, 0, false, false},
+    {nullptr,                       0, false, false, 0, false, false},  // 14: a hole
+    {"EntropyParametersMLIC",       0, false, false, 0, false, false},
+    {"ChannelContext",              0, false, false, 0, false, false},
+    {"LatentResidualPrediction",    0, false, false, 0, false, false},
 };
 constexpr bool family_ok(int f) { return f >= 0 && f < kFamilies && kFamilyTable[f].name; }
 constexpr const FamilyRow& family_row(Family f) { return kFamilyTable[(int)f]; }
@@ -307,7 +315,7 @@ struct rgbd_elic {
     const FamilyRow& row() const { return family_row(family); }
     bool single() const { return row().nm == 1; }
     int in_ch = 3;    // image channels of the single-modal codecs (Spatial_aligner: channels of x and guided; contexts: dim;
-                      // SynthesisTransformPlus: M)
+                      // SynthesisTransformPlus: M; the per-slice networks of MLIC++: in_dim)
     int out_ch = 0;   // module handles: output channels
     int ctx_heads = 0;  // contexts: num_heads
     // what the call paths (engine.hip) need to know about one versus two modalities; arrays are read at [0, nm)
@@ -992,6 +1000,19 @@ struct rgbd_elic {
     int run_synthesis_plus(const float* yhat_dev, const float* const up_dev[3], int B, int h, int w, float* out_dev);
     // the contexts: x1 (and, LinearGlobalIntraContext, x2) [B,in_ch,H,W] -> out [B,out_ch,H,W]
     int run_context(const float* x1_dev, const float* x2_dev, int B, int H, int W, float* out_dev);
+    // ---- the per-slice networks of MLIC++, each a block of its own (families 15-17; engine_swin.hip) -------------------------
+    // EntropyParametersMLIC.forward (entropy.py:43-53) on the concatenation of nseg tensors: ONE launch_pixel_mlp4 that reads the
+    // segments where they are (mlp_fused), or the concatenation written out and four conv() launches with the GELU epilogue.
+    // part: 0 the whole grid, 1 / 2 the anchor / non-anchor pixels only (Epi::ckbd); then dst holds the other pixels' values.
+    bool mlp_fused = true;  // rgbd_entropy_params_mlic_set_fused
+    Act entropy_params_mlic(const Act* seg, int nseg, int part, const Act* dst);
+    // ChannelContext.forward (context.py:152-160): three 3x3 convolutions, GELU between them
+    Act channel_context_mlic(const Act& x);
+    // LatentResidualPrediction.forward (LRP.py:22-26): four 3x3 convolutions, GELU between them, then 0.5 * tanh
+    Act lrp_mlic(const Act& x);
+    // seg_dev[i] [B,seg_c[i],H,W] (one tensor of in_ch channels for the two 3x3 modules) -> out [B,out_ch,H,W]; parity -1 / 0 / 1
+    // (EntropyParametersMLIC only): all pixels / the anchor pixels / the others, the rest of out keeps its values
+    int run_slice_net(const float* const* seg_dev, const int* seg_c, int nseg, int parity, int B, int H, int W, float* out_dev);
     int ensure_arena(size_t bytes);
 };
 

@@ -734,6 +734,38 @@ int rgbd_elic::run_context(const float* x1_dev, const float* x2_dev, int B, int 
     return r;
 }
 
+// A per-slice network of MLIC++ alone (families 15-17).  EntropyParametersMLIC takes its input as nseg tensors, each converted
+// to an NHWC tensor of its own: the fused launch reads them in place.  Under a parity the current content of out_dev is
+// converted too, so that the pixels the launch leaves alone come back as they were.
+int rgbd_elic::run_slice_net(const float* const* seg_dev, const int* seg_c, int nseg, int parity, int B, int H, int W, float* out_dev)
+{
+    begin_call(B, true);
+    Act seg[PIXEL_MLP_MAX_SEGS];
+    for (int i = 0; i < nseg; ++i) seg[i] = alloc(B, H, W, seg_c[i]);
+    const Act kept = parity >= 0 ? alloc(B, H, W, out_ch) : Act();
+    if (!dry()) {
+        int r = 0;
+        for (int i = 0; i < nseg && !r; ++i) r = launch_nchw_to_nhwc16(seg_dev[i], B, seg_c[i], H, W, seg[i].p, seg[i].cs, s);
+        if (!r && parity >= 0) r = launch_nchw_to_nhwc16(out_dev, B, out_ch, H, W, kept.p, kept.cs, s);
+        if (r) return r;
+    }
+    // ==== body: captured into / replayed from a HIP graph per call shape ====
+    Act out;
+    if (body_begin()) {
+        if (family == Family::EntropyParametersMLIC) out = entropy_params_mlic(seg, nseg, parity + 1, parity >= 0 ? &kept : nullptr);
+        else if (family == Family::ChannelContext) out = channel_context_mlic(seg[0]);
+        else out = lrp_mlic(seg[0]);
+        if (cur_ge && !dry()) cur_ge->out[0] = out;
+    } else {
+        out = cur_ge->out[0];
+    }
+    if (const int r = finish_body()) return r;
+    if (dry()) return RGBD_OK;
+    int r = launch_nhwc_to_nchw_clamp(out.p, B, out_ch, H, W, out.cs, out_dev, 0, s);
+    if (!r) r = wait_stream();
+    return r;
+}
+
 // decompress: elic_united.py:462-578, elic.py:255-325, stf.py:766-816, Cheng2020withCKBD.py:138-174; h x w: the latent grid
 int rgbd_elic::run_decompress(int nm, const uint8_t* const* ys[2], const int64_t* ylen[2], int n_y, const uint8_t* const* zs[2],
                               const int64_t* zlen[2], int B, int h, int w, Out2 xhat_dev, const Latents* lat, const Mid3* up)

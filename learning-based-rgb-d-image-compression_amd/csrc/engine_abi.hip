@@ -149,6 +149,9 @@ int tensor_kind(Family f, const std::string& name, const int64_t* shape, int ndi
     if (ends_with(name, "recovery.weight") && ndim == 4 && shape[2] == 2 && shape[3] == 2) return RGBD_KIND_RECOVERY_DECONV;
     if (family_row(f).dense4d && weight && ndim == 4 && (name == "fusion.weight" || (shape[1] == 1 && shape[2] == 3 && shape[3] == 3)))
         return RGBD_KIND_CONTEXT_DENSE;
+    // EntropyParametersMLIC.fusion.{0,2,4,6}: packed twice, for the conv kernels and as the fragments of launch_pixel_mlp4
+    if (f == Family::EntropyParametersMLIC && weight && ndim == 4 && shape[2] == 1 && shape[3] == 1 && name.rfind("fusion.", 0) == 0)
+        return RGBD_KIND_PIXEL_MLP;
     if (weight && ndim == 4) {
         // ConvTranspose2d layers: g_s stages 1/6/12/17 and the h_s deconvs (single-modal ELIC: g_s stages 1/5/10/14 and
         // h_s.increase.*; stage numbers that are not a bare "<stage>.weight" in the other model belong to blocks with
@@ -290,6 +293,17 @@ struct Packer {
             convs[sibling(name, "weight", "subpix.weight")] = ps;
         }
         return RGBD_OK;
+    }
+
+    // a 1x1 layer of EntropyParametersMLIC: as every Conv2d (the four conv() launches of the unfused form; its bias is read
+    // by both forms), and "<layer>.fragments" for launch_pixel_mlp4.  Channel counts that are no multiples of 16 are refused.
+    int pack_pixel_mlp(const std::string& name, const HostTensor& t)
+    {
+        if (t.shape[0] % 16 || t.shape[1] % 16) return RGBD_EINVAL;
+        if (const int r = pack_conv_layer(name, t, false)) return r;
+        std::vector<float> frag(t.v.size());
+        if (const int r = pixel_mlp4_pack(t.v.data(), (int)t.shape[0], (int)t.shape[1], frag.data())) return r;
+        return dev_copy(frag.data(), frag.size(), &dense[sibling(name, "weight", "fragments")]);
     }
 
     // GDN / IGDN (layers/gdn.py): NonNegativeParametrizer.forward applied once here, in fp32; packed for gdn.hip
@@ -472,12 +486,37 @@ int rgbd_linear_intra_create(int32_t dim, int32_t heads, rgbd_elic** out)
     return module_new(Family::LinearGlobalIntraContext, dim, 2 * dim, heads, out);
 }
 
+// The per-slice networks of MLIC++ alone.  EntropyParametersMLIC (modules/transform/entropy.py:31-53): what launch_pixel_mlp4 takes
+int rgbd_entropy_params_mlic_create(int32_t in_dim, int32_t out_dim, rgbd_elic** out)
+{
+    if (!out || in_dim < 16 || in_dim > 960 || in_dim % 16 || out_dim < 16 || out_dim > 128 || out_dim % 16) return RGBD_EINVAL;
+    return module_new(Family::EntropyParametersMLIC, in_dim, out_dim, 0, out);
+}
+
+// ChannelContext (modules/transform/context.py:140-160): in_dim -> 192 -> 128 -> 4 out_dim
+int rgbd_channel_context_create(int32_t in_dim, int32_t out_dim, rgbd_elic** out)
+{
+    if (!out || in_dim < 1 || in_dim > 1024 || out_dim < 1 || out_dim > 256) return RGBD_EINVAL;
+    return module_new(Family::ChannelContext, in_dim, 4 * out_dim, 0, out);
+}
+
+// LatentResidualPrediction (modules/transform/LRP.py:9-26): widths in - d / 4, in - d / 2, in - 3 d / 4, out with d = |out - in|
+// in integer division, all of which must be positive
+int rgbd_lrp_create(int32_t in_dim, int32_t out_dim, rgbd_elic** out)
+{
+    if (!out || in_dim < 1 || in_dim > 1024 || out_dim < 1 || out_dim > 1024) return RGBD_EINVAL;
+    const int d = std::abs(out_dim - in_dim);
+    if (in_dim - d * 3 / 4 < 1) return RGBD_EINVAL;
+    return module_new(Family::LatentResidualPrediction, in_dim, out_dim, 0, out);
+}
+
 int rgbd_elic_clone_shared(const rgbd_elic* src, rgbd_elic** out)
 {
     if (!src || !out || !src->finalized) return RGBD_EINVAL;
     rgbd_elic* m = engine_make(src->family, src->N, src->M, src->slice_ch.data(), (int32_t)src->slice_ch.size(), src->in_ch,
                                src->out_ch, src->ctx_heads);
     m->refnum = src->refnum;  // (what the shared weights were packed for)
+    m->mlp_fused = src->mlp_fused;
     m->ref_threads = src->ref_threads;
     m->ref_tab = src->ref_tab;
     m->convs = src->convs;    // device pointers are shared, read-only; the generations below keep them alive
@@ -609,6 +648,59 @@ int rgbd_linear_intra_forward(rgbd_elic* m, const float* x1_dev, const float* x2
     return context_forward(m, Family::LinearGlobalIntraContext, x1_dev, x2_dev, B, H, W, out_dev, stream);
 }
 
+int rgbd_entropy_params_mlic_forward(rgbd_elic* m, const float* const* seg_dev, const int32_t* seg_channels, int32_t n_seg, int32_t B,
+                                     int32_t H, int32_t W, int32_t parity, float* out_dev, void* stream)
+{
+    if (const int r = module_ready(m, Family::EntropyParametersMLIC)) return r;
+    if (!seg_dev || !seg_channels || n_seg < 1 || n_seg > PIXEL_MLP_MAX_SEGS || !out_dev || B <= 0 || H <= 0 || W <= 0 ||
+        (int64_t)B * H * W * m->in_ch > 0x7fffffff || parity < -1 || parity > 1 || (parity >= 0 && (W & 1)))
+        return RGBD_EINVAL;
+    int sum = 0;
+    std::string key = call_key("ep|%d|%d|%d|%d|%d", B, H, W, parity, m->mlp_fused ? 1 : 0);
+    for (int i = 0; i < n_seg; ++i) {
+        if (!seg_dev[i] || seg_channels[i] < 16 || seg_channels[i] % 16 || seg_channels[i] > m->in_ch - sum) return RGBD_EINVAL;
+        sum += seg_channels[i];
+        key += "|" + std::to_string(seg_channels[i]);
+    }
+    if (sum != m->in_ch) return RGBD_EINVAL;
+    return run_call(m, stream, key, kForwardTail,
+                    [&]() { return m->run_slice_net(seg_dev, seg_channels, n_seg, parity, B, H, W, out_dev); });
+}
+
+// 1 (default): the four layers as one launch_pixel_mlp4; 0: as four conv() launches (the yardstick and the probe's A/B).  Like
+// the other switches it drops the cached graphs; refused with RGBD_ESTATE inside a running call of the engine.
+int rgbd_entropy_params_mlic_set_fused(rgbd_elic* m, int32_t on)
+{
+    std::unique_lock<std::shared_mutex> cap_lk(g_capture_mu);
+    if (!m || m->family != Family::EntropyParametersMLIC || on < 0 || on > 1) return RGBD_EINVAL;
+    if (m->body_mode) return RGBD_ESTATE;
+    if (m->mlp_fused != (on != 0)) m->graphs_invalidate();
+    m->mlp_fused = on != 0;
+    return RGBD_OK;
+}
+
+// ChannelContext and LatentResidualPrediction: 3x3 layers.  Maps of one row or one column are refused here, before any launch
+// (a 1 x 5 map through the MFMA 3x3 kernel once never returned, cause not found)
+static int conv3_stack_forward(rgbd_elic* m, Family f, const float* x_dev, int32_t B, int32_t H, int32_t W, float* out_dev, void* stream)
+{
+    if (const int r = module_ready(m, f)) return r;
+    if (!x_dev || !out_dev || B <= 0 || H < 2 || W < 2 || (int64_t)B * H * W * std::max(m->in_ch, m->out_ch) > 0x7fffffff) return RGBD_EINVAL;
+    const float* const seg[1] = {x_dev};
+    const int c[1] = {m->in_ch};
+    return run_call(m, stream, call_key("sn%d|%d|%d|%d", (int)f, B, H, W), kForwardTail,
+                    [&]() { return m->run_slice_net(seg, c, 1, -1, B, H, W, out_dev); });
+}
+
+int rgbd_channel_context_forward(rgbd_elic* m, const float* x_dev, int32_t B, int32_t H, int32_t W, float* out_dev, void* stream)
+{
+    return conv3_stack_forward(m, Family::ChannelContext, x_dev, B, H, W, out_dev, stream);
+}
+
+int rgbd_lrp_forward(rgbd_elic* m, const float* x_dev, int32_t B, int32_t H, int32_t W, float* out_dev, void* stream)
+{
+    return conv3_stack_forward(m, Family::LatentResidualPrediction, x_dev, B, H, W, out_dev, stream);
+}
+
 void rgbd_elic_destroy(rgbd_elic* m)
 {
     const bool dbg = g_dbg_destroy;
@@ -737,6 +829,7 @@ int rgbd_elic_finalize(rgbd_elic* m)
         case RGBD_KIND_LINEAR: r = p.pack_linear(name, t); break;
         case RGBD_KIND_ARRAY: r = p.pack_array(name, t); break;
         case RGBD_KIND_QUANTILES: r = p.pack_quantiles(name, t); break;
+        case RGBD_KIND_PIXEL_MLP: r = p.pack_pixel_mlp(name, t); break;
         default: break;  // RGBD_KIND_IGNORED: biases, betas, bottleneck matrices (read by the packer of their weight), buffers
         }
         if (r) return r;

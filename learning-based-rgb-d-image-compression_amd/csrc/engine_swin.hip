@@ -169,6 +169,76 @@ Act rgbd_elic::linear_context(const Act& xk, const Act& xq, const Act& xv, int m
     return conv("mlp.4", h2, 1, 0, e);
 }
 
+Act rgbd_elic::entropy_params_mlic(const Act* seg, int nseg, int part, const Act* dst)
+{
+    const Act& x0 = seg[0];
+    const Act out = dst ? *dst : alloc(x0.n, x0.h, x0.w, out_ch);
+    const size_t mark = arena.top;
+    if (mlp_fused) {
+        PixelMlp4 d{};
+        for (int i = 0; i < nseg; ++i) {
+            d.seg[i] = seg[i].p;
+            d.seg_c[i] = seg[i].c;
+            d.seg_cs[i] = seg[i].cs;
+        }
+        d.nseg = nseg;
+        bool have = true;
+        for (int l = 0; l < 4; ++l) {
+            const std::string n = "fusion." + std::to_string(2 * l);
+            const PackedConv* pc = conv_of(n + ".weight");  // (its bias: plain channel order, cout a multiple of 16)
+            d.w[l] = dense_of(n + ".fragments");
+            d.bias[l] = pc ? pc->bias : nullptr;
+            have = have && pc && d.w[l];
+        }
+        d.out_dim = out_ch;
+        d.B = x0.n;
+        d.H = x0.h;
+        d.W = x0.w;
+        d.parity = part - 1;
+        d.y = out.p;
+        d.ycs = out.cs;
+        if (!dry() && !rc && have) {
+            const int r = launch_pixel_mlp4(d, s);
+            if (r) fail(r);
+        }
+        return out;
+    }
+    Act t = x0;
+    if (nseg > 1) {  // torch.cat([...], dim=1), written out
+        t = alloc(x0.n, x0.h, x0.w, in_ch);
+        for (int i = 0, c0 = 0; i < nseg; c0 += seg[i].c, ++i) copy_ch(seg[i], view(t, c0, seg[i].c));
+    }
+    Epi gelu;
+    gelu.act = ACT_GELU;
+    for (int l = 0; l < 3; ++l) t = conv("fusion." + std::to_string(2 * l), t, 1, 0, gelu);
+    Epi last;
+    last.ckbd = part;
+    conv("fusion.6", t, 1, 0, last, &out);
+    arena.top = mark;
+    return out;
+}
+
+Act rgbd_elic::channel_context_mlic(const Act& x)
+{
+    Epi gelu;
+    gelu.act = ACT_GELU;
+    return conv("fushion.4", conv("fushion.2", conv("fushion.0", x, 1, 1, gelu), 1, 1, gelu), 1, 1);
+}
+
+Act rgbd_elic::lrp_mlic(const Act& x)
+{
+    Epi gelu;
+    gelu.act = ACT_GELU;
+    Act t = x;
+    for (int l = 0; l < 3; ++l) t = conv("lrp_transform." + std::to_string(2 * l), t, 1, 1, gelu);
+    const Act out = conv("lrp_transform.6", t, 1, 1);
+    if (!dry() && !rc) {
+        const int r = launch_half_tanh(out.p, out.cs, out.p, out.cs, (size_t)out.n * out.h * out.w, out.cs, s);
+        if (r) fail(r);
+    }
+    return out;
+}
+
 void rgbd_elic::basic_layer2(int nm, const std::string p[2], const Act x_in[2], int depth, int heads, int down, Act out[2])
 {
     Act x[2] = {x_in[0], x_in[nm - 1]};

@@ -390,6 +390,30 @@ int launch_fill_zero(float* p, size_t n, hipStream_t s)
     return RGBD_OK;
 }
 
+// LatentResidualPrediction's tail (modules/transform/LRP.py:24-25): y = 0.5 * tanh(x) over the first C channels of NHWC
+// tensors, element by element (tanh(0) = 0: pad channels that are computed along stay zero)
+__global__ void half_tanh_kernel(const float* x, int xcs, float* y, int ycs, size_t npix, int C4)  // (x may be y)
+{
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < npix * C4; i += (size_t)gridDim.x * blockDim.x) {
+        const size_t p = i / C4;
+        const int c = 4 * (int)(i - p * C4);
+        const f32x4 v = *(const f32x4*)(x + p * xcs + c);
+        f32x4 o;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) o[r] = 0.5f * tanhf(v[r]);
+        *(f32x4*)(y + p * ycs + c) = o;
+    }
+}
+
+int launch_half_tanh(const float* x, int xcs, float* y, int ycs, size_t npix, int C, hipStream_t s)
+{
+    if (!x || !y || !npix || C < 4 || C % 4 || xcs < C || ycs < C || xcs % 4 || ycs % 4 || ((uintptr_t)x & 15) || ((uintptr_t)y & 15))
+        return RGBD_EINVAL;
+    hipLaunchKernelGGL(half_tanh_kernel, dim3(grid_for(npix * (C / 4))), dim3(256), 0, s, x, xcs, y, ycs, npix, C / 4);
+    HIP_TRY(hipGetLastError());
+    return RGBD_OK;
+}
+
 // ---------------------------------------------------------------------------------------------
 // Small-tensor convolution in the arithmetic of the reference's CPU path for such tensors (torch's im2col + MKL sgemm route:
 // batch 1, kernel <= 3, at most 20480 input elements; DESIGN.md 4a, oracle/cpu_arith.c orc_conv_im2col_kblocks): per output

@@ -5,6 +5,7 @@ and its device, uploads, and shared-weight clones.  Of entropy coding it knows o
     ├── Spatial_aligner               aligner.py
     ├── SynthesisTransformPlus        aligner.py
     ├── LocalContext, LinearGlobalIntraContext, LinearGlobalInterContext    mlic_context.py
+    ├── EntropyParametersMLIC, ChannelContext, LatentResidualPrediction     mlic_slice.py
     └── Codec                         elic_united.py: entropy-table holders, streams, debug / profile hooks
         ├── ELIC_united               elic_united.py (ELIC_united_R2D, SymmetricalTransFormerUnited under it)
         └── SingleCodec               elic.py (ELIC, SymmetricalTransFormer, Cheng2020AnchorwithCheckerboard under it)

@@ -13,7 +13,7 @@ from collections import OrderedDict
 
 import numpy as np
 
-from .arch import (STF_SLICES, Entry, channel_aligner_entries, feature_decoder_entries, feature_encoder_entries, linear_global_inter_entries, linear_global_intra_entries, local_context_entries,
+from .arch import (STF_SLICES, Entry, channel_aligner_entries, channel_context_entries, entropy_params_mlic_entries, lrp_entries, feature_decoder_entries, feature_encoder_entries, linear_global_inter_entries, linear_global_intra_entries, local_context_entries,
                    spatial_aligner_entries, synthesis_plus_entries, ckbd_config, ckbd_entries, elic_entries, elic_united_entries, elic_united_r2d_entries, model_config, stf_config,
                    stf_entries, stf_single_config, stf_united_entries)
 
@@ -122,7 +122,7 @@ def make_tensor(name: str, e: Entry, seed: int) -> np.ndarray:
 def synthetic_state_dict(seed: int = 0, config=None, stress: bool = True, as_torch: bool = True,
                          model: str = "ELIC_united", channel: int = 3, recipe: str = None, N: int = 192,
                          in_channel: int = 192, out_channel: int = 192, dim: int = 32, out_dim: int = 64, num_heads: int = 2,
-                         M: int = 320):
+                         M: int = 320, in_dim: int = 640):
     """Full state_dict (parameters + buffers) of ELIC_united (default), ELIC_united_R2D, STF_united, the single-modal STF
     (model="STF": recipes "stress" and "plain"), the checkerboard Cheng2020 model (model="ckbd", width N, the same two recipes)
     or the single-modal ELIC with deterministic synthetic values.  `recipe`: "stress" (= stress=True, the default: ~22 bpp, wide CDF rows, 17 % escapes -- the worst
@@ -136,7 +136,18 @@ def synthetic_state_dict(seed: int = 0, config=None, stress: bool = True, as_tor
     model="Channel_aligner": the block alone (the reference's constant widths), always with _apply_stress_chalign.
     model="Feature_encoder" (in_channel) or "Feature_decoder" (in_channel, out_channel): a feature network of ELIC_master alone,
     always with _apply_stress_feature.  model="SynthesisTransformPlus" (N, M, channel = its `ch`): the guided synthesis transform
-    alone, always with _apply_stress_synplus."""
+    alone, always with _apply_stress_synplus.  model="EntropyParametersMLIC", "ChannelContext" or "LatentResidualPrediction"
+    (in_dim, out_dim): a per-slice network of MLIC++ alone, always with _apply_stress_mlic_slice."""
+    if model in ("EntropyParametersMLIC", "ChannelContext", "LatentResidualPrediction"):
+        entries = {"EntropyParametersMLIC": entropy_params_mlic_entries, "ChannelContext": channel_context_entries,
+                   "LatentResidualPrediction": lrp_entries}[model](in_dim, out_dim)
+        sd = OrderedDict((name, make_tensor(name, e, seed)) for name, e in entries.items())
+        _apply_stress_mlic_slice(sd, model)
+        if as_torch:
+            import torch
+
+            return OrderedDict((k, torch.from_numpy(np.ascontiguousarray(v))) for k, v in sd.items())
+        return sd
     if model in ("Feature_encoder", "Feature_decoder"):
         entries = feature_encoder_entries(in_channel) if model == "Feature_encoder" else feature_decoder_entries(in_channel, out_channel)
         sd = OrderedDict((name, make_tensor(name, e, seed)) for name, e in entries.items())
@@ -295,6 +306,27 @@ def _apply_stress_context(sd, seed):
         for n in ("keys.1", "queries.1"):
             sd[f"{n}.weight"] = sd[f"{n}.weight"] * np.float32(LINEAR_QK_GAIN)
             sd[f"{n}.bias"] = sd[f"{n}.bias"] * np.float32(LINEAR_QK_GAIN)
+
+
+MLIC_SLICE_FIRST_GAIN = math.sqrt(3.0)
+MLIC_SLICE_GELU_GAIN = math.sqrt(3.0 / 0.425)
+MLIC_SLICE_LRP_OUT = 0.7
+
+
+def _apply_stress_mlic_slice(sd, model):
+    """EntropyParametersMLIC, ChannelContext, LatentResidualPrediction: pre-activations of order 1 at every layer, for inputs of
+    unit variance.  The default initialisation (variance 1 / (3 fan_in)) shrinks a map by 0.58 per layer and a GELU by another
+    0.65 (E gelu(x)^2 = 0.425 for a standard normal x), so that the third GELU would see arguments of a few hundredths, where
+    it is the line x / 2 and its erf and tanh forms agree to 1e-7.  The first layer's weights are scaled by sqrt(3) and those
+    behind a GELU by sqrt(3 / 0.425): every GELU sees both signs out to |x| of 3 to 5.  The last layer of the LRP is scaled by a
+    further 0.7, so that the largest |x| in front of tanh is 1 to 3: past the linear part, short of saturation.  Biases keep
+    their initialisation (a few hundredths, 1e4 times the tests' bound)."""
+    names = [k for k in sd if k.endswith(".weight")]
+    for i, name in enumerate(names):
+        g = MLIC_SLICE_FIRST_GAIN if i == 0 else MLIC_SLICE_GELU_GAIN
+        if model == "LatentResidualPrediction" and i == len(names) - 1:
+            g *= MLIC_SLICE_LRP_OUT
+        sd[name] = sd[name] * np.float32(g)
 
 
 CHALIGN_TRUNK_GAIN = math.sqrt(6.0)
