@@ -334,7 +334,7 @@ int rgbd_elic_finalize(rgbd_elic* m);
 /* What finalize takes a state-dict entry for, decided by the family, the name and the shape alone (test hook; host only, no
  * GPU needed).  family: 0 ELIC_united, 1 ELIC, 2 STF_united, 3 ELIC_united_R2D, 4 STF, 5 checkerboard Cheng2020,
  * 6 Spatial_aligner, 7 LocalContext, 8 LinearGlobalInterContext, 9 LinearGlobalIntraContext, 13 SynthesisTransformPlus,
- * 15 EntropyParametersMLIC, 16 ChannelContext, 17 LatentResidualPrediction (10 to 12 are reserved, 14 is unused).  Returns one of
+ * 15 EntropyParametersMLIC, 16 ChannelContext, 17 LatentResidualPrediction, 19 MLIC++ (10 to 12 are reserved, 14 and 18 unused).  Returns one of
  * the kinds below, or RGBD_EINVAL for another family, a NULL pointer, ndim outside 1..4 or an extent < 1. */
 enum {
     RGBD_KIND_IGNORED = 0,         /* read by no packer of its own: biases, betas, bottleneck matrices, buffers */
@@ -417,6 +417,31 @@ int rgbd_elic_create_stf_single(int32_t in_ch, rgbd_elic** out);
  * rgbd_elic_get_refnum returns 0; rgbd_elic_set_forced_symbols works for modality 0.  Debug tensors: y, z, zhat, hyper, yhat,
  * ctx, means, scales. */
 int rgbd_elic_create_ckbd(int32_t N, int32_t in_ch, rgbd_elic** out);
+/* MLIC++ (models/mlicpp.py: MLICPlusPlus; N a multiple of 16, slice_num 2 ... 10 slices of 32 channels, M = 32 slice_num,
+ * in_ch 1 ... 16; anything else is RGBD_EINVAL before any allocation): residual blocks of 3x3 / 1x1 convolutions with GDN / IGDN
+ * and GELU, sub-pixel up-sampling, GELU hyper transforms, and per slice two checkerboard coding parts under the attention
+ * contexts (LocalContext, LinearGlobalIntraContext, LinearGlobalInterContext), ChannelContext, EntropyParametersMLIC (one fused
+ * launch per part) and LatentResidualPrediction, whose correction is added in place at the part's own pixels
+ * (rgbd_mlic_lrp_apply).  State-dict names are the reference's: ten of each network under `local_context.{i}.` and so on.
+ * Served by the three *_single entry points of this section, with image sides that are multiples of 64 and at least 128 (the
+ * z grid runs 3x3 layers; a one-row or one-column z map is RGBD_EINVAL before any launch): compress (:199-312) puts all parts of
+ * all images of a call into ONE y stream, slice-major, anchor part then non-anchor part, each in (n, c, row, w/2) order
+ * (per_image_streams: one stream per image); decompress (:314-413) does not clamp x_hat; forward is the eval forward()
+ * (:77-188).  rgbd_elic_get_refnum returns 0; rgbd_elic_set_coder(format 1) is refused; rgbd_elic_set_forced_symbols works for
+ * modality 0.  Debug tensors: y, z, zhat, hyper, yhat. */
+int rgbd_elic_create_mlic(int32_t N, int32_t M, int32_t slice_num, int32_t in_ch, rgbd_elic** out);
+/* The two updates MLIC++'s slice loop makes to a 32-channel slot of its NHWC state buffer, alone (test hooks; asynchronous on
+ * `stream`).  slot_dev [B][h][w][slot_cs] points at the slot's first channel inside a buffer of channel stride slot_cs;
+ * parity 0: the pixels with (row + col) odd (the anchors), 1: the others.  Pixels of the other parity and channels outside the
+ * slot are neither read nor written.
+ *   rgbd_mlic_lrp_apply: slot += 0.5 * tanh(r) -- the value of rgbd_pw_half_tanh followed by one fp32 add; r_dev [B][h][w][r_cs].
+ *   rgbd_mlic_slot_clear: slot = 0.
+ * RGBD_EINVAL before any launch: channels other than 32, a stride below 32 or not a multiple of 4, a pointer that is NULL or
+ * not 16-byte aligned, B, h or w below 1, a parity other than 0 / 1, 2^31 elements or more, r_dev == slot_dev. */
+int rgbd_mlic_lrp_apply(float* slot_dev, int32_t slot_cs, const float* r_dev, int32_t r_cs, int32_t channels, int32_t B, int32_t h,
+                        int32_t w, int32_t parity, void* stream);
+int rgbd_mlic_slot_clear(float* slot_dev, int32_t slot_cs, int32_t channels, int32_t B, int32_t h, int32_t w, int32_t parity,
+                         void* stream);
 /* Eval-mode forward() of the single-modal model (models/elic.py:60-161 with config quant = "ste"): x_hat [B,in_ch,H,W]
  * (not clamped), likelihoods of y [B,M,H/16,W/16] and of z [B,N,H/64,W/64] ("y_likelihoods" / "z_likelihoods"). */
 int rgbd_elic_forward_single(rgbd_elic* m, const float* x_dev, int32_t B, int32_t H, int32_t W, float* xhat_dev, float* lik_y,
@@ -666,6 +691,9 @@ int rgbd_pw_copy_channels(const float* src_dev, int32_t scs, float* dst_dev, int
 int rgbd_pw_im2col5s2(const float* x_dev, int32_t N, int32_t H, int32_t W, int32_t cs, int32_t C, float* y_dev, int32_t KP,
                       void* stream);
 int rgbd_pw_fill_zero(float* p_dev, int64_t n, void* stream);
+/* y = 0.5 * tanh(x) over the first C channels (a multiple of 4) of npix NHWC pixels with channel strides xcs / ycs (multiples of
+ * 4, 16-byte aligned pointers); x_dev == y_dev is allowed.  LatentResidualPrediction's tail (modules/transform/LRP.py:24-25). */
+int rgbd_pw_half_tanh(const float* x_dev, int32_t xcs, float* y_dev, int32_t ycs, int64_t npix, int32_t C, void* stream);
 int rgbd_pw_nchw_to_nhwc(const float* src_dev, int32_t N, int32_t C, int32_t H, int32_t W, float* dst_dev, int32_t cs, int32_t perm,
                          void* stream);
 int rgbd_pw_nhwc_to_nchw(const float* src_dev, int32_t N, int32_t C, int32_t H, int32_t W, int32_t cs, float* dst_dev,
@@ -885,6 +913,9 @@ int rgbd_elic_graph_count(const rgbd_elic* m);
  * them).  The affected calls must still return correct results (they re-run eagerly); an entry that loses three captures
  * keeps launching eagerly. */
 int rgbd_debug_fail_captures(int32_t n);
+/* on = 1: event pairs around every conv / GDN launch (graphs off while it is set); 2: the layer names carry the launch's shape key;
+ * 3 (MLIC++ handles): pairs around the PHASES of a call instead -- rows "phase.transforms", "phase.contexts", "phase.params",
+ * "phase.lrp", "phase.coder" of rgbd_elic_profile_dump -- and none around the launches inside them; 0: off. */
 int rgbd_elic_set_profile(rgbd_elic* m, int32_t on);
 int rgbd_elic_profile_read(rgbd_elic* m, double* conv_ms, int64_t* launches, double* flops);
 /* `flops` above are ALGORITHMIC: the FLOPs of the reference's layers (what bench.py's roofline divides by time).  A launch that

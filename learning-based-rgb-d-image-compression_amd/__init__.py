@@ -14,6 +14,7 @@ from .elic import ELIC  # noqa: F401,E402
 from .stf_united import STF_united, SymmetricalTransFormerUnited  # noqa: F401,E402
 from .stf import STF, SymmetricalTransFormer  # noqa: F401,E402
 from .ckbd import Cheng2020AnchorwithCheckerboard  # noqa: F401,E402
+from .mlic import MLICPlusPlus  # noqa: F401,E402
 
 # models/__init__.py:11-20, "the complex ones first": the testers take the first zoo name that is a substring of the model
 # name, so "ELIC_united_R2D" stands before "ELIC_united" before "ELIC", and "STF_united" before "STF"; "ckbd" comes last (no
@@ -21,6 +22,24 @@ from .ckbd import Cheng2020AnchorwithCheckerboard  # noqa: F401,E402
 modelZoo = {"ELIC_united_R2D": ELIC_united_R2D, "ELIC_united": ELIC_united, "ELIC": ELIC,
             "STF_united": SymmetricalTransFormerUnited, "STF": SymmetricalTransFormer, "ckbd": Cheng2020AnchorwithCheckerboard}
 elic_united.modelZoo = modelZoo  # (`from rgbd_amd.elic_united import modelZoo`, the name's first home, is this dict)
+# Entries that came after tests/golden/model_surface_record.json was taken: `modelZoo` is held to that record's six names and
+# their order (tests/test_model_surface.py), so younger classes stand here, and the testers look a name up in both (zoo_lookup).
+# models/__init__.py:19: "MLIC" (no name of either table contains it and it contains none of them)
+modelZooExtra = {"MLIC": MLICPlusPlus}
+elic_united.modelZooExtra = modelZooExtra
+
+
+def zoo_lookup(model_name):
+    """The class of the first table name that is a substring of `model_name` (modelZoo first, in its order, then
+    modelZooExtra), as the reference's testers pick a model (testing/tester.py:55-62); None when there is none."""
+    for table in (modelZoo, modelZooExtra):
+        for name, cls in table.items():
+            if model_name.find(name) != -1:
+                return cls
+    return None
+
+
+elic_united.zoo_lookup = zoo_lookup
 from .aligner import Spatial_aligner, SynthesisTransformPlus  # noqa: F401,E402
 from .mlic_context import LinearGlobalInterContext, LinearGlobalIntraContext, LocalContext  # noqa: F401,E402
 from .mlic_slice import ChannelContext, EntropyParametersMLIC, LatentResidualPrediction  # noqa: F401,E402

@@ -11,7 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _SO = os.path.join(_HERE, "librgbd_amd.so")
 _SO = os.environ.get("RGBD_AMD_LIB", _SO)  # A/B builds: point at another librgbd_amd.so
 _SRCS = ["conv_mfma.hip", "conv_mfma_blk.hip", "pointwise.hip", "swin.hip", "entropy.hip", "rans_wide.hip", "metrics.hip", "coder_abi.hip", "gdn.hip", "context_attn.hip", "pooled_head.hip", "thin_conv.hip", "pixel_mlp.hip", "engine_pack.hip", "engine_graph.hip", "engine_conv.hip", "engine_elic.hip", "engine_swin.hip",
-         "engine_ckbd.hip", "engine.hip", "engine_abi.hip", "hooks_abi.hip"]
+         "engine_ckbd.hip", "mlic_loop.hip", "mlic_engine.hip", "engine.hip", "engine_abi.hip", "hooks_abi.hip"]
 _LIB = None
 _INCLUDE = re.compile(r'^[ \t]*#[ \t]*include[ \t]+"([^"]+)"', re.M)  # (indented too: conv_mfma.hip includes its tile tables inside an initializer)
 
@@ -175,6 +175,10 @@ def lib():
         "rgbd_elic_create_single": (ctypes.c_int, [c_i32, c_i32, i32p, c_i32, c_i32, ctypes.POINTER(c_vp)]),
         "rgbd_elic_create_stf_single": (ctypes.c_int, [c_i32, ctypes.POINTER(c_vp)]),
         "rgbd_elic_create_ckbd": (ctypes.c_int, [c_i32, c_i32, ctypes.POINTER(c_vp)]),
+        "rgbd_elic_create_mlic": (ctypes.c_int, [c_i32, c_i32, c_i32, c_i32, ctypes.POINTER(c_vp)]),
+        "rgbd_mlic_lrp_apply": (ctypes.c_int, [c_vp, c_i32, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp]),
+        "rgbd_mlic_slot_clear": (ctypes.c_int, [c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp]),
+        "rgbd_pw_half_tanh": (ctypes.c_int, [c_vp, c_i32, c_vp, c_i32, c_i64, c_i32, c_vp]),
         "rgbd_slice_quant_index": (ctypes.c_int, [c_vp, c_i32, c_vp, c_i32, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i64,
                                                   c_i64, f32p, c_vp, c_vp, c_vp, c_i32, c_vp, c_i32, c_vp]),
         "rgbd_slice_dequant": (ctypes.c_int, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i64, c_i64, c_vp, c_i32,
@@ -300,7 +304,8 @@ EXPORTS = ["rgbd_abi_version", "rgbd_set_blocking_sync", "rgbd_get_blocking_sync
            "rgbd_rans_wide_decode_batch_dev", "rgbd_elic_set_coder", "rgbd_synthesis_plus_create", "rgbd_synthesis_plus_forward",
            "rgbd_debug_synthesis_plus_guides", "rgbd_entropy_params_mlic_create", "rgbd_entropy_params_mlic_forward",
            "rgbd_entropy_params_mlic_set_fused", "rgbd_channel_context_create", "rgbd_channel_context_forward", "rgbd_lrp_create",
-           "rgbd_lrp_forward", "rgbd_pixel_mlp4_pack", "rgbd_pixel_mlp4"]
+           "rgbd_lrp_forward", "rgbd_pixel_mlp4_pack", "rgbd_pixel_mlp4", "rgbd_elic_create_mlic", "rgbd_mlic_lrp_apply",
+           "rgbd_mlic_slot_clear", "rgbd_pw_half_tanh"]
 
 
 _BS_HOLDERS = 0

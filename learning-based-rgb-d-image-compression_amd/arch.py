@@ -764,6 +764,93 @@ def ckbd_entries(N: int = 192, channel: int = 3) -> "OrderedDict[str, Entry]":
     return b.entries
 
 
+MLIC_SLICE_CH = 32  # LocalContext's kernel and the head counts slice_ch * i / 32 of the inter contexts (models/mlicpp.py:40-51)
+
+
+def mlic_config(N: int = 192, M: int = 320, slice_num: int = 10) -> Config:
+    """MLIC++ (config/config.py: N 192, M 320, ten slices of 32 channels, context window 5)."""
+    if int(M) != MLIC_SLICE_CH * int(slice_num) or not 2 <= int(slice_num) <= 10 or int(N) % 16:
+        raise ValueError(f"MLIC: M must be 32 * slice_num with 2 ... 10 slices and N a multiple of 16, got N={N}, M={M}, slice_num={slice_num}")
+    cfg = model_config()
+    cfg["N"], cfg["M"], cfg["slice_num"], cfg["slice_ch"] = int(N), int(M), int(slice_num), [MLIC_SLICE_CH] * int(slice_num)
+    cfg["context_window"] = 5
+    return cfg
+
+
+def _prefixed(b: "_Builder", prefix: str, entries):
+    for name, e in entries.items():
+        b.entries[prefix + name] = e
+
+
+def mlic_entries(N: int = 192, M: int = 320, slice_num: int = 10, channel: int = 3) -> "OrderedDict[str, Entry]":
+    """Every state_dict entry of MLICPlusPlus (reference: models/mlicpp.py:15-75), in the reference's order: the entropy
+    bottleneck, g_a / g_s (residual blocks with GDN / IGDN, modules/layers/res_blk.py:30-119), h_a / h_s, the Gaussian
+    conditional, then per network kind the modules of slices 0 ... slice_num - 1 -- assembled from the per-module entry functions
+    under the reference's prefixes.  channel_context, global_inter_context and global_intra_context hold None at i = 0."""
+    C = M // slice_num
+    b = _Builder()
+    b.entropy_bottleneck("entropy_bottleneck", N)
+
+    def gdn(name, c):  # layers/gdn.py:35-50, ops/parametrizers.py:28-37
+        b.entries[f"{name}.beta"] = Entry((c,), "gdn_beta")
+        b.entries[f"{name}.gamma"] = Entry((c, c), "gdn_gamma")
+        for r in ("beta_reparam", "gamma_reparam"):
+            b.buffer(f"{name}.{r}.pedestal", (1,))
+            b.buffer(f"{name}.{r}.lower_bound.bound", (1,))
+
+    def res_block(name, cin, cout):  # res_blk.py:30-58
+        b.conv(f"{name}.conv1", cin, cout, 3)
+        b.conv(f"{name}.conv2", cout, cout, 3)
+        if cin != cout:
+            b.conv(f"{name}.skip", cin, cout, 1)
+
+    root = "g_a.analysis_transform"  # modules/transform/analysis.py:11-26
+    for i in range(3):
+        cin = channel if i == 0 else N
+        p = f"{root}.{2 * i}"  # ResidualBlockWithStride, res_blk.py:61-91
+        b.conv(f"{p}.conv1", cin, N, 3)
+        b.conv(f"{p}.conv2", N, N, 3)
+        gdn(f"{p}.gdn", N)
+        b.conv(f"{p}.skip", cin, N, 1)
+        res_block(f"{root}.{2 * i + 1}", N, N)
+    b.conv(f"{root}.6", N, M, 3)
+    root = "g_s.synthesis_transform"  # modules/transform/synthesis.py:12-29
+    for i in range(3):
+        res_block(f"{root}.{2 * i}", M if i == 0 else N, N)
+        p = f"{root}.{2 * i + 1}"  # ResidualBlockUpsample, res_blk.py:94-119
+        b.conv(f"{p}.subpel_conv.0", N, 4 * N, 3)
+        b.conv(f"{p}.conv", N, N, 3)
+        gdn(f"{p}.igdn", N)
+        b.conv(f"{p}.upsample.0", N, 4 * N, 3)
+    res_block(f"{root}.6", N, N)
+    b.conv(f"{root}.7.0", N, 4 * channel, 3)
+    for k, cin in zip(range(5), (M, N, N, N, N)):  # analysis.py:180-204
+        b.conv(f"h_a.reduction.{2 * k}", cin, N, 3)
+    M32 = M * 3 // 2
+    b.conv("h_s.increase.0", N, M, 3)  # synthesis.py:248-273
+    b.conv("h_s.increase.2.0", M, 4 * M, 3)
+    b.conv("h_s.increase.4", M, M32, 3)
+    b.conv("h_s.increase.6.0", M32, 4 * M32, 3)
+    b.conv("h_s.increase.8", M32, 2 * M, 3)
+    b.gaussian_conditional("gaussian_conditional")
+    for i in range(slice_num):
+        _prefixed(b, f"local_context.{i}.", local_context_entries(C))
+    for i in range(1, slice_num):
+        _prefixed(b, f"channel_context.{i}.", channel_context_entries(C * i, C))
+    for i in range(1, slice_num):
+        _prefixed(b, f"global_inter_context.{i}.", linear_global_inter_entries(C * i, 2 * C))
+    for i in range(1, slice_num):
+        _prefixed(b, f"global_intra_context.{i}.", linear_global_intra_entries(C))
+    for i in range(slice_num):
+        _prefixed(b, f"entropy_parameters_anchor.{i}.", entropy_params_mlic_entries(2 * M + (6 * C if i else 0), 2 * C))
+    for i in range(slice_num):
+        _prefixed(b, f"entropy_parameters_nonanchor.{i}.", entropy_params_mlic_entries(2 * M + (10 * C if i else 2 * C), 2 * C))
+    for kind in ("lrp_anchor", "lrp_nonanchor"):
+        for i in range(slice_num):
+            _prefixed(b, f"{kind}.{i}.", lrp_entries(M + (i + 1) * C, C))
+    return b.entries
+
+
 def count_parameters(entries) -> int:
     n = 0
     for e in entries.values():

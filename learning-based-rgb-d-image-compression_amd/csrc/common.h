@@ -235,6 +235,19 @@ int launch_scatter_phase(const float* src, int B, int h, int jw, int scs, int j0
 int launch_fill_zero(float* p, size_t n, hipStream_t s);
 // y = 0.5 * tanh(x) over the first C channels (a multiple of 4) of npix NHWC pixels; x == y is allowed
 int launch_half_tanh(const float* x, int xcs, float* y, int ycs, size_t npix, int C, hipStream_t s);
+// ... the value of one element: half_tanh_kernel and mlic_lrp_apply_kernel (mlic_loop.hip) share it, so that the LRP correction the
+// codec adds is the module's output bit for bit
+__device__ __forceinline__ float half_tanh_of(float v) { return 0.5f * tanhf(v); }
+
+// ---- MLIC++'s slice loop (mlic_loop.hip; models/mlicpp.py:220-303): what a coding part does to its 32-channel slot of the
+// state buffer besides the networks.  slot [B][h][w][scs] points at the slot's first channel; parity 0: the anchor pixels
+// ((row + col) odd), 1: the others.  Both check their arguments (RGBD_EINVAL before any launch): C must be 32, strides multiples
+// of 4 floats and >= C, pointers 16-byte aligned, B, h, w > 0 ----
+#define MLIC_SLOT_CH 32
+// slot += 0.5 * tanh(r) at the pixels of `parity` (r [B][h][w][rcs]: the LRP's last conv output); the other pixels are not touched
+int launch_mlic_lrp_apply(float* slot, int scs, const float* r, int rcs, int C, int B, int h, int w, int parity, hipStream_t s);
+// slot = 0 at the pixels of `parity`
+int launch_mlic_slot_clear(float* slot, int scs, int C, int B, int h, int w, int parity, hipStream_t s);
 // packed input of the first analysis conv: y[n][oy][ox][KP], see im2col5s2_kernel
 int launch_im2col5s2(const float* x, int N, int H, int W, int cs, int C, float* y, int OH, int OW, int KP, hipStream_t s);
 // swin.hip (STF_united)

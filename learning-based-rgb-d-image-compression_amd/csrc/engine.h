@@ -8,6 +8,7 @@
 //   engine_elic.hip   the blocks of nm modalities, the ELIC-type transforms and the checkerboard slice loop
 //   engine_swin.hip   Swin blocks, Spatial_aligner, the MLIC++ contexts and per-slice networks, the STF transforms and their slice loop
 //   engine_ckbd.hip   the checkerboard Cheng2020 family
+//   mlic_engine.hip   MLIC++: its transforms and the ten-slice loop over the contexts and per-slice networks of engine_swin.hip
 //   engine.hip        the call paths (compress / decompress / forward: one per direction for one or two modalities; a family
 //                     enters them through the four `*_family` hooks)
 // engine_abi.hip and hooks_abi.hip are the C ABI (include/rgbd_amd.h): the engine's entry points, and the operator hooks and
@@ -249,10 +250,11 @@ int small_conv_set_kblocks(SmallConvArgs* a, const int* lens, int n, int Kt);
 }  // namespace rgbd_rt
 using namespace rgbd_rt;
 
-// What an engine handle is: a codec (0-5) or one module alone (6-9, 13, 15-17: no codec calls, no tables, its own forward entry
-// point).  DESIGN.md and the history name the families by these numbers, so the numbers stay; 10-12 are reserved for the
-// held-back modules of ELIC_master and refused everywhere, and so is 14, which nothing has claimed
-// (tests/test_synplus_kinds_cpu.py holds it refused): the table has holes, not a renumbering.
+// What an engine handle is: a codec (0-5, 19) or one module alone (6-9, 13, 15-17: no codec calls, no tables, its own forward
+// entry point).  DESIGN.md and the history name the families by these numbers, so the numbers stay; 10-12 are reserved for the
+// held-back modules of ELIC_master and refused everywhere, and so are 14 and 18, which nothing has claimed
+// (tests/test_synplus_kinds_cpu.py and tests/test_mlic_slice_kinds_cpu.py hold them refused): the table has holes, not a
+// renumbering.
 enum class Family : int {
     ELIC_united = 0,      // RGB + depth (models/elic_united.py)
     ELIC = 1,             // single-modal ELIC (models/elic.py)
@@ -268,8 +270,9 @@ enum class Family : int {
     EntropyParametersMLIC = 15,    // the per-slice networks of MLIC++: modules/transform/entropy.py:31-53, rgbd_entropy_params_mlic_forward /
     ChannelContext = 16,           // modules/transform/context.py:140-160, rgbd_channel_context_forward /
     LatentResidualPrediction = 17, // modules/transform/LRP.py:9-26, rgbd_lrp_forward only
+    MLIC = 19,                     // MLIC++ (models/mlicpp.py): the codec over families 7-9 and 15-17
 };
-constexpr int kFamilies = 18;
+constexpr int kFamilies = 20;
 
 struct FamilyRow {
     const char* name;
@@ -304,6 +307,8 @@ constexpr FamilyRow kFamilyTable[kFamilies] = {
     {"EntropyParametersMLIC",       0, false, false, 0, false, false},
     {"ChannelContext",              0, false, false, 0, false, false},
     {"LatentResidualPrediction",    0, false, false, 0, false, false},
+    {nullptr,                       0, false, false, 0, false, false},  // 18: a hole
+    {"MLIC",                        1, true,  false, 0, true,  true},   // (mlicpp.py:406-413: x_hat is not clamped)
 };
 constexpr bool family_ok(int f) { return f >= 0 && f < kFamilies && kFamilyTable[f].name; }
 constexpr const FamilyRow& family_row(Family f) { return kFamilyTable[(int)f]; }
@@ -397,6 +402,23 @@ struct rgbd_elic {
 
     // conv-kernel profiling (bench.py roofline): HIP event pairs around every conv launch on the launch stream
     bool profile = false;
+    // rgbd_elic_set_profile(m, 3): event pairs around the PHASES of an MLIC++ call instead of its launches (tools/mlic_probe.py):
+    // "phase.transforms", "phase.contexts", "phase.params", "phase.lrp", "phase.coder".  Pairs are never nested (profile_collect
+    // names them in recording order), so the launches inside a phase record none of their own: `profile` stays off.
+    bool profile_phases = false;
+    struct Phase {
+        rgbd_elic* m;
+        const char* name;
+        hipEvent_t e1 = nullptr;
+        Phase(rgbd_elic* m_, const char* n) : m(m_), name(n)
+        {
+            if (m->profile_phases && !m->dry() && !m->rc && !m->prof_begin(&e1)) e1 = nullptr;
+        }
+        ~Phase()
+        {
+            if (e1) m->prof_end(e1, name, 0.0, 0.0);
+        }
+    };
     bool profile_keys = false;  // rgbd_elic_set_profile(m, 2): the recorded layer names carry the launch's shape key (tools/tune_insitu.py)
     std::vector<hipEvent_t> ev_pool;
     size_t ev_used = 0;
@@ -821,11 +843,11 @@ struct rgbd_elic {
     Act dwconv(const std::string& name, const Act& x, bool gelu);
     // LocalContext.forward (:82-137): norm1, qkv_proj, the 5x5 window attention with `fusion` (one launch), proj, and
     // x + mlp(norm2(x)); the Linear layers are 1x1 convolutions, GELU and the add their epilogues
-    Act local_context(const Act& x);
+    Act local_context(const Act& x, const std::string& p = "", int heads = -1);
     // LinearGlobalInterContext.forward (:243-262; xk = xq = xv = x1, mode 0, with `skip`) and LinearGlobalIntraContext.forward
     // (:189-213; xk = anchor half of x1, xq = the other half, xv = x2, mode 1, no `skip`): three 1x1 + depthwise branches, the
     // linear attention, the 5x5 reprojection, and skip(a) (or a) + mlp(a)
-    Act linear_context(const Act& xk, const Act& xq, const Act& xv, int mode, bool skip);
+    Act linear_context(const Act& xk, const Act& xq, const Act& xv, int mode, bool skip, const std::string& p = "", int heads = -1);
     // stf_united.py:270-366 for both modalities; down: 0 none, 1 PatchMerging (:217-249), 2 PatchSplit (:252-267)
     void basic_layer2(int nm, const std::string p[2], const Act x_in[2], int depth, int heads, int down, Act out[2]);
     void stf_stack(const std::string& root, const char* kind, const Act& r_in, const Act& d_in, const int* depths,
@@ -868,6 +890,26 @@ struct rgbd_elic {
     // subpel_conv3x3 = 3x3 conv to 4 C channels + PixelShuffle(2); the GELU behind it is pointwise, so it rides in the conv's
     // epilogue.  The last layers write the first 384 channels of the two context buffers.
     void h_s_stf1(const Act& zhat, const Act& means_dst, const Act& scales_dst);
+
+    // ---- MLIC++ (models/mlicpp.py; mlic_engine.hip): residual blocks with GDN / IGDN as in the checkerboard Cheng2020 family but
+    // with GELU (stride / up-sampling blocks) and ReLU (plain blocks), GELU hyper transforms, and a loop over slice_num slices of
+    // 32 channels, each coded in two checkerboard parts under the attention contexts and per-slice networks above ---------------
+    // res_blk.py:30-58: relu(conv2(relu(conv1 x))) + x, or + skip(x) (1x1) where the widths differ
+    Act ml_res_block(const std::string& p, const Act& x);
+    // res_blk.py:61-91: GDN(conv2(gelu(conv1 x, stride 2))) + skip(x) (1x1, stride 2)
+    Act ml_res_block_stride(const std::string& p, const Act& x);
+    // res_blk.py:94-119: IGDN(conv(gelu(subpel_conv x))) + upsample(x); the two sub-pixel convs as one grouped launch
+    Act ml_res_block_up(const std::string& p, const Act& x);
+    Act g_a_mlic(const Act& img);   // analysis.py:11-26
+    Act g_s_mlic(const Act& yhat);  // synthesis.py:12-29
+    Act h_a_mlic(const Act& y);     // analysis.py:180-204
+    // synthesis.py:248-273, widths M, 3M/2, 2M; the last layer writes `dst` = hyper_params (scales | means)
+    void h_s_mlic(const Act& zhat, const Act& dst);
+    // mlicpp.py:220-303 / 331-404 / 105-182.  state [B,h,w,2M]: hyper_means in channels [0, M), y_hat slot i in
+    // [M + 32 i, M + 32 i + 32).  Every concatenation the reference forms over decoded slices is a channel view of it: the LRP
+    // input is the prefix [0, M + 32 (i + 1)), cat(y_hat_slices) is [M, M + 32 i), y_hat itself is [M, 2M).  hyper [B,h,w,2M]:
+    // hyper_params, a segment of its own for the parameter networks.  y: null when decoding.
+    void slice_loop_mlic(Coding& cd, const Act* y, const Act& hyper, const Act& state);
 
     ScaleTab scale_tab{};  // host copy of the Gaussian scale table: the slice kernels take it by value
 
@@ -1005,11 +1047,11 @@ struct rgbd_elic {
     // segments where they are (mlp_fused), or the concatenation written out and four conv() launches with the GELU epilogue.
     // part: 0 the whole grid, 1 / 2 the anchor / non-anchor pixels only (Epi::ckbd); then dst holds the other pixels' values.
     bool mlp_fused = true;  // rgbd_entropy_params_mlic_set_fused
-    Act entropy_params_mlic(const Act* seg, int nseg, int part, const Act* dst);
+    Act entropy_params_mlic(const Act* seg, int nseg, int part, const Act* dst, const std::string& p = "", int out_dim = -1);
     // ChannelContext.forward (context.py:152-160): three 3x3 convolutions, GELU between them
-    Act channel_context_mlic(const Act& x);
+    Act channel_context_mlic(const Act& x, const std::string& p = "");
     // LatentResidualPrediction.forward (LRP.py:22-26): four 3x3 convolutions, GELU between them, then 0.5 * tanh
-    Act lrp_mlic(const Act& x);
+    Act lrp_mlic(const Act& x, const std::string& p = "", bool tanh = true);
     // seg_dev[i] [B,seg_c[i],H,W] (one tensor of in_ch channels for the two 3x3 modules) -> out [B,out_ch,H,W]; parity -1 / 0 / 1
     // (EntropyParametersMLIC only): all pixels / the anchor pixels / the others, the rest of out keeps its values
     int run_slice_net(const float* const* seg_dev, const int* seg_c, int nseg, int parity, int B, int H, int W, float* out_dev);

@@ -337,7 +337,7 @@ void rgbd_elic::y_encode(int nm, int B, const EncBufs& e)
 
 // ---- the family hooks: ELIC_united (family 0, models/elic_united.py), ELIC (1, models/elic.py), STF_united (2,
 // models/stf_united.py), ELIC_united_R2D (3, models/elic_united_R2D.py), STF (4, models/stf.py) and the checkerboard Cheng2020
-// (5, models/Cheng2020withCKBD.py) share one call path per direction; a family enters through the four hooks below ----------
+// (5, models/Cheng2020withCKBD.py) and MLIC++ (14, models/mlicpp.py) share one call path per direction; a family enters through the four hooks below ----------
 void rgbd_elic::g_a_family(const Act x[2], Act y[2])
 {
     switch (family) {
@@ -346,6 +346,7 @@ void rgbd_elic::g_a_family(const Act x[2], Act y[2])
     case Family::ELIC_united_R2D: g_a_r2d(x, y); break;
     case Family::STF: y[0] = g_a_stf1(x[0]); break;
     case Family::Cheng2020_ckbd: y[0] = g_a_ckbd(x[0]); break;
+    case Family::MLIC: y[0] = g_a_mlic(x[0]); break;
     default: g_a(x, y);
     }
 }
@@ -356,6 +357,7 @@ void rgbd_elic::h_a_family(const Act y[2], Act z[2])
     case Family::ELIC: z[0] = h_a1(y[0]); break;
     case Family::STF: z[0] = h_a_stf1(y[0]); break;
     case Family::Cheng2020_ckbd: z[0] = h_a_ckbd(y[0]); break;
+    case Family::MLIC: z[0] = h_a_mlic(y[0]); break;
     default: h_a(y[0], y[1], &z[0], &z[1]);
     }
 }
@@ -368,6 +370,7 @@ void rgbd_elic::g_s_family(const Act yhat[2], Act xhat[2])
     case Family::ELIC_united_R2D: g_s_r2d(yhat, xhat); break;
     case Family::STF: xhat[0] = g_s_stf1(yhat[0]); break;
     case Family::Cheng2020_ckbd: xhat[0] = g_s_ckbd(yhat[0]); break;
+    case Family::MLIC: xhat[0] = g_s_mlic(yhat[0]); break;
     default: g_s(yhat, xhat);
     }
 }
@@ -381,6 +384,8 @@ void rgbd_elic::g_s_family(const Act yhat[2], Act xhat[2])
 //     (the reference's decompress handles one image only, stf.py:799).
 //   Checkerboard: both halves of all images of the call go into ONE y stream, anchor half first (per-image streams: one per
 //     image, each with its own two halves); the decoder resumes its rANS state between the halves.
+//   MLIC++: one state buffer [hyper_means M | y_hat M] that the loop's networks read as channel views (slice_loop_mlic); y_hat is
+//     its upper half.  Streams as for ELIC: slice-major, anchor part then non-anchor part (mlicpp.py:220-305).
 //   The two-modality codecs: hyper synthesis and the same slice loop over both modalities (Bi-CEE, elic_united.py:265-348).
 void rgbd_elic::latent_family(Coding& cd, int B, int h, int w, const Act* y, const Act* zhat, const Act* hyp, Act yhat[2])
 {
@@ -458,6 +463,16 @@ void rgbd_elic::latent_family(Coding& cd, int B, int h, int w, const Act* y, con
             }
             if (r) fail(r);
         }
+        break;
+    }
+    case Family::MLIC: {
+        const Act state = alloc(B, h, w, 2 * M), hyper = alloc(B, h, w, 2 * M);
+        h_s_mlic(zhat[0], hyper);
+        copy_ch(view(hyper, M, M), view(state, 0, M));  // hyper_scales, hyper_means = hyper_params.chunk(2, 1)
+        yhat[0] = view(state, M, M);
+        named["hyper"] = hyper;
+        if (cd.estimate) cd.lik[0] = alloc(B, h, w, M);
+        slice_loop_mlic(cd, y, hyper, state);
         break;
     }
     default: {
@@ -552,7 +567,10 @@ int rgbd_elic::run_compress(int nm, In2 x_dev, int B, int H, int W, int per_imag
         }
         Coding cd = enc_coding(e, per_image, T, fy);
         latent_family(cd, B, h, w, y, lat ? nullptr : zhat, lat ? hyp : nullptr, yhat);
-        y_encode(nm, B, e);
+        {
+            Phase ph(this, "phase.coder");
+            y_encode(nm, B, e);
+        }
     }
     if (const int r = finish_body()) return r;
     if (dry()) return RGBD_OK;

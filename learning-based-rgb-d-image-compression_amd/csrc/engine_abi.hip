@@ -127,12 +127,15 @@ int run_call(rgbd_elic* m, void* stream, const std::string& key, Tail tail, Body
         m->dec_err_pending = false;
         if (tail.wait && !r && m->res_pin[rgbd_elic::kResPinBytes / sizeof(int64_t) - 1]) r = RGBD_EINVAL;
     }
-    if (m->profile && (tail.profile == Tail::kAlways || (tail.profile == Tail::kOnSuccess && !r))) m->profile_collect();
+    if ((m->profile || m->profile_phases) && (tail.profile == Tail::kAlways || (tail.profile == Tail::kOnSuccess && !r))) m->profile_collect();
     return r;
 }
 
 inline bool hw64(int32_t B, int32_t H, int32_t W) { return B > 0 && H > 0 && W > 0 && !(H % 64) && !(W % 64); }
 inline bool one_or_b(int32_t n_y, int32_t B) { return n_y == 1 || n_y == B; }
+// MLIC++ runs 3x3 layers on the z grid (h_a, h_s): a z map of one row or one column is refused before any launch, as the 3x3
+// modules refuse H < 2 or W < 2 -- image sides of at least 128
+inline bool z_grid_ok(const rgbd_elic* m, int32_t zh, int32_t zw) { return m->family != Family::MLIC || (zh >= 2 && zw >= 2); }
 
 // ---- finalize, first half: what a tensor of the state dict is ---------------------------------------------------------
 bool ends_with(const std::string& s, const char* suf)
@@ -146,18 +149,28 @@ bool ends_with(const std::string& s, const char* suf)
 int tensor_kind(Family f, const std::string& name, const int64_t* shape, int ndim)
 {
     const bool weight = ends_with(name, ".weight");
+    // MLIC++ holds ten of each context and per-slice network under these prefixes (mlicpp.py:40-75); behind the prefix the names
+    // are the module handles' and so are the kinds
+    const bool mlic = f == Family::MLIC;
+    const bool mlic_local = mlic && name.rfind("local_context.", 0) == 0;
+    const bool mlic_ctx = mlic_local || (mlic && (name.rfind("global_inter_context.", 0) == 0 || name.rfind("global_intra_context.", 0) == 0));
     if (ends_with(name, "recovery.weight") && ndim == 4 && shape[2] == 2 && shape[3] == 2) return RGBD_KIND_RECOVERY_DECONV;
-    if (family_row(f).dense4d && weight && ndim == 4 && (name == "fusion.weight" || (shape[1] == 1 && shape[2] == 3 && shape[3] == 3)))
+    if (family_row(f).dense4d && weight && ndim == 4 && (mlic ? (mlic_local && ends_with(name, ".fusion.weight")) : name == "fusion.weight"))
+        return RGBD_KIND_CONTEXT_DENSE;
+    if (family_row(f).dense4d && weight && ndim == 4 && (!mlic || mlic_ctx) && shape[1] == 1 && shape[2] == 3 && shape[3] == 3)
         return RGBD_KIND_CONTEXT_DENSE;
     // EntropyParametersMLIC.fusion.{0,2,4,6}: packed twice, for the conv kernels and as the fragments of launch_pixel_mlp4
     if (f == Family::EntropyParametersMLIC && weight && ndim == 4 && shape[2] == 1 && shape[3] == 1 && name.rfind("fusion.", 0) == 0)
+        return RGBD_KIND_PIXEL_MLP;
+    if (mlic && weight && ndim == 4 && shape[2] == 1 && shape[3] == 1 && name.rfind("entropy_parameters_", 0) == 0 &&
+        name.find(".fusion.") != std::string::npos)
         return RGBD_KIND_PIXEL_MLP;
     if (weight && ndim == 4) {
         // ConvTranspose2d layers: g_s stages 1/6/12/17 and the h_s deconvs (single-modal ELIC: g_s stages 1/5/10/14 and
         // h_s.increase.*; stage numbers that are not a bare "<stage>.weight" in the other model belong to blocks with
         // sub-names, so the union is unambiguous)
-        bool transposed = name.find(".deconv.") != std::string::npos || name.rfind("h_s.increase.", 0) == 0;
-        if (name.rfind("g_s.", 0) == 0)
+        bool transposed = name.find(".deconv.") != std::string::npos || (!mlic && name.rfind("h_s.increase.", 0) == 0);
+        if (!mlic && name.rfind("g_s.", 0) == 0)  // (MLIC++'s transforms hold no transposed convolution: sub-pixel convs throughout)
             for (const char* suf : {"_transform.1.weight", "_transform.6.weight", "_transform.12.weight", "_transform.17.weight",
                                     "_transform.5.weight", "_transform.10.weight", "_transform.14.weight"})
                 transposed = transposed || ends_with(name, suf);
@@ -173,7 +186,8 @@ int tensor_kind(Family f, const std::string& name, const int64_t* shape, int ndi
     // Swin LayerNorm affine parameters and relative position bias tables; LocalContext names its own without a module prefix
     const bool local = f == Family::LocalContext;
     if ((ndim == 1 && (name.find(".norm") != std::string::npos || (local && name.rfind("norm", 0) == 0))) ||
-        ends_with(name, "relative_position_bias_table") || (local && name == "relative_position_table"))
+        ends_with(name, "relative_position_bias_table") || (local && name == "relative_position_table") ||
+        (mlic_local && ends_with(name, ".relative_position_table")))
         return RGBD_KIND_ARRAY;
     if (ends_with(name, "entropy_bottleneck.quantiles")) return RGBD_KIND_QUANTILES;
     return RGBD_KIND_IGNORED;
@@ -449,6 +463,18 @@ int rgbd_elic_create_ckbd(int32_t N, int32_t in_ch, rgbd_elic** out)
     return engine_new(Family::Cheng2020_ckbd, N, N, &slice, 1, in_ch, 0, 0, out);
 }
 
+// MLICPlusPlus (models/mlicpp.py:15-75): slice_num slices of M / slice_num channels.  LocalContext's kernel and the head counts
+// slice_ch * i / 32 of the inter contexts are built for 32-channel slices; the widest parameter network reads 2M + 10 * 32
+// channels, which launch_pixel_mlp4 takes up to 960.  Everything is checked before anything is allocated.
+int rgbd_elic_create_mlic(int32_t N, int32_t M, int32_t slice_num, int32_t in_ch, rgbd_elic** out)
+{
+    if (!out || slice_num < 2 || slice_num > 10 || N < 16 || N > 512 || N % 16 || M != slice_num * MLIC_SLOT_CH || in_ch < 1 || in_ch > 16)
+        return RGBD_EINVAL;
+    int32_t slices[10];
+    for (int i = 0; i < slice_num; ++i) slices[i] = MLIC_SLOT_CH;
+    return engine_new(Family::MLIC, N, M, slices, slice_num, in_ch, 0, 0, out);
+}
+
 // Spatial_aligner alone (modules/transform/spatialAligner.py:341-390): embed_dim 96, 3 heads, 4x4 windows
 int rgbd_aligner_create(int32_t in_ch, int32_t out_ch, rgbd_elic** out)
 {
@@ -537,7 +563,7 @@ int rgbd_elic_compress_single(rgbd_elic* m, const float* x_dev, int32_t B, int32
                               void* stream)
 {
     if (const int r = check_ready(m)) return r;
-    if (!m->single() || !x_dev || !hw64(B, H, W)) return RGBD_EINVAL;
+    if (!m->single() || !x_dev || !hw64(B, H, W) || !z_grid_ok(m, H / 64, W / 64)) return RGBD_EINVAL;
     const int per_image = (per_image_streams || B == 1) ? 1 : 0;
     return run_call(m, stream, call_key("c1|%d|%d|%d|%d", B, H, W, per_image), kCompressTail,
                     [&]() { return m->run_compress(1, {x_dev}, B, H, W, per_image); });
@@ -547,7 +573,7 @@ int rgbd_elic_forward_single(rgbd_elic* m, const float* x_dev, int32_t B, int32_
                              float* lik_z, void* stream)
 {
     if (const int r = check_ready(m)) return r;
-    if (!m->single() || !x_dev || !xhat_dev || !lik_y || !lik_z || !hw64(B, H, W)) return RGBD_EINVAL;
+    if (!m->single() || !x_dev || !xhat_dev || !lik_y || !lik_z || !hw64(B, H, W) || !z_grid_ok(m, H / 64, W / 64)) return RGBD_EINVAL;
     return run_call(m, stream, call_key("f1|%d|%d|%d", B, H, W), kForwardTail,
                     [&]() { return m->run_forward(1, {x_dev}, B, H, W, {xhat_dev}, {lik_y}, {lik_z}); });
 }
@@ -557,7 +583,8 @@ int rgbd_elic_decompress_single(rgbd_elic* m, const uint8_t* const* y, const int
                                 float* x_dev, void* stream)
 {
     if (const int r = check_ready(m)) return r;
-    if (!m->single() || !y || !y_len || !z || !z_len || !x_dev || B <= 0 || zh <= 0 || zw <= 0 || !one_or_b(n_y, B)) return RGBD_EINVAL;
+    if (!m->single() || !y || !y_len || !z || !z_len || !x_dev || B <= 0 || zh <= 0 || zw <= 0 || !one_or_b(n_y, B) || !z_grid_ok(m, zh, zw))
+        return RGBD_EINVAL;
     return run_call(m, stream, call_key("d1|%d|%d|%d|%d", B, zh, zw, n_y), kDecompressTail,
                     [&]() { return m->run_decompress(1, &y, &y_len, n_y, &z, &z_len, B, zh * 4, zw * 4, {x_dev}); });
 }
@@ -952,8 +979,9 @@ int rgbd_elic_graph_count(const rgbd_elic* m)
 int rgbd_elic_set_profile(rgbd_elic* m, int32_t on)
 {
     if (!m) return RGBD_EINVAL;
-    m->profile = on != 0;
+    m->profile = on != 0 && on != 3;
     m->profile_keys = on == 2;
+    m->profile_phases = on == 3;  // (phases are bracketed in mlic_engine.hip only: another family records nothing)
     m->ev_used = 0;
     m->prof_flops = m->prof_flops_exec = m->prof_ms = 0.0;
     m->prof_launches = 0;
@@ -1049,7 +1077,8 @@ int rgbd_elic_set_forced_symbols(rgbd_elic* m, int32_t modality, const int32_t* 
 {
     std::unique_lock<std::shared_mutex> cap_lk(g_capture_mu);
     if (!m || modality < 0 || modality > 1 || n_y < 0 || n_z < 0 || (n_y && !y_sym) || (n_z && !z_sym)) return RGBD_EINVAL;
-    if (m->single() && (m->family != Family::Cheng2020_ckbd || modality != 0)) return RGBD_EINVAL;  // (the two-modality codecs, and modality 0 of the checkerboard Cheng2020 model)
+    // (the two-modality codecs, and modality 0 of the checkerboard Cheng2020 model and of MLIC++)
+    if (m->single() && ((m->family != Family::Cheng2020_ckbd && m->family != Family::MLIC) || modality != 0)) return RGBD_EINVAL;
     m->graphs_invalidate();  // the workspace layout and the launch list change
     m->force_y[modality].assign(y_sym, y_sym + n_y);
     m->force_z[modality].assign(z_sym, z_sym + n_z);

@@ -107,7 +107,7 @@ void rgbd_elic::graphs_invalidate()
 
 rgbd_elic::GraphEntry* rgbd_elic::graph_entry(const std::string& key)
 {
-    if (!use_graphs || profile || !s) return nullptr;  // (the NULL stream cannot be captured)
+    if (!use_graphs || profile || profile_phases || !s) return nullptr;  // (the NULL stream cannot be captured)
     // (the stream is part of the key: a graph is replayed on the stream it was captured on)
     char sk[32];
     snprintf(sk, sizeof(sk), "|%p", (void*)s);

@@ -118,61 +118,64 @@ Act rgbd_elic::dwconv(const std::string& name, const Act& x, bool gelu)
     return y;
 }
 
-Act rgbd_elic::local_context(const Act& x)
+Act rgbd_elic::local_context(const Act& x, const std::string& p, int heads)
 {
-    const Act t = layernorm("norm1", x);
-    const Act qkv = conv("qkv_proj", t, 1, 0);
+    if (heads < 0) heads = ctx_heads;
+    const Act t = layernorm(p + "norm1", x);
+    const Act qkv = conv(p + "qkv_proj", t, 1, 0);
     const Act a = alloc(x.n, x.h, x.w, 2 * x.c);
-    float* tab = dense_of("relative_position_table");
-    float* fw = dense_of("fusion.weight");
-    float* fb = dense_of("fusion.bias");
+    float* tab = dense_of(p + "relative_position_table");
+    float* fw = dense_of(p + "fusion.weight");
+    float* fb = dense_of(p + "fusion.bias");
     if (!dry() && !rc && tab && fw && fb) {
-        const int r = launch_local_ckbd_attention(qkv.p, qkv.cs, x.n, x.h, x.w, x.c, ctx_heads, tab, fw, fb, a.p, a.cs, s);
+        const int r = launch_local_ckbd_attention(qkv.p, qkv.cs, x.n, x.h, x.w, x.c, heads, tab, fw, fb, a.p, a.cs, s);
         if (r) fail(r);
     }
-    const Act x1 = conv("proj", a, 1, 0);
-    const Act t2 = layernorm("norm2", x1);
+    const Act x1 = conv(p + "proj", a, 1, 0);
+    const Act t2 = layernorm(p + "norm2", x1);
     Epi g;
     g.act = ACT_GELU;
-    const Act hdn = conv("mlp.fc1", t2, 1, 0, g);
+    const Act hdn = conv(p + "mlp.fc1", t2, 1, 0, g);
     Epi e;
     e.res1 = &x1;
-    return conv("mlp.fc2", hdn, 1, 0, e);
+    return conv(p + "mlp.fc2", hdn, 1, 0, e);
 }
 
-Act rgbd_elic::linear_context(const Act& xk, const Act& xq, const Act& xv, int mode, bool skip)
+Act rgbd_elic::linear_context(const Act& xk, const Act& xq, const Act& xv, int mode, bool skip, const std::string& p, int heads)
 {
-    const Act k = dwconv("keys.1", conv("keys.0", xk, 1, 0), false);
-    const Act q = dwconv("queries.1", conv("queries.0", xq, 1, 0), false);
-    const Act v = dwconv("values.1", conv("values.0", xv, 1, 0), false);
+    if (heads < 0) heads = ctx_heads;
+    const Act k = dwconv(p + "keys.1", conv(p + "keys.0", xk, 1, 0), false);
+    const Act q = dwconv(p + "queries.1", conv(p + "queries.0", xq, 1, 0), false);
+    const Act v = dwconv(p + "values.1", conv(p + "values.0", xv, 1, 0), false);
     const Act a = alloc(k.n, k.h, k.w, k.c);
-    const int hd = k.c / ctx_heads;
-    const int64_t wsf = linear_attention_ws_floats(k.n, k.h, k.w, ctx_heads, hd, mode);
+    const int hd = k.c / heads;
+    const int64_t wsf = linear_attention_ws_floats(k.n, k.h, k.w, heads, hd, mode);
     if (wsf <= 0) {
         fail(RGBD_EINVAL);
         return a;
     }
     float* ws = (float*)arena.take((size_t)wsf * sizeof(float));
     if (!dry() && !rc) {
-        const int r = launch_linear_attention(k.p, k.cs, q.p, q.cs, v.p, v.cs, k.n, k.h, k.w, ctx_heads, hd, mode, a.p, a.cs, ws,
+        const int r = launch_linear_attention(k.p, k.cs, q.p, q.cs, v.p, v.cs, k.n, k.h, k.w, heads, hd, mode, a.p, a.cs, ws,
                                               wsf, s);
         if (r) fail(r);
     }
-    const Act att = conv("reprojection", a, 1, 2);
+    const Act att = conv(p + "reprojection", a, 1, 2);
     Epi g;
     g.act = ACT_GELU;
-    const Act h1 = conv("mlp.0", att, 1, 0, g);
-    const Act h2 = dwconv("mlp.2", h1, true);
-    const Act sk = skip ? conv("skip", att, 1, 0) : att;
+    const Act h1 = conv(p + "mlp.0", att, 1, 0, g);
+    const Act h2 = dwconv(p + "mlp.2", h1, true);
+    const Act sk = skip ? conv(p + "skip", att, 1, 0) : att;
     Epi e;
     e.res1 = &sk;
-    return conv("mlp.4", h2, 1, 0, e);
+    return conv(p + "mlp.4", h2, 1, 0, e);
 }
 
-Act rgbd_elic::entropy_params_mlic(const Act* seg, int nseg, int part, const Act* dst)
+Act rgbd_elic::entropy_params_mlic(const Act* seg, int nseg, int part, const Act* dst, const std::string& p, int out_dim)
 {
+    if (out_dim < 0) out_dim = out_ch;
     const Act& x0 = seg[0];
-    const Act out = dst ? *dst : alloc(x0.n, x0.h, x0.w, out_ch);
+    const Act out = dst ? *dst : alloc(x0.n, x0.h, x0.w, out_dim);
     const size_t mark = arena.top;
     if (mlp_fused) {
         PixelMlp4 d{};
@@ -184,13 +187,13 @@ Act rgbd_elic::entropy_params_mlic(const Act* seg, int nseg, int part, const Act
         d.nseg = nseg;
         bool have = true;
         for (int l = 0; l < 4; ++l) {
-            const std::string n = "fusion." + std::to_string(2 * l);
+            const std::string n = p + "fusion." + std::to_string(2 * l);
             const PackedConv* pc = conv_of(n + ".weight");  // (its bias: plain channel order, cout a multiple of 16)
             d.w[l] = dense_of(n + ".fragments");
             d.bias[l] = pc ? pc->bias : nullptr;
             have = have && pc && d.w[l];
         }
-        d.out_dim = out_ch;
+        d.out_dim = out_dim;
         d.B = x0.n;
         d.H = x0.h;
         d.W = x0.w;
@@ -205,34 +208,36 @@ Act rgbd_elic::entropy_params_mlic(const Act* seg, int nseg, int part, const Act
     }
     Act t = x0;
     if (nseg > 1) {  // torch.cat([...], dim=1), written out
-        t = alloc(x0.n, x0.h, x0.w, in_ch);
+        int in_dim = 0;
+        for (int i = 0; i < nseg; ++i) in_dim += seg[i].c;
+        t = alloc(x0.n, x0.h, x0.w, in_dim);
         for (int i = 0, c0 = 0; i < nseg; c0 += seg[i].c, ++i) copy_ch(seg[i], view(t, c0, seg[i].c));
     }
     Epi gelu;
     gelu.act = ACT_GELU;
-    for (int l = 0; l < 3; ++l) t = conv("fusion." + std::to_string(2 * l), t, 1, 0, gelu);
+    for (int l = 0; l < 3; ++l) t = conv(p + "fusion." + std::to_string(2 * l), t, 1, 0, gelu);
     Epi last;
     last.ckbd = part;
-    conv("fusion.6", t, 1, 0, last, &out);
+    conv(p + "fusion.6", t, 1, 0, last, &out);
     arena.top = mark;
     return out;
 }
 
-Act rgbd_elic::channel_context_mlic(const Act& x)
+Act rgbd_elic::channel_context_mlic(const Act& x, const std::string& p)
 {
     Epi gelu;
     gelu.act = ACT_GELU;
-    return conv("fushion.4", conv("fushion.2", conv("fushion.0", x, 1, 1, gelu), 1, 1, gelu), 1, 1);
+    return conv(p + "fushion.4", conv(p + "fushion.2", conv(p + "fushion.0", x, 1, 1, gelu), 1, 1, gelu), 1, 1);
 }
 
-Act rgbd_elic::lrp_mlic(const Act& x)
+Act rgbd_elic::lrp_mlic(const Act& x, const std::string& p, bool tanh)
 {
     Epi gelu;
     gelu.act = ACT_GELU;
     Act t = x;
-    for (int l = 0; l < 3; ++l) t = conv("lrp_transform." + std::to_string(2 * l), t, 1, 1, gelu);
-    const Act out = conv("lrp_transform.6", t, 1, 1);
-    if (!dry() && !rc) {
+    for (int l = 0; l < 3; ++l) t = conv(p + "lrp_transform." + std::to_string(2 * l), t, 1, 1, gelu);
+    const Act out = conv(p + "lrp_transform.6", t, 1, 1);
+    if (tanh && !dry() && !rc) {
         const int r = launch_half_tanh(out.p, out.cs, out.p, out.cs, (size_t)out.n * out.h * out.w, out.cs, s);
         if (r) fail(r);
     }

@@ -422,6 +422,13 @@ int rgbd_pw_im2col5s2(const float* x_dev, int32_t N, int32_t H, int32_t W, int32
     return launch_im2col5s2(x_dev, N, H, W, cs, C, y_dev, (H + 1) / 2, (W + 1) / 2, KP, (hipStream_t)stream);
 }
 
+int rgbd_pw_half_tanh(const float* x_dev, int32_t xcs, float* y_dev, int32_t ycs, int64_t npix, int32_t C, void* stream)
+{
+    if (!x_dev || !y_dev || !pw_tensor_ok(1, npix, C, xcs) || !pw_tensor_ok(1, npix, C, ycs) || C % 4 || !pw_al16(x_dev) || !pw_al16(y_dev))
+        return RGBD_EINVAL;
+    return launch_half_tanh(x_dev, xcs, y_dev, ycs, (size_t)npix, C, (hipStream_t)stream);
+}
+
 int rgbd_pw_fill_zero(float* p_dev, int64_t n, void* stream)
 {
     if (!p_dev || n <= 0 || n >= ((int64_t)1 << 31)) return RGBD_EINVAL;

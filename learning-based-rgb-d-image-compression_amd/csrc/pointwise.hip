@@ -400,7 +400,7 @@ __global__ void half_tanh_kernel(const float* x, int xcs, float* y, int ycs, siz
         const f32x4 v = *(const f32x4*)(x + p * xcs + c);
         f32x4 o;
 #pragma unroll
-        for (int r = 0; r < 4; ++r) o[r] = 0.5f * tanhf(v[r]);
+        for (int r = 0; r < 4; ++r) o[r] = half_tanh_of(v[r]);
         *(f32x4*)(y + p * ycs + c) = o;
     }
 }

@@ -1,5 +1,5 @@
 """Single-modal `ELIC` on MI355X: the reference's model API (models/elic.py) over the HIP engine -- and `SingleCodec`, the
-base it shares with the other one-tensor models (stf.py, ckbd.py).
+base it shares with the other one-tensor models (stf.py, ckbd.py, mlic.py).
 
     net = ELIC(config=model_config(), channel=3).eval()
     net.load_state_dict(checkpoint["state_dict"]); net.update(force=True); net = net.to("cuda")

@@ -8,7 +8,7 @@ and its device, uploads, and shared-weight clones.  Of entropy coding it knows o
     ├── EntropyParametersMLIC, ChannelContext, LatentResidualPrediction     mlic_slice.py
     └── Codec                         elic_united.py: entropy-table holders, streams, debug / profile hooks
         ├── ELIC_united               elic_united.py (ELIC_united_R2D, SymmetricalTransFormerUnited under it)
-        └── SingleCodec               elic.py (ELIC, SymmetricalTransFormer, Cheng2020AnchorwithCheckerboard under it)
+        └── SingleCodec               elic.py (ELIC, SymmetricalTransFormer, Cheng2020AnchorwithCheckerboard, MLICPlusPlus under it)
 
 A subclass fills in: `_MODEL` (its name in messages and in synth.synthetic_state_dict), `_synth_args()` (the other keyword
 arguments of synth.synthetic_state_dict), `_create_engine()` (one `self._create(...)` line) and, where it sends more than
@@ -184,7 +184,7 @@ class EngineModule:
         streams byte for byte) or "wide" -- `lanes` (1, 2, 4 ... 64) interleaved rANS states coded by one GPU lane each, for
         callers who want a short single call and do not need CompressAI-compatible streams.  A wide y string starts with the
         tag b"RW\x01" + bytes([lanes]) and is 4 + 8 * (lanes - 1) bytes longer; the z strings do not change.  Models whose
-        engine has no wide path (STF, STF_united, ELIC_united_R2D, the checkerboard Cheng2020) refuse "wide" here."""
+        engine has no wide path (STF, STF_united, ELIC_united_R2D, the checkerboard Cheng2020, MLIC++) refuse "wide" here."""
         if coder not in ("reference", "wide"):
             raise ValueError(f"coder must be 'reference' or 'wide', got {coder!r}")
         if coder == "wide" and lanes not in (1, 2, 4, 8, 16, 32, 64):

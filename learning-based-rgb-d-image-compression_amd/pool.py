@@ -18,7 +18,7 @@ from .sched import balanced_workers  # noqa: F401  (re-exported: rgbd_amd.pool.b
 
 class CodecPool:
     """W engine instances of one model on one GPU.  `model_cls`: ELIC_united (default), STF_united, ELIC_united_R2D -- or a
-    single-modal class (ELIC, STF, ckbd), whose calls take one tensor: roundtrip(x) -> (outs, x_hat), batches = [(x,), ...].
+    single-modal class (ELIC, STF, ckbd, MLIC), whose calls take one tensor: roundtrip(x) -> (outs, x_hat), batches = [(x,), ...].
     Use as a context manager, or call close(): the pool switches the DEVICE to blocking waits and close() switches it back."""
 
     def __init__(self, state_dict, config=None, workers: int = 2, device="cuda", per_image_streams: bool = True,

@@ -15,7 +15,7 @@ import numpy as np
 
 from .arch import (STF_SLICES, Entry, channel_aligner_entries, channel_context_entries, entropy_params_mlic_entries, lrp_entries, feature_decoder_entries, feature_encoder_entries, linear_global_inter_entries, linear_global_intra_entries, local_context_entries,
                    spatial_aligner_entries, synthesis_plus_entries, ckbd_config, ckbd_entries, elic_entries, elic_united_entries, elic_united_r2d_entries, model_config, stf_config,
-                   stf_entries, stf_single_config, stf_united_entries)
+                   stf_entries, stf_single_config, stf_united_entries, MLIC_SLICE_CH, mlic_config, mlic_entries)
 
 _IH_STD = math.sqrt(4.0 * (65536.0**2 - 1.0) / 12.0)  # std of the sum of four uniform 16-bit ints
 _IH_MEAN = 2.0 * 65535.0
@@ -137,7 +137,8 @@ def synthetic_state_dict(seed: int = 0, config=None, stress: bool = True, as_tor
     model="Feature_encoder" (in_channel) or "Feature_decoder" (in_channel, out_channel): a feature network of ELIC_master alone,
     always with _apply_stress_feature.  model="SynthesisTransformPlus" (N, M, channel = its `ch`): the guided synthesis transform
     alone, always with _apply_stress_synplus.  model="EntropyParametersMLIC", "ChannelContext" or "LatentResidualPrediction"
-    (in_dim, out_dim): a per-slice network of MLIC++ alone, always with _apply_stress_mlic_slice."""
+    (in_dim, out_dim): a per-slice network of MLIC++ alone, always with _apply_stress_mlic_slice.  model="MLIC" (N, M with
+    M / 32 slices, channel): the MLIC++ codec, recipes "stress" (_apply_stress_mlic) and "plain"."""
     if model in ("EntropyParametersMLIC", "ChannelContext", "LatentResidualPrediction"):
         entries = {"EntropyParametersMLIC": entropy_params_mlic_entries, "ChannelContext": channel_context_entries,
                    "LatentResidualPrediction": lrp_entries}[model](in_dim, out_dim)
@@ -207,6 +208,9 @@ def synthetic_state_dict(seed: int = 0, config=None, stress: bool = True, as_tor
     elif model == "ckbd":
         cfg = ckbd_config(N)
         entries = ckbd_entries(N, channel)
+    elif model == "MLIC":
+        cfg = mlic_config(N, M, M // MLIC_SLICE_CH)
+        entries = mlic_entries(N, M, M // MLIC_SLICE_CH, channel)
     else:
         cfg = model_config() if config is None else config
         entries = {"ELIC_united": elic_united_entries, "ELIC_united_R2D": elic_united_r2d_entries}.get(model)
@@ -224,6 +228,8 @@ def synthetic_state_dict(seed: int = 0, config=None, stress: bool = True, as_tor
         _apply_stress_stf(sd)
     elif stress and model == "ckbd":
         _apply_stress_ckbd(sd, seed, N)
+    elif stress and model == "MLIC":
+        _apply_stress_mlic(sd, seed, M // MLIC_SLICE_CH)
     elif stress:
         _apply_stress_single(sd, cfg)
     if recipe == "trained_like":
@@ -287,25 +293,26 @@ LOCAL_QK_GAIN = 3.5
 LINEAR_QK_GAIN = 8.0
 
 
-def _apply_stress_context(sd, seed):
+def _apply_stress_context(sd, seed, prefix=""):
     """The attention contexts of MLIC++: what makes a wrong attention visible.  LocalContext: relative position biases of
     order 1, LayerNorm weights in [0.5, 1.5], the query and key rows of qkv_proj scaled so that the scores (std ~0.3 with the
     default initialisation) reach |S| of 10 to 40 -- far from a uniform softmax, and still well below the mask's 100.  The
     linear contexts: the depthwise layers behind keys and queries scaled so that both softmaxes (over tokens, over channels)
-    see arguments of order 10."""
-    if "relative_position_table" in sd:
-        sd["relative_position_table"] = (sd["relative_position_table"] / np.float32(0.3)).astype(np.float32)
+    see arguments of order 10.  prefix: "" or the module's name inside a model with its dot ("local_context.3.")."""
+    p = prefix
+    if p + "relative_position_table" in sd:
+        sd[p + "relative_position_table"] = (sd[p + "relative_position_table"] / np.float32(0.3)).astype(np.float32)
         for n in ("norm1", "norm2"):
-            name = f"{n}.weight"
+            name = f"{p}{n}.weight"
             sd[name] = (1.0 + uniform_like(name + "#stress", seed, sd[name].shape, -0.5, 0.5)).astype(np.float32)
-        C = sd["qkv_proj.weight"].shape[1]
-        sd["qkv_proj.weight"][:2 * C] *= np.float32(LOCAL_QK_GAIN)  # the query and key rows; the value rows keep their scale
-        if "qkv_proj.bias" in sd:
-            sd["qkv_proj.bias"][:2 * C] *= np.float32(LOCAL_QK_GAIN)
+        C = sd[p + "qkv_proj.weight"].shape[1]
+        sd[p + "qkv_proj.weight"][:2 * C] *= np.float32(LOCAL_QK_GAIN)  # the query and key rows; the value rows keep their scale
+        if p + "qkv_proj.bias" in sd:
+            sd[p + "qkv_proj.bias"][:2 * C] *= np.float32(LOCAL_QK_GAIN)
     else:
         for n in ("keys.1", "queries.1"):
-            sd[f"{n}.weight"] = sd[f"{n}.weight"] * np.float32(LINEAR_QK_GAIN)
-            sd[f"{n}.bias"] = sd[f"{n}.bias"] * np.float32(LINEAR_QK_GAIN)
+            sd[f"{p}{n}.weight"] = sd[f"{p}{n}.weight"] * np.float32(LINEAR_QK_GAIN)
+            sd[f"{p}{n}.bias"] = sd[f"{p}{n}.bias"] * np.float32(LINEAR_QK_GAIN)
 
 
 MLIC_SLICE_FIRST_GAIN = math.sqrt(3.0)
@@ -313,15 +320,15 @@ MLIC_SLICE_GELU_GAIN = math.sqrt(3.0 / 0.425)
 MLIC_SLICE_LRP_OUT = 0.7
 
 
-def _apply_stress_mlic_slice(sd, model):
+def _apply_stress_mlic_slice(sd, model, prefix=""):
     """EntropyParametersMLIC, ChannelContext, LatentResidualPrediction: pre-activations of order 1 at every layer, for inputs of
     unit variance.  The default initialisation (variance 1 / (3 fan_in)) shrinks a map by 0.58 per layer and a GELU by another
     0.65 (E gelu(x)^2 = 0.425 for a standard normal x), so that the third GELU would see arguments of a few hundredths, where
     it is the line x / 2 and its erf and tanh forms agree to 1e-7.  The first layer's weights are scaled by sqrt(3) and those
     behind a GELU by sqrt(3 / 0.425): every GELU sees both signs out to |x| of 3 to 5.  The last layer of the LRP is scaled by a
     further 0.7, so that the largest |x| in front of tanh is 1 to 3: past the linear part, short of saturation.  Biases keep
-    their initialisation (a few hundredths, 1e4 times the tests' bound)."""
-    names = [k for k in sd if k.endswith(".weight")]
+    their initialisation (a few hundredths, 1e4 times the tests' bound).  prefix: "" or the module's name inside a model with its dot."""
+    names = [k for k in sd if k.endswith(".weight") and k.startswith(prefix)]
     for i, name in enumerate(names):
         g = MLIC_SLICE_FIRST_GAIN if i == 0 else MLIC_SLICE_GELU_GAIN
         if model == "LatentResidualPrediction" and i == len(names) - 1:
@@ -479,6 +486,59 @@ def _apply_stress_ckbd(sd, seed, N):
     sd["entropy_parameters.4.bias"][:N] = g["scale_b"]  # chunk(2, 1): scales first
     sd["entropy_parameters.4.weight"][N:] *= g["mean_w"]
     sd["context_prediction.weight"] *= g["ctx"]
+
+
+# MLIC++: conv in front of a GDN / an IGDN, y, z, hyper, scale head (weight, bias), mean head, the LRPs' last layer, and the
+# linear contexts' reprojection and depthwise mlp layer
+MLIC_GAINS = {"gdn_in": 6.0, "igdn_in": 3.5, "y": 5.0, "z": 8.0, "hyper": 4.0, "scale_w": 2.0, "scale_b": 0.7, "mean_w": 1.0,
+              "lrp_out": 0.45, "inter_reproj": 4.0, "intra_reproj": 10.0, "ctx_dw": 2.0}
+
+
+def _apply_stress_mlic(sd, seed, slice_num):
+    """MLIC++, composed from the recipes of its parts: GDN / IGDN, latents, z and hyper parameters in the manner of
+    _apply_stress_ckbd (a beta per channel, a dense gamma partly below the parametrizer's bound, activations of a few units in
+    front of every GDN), _apply_stress_context on the thirty attention contexts and _apply_stress_mlic_slice on the channel
+    contexts, parameter networks and LRPs.  The parameter networks end in (scales | means): the scale half gets a positive bias
+    and a gain, so that every coding part sees a handful of scale-table rows and some escapes.  Every GELU is to see arguments
+    on both sides of +-1: the hyper transforms' inner layers take the gain that undoes a default layer and a GELU
+    (MLIC_SLICE_GELU_GAIN; z and hyper gains are the smaller for it), the linear contexts' reprojection and depthwise mlp layer
+    gains of their own, and the LRPs' last layer is scaled down until tanh sees a largest |x| of 1 to 3 on latents of several
+    units."""
+    g = {k: np.float32(v) for k, v in MLIC_GAINS.items()}
+    for name in ("h_a.reduction.2", "h_a.reduction.4", "h_a.reduction.6", "h_s.increase.2.0", "h_s.increase.4", "h_s.increase.6.0"):
+        sd[name + ".weight"] *= np.float32(MLIC_SLICE_GELU_GAIN)
+    for name in [k for k in sd if k.endswith(".beta")]:
+        sd[name] = np.sqrt(uniform_like(name, seed, sd[name].shape, 0.5, 2.0) + GDN_PEDESTAL).astype(np.float32)
+    for name in [k for k in sd if k.endswith(".gamma")]:
+        c = sd[name].shape[0]
+        dense = uniform_like(name, seed, (c, c), -0.02, 0.08)  # a fifth of the raw values below the bound; gamma <= 0.0064
+        sd[name] = (sd[name] + dense).astype(np.float32)
+    for i in (0, 2, 4):
+        sd[f"g_a.analysis_transform.{i}.conv2.weight"] *= g["gdn_in"]
+    for i in (1, 3, 5):
+        sd[f"g_s.synthesis_transform.{i}.conv.weight"] *= g["igdn_in"]
+    sd["g_a.analysis_transform.6.weight"] *= g["y"]
+    sd["h_a.reduction.8.weight"] *= g["z"]
+    sd["h_s.increase.8.weight"] *= g["hyper"]
+    for i in range(slice_num):
+        _apply_stress_context(sd, seed, f"local_context.{i}.")
+        for kind in ("entropy_parameters_anchor", "entropy_parameters_nonanchor"):
+            p = f"{kind}.{i}."
+            _apply_stress_mlic_slice(sd, "EntropyParametersMLIC", p)
+            half = sd[p + "fusion.6.bias"].shape[0] // 2
+            sd[p + "fusion.6.weight"][:half] *= g["scale_w"]
+            sd[p + "fusion.6.bias"][:half] = g["scale_b"]  # chunk(2, 1): scales first
+            sd[p + "fusion.6.weight"][half:] *= g["mean_w"]
+        for kind in ("lrp_anchor", "lrp_nonanchor"):
+            _apply_stress_mlic_slice(sd, "LatentResidualPrediction", f"{kind}.{i}.")
+            sd[f"{kind}.{i}.lrp_transform.6.weight"] *= g["lrp_out"]
+        if i:
+            _apply_stress_context(sd, seed, f"global_inter_context.{i}.")
+            _apply_stress_context(sd, seed, f"global_intra_context.{i}.")
+            for kind in ("global_inter_context", "global_intra_context"):
+                sd[f"{kind}.{i}.reprojection.weight"] *= g["inter_reproj" if kind == "global_inter_context" else "intra_reproj"]
+                sd[f"{kind}.{i}.mlp.2.weight"] *= g["ctx_dw"]
+            _apply_stress_mlic_slice(sd, "ChannelContext", f"channel_context.{i}.")
 
 
 def synthetic_pair(index: int, H: int, W: int, config_id: int = 0, smooth: bool = False):

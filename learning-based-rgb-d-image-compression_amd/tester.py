@@ -14,9 +14,8 @@ from pathlib import Path
 import numpy as np
 import torch
 
-from .arch import model_config
+from .arch import mlic_config, model_config
 from .datautils import crop0, crop1, pad
-from .elic_united import modelZoo
 from .ioutils import filesize, read_body, read_uints, write_body, write_uints
 from .metrics import AverageMeter, compute_metrics, finish_metrics, metrics_batch
 
@@ -80,7 +79,8 @@ class TesterUnited:
         self.exp_name = args.experiment or self.get_exp_name(args.dataset, args.channel, args.model, args.quality)
         self.exp_dir_path = os.path.join("../experiments_test" if self.debug else "../experiments", self.exp_name)
         self.ckpt_dir_path = os.path.join(self.exp_dir_path, "checkpoints")
-        self.model_config = config or model_config()
+        # (playground/test.py:29-32: a model name with "MLIC" in it selects MLIC_model_config())
+        self.model_config = config or (mlic_config() if str(args.model).find("MLIC") != -1 else model_config())
         self.net = net
         self.epoch = 0
         if net is None:
@@ -91,12 +91,12 @@ class TesterUnited:
 
     # tester.py:55-108
     def get_net(self, model_config_, model_name, ckpt_path):
-        for name, model in modelZoo.items():
-            if model_name.find(name) != -1:
-                self.net = model(config=model_config_, channel=self.channel).eval()
-                break
-        else:
+        from . import elic_united
+
+        model = elic_united.zoo_lookup(model_name)  # modelZoo, then the younger entries (rgbd_amd.zoo_lookup)
+        if model is None:
             raise ValueError(f"model {model_name} is not provided by rgbd_amd (ELIC_united and ELIC only)")
+        self.net = model(config=model_config_, channel=self.channel).eval()
         best = os.path.join(self.ckpt_dir_path, "checkpoint_best_loss.pth.tar")
         if ckpt_path is None and os.path.exists(best):
             ckpt_path = best
