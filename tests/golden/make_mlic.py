@@ -24,6 +24,14 @@ build_indexes(), tensors by forward hooks.  The generator ASSERTS the fixture co
 stream; >= 50 % non-zero z symbols; in every GDN / IGDN layer max (norm - beta) / beta >= 1; every LRP's tanh sees a largest
 |x| in 0.8 ... 3.2; every GELU sees arguments below -1 and above +1; at most 0.5 % of the decisions lie inside the
 near-boundary windows of make_margins.py (ROUND_WINDOW = SCALE_WINDOW = 2e-4).
+
+The two cases of LRP_BULK (s2_448x192, s2_b2_192x128: the weights of s2_128x128 on a 28x12 and a 2 x 12x8 latent grid) replace
+the LRP condition, and only that one.  The band on the largest |x| is tuned to the 8x8 map, most of which is border: with the
+seed-3 weights the largest |x| per LRP is 1.67 ... 2.10 at 128x128, 2.61 ... 3.54 at 2x192x128 and 5.39 ... 9.62 at 448x192, so no
+weight set meets the band at both 128x128 and 448x192, and the three s2 cases have to share one weight set (one model across
+shapes).  What the band is there for -- the tanh neither linear nor saturated over what it sees -- is asked of the bulk of the
+values instead: in every LRP at least 85 % of the pre-tanh values have |x| <= 3.2 and at least 10 % have |x| >= 0.8 (the hook
+keeps the values, not only their maximum; the shares are printed for every case).  The three older cases keep the maximum band.
 """
 import hashlib
 import json
@@ -47,7 +55,11 @@ SCALE_WINDOW = 2e-4  # |scale / table_entry - 1| <= SCALE_WINDOW
 
 # name -> (N, M, slice_num, B, H, W, image config id, weight seed)
 CASES = {"s2_128x128": (64, 64, 2, 1, 128, 128, 81, 3), "s3_b2_128x192": (64, 96, 3, 2, 128, 192, 82, 4),
-         "full_128x128": (192, 320, 10, 1, 128, 128, 83, 5)}
+         "full_128x128": (192, 320, 10, 1, 128, 128, 83, 5),
+         # the weights of s2_128x128 at two more shapes (tests/test_gpu_mlic.py runs one model across the three)
+         "s2_448x192": (64, 64, 2, 1, 448, 192, 84, 3), "s2_b2_192x128": (64, 64, 2, 2, 192, 128, 85, 3)}
+LRP_BULK = {"s2_448x192", "s2_b2_192x128"}  # the LRP condition on the share of the values, not on the largest (docstring)
+LRP_BULK_BELOW, LRP_BULK_ABOVE = 0.85, 0.10  # share of the pre-tanh values with |x| <= 3.2, with |x| >= 0.8
 
 
 def sha_f32(t) -> str:
@@ -100,7 +112,7 @@ def case(mod, synth, name, N, M, S, B, H, W, config_id, seed):
     assert net.update(force=True)
     r, _ = synth.synthetic_batch(B, H, W, config_id=config_id)
     x = torch.from_numpy(r)
-    seen, gdn_ratio, gelu_range, pretanh, floats = {}, {}, {}, {}, {"x": [], "s": []}
+    seen, gdn_ratio, gelu_range, pretanh, pretanh_all, floats = {}, {}, {}, {}, {}, {"x": [], "s": []}
     hooks = [net.h_a.register_forward_hook(lambda m, i, o: seen.update(y=i[0].detach().clone(), z=o.detach().clone())),
              net.g_s.register_forward_hook(lambda m, i, o: seen.update(yhat=i[0].detach().clone()))]
 
@@ -123,6 +135,7 @@ def case(mod, synth, name, N, M, S, B, H, W, config_id, seed):
     def lrp_hook(label):
         def fn(m, i, o):
             pretanh[label] = max(pretanh.get(label, 0.0), float(o.detach().abs().max()))
+            pretanh_all.setdefault(label, []).append(o.detach().abs().reshape(-1).numpy().copy())
         return fn
 
     for label, m in net.named_modules():
@@ -182,6 +195,9 @@ def case(mod, synth, name, N, M, S, B, H, W, config_id, seed):
     print("   parts (non-zero %, max |s|, scale indexes):", [(round(100 * a), b, c) for a, b, c in stats])
     print("   GDN max (norm - beta) / beta:", {k.split("transform.")[1]: round(v, 2) for k, v in gdn_ratio.items()})
     print("   LRP max |x| in front of tanh:", {k[:-len(".lrp_transform")]: round(v, 2) for k, v in pretanh.items()})
+    lrp_share = {k: (float(np.mean(np.concatenate(v) <= 3.2)), float(np.mean(np.concatenate(v) >= 0.8))) for k, v in pretanh_all.items()}
+    print("   LRP share of the pre-tanh values with |x| <= 3.2, |x| >= 0.8 (%):",
+          {k[:-len(".lrp_transform")]: (round(100 * lo, 2), round(100 * hi, 2)) for k, (lo, hi) in lrp_share.items()})
     g_lo, g_hi = max(lo for lo, hi in gelu_range.values()), min(hi for lo, hi in gelu_range.values())
     print(f"   GELU arguments over {len(gelu_range)} modules: every minimum <= {g_lo:.2f}, every maximum >= {g_hi:.2f}", flush=True)
     for i, st in enumerate(stats):
@@ -189,7 +205,11 @@ def case(mod, synth, name, N, M, S, B, H, W, config_id, seed):
     assert esc >= 0.001, (name, esc)
     assert znz >= 0.5, (name, znz)
     assert len(gdn_ratio) == 6 and min(gdn_ratio.values()) >= 1.0, (name, gdn_ratio)
-    assert len(pretanh) == 2 * S and all(0.8 <= t <= 3.2 for t in pretanh.values()), (name, pretanh)
+    if name in LRP_BULK:
+        assert len(lrp_share) == 2 * S, (name, lrp_share)
+        assert all(lo >= LRP_BULK_BELOW and hi >= LRP_BULK_ABOVE for lo, hi in lrp_share.values()), (name, lrp_share)
+    else:
+        assert len(pretanh) == 2 * S and all(0.8 <= t <= 3.2 for t in pretanh.values()), (name, pretanh)
     assert g_lo < -1.0 and g_hi > 1.0, (name, {k: v for k, v in gelu_range.items() if v[0] >= -1.0 or v[1] <= 1.0})
     assert near <= 0.005, (name, near)
     assert np.abs(sym).max() < 32768 and idx.max() < 128 and int(zsym.abs().max()) < 32768

@@ -1,5 +1,8 @@
-"""MLIC++ (rgbd_amd.mlic; reference models/mlicpp.py) on the GPU, on the three fixtures the unmodified reference produced
-(tests/golden/mlic_*.npz, conditions asserted by tests/golden/make_mlic.py):
+"""MLIC++ (rgbd_amd.mlic; reference models/mlicpp.py) on the GPU, on the five fixtures the unmodified reference produced
+(tests/golden/mlic_*.npz, conditions asserted by tests/golden/make_mlic.py).  Three of them share one set of weights at three
+shapes: 128x128 (8x8 latents), 448x192 (28x12: taller than wide, a 7x3 z grid, 336 tokens = linear-attention chunks of
+128 / 128 / 80 and 128 / 40 per checkerboard half, 168 pixels per parity = ten full 16-pixel tiles of the fused parameter network
+and one of eight, a 14x3 tile grid of the local attention) and 2 x 192x128 (12x8, a 3x2 z grid, one y stream and two z streams):
 
  (a) the two kernels of csrc/mlic_loop.hip alone against numpy: rgbd_mlic_lrp_apply and rgbd_mlic_slot_clear at 2x2, 3x5 and
      8x12 with B = 1, 2, both parities, on a slot in the middle of a wider buffer; every pixel of the other parity and every
@@ -15,7 +18,11 @@
  (e) free-running identity with the reference: measured, recorded by RGBD_RECORD_MLIC_FLOORS=<path> into
      tests/golden/mlic_floors.json, asserted where the recording run observed it (the measured values are ceilings);
  (f) forward(): keys, and likelihood sums against the fixture within 8 * the reference's own fp32 - fp64 gap;
- (g) every refusal: nothing is written and the handle works afterwards.
+ (g) every refusal: nothing is written and the handle works afterwards;
+ (h) one model across shapes: small, large (the workspace regrows), batch of two, small (a larger call's leftovers in the
+     workspace), large, small, eagerly and then through the per-shape graph cache on a side stream: every call gives the bits of
+     a model that never saw another shape;
+ (i) the single-image tester on two files of different sizes, building the model itself from its name and a checkpoint file.
 """
 import json
 import os
@@ -31,7 +38,8 @@ from rgbd_amd._lib import lib
 pytestmark = pytest.mark.gpu
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-CASES = ["s2_128x128", "s3_b2_128x192", "full_128x128"]
+CASES = ["s2_128x128", "s3_b2_128x192", "full_128x128", "s2_448x192", "s2_b2_192x128"]
+SHAPES_OF_ONE_MODEL = ["s2_128x128", "s2_448x192", "s2_b2_192x128"]  # small, large, batch of two: one set of weights, key (3, 64, 64)
 FACTOR = 8.0
 _NETS, _RUNS, _FORCED = {}, {}, {}
 
@@ -44,14 +52,18 @@ def _key(g):
     return int(g["seed"]), int(g["N"]), int(g["M"])
 
 
+def _fresh_net(key):
+    require_gpu()
+    m = MLICPlusPlus(N=key[1], M=key[2], slice_num=key[2] // 32).eval()
+    m.load_state_dict(synth.synthetic_state_dict(key[0], model="MLIC", N=key[1], M=key[2]), strict=True)
+    assert m.update(force=True)
+    return m.to("cuda")
+
+
 def _net(key):
     """One model per configuration for the whole module (the full configuration's weights are large)."""
-    require_gpu()
     if key not in _NETS:
-        m = MLICPlusPlus(N=key[1], M=key[2], slice_num=key[2] // 32).eval()
-        m.load_state_dict(synth.synthetic_state_dict(key[0], model="MLIC", N=key[1], M=key[2]), strict=True)
-        assert m.update(force=True)
-        _NETS[key] = m.to("cuda")
+        _NETS[key] = _fresh_net(key)
     return _NETS[key]
 
 
@@ -185,8 +197,9 @@ def test_three_calls_in_a_row_give_the_same_streams(name):
         assert r["net"].compress(r["x"].cuda())["strings"] == r["out"]["strings"]
 
 
-def test_image_of_a_batch_and_alone_give_the_same_streams():
-    r = _run("s3_b2_128x192")
+@pytest.mark.parametrize("name", ["s3_b2_128x192", "s2_b2_192x128"])
+def test_image_of_a_batch_and_alone_give_the_same_streams(name):
+    r = _run(name)
     net, x = r["net"], r["x"].cuda()
     ones = [net.compress(x[i:i + 1]) for i in range(2)]
     net.per_image_streams = True
@@ -220,6 +233,78 @@ def test_captured_replay_equals_the_eager_call():
             again = round_trip()
             assert again[0] == first[0] and all(torch.equal(a, b) for a, b in zip(again[1:], first[1:]))
         assert net.graph_count() >= 3  # compress, decompress and forward of this shape replay
+    torch.cuda.synchronize()
+
+
+# ---- (h) one model across shapes ------------------------------------------------------------------------------------------------
+def _u32(a):
+    return np.ascontiguousarray(a).view(np.uint32)
+
+
+def _alone(name):
+    """What a model that never sees another shape gives for a fixture's image: the yardstick of test_one_model_across_shapes."""
+    g = _fixture(name)
+    assert _key(g) == (3, 64, 64)
+    net, x = _fresh_net(_key(g)), _images(g).cuda()
+    out = net.compress(x)
+    yhat = _u32(net.debug_tensor("yhat")).copy()
+    rec = net.decompress(out["strings"], out["shape"])
+    assert np.array_equal(_u32(net.debug_tensor("yhat")), yhat)
+    fw = net.forward(x)
+    assert np.array_equal(_u32(net.debug_tensor("yhat")), yhat)
+    want = dict(x=x, strings=out["strings"], shape=tuple(out["shape"]), yhat=yhat, xh=rec["x_hat"].cpu(), fw_xh=fw["x_hat"].cpu(),
+                fw_ly=fw["likelihoods"]["y_likelihoods"].cpu(), fw_lz=fw["likelihoods"]["z_likelihoods"].cpu())
+    assert all(bool(torch.isfinite(want[k]).all()) for k in ("xh", "fw_xh", "fw_ly", "fw_lz"))
+    return want
+
+
+def _same_compress(net, want, where):
+    out = net.compress(want["x"])
+    assert out["strings"] == want["strings"] and tuple(out["shape"]) == want["shape"], where
+    assert np.array_equal(_u32(net.debug_tensor("yhat")), want["yhat"]), where
+
+
+def _same_decompress(net, want, where):
+    rec = net.decompress(want["strings"], want["shape"])
+    assert np.array_equal(_u32(net.debug_tensor("yhat")), want["yhat"]), where
+    assert torch.equal(rec["x_hat"].cpu(), want["xh"]), where
+
+
+def _same_forward(net, want, where):
+    fw = net.forward(want["x"])
+    assert np.array_equal(_u32(net.debug_tensor("yhat")), want["yhat"]), where
+    assert torch.equal(fw["x_hat"].cpu(), want["fw_xh"]), where
+    assert torch.equal(fw["likelihoods"]["y_likelihoods"].cpu(), want["fw_ly"]), where
+    assert torch.equal(fw["likelihoods"]["z_likelihoods"].cpu(), want["fw_lz"]), where
+
+
+def test_one_model_across_shapes():
+    """Three models that each see one shape only (128x128, 448x192, 2 x 192x128; one set of weights) are the yardstick.  A fourth
+    model sees the shapes in turn: its workspace regrows at the first large call, and from then on every call finds what a call
+    of another shape left there -- the state buffer [B, h, w, 2M] included, whose slots are only written as they are decoded.
+    Every call gives the bits of the model that never saw another shape: streams, y_hat as uint32, x_hat under torch.equal.
+    Eagerly on the current stream first, then on a side stream through the per-shape graph cache (eager, captured, replayed)."""
+    small, large, two = (_alone(n) for n in SHAPES_OF_ONE_MODEL)
+    net = _fresh_net((3, 64, 64))
+    sizes = []
+    for step, (want, forward) in enumerate(((small, False), (large, True), (two, False), (small, True), (large, False), (small, False)), 1):
+        _same_compress(net, want, ("compress", step))
+        if step == 5:  # the small streams behind a large compress(), with no call of the small shape in between
+            _same_decompress(net, small, ("decompress of the small streams", step))
+        _same_decompress(net, want, ("decompress", step))
+        if forward:
+            _same_forward(net, want, ("forward", step))
+        sizes.append(net.workspace_bytes())
+    assert sizes[1] > sizes[0] and sizes[1:] == [sizes[1]] * 5, sizes  # the workspace grew at step 2, and only there
+    # on a side stream (the NULL stream is not captured: test_captured_replay_equals_the_eager_call)
+    clone = net.clone_shared()
+    with torch.cuda.stream(torch.cuda.Stream()):
+        for rnd in range(3):
+            for want in (small, large, two):
+                _same_compress(clone, want, ("compress, side stream", rnd))
+                _same_decompress(clone, want, ("decompress, side stream", rnd))
+                _same_forward(clone, want, ("forward, side stream", rnd))
+        assert clone.graph_count() >= 3
     torch.cuda.synchronize()
 
 
@@ -318,6 +403,51 @@ def test_forward(name):
         print(f"{name}: forward -log2 likelihood sum {k}: {got:.3f} vs the reference's {ref_bits:.3f}: relative {abs(got - ref_bits) / ref_bits:.2e}, "
               f"tolerance {tol:.2e} (8 * the reference's fp32 - fp64 gap)")
         assert abs(got - ref_bits) <= tol * ref_bits, (k, got, ref_bits, tol)
+
+
+# ---- (i) the tester on files ----------------------------------------------------------------------------------------------------
+def test_tester_single_on_files_mlic(tmp_path, monkeypatch):
+    """testing/tester_single.py with `-m MLIC --channel 3` and a checkpoint file: the tester itself looks the class up by name and
+    builds it from the configuration (tester.py get_net, net=None), and its loop changes shape between the two files."""
+    import types
+
+    from PIL import Image
+
+    import rgbd_amd
+
+    require_gpu()
+    root = tmp_path / "nyu_test"
+    (root / "rgb").mkdir(parents=True)
+    sizes = [(100, 150), (150, 100)]  # replicate0 pads them to 128 x 192 and 192 x 128
+    for i, (H, W) in enumerate(sizes):
+        r, _ = synth.synthetic_pair(i, H, W, config_id=6, smooth=True)
+        Image.fromarray((r.transpose(1, 2, 0) * 255).astype(np.uint8)).save(root / "rgb" / f"{i:04d}.png")
+    ckpt = tmp_path / "checkpoint.pth.tar"
+    torch.save({"state_dict": synth.synthetic_state_dict(3, model="MLIC", N=64, M=64), "epoch": 7}, ckpt)
+    work = tmp_path / "work"  # (the tester writes to ../experiments)
+    work.mkdir()
+    monkeypatch.chdir(work)
+    args = types.SimpleNamespace(channel=3, debug=False, experiment=None, dataset=str(root), model="MLIC", quality="1",
+                                 checkpoint=str(ckpt))
+    t = rgbd_amd.TesterSingle(args, rgbd_amd.arch.mlic_config(64, 64, 2), net=None)
+    assert t.exp_name == "nyuv2_rgb_MLIC_1"
+    assert type(t.net) is MLICPlusPlus and (t.net.N, t.net.M, t.net.slice_num, t.net.channel) == (64, 64, 2, 3) and t.epoch == 7
+    rows, meters = t.test_model(padding_mode="replicate0", padding=True)
+    rec_dir = t.get_rec_dir(padding=True, padding_mode="replicate0")
+    assert os.path.basename(rec_dir) == "7-padding-replicate0" and os.path.isdir(tmp_path / "experiments" / t.exp_name)
+    assert len(rows) == 2 and len(os.listdir(os.path.join(rec_dir, "rgb_rec"))) == 2
+    direct = _net((3, 64, 64))  # the same weights, loaded without the checkpoint file
+    for i, ((H, W), row) in enumerate(zip(sizes, rows)):
+        assert row["name"] == f"{i:04d}"
+        assert row["bpp"] == os.path.getsize(os.path.join(rec_dir, "rgb_bin", row["name"])) * 8.0 / (H * W)
+        assert np.isfinite(row["psnr"]) and row["enc_time"] > 0 and row["dec_time"] > 0
+        img, name = t.test_dataloader[i]
+        xp = rgbd_amd.datautils.pad(img.cuda(), "replicate0")
+        assert tuple(xp.shape[2:]) == (128 + 64 * i, 192 - 64 * i)
+        out = direct.compress(xp)
+        rec = direct.decompress(out["strings"], out["shape"])
+        xh, _ = t.decompress_one_image(os.path.join(rec_dir, "rgb_bin"), name[0], mode="replicate0")
+        assert torch.equal(xh, rec["x_hat"][:, :, :H, :W])
 
 
 # ---- (g) refusals ---------------------------------------------------------------------------------------------------------------

@@ -17,7 +17,7 @@ from rgbd_amd import MLICPlusPlus, arch, synth  # (the feature: without it this 
 from rgbd_amd._lib import lib
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-CASES = ["s2_128x128", "s3_b2_128x192", "full_128x128"]
+CASES = ["s2_128x128", "s3_b2_128x192", "full_128x128", "s2_448x192", "s2_b2_192x128"]
 ROUND_WINDOW = SCALE_WINDOW = 2e-4  # tests/golden/make_margins.py
 FAMILY = 19
 IGNORED, RECOVERY, DENSE, CONV, DECONV, GDN, LINEAR, ARRAY, QUANTILES, PIXEL_MLP = range(10)  # RGBD_KIND_* of include/rgbd_amd.h
@@ -218,6 +218,28 @@ def test_model_lookup_by_name():
     t = T(types.SimpleNamespace(channel=3, debug=False, experiment="x", model="MLIC", quality="2_2", checkpoint=None, dataset=None))
     assert t.seen[1] is MLICPlusPlus and (t.seen[0]["M"], t.seen[0]["slice_num"]) == (320, 10)
     assert MLICPlusPlus(config=t.seen[0], channel=3).slice_ch == [32] * 10
+
+
+@pytest.mark.parametrize("tester_name", ["TesterSingle", "TesterUnited"])
+def test_tester_takes_the_configuration_by_model_name(tester_name):
+    """playground/test.py:29-32: without a configuration of the caller's, a model name with "MLIC" in it selects MLIC's own and
+    every other name the common one (tester.py; no model is built: the tester is handed a stand-in net)."""
+    import types
+
+    import rgbd_amd
+
+    cls = getattr(rgbd_amd, tester_name)
+    for model, want in (("MLIC", arch.mlic_config()), ("MLIC_q3", arch.mlic_config()), ("nyuv2_rgb_MLIC_1", arch.mlic_config()),
+                        ("ELIC", arch.model_config()), ("STF", arch.model_config()), ("ckbd", arch.model_config()),
+                        ("ELIC_united", arch.model_config()), ("mlic", arch.model_config())):
+        args = types.SimpleNamespace(channel=3, debug=False, experiment="x", dataset=None, model=model, quality="1", checkpoint=None)
+        stand_in = object()
+        t = cls(args, None, net=stand_in)
+        assert t.model_config == want and t.net is stand_in and t.epoch == 0, model
+        assert (t.model_config == arch.mlic_config()) == ("MLIC" in model), model  # (the two configurations differ)
+    own = arch.mlic_config(64, 64, 2)
+    args = types.SimpleNamespace(channel=3, debug=False, experiment="x", dataset=None, model="MLIC", quality="1", checkpoint=None)
+    assert rgbd_amd.TesterSingle(args, own, net=object()).model_config is own  # the caller's configuration wins
 
 
 def test_host_side_refusals():
