@@ -2,6 +2,7 @@
 import numpy as np
 import pytest
 
+import gridcap_cases as gc
 from gpu_utils import require_gpu
 from oracle import coder
 
@@ -466,3 +467,58 @@ def test_ckbd_quant_index_misaligned_vs_oracle(n, c, h, w, misaligned, kat):
         prev = back
         for base in (yhat_base, back_base):  # the floats on either side of a misplaced y_hat are not the kernel's
             assert base is None or (float(base[0]) == GUARD and float(base[-1]) == GUARD)
+
+
+@pytest.mark.parametrize("misaligned", [False, True], ids=["aligned", "misaligned"])
+@pytest.mark.parametrize("case", gc.CKBD_CASES, ids=lambda c: "%(n)dx%(c)dx%(h)dx%(w)d" % c)
+def test_ckbd_quant_index_past_the_grid_cap(case, misaligned, kat):
+    """ckbd_nchw_kernel<0 / 2> past the 8192 x 256 grid cap (2 125 440 column pairs: two sweeps, the second one ragged), vectorised
+    and -- with y, means, scales and y_hat one float into their allocations -- scalar: test_ckbd_quant_index_vs_oracle's inputs,
+    oracle and bit-for-bit rule, anchor 1 then 0.  Symbols and indexes start from a pre-fill as well, the guard floats on either
+    side of a misplaced y_hat are compared with it, and two runs give the same bits."""
+    dev = require_gpu()
+    import ctypes
+
+    import torch
+
+    from oracle import elic_oracle as eo
+    from rgbd_amd._lib import check, lib
+
+    bc = gc.build_ckbd(case, eo, misaligned)
+    n, c, h, w, m, numel = case["n"], case["c"], case["h"], case["w"], bc["m"], bc["numel"]
+    tb = bc["table"].ctypes.data_as(ctypes.POINTER(ctypes.c_float))
+
+    def place(a):
+        """-> (the tensor the kernel sees, its whole allocation)"""
+        t = torch.from_numpy(np.ascontiguousarray(a, np.float32).reshape(-1))
+        if not misaligned:
+            out = t.to(dev)
+            assert out.data_ptr() % 8 == 0
+            return out, out
+        base = torch.full((numel + 2,), float(gc.CKBD_GUARD), device=dev)
+        base[1:1 + numel].copy_(t)
+        assert base[1:].data_ptr() % 8 == 4
+        return base[1:1 + numel], base
+
+    (yd, _), (md, _), (sd, _) = place(bc["y"]), place(bc["means"]), place(bc["scales"])
+    runs = []
+    for _ in range(2):
+        got = {}
+        yhat, yhat_base = place(np.full(numel, gc.CKBD_FSENT, np.float32))
+        prev = None
+        for anchor in (1, 0):
+            sym = torch.full((m,), gc.CKBD_ISENT, dtype=torch.int32, device=dev)
+            idx = torch.full((m,), gc.CKBD_ISENT, dtype=torch.int32, device=dev)
+            check(lib().rgbd_ckbd_quant_index(_vp(yd), _vp(md), _vp(sd), n, c, h, w, anchor, tb, _vp(sym), _vp(idx), _vp(yhat), None),
+                  "ckbd_quant_index")
+            torch.cuda.synchronize()
+            got[f"quant_a{anchor}"] = dict(sym=sym.cpu().numpy(), idx=idx.cpu().numpy(), yhat=yhat_base.cpu().numpy())
+            back, back_base = place(np.full(numel, gc.CKBD_FSENT, np.float32) if anchor else prev)
+            check(lib().rgbd_ckbd_dequant(_vp(sym), _vp(md), n, c, h, w, anchor, _vp(back), None), "ckbd_dequant")
+            torch.cuda.synchronize()
+            got[f"dequant_a{anchor}"] = dict(back=back_base.cpu().numpy())
+            prev = back.cpu().numpy()
+        runs.append(got)
+    for name, stage in bc["stages"].items():
+        assert stage["accept"](runs[0][name]) == [], name
+        assert all(gc.same_bits(runs[0][name][k], runs[1][name][k]) for k in runs[0][name]), name

@@ -58,6 +58,7 @@ import pytest
 import torch
 
 import convforms_cases as cc
+import gridcap_cases as gc
 from gpu_utils import require_gpu
 
 pytestmark = pytest.mark.gpu
@@ -261,6 +262,19 @@ def test_against_reference(c):
                     print(f"{what} {key}: max err {err.max():.3e}, bound {ref['bound_' + key]:.3e}")
                     assert (err <= ref["bound_" + key]).all(), _report_tol(got[key][..., mask], ref[key][..., mask], ref["bound_" + key],
                                                                             what + " " + key)
+
+
+def test_splitk_reducer_past_the_grid_cap():
+    """splitk_reduce_kernel past its 2048 x 256 grid cap (tests/gridcap_cases.py: 181 x 243 pixels of 12 float4s, two partial
+    planes, res1 and ReLU in the reducer; two sweeps, the second one ragged) under test_against_reference's rule: every computed
+    position written, within the case's derived bound of the fp64 reference; a second run gives the same bits."""
+    dev = require_gpu()
+    bc = gc.build_splitk(cc)
+    c = bc["case"]
+    outs = [run(c, [bc["ins"]], dev)[0] for _ in range(2)]
+    check_untouched(c, outs[0], c["id"])
+    assert bc["stages"]["splitk"]["accept"]({"y": outs[0]["y"]}) == []
+    assert _same_bits(outs[0]["y"], outs[1]["y"])
 
 
 def _chain_cases(c, ins):

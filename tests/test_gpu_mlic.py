@@ -7,7 +7,8 @@ and one of eight, a 14x3 tile grid of the local attention) and 2 x 192x128 (12x8
  (a) the two kernels of csrc/mlic_loop.hip alone against numpy: rgbd_mlic_lrp_apply and rgbd_mlic_slot_clear at 2x2, 3x5 and
      8x12 with B = 1, 2, both parities, on a slot in the middle of a wider buffer; every pixel of the other parity and every
      channel outside the slot keeps its bits; the updated values are rgbd_pw_half_tanh's followed by one fp32 add, bit for bit;
-     refusals write nothing;
+     refusals write nothing; the same at 2x182x361, past the kernels' grid cap (tests/gridcap_cases.py), and rgbd_pw_half_tanh
+     itself past its own;
  (b) self-consistency, asserted hard: decompress(compress(x)) returns and the decoder's y_hat is the encoder's bit for bit;
      image b of a batch and the image alone give the same streams; three calls in a row give the same streams; a replayed
      HIP graph gives what the eager call gave;
@@ -31,6 +32,7 @@ import numpy as np
 import pytest
 import torch
 
+import gridcap_cases as gc
 from gpu_utils import require_gpu
 from rgbd_amd import MLICPlusPlus, RgbdError, synth  # (the feature: without it this import fails)
 from rgbd_amd._lib import lib
@@ -173,6 +175,50 @@ def test_slot_kernels_alone(h, w, B):
         assert lib().rgbd_mlic_slot_clear(buf.data_ptr() + 4 * c0, cs, 32, B, h, w, 2, None) == -22
         torch.cuda.synchronize()
         assert torch.equal(buf, buf0)
+
+
+@pytest.mark.parametrize("case", gc.MLIC_CASES, ids=lambda c: "%(B)dx%(h)dx%(w)d" % c)
+def test_slot_kernels_past_the_grid_cap(case):
+    """Both kernels at 2 x 182 x 361 (527 072 quads against the 2048 x 256 grid cap: two sweeps, the second one ragged; an odd
+    width), both parities, under test_slot_kernels_alone's rules: the whole 96-channel buffer bit for bit after ONE call -- an
+    element updated in two sweeps would carry 0.5 * tanh twice -- and the same bits from a second call on a fresh copy."""
+    dev = require_gpu()
+    B, h, w = case["B"], case["h"], case["w"]
+    cs, c0 = gc.MLIC_CS, gc.MLIC_C0
+    buf0, r = gc.mlic_inputs(case)
+    rd, b0 = torch.from_numpy(r).to(dev), torch.from_numpy(buf0).to(dev)
+    bc = gc.build_mlic(case, _anchor, buf0, r, _half_tanh(rd).cpu().numpy())
+    for parity in (0, 1):
+        for kernel in ("lrp_apply", "slot_clear"):
+            outs = []
+            for _ in range(2):
+                buf = b0.clone()
+                if kernel == "lrp_apply":
+                    assert lib().rgbd_mlic_lrp_apply(buf.data_ptr() + 4 * c0, cs, rd.data_ptr(), 32, 32, B, h, w, parity, None) == 0
+                else:
+                    assert lib().rgbd_mlic_slot_clear(buf.data_ptr() + 4 * c0, cs, 32, B, h, w, parity, None) == 0
+                torch.cuda.synchronize()
+                outs.append(buf.cpu().numpy())
+            assert bc["stages"][f"{kernel}_p{parity}"]["accept"]({"buf": outs[0]}) == [], (kernel, parity)
+            assert gc.same_bits(outs[0], outs[1]), (kernel, parity)
+
+
+@pytest.mark.parametrize("case", gc.HALF_TANH_CASES, ids=lambda c: "%(npix)d" % c)
+def test_half_tanh_past_the_grid_cap(case):
+    """rgbd_pw_half_tanh (the reference of the slot tests above) itself, past its grid cap and between two unequal strides:
+    against numpy's 0.5 * tanh under test_slot_kernels_alone's bound; the channels behind C keep the pre-fill; NaN in the
+    input's pads; two calls, the same bits."""
+    dev = require_gpu()
+    bc = gc.build_half_tanh(case)
+    xd = torch.from_numpy(bc["x"]).to(dev)
+    outs = []
+    for _ in range(2):
+        y = torch.full((case["npix"], case["ycs"]), float(gc.HALF_TANH_SENT), device=dev)
+        assert lib().rgbd_pw_half_tanh(xd.data_ptr(), case["xcs"], y.data_ptr(), case["ycs"], case["npix"], case["C"], None) == 0
+        torch.cuda.synchronize()
+        outs.append(y.cpu().numpy())
+    assert bc["stages"]["half_tanh"]["accept"]({"y": outs[0]}) == []
+    assert gc.same_bits(outs[0], outs[1])
 
 
 # ---- (b) self-consistency -----------------------------------------------------------------------------------------------------

@@ -15,6 +15,7 @@ import os
 import pytest
 import torch
 
+import gridcap_cases as gc
 import mlic_context_cases as mc
 from gpu_utils import require_gpu
 
@@ -317,6 +318,21 @@ def test_dwconv_kernel(H, W, C, gelu, B):
     assert _bits(_dw_gpu(L, x, w, b, gelu, pad), out)
     for i in range(B):
         assert _bits(_dw_gpu(L, x[i:i + 1], w, b, gelu)[..., :C], out[i:i + 1, ..., :C])
+
+
+@pytest.mark.parametrize("case", gc.DWCONV_CASES, ids=lambda c: "gelu%(gelu)d" % c)
+def test_dwconv_kernel_past_the_grid_cap(case):
+    """1 x 86 x 85 x 288 = 2 105 280 outputs against the 8192 x 256 grid cap (two sweeps, the second one ragged), under
+    test_dwconv_kernel's reference and bound; the whole destination is compared, the channels behind C keep the sentinel, two
+    calls give the same bits, and so does the call without pad channels."""
+    L = _lib()
+    bc = gc.build_dwconv(case, mc, SENTINEL)
+    C = case["C"]
+    outs = [_dw_gpu(L, bc["x"], bc["w"], bc["b"], case["gelu"], gc.DWCONV_PAD).numpy() for _ in range(2)]
+    assert bc["stages"]["dwconv"]["accept"]({"y": outs[0]}) == []
+    assert gc.same_bits(outs[0], outs[1])
+    alone = _dw_gpu(L, bc["x"], bc["w"], bc["b"], case["gelu"]).numpy()
+    assert gc.same_bits(alone, outs[0][..., :C])
 
 
 def test_dwconv_rejects_bad_arguments():

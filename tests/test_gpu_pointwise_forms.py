@@ -20,6 +20,7 @@ import numpy as np
 import pytest
 import torch
 
+import gridcap_cases as gc
 import pointwise_forms_cases as pc
 from gpu_utils import require_gpu
 
@@ -291,6 +292,105 @@ def test_layout_kernels_each_direction_alone(N, C, H, W, cs, perm):
     nd = _dev(nhwc)
     back = _twice(N * C * H * W, W, lambda p: L.rgbd_pw_nhwc_to_nchw(nd.data_ptr(), N, C, H, W, cs, p, 0, perm, _stream()))
     assert pc.same_bits(back.reshape(N, C, H, W), src)
+
+
+# ---- past the grid cap -----------------------------------------------------------------------------------------------------
+# grid_for() cuts every grid at 2048 blocks of 256: above 524 288 work items the kernels' grid-stride loops take a second sweep.
+# Cases, owners and acceptance: tests/gridcap_cases.py (two sweeps, the second one ragged; copy and fill also three); the
+# builders, references and rules are the ones of the tests above.  The whole allocation -- destination and guard band -- goes
+# through the case's acceptance function; two calls must give the same bits.
+def _whole_twice(n, launch):
+    outs = []
+    for _ in range(2):
+        dst = torch.full((n,), pc.SENTINEL, device="cuda")
+        assert launch(dst.data_ptr()) == 0
+        torch.cuda.synchronize()
+        outs.append(dst.cpu().numpy())
+    assert pc.same_bits(outs[0], outs[1]), "two calls, different bits"
+    return outs[0]
+
+
+def _accepted(bc, got):
+    for name, stage in bc["stages"].items():
+        assert stage["accept"]({"dst": got}) == [], name
+
+
+@pytest.mark.parametrize("case", gc.COPY_CASES, ids=lambda c: "%(npix)dx%(C)d" % c)
+def test_copy_channels_past_the_grid_cap(case):
+    L = _lib()
+    bc = gc.build_copy(case)
+    sd = _dev(bc["src"])
+    npix, C, scs, dcs = (case[k] for k in ("npix", "C", "scs", "dcs"))
+    _accepted(bc, _whole_twice(npix * dcs + bc["guard"], lambda p: L.rgbd_pw_copy_channels(sd.data_ptr(), scs, p, dcs, npix, C, _stream())))
+
+
+@pytest.mark.parametrize("case", gc.FILL_CASES, ids=lambda c: "%(n)d" % c)
+def test_fill_zero_past_the_grid_cap(case):
+    L = _lib()
+    n = case["n"]
+    _accepted(gc.build_fill(case), _whole_twice(gc.FILL_LEAD + n + gc.FILL_GUARD, lambda p: L.rgbd_pw_fill_zero(p + 4 * gc.FILL_LEAD, n, _stream())))
+
+
+@pytest.mark.parametrize("case", gc.SCALE_CASES, ids=lambda c: "hw%(HW)d-mode%(mode)d" % c)
+def test_channel_scale_past_the_grid_cap(case):
+    """the se_cat_to form of test_channel_scale_into_the_halves_of_a_wider_tensor: both launches cross the cap"""
+    L = _lib()
+    bc = gc.build_scale(case)
+    c, HW, mode = pc.CAT, case["HW"], case["mode"]
+    od, td, gd = _dev(bc["own"]), _dev(bc["other"]), _dev(bc["gate"])
+    N, oc = c["N"], c["own_c"]
+
+    def both(p):
+        rc = L.rgbd_pw_channel_scale(od.data_ptr(), N, HW, c["own_cs"], oc, gd.data_ptr(), c["sstride"], mode, p, c["dst_cs"], _stream())
+        return rc or L.rgbd_pw_channel_scale(td.data_ptr(), N, HW, c["other_cs"], c["other_c"], gd.data_ptr() + 4 * oc, c["sstride"],
+                                             mode, p + 4 * oc, c["dst_cs"], _stream())
+
+    _accepted(bc, _whole_twice(N * HW * c["dst_cs"] + bc["guard"], both))
+
+
+@pytest.mark.parametrize("case", gc.BILINEAR_CASES, ids=lambda c: "%(h)dx%(w)d-%(H)dx%(W)d" % c)
+def test_bilinear_past_the_grid_cap(case):
+    L = _lib()
+    bc = gc.build_bilinear(case)
+    N, h, w, cs, H, W = (case[k] for k in ("N", "h", "w", "cs", "H", "W"))
+    xd = _dev(bc["x"])
+    _accepted(bc, _whole_twice(N * H * W * cs + bc["guard"],
+                               lambda p: L.rgbd_pw_bilinear(xd.data_ptr(), N, h, w, cs, p, H, W, None, None, 0, _stream())))
+
+
+@pytest.mark.parametrize("case", gc.MAXPOOL_CASES, ids=lambda c: "%(H)dx%(W)dx%(cs)d" % c)
+def test_maxpool7s3_past_the_grid_cap(case):
+    L = _lib()
+    bc = gc.build_maxpool(case)
+    N, H, W, cs = (case[k] for k in ("N", "H", "W", "cs"))
+    xd = _dev(bc["x"])
+    _accepted(bc, _whole_twice(bc["n"] + bc["guard"], lambda p: L.rgbd_pw_maxpool7s3(xd.data_ptr(), N, H, W, cs, p, None, None, _stream())))
+
+
+@pytest.mark.parametrize("case", gc.IM2COL_CASES, ids=lambda c: "%(N)dx%(H)dx%(W)d-kp%(KP)d" % c)
+def test_im2col5s2_past_the_grid_cap(case):
+    L = _lib()
+    bc = gc.build_im2col(case)
+    N, H, W, C, KP = (case[k] for k in ("N", "H", "W", "C", "KP"))
+    xd = _dev(bc["x"])
+    _accepted(bc, _whole_twice(bc["n"] + bc["guard"], lambda p: L.rgbd_pw_im2col5s2(xd.data_ptr(), N, H, W, pc.IM2COL_CS, C, p, KP, _stream())))
+
+
+@pytest.mark.parametrize("perm", [0, 1])
+def test_layout_kernels_past_the_grid_cap(perm):
+    """each direction at a shape of its own (the two work formulas differ), perm 0 and 1; clamp01 with perm 1"""
+    L = _lib()
+    case = gc.TO_NHWC_CASES[perm]
+    bc = gc.build_to_nhwc(case)
+    N, C, H, W, cs = (case[k] for k in ("N", "C", "H", "W", "cs"))
+    sd = _dev(bc["src"])
+    _accepted(bc, _whole_twice(bc["n"] + bc["guard"], lambda p: L.rgbd_pw_nchw_to_nhwc(sd.data_ptr(), N, C, H, W, p, cs, perm, _stream())))
+    case = gc.TO_NCHW_CASES[perm]
+    bc = gc.build_to_nchw(case)
+    N, C, H, W, cs, clamp01 = (case[k] for k in ("N", "C", "H", "W", "cs", "clamp01"))
+    xd = _dev(bc["x"])
+    _accepted(bc, _whole_twice(bc["n"] + bc["guard"],
+                               lambda p: L.rgbd_pw_nhwc_to_nchw(xd.data_ptr(), N, C, H, W, cs, p, clamp01, perm, _stream())))
 
 
 # ---- refusals --------------------------------------------------------------------------------------------------------------

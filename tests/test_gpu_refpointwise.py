@@ -11,6 +11,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import gridcap_cases as gc
 import refpointwise_cases as rc
 from gpu_utils import require_gpu
 
@@ -228,6 +229,53 @@ def test_deconv_s2_recipe_bit_exact(case):
     if case["act"] == rc.ACT_LEAKY:
         ref = F.leaky_relu(ref, 0.01)
     _torch_bound(got, ref.numpy())
+
+
+# ------------------------------------------------------------------------------------------------ past the grid caps
+# tests/gridcap_cases.py: sigmoid_gate_ref_kernel past 8192 x 256, small_conv_ref_kernel and the deconv route's gather / scatter
+# kernels past 2048 x 256 (two sweeps, the last one ragged; the 9- and 6-tap gathers three and two; the weight gather in a case
+# of its own).  Same oracle, same bit-for-bit
+# rule as the tests above, over the whole pre-filled output; twice the same bits.
+def test_sigmoid_gate_past_the_grid_cap():
+    dev = require_gpu()
+    bc = gc.build_sigmoid(rc)
+    c = bc["case"]
+    outs = [gpu_sigmoid_gate(bc["t"], bc["mul"], bc["res"], c["per_image"], c["threads"], dev) for _ in range(2)]
+    assert bc["stages"]["sigmoid"]["accept"]({"y": outs[0]}) == []
+    assert rc.bits_equal(outs[1], outs[0])
+
+
+def test_small_conv_past_the_grid_cap():
+    dev = require_gpu()
+    bc = gc.build_small_conv(rc)
+    outs = [gpu_small_conv(bc["case"], bc["x"], bc["wt"], bc["b"], bc["extra"], dev)[0] for _ in range(2)]
+    assert bc["stages"]["small_conv"]["accept"]({"y": outs[0]}) == []
+    assert np.array_equal(outs[1], outs[0])
+
+
+def test_deconv_s2_past_the_grid_cap():
+    dev = require_gpu()
+    bc = gc.build_deconv(rc)
+    outs = [gpu_deconv(bc["case"], bc["x"], bc["wt"], bc["b"], dev) for _ in range(2)]
+    for name, stage in bc["stages"].items():
+        assert stage["accept"]({"y": outs[0]}) == [], name
+    assert np.array_equal(outs[1], outs[0])
+    ref = F.leaky_relu(F.conv_transpose2d(torch.from_numpy(bc["x"]), torch.from_numpy(bc["wt"]), torch.from_numpy(bc["b"]), stride=2, padding=2,
+                                          output_padding=1), 0.01)
+    _torch_bound(outs[0], ref.numpy())
+
+
+def test_deconv_s2_wide_layer_past_the_grid_cap():
+    """gather_wslabs_kernel past 2048 x 256: its work is the layer's (cout_pad x taps x cin_pad / 4 float4s), so a 496 -> 496 layer
+    on 2 x 4 pixels crosses at the 9-tap phase.  test_deconv_s2_recipe_bit_exact's rule."""
+    dev = require_gpu()
+    bc = gc.build_deconv_wide(rc)
+    outs = [gpu_deconv(bc["case"], bc["x"], bc["wt"], bc["b"], dev) for _ in range(2)]
+    assert bc["stages"]["wslabs_ph0"]["accept"]({"y": outs[0]}) == []
+    assert np.array_equal(outs[1], outs[0])
+    ref = F.leaky_relu(F.conv_transpose2d(torch.from_numpy(bc["x"]), torch.from_numpy(bc["wt"]), torch.from_numpy(bc["b"]), stride=2, padding=2,
+                                          output_padding=1), 0.01)
+    _torch_bound(outs[0], ref.numpy())
 
 
 # ------------------------------------------------------------------------------------------------ refusals

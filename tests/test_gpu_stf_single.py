@@ -17,6 +17,7 @@ import numpy as np
 import pytest
 import torch
 
+import gridcap_cases as gc
 import stf_single_ref as ref
 from gpu_utils import require_gpu
 from oracle import coder
@@ -176,6 +177,44 @@ def test_lrp_tanh_alone_is_one_rounding():
     err = np.abs(out.cpu().numpy().astype(np.float64) - want) / ulp
     print(f"0.5 * tanh: max error {err.max():.3f} ulp")
     assert err.max() <= 1.5  # one rounding (0.5 ulp), counted double where the exact value sits just below a binade boundary
+
+
+@pytest.mark.parametrize("case", gc.SLICE_CASES, ids=lambda c: "%(B)dx%(C)dx%(h)dx%(w)d-pi%(per_image)d" % c)
+def test_slice_kernels_past_the_grid_cap(case):
+    """slice_part_kernel<0 / 2> and lrp_update_kernel past their 2048 x 256 grid cap (tests/gridcap_cases.py: two sweeps, the
+    second one ragged), against _np_slice and float64 under the rules of test_slice_kernels_against_numpy.  Every destination --
+    streams, pad channels, the element behind the stream -- is pre-filled and compared whole; two calls give the same bits; the
+    in-place LRP is compared after ONE call (an element done in two sweeps would carry the update twice)."""
+    require_gpu()
+    from rgbd_amd._lib import check, lib
+
+    L = lib()
+    bc = gc.build_slice(case, _np_slice, eo.scale_table().numpy())
+    B, C, h, w, per_image = (case[k] for k in ("B", "C", "h", "w", "per_image"))
+    s, n, st = bc["strides"], bc["n"], torch.cuda.current_stream().cuda_stream
+    dy, dmu, dsg, dl = (torch.from_numpy(bc[k]).cuda() for k in ("y", "mu", "sg", "lrp"))
+    tb = bc["table"].ctypes.data_as(ctypes.POINTER(ctypes.c_float))
+    ints = lambda: torch.full((n + 1,), gc.SLICE_ISENT, dtype=torch.int32).cuda()  # noqa: E731
+    flt = lambda cs: torch.full((B, h, w, cs), float(gc.SLICE_FSENT)).cuda()  # noqa: E731
+    runs = []
+    for _ in range(2):
+        dsym, didx, o0, o1, q0 = ints(), ints(), flt(s["cs0"]), flt(s["cs1"]), flt(s["cs0"])
+        check(L.rgbd_slice_quant_index(dy.data_ptr(), s["ycs"], dmu.data_ptr(), s["mcs"], dsg.data_ptr(), s["scs"], B, C, h, w, per_image,
+                                       bc["image_stride"], bc["slice_off"], tb, dsym.data_ptr(), didx.data_ptr(), o0.data_ptr(), s["cs0"],
+                                       o1.data_ptr(), s["cs1"], st), "slice_quant_index")
+        check(L.rgbd_slice_dequant(dsym.data_ptr(), dmu.data_ptr(), s["mcs"], B, C, h, w, per_image, bc["image_stride"], bc["slice_off"],
+                                   q0.data_ptr(), s["cs0"], None, 0, st), "slice_dequant")
+        a, b2, inplace = flt(s["cs1"]), flt(C), o0.clone()
+        check(L.rgbd_lrp_update(dl.data_ptr(), s["lcs"], o0.data_ptr(), s["cs0"], B * h * w, C, a.data_ptr(), s["cs1"], b2.data_ptr(), C,
+                                None, 0, st), "lrp_update")
+        check(L.rgbd_lrp_update(dl.data_ptr(), s["lcs"], inplace.data_ptr(), s["cs0"], B * h * w, C, inplace.data_ptr(), s["cs0"], None, 0,
+                                None, 0, st), "lrp_update in place")
+        torch.cuda.synchronize()
+        runs.append({k: v.cpu().numpy() for k, v in dict(sym=dsym, idx=didx, o0=o0, o1=o1, q0=q0, a=a, b2=b2, inplace=inplace).items()})
+    got = runs[0]
+    for name, stage in bc["stages"].items():
+        assert stage["accept"](got) == [], name
+    assert all(gc.same_bits(runs[0][k], runs[1][k]) for k in got), "two calls, different bits"
 
 
 # ---- 2. - 6. the layered contract on every fixture -----------------------------------------------------------------------
