@@ -334,7 +334,9 @@ int rgbd_elic_finalize(rgbd_elic* m);
 /* What finalize takes a state-dict entry for, decided by the family, the name and the shape alone (test hook; host only, no
  * GPU needed).  family: 0 ELIC_united, 1 ELIC, 2 STF_united, 3 ELIC_united_R2D, 4 STF, 5 checkerboard Cheng2020,
  * 6 Spatial_aligner, 7 LocalContext, 8 LinearGlobalInterContext, 9 LinearGlobalIntraContext, 13 SynthesisTransformPlus,
- * 15 EntropyParametersMLIC, 16 ChannelContext, 17 LatentResidualPrediction, 19 MLIC++ (10 to 12 are reserved, 14 and 18 unused).  Returns one of
+ * 15 EntropyParametersMLIC, 16 ChannelContext, 17 LatentResidualPrediction, 19 MLIC++, 20 ELIC_master_latent (10 to 12 are
+ * reserved, 14 and 18 unused).  Family 20 ignores ELIC_master's outer blocks (aux_encoder., master_encoder., master_decoder.,
+ * channel_aligner.).  Returns one of
  * the kinds below, or RGBD_EINVAL for another family, a NULL pointer, ndim outside 1..4 or an extent < 1. */
 enum {
     RGBD_KIND_IGNORED = 0,         /* read by no packer of its own: biases, betas, bottleneck matrices, buffers */
@@ -430,6 +432,30 @@ int rgbd_elic_create_ckbd(int32_t N, int32_t in_ch, rgbd_elic** out);
  * (:77-188).  rgbd_elic_get_refnum returns 0; rgbd_elic_set_coder(format 1) is refused; rgbd_elic_set_forced_symbols works for
  * modality 0.  Debug tensors: y, z, zhat, hyper, yhat. */
 int rgbd_elic_create_mlic(int32_t N, int32_t M, int32_t slice_num, int32_t in_ch, rgbd_elic** out);
+/* The latent codec of ELIC_master (models/elic_master.py; family 20): everything between the model's outer blocks -- g_a =
+ * AnalysisTransformEX(N, M, ch = 128) on f = cat(fv, fv_bar) (:67, 113-115), h_a / h_s (:70-71), the checkerboard slice loop with
+ * EntropyParametersEX nets over cat(local_ctx, channel_ctx, hyper_params) (:128-208; SE rescale, 1x1 / 3x3 / 5x5), and g_s =
+ * SynthesisTransformPlus(N, M, ch = N) under the guides up1..up3 of the aux decoder (:68, 213-216).  Feature_encoder,
+ * Feature_decoder and Channel_aligner are not part of it.  N must be 192 (sp1..sp3 are built with 192 channels whatever N is);
+ * slice_ch as for rgbd_elic_create_single.  State-dict names are the reference's (g_a.*, g_s.synthesis_transform.*, g_s.sp1|2|3.*
+ * with Linear weights as [out][in][1][1], h_a.*, h_s.*, local_context.*, channel_context.*, entropy_parameters_*.*,
+ * entropy_bottleneck.*).  Single-chain float arithmetic (rgbd_elic_get_refnum returns 0); rgbd_elic_set_coder(format 1) is
+ * refused; rgbd_elic_set_forced_symbols works for modality 0.  Debug tensors: y, z, zhat, hyper, yhat.
+ *   compress (:228-304): rgbd_elic_compress_single with f [B,128,H,W] (NCHW fp32, H and W multiples of 64): one y stream per call
+ *     (per_image_streams: per image), one z stream per image; g_s does not run and no guides are taken.
+ *   rgbd_master_latent_decompress (:319-378): the streams and up1 [B,N,H/8,W/8], up2 [B,N,H/4,W/4], up3 [B,N,H/2,W/2] -> f_hat
+ *     [B,N,H,W], the tensor of :378 before its cat with fv_bar; not clamped.
+ *   rgbd_master_latent_forward (:115-216, eval mode with quant = "ste"): f and the guides -> f_hat, y_likelihoods [B,M,H/16,W/16],
+ *     z_likelihoods [B,N,H/64,W/64].
+ * RGBD_EINVAL before any write: a NULL pointer (a missing guide included), H or W not a multiple of 64 (zh, zw < 1), B < 1, a
+ * tensor of 2^31 elements or more, a handle of another family; rgbd_elic_forward_single and rgbd_elic_decompress_single refuse a
+ * handle of this family (they take no guides). */
+int rgbd_master_latent_create(int32_t N, int32_t M, const int32_t* slice_ch, int32_t n_slices, rgbd_elic** out);
+int rgbd_master_latent_forward(rgbd_elic* m, const float* f_dev, const float* up1_dev, const float* up2_dev, const float* up3_dev,
+                               int32_t B, int32_t H, int32_t W, float* fhat_dev, float* lik_y, float* lik_z, void* stream);
+int rgbd_master_latent_decompress(rgbd_elic* m, const uint8_t* const* y, const int64_t* y_len, int32_t n_y, const uint8_t* const* z,
+                                  const int64_t* z_len, int32_t B, int32_t zh, int32_t zw, const float* up1_dev, const float* up2_dev,
+                                  const float* up3_dev, float* fhat_dev, void* stream);
 /* The two updates MLIC++'s slice loop makes to a 32-channel slot of its NHWC state buffer, alone (test hooks; asynchronous on
  * `stream`).  slot_dev [B][h][w][slot_cs] points at the slot's first channel inside a buffer of channel stride slot_cs;
  * parity 0: the pixels with (row + col) odd (the anchors), 1: the others.  Pixels of the other parity and channels outside the

@@ -15,6 +15,7 @@ from .stf_united import STF_united, SymmetricalTransFormerUnited  # noqa: F401,E
 from .stf import STF, SymmetricalTransFormer  # noqa: F401,E402
 from .ckbd import Cheng2020AnchorwithCheckerboard  # noqa: F401,E402
 from .mlic import MLICPlusPlus  # noqa: F401,E402
+from .master import MasterLatentCodec  # noqa: F401,E402  (in neither zoo table: DESIGN.md 7)
 
 # models/__init__.py:11-20, "the complex ones first": the testers take the first zoo name that is a substring of the model
 # name, so "ELIC_united_R2D" stands before "ELIC_united" before "ELIC", and "STF_united" before "STF"; "ckbd" comes last (no

@@ -176,6 +176,10 @@ def lib():
         "rgbd_elic_create_stf_single": (ctypes.c_int, [c_i32, ctypes.POINTER(c_vp)]),
         "rgbd_elic_create_ckbd": (ctypes.c_int, [c_i32, c_i32, ctypes.POINTER(c_vp)]),
         "rgbd_elic_create_mlic": (ctypes.c_int, [c_i32, c_i32, c_i32, c_i32, ctypes.POINTER(c_vp)]),
+        "rgbd_master_latent_create": (ctypes.c_int, [c_i32, c_i32, i32p, c_i32, ctypes.POINTER(c_vp)]),
+        "rgbd_master_latent_forward": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
+        "rgbd_master_latent_decompress": (ctypes.c_int, [c_vp, u8pp, i64p, c_i32, u8pp, i64p, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp,
+                                                          c_vp, c_vp]),
         "rgbd_mlic_lrp_apply": (ctypes.c_int, [c_vp, c_i32, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp]),
         "rgbd_mlic_slot_clear": (ctypes.c_int, [c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp]),
         "rgbd_pw_half_tanh": (ctypes.c_int, [c_vp, c_i32, c_vp, c_i32, c_i64, c_i32, c_vp]),
@@ -305,7 +309,8 @@ EXPORTS = ["rgbd_abi_version", "rgbd_set_blocking_sync", "rgbd_get_blocking_sync
            "rgbd_debug_synthesis_plus_guides", "rgbd_entropy_params_mlic_create", "rgbd_entropy_params_mlic_forward",
            "rgbd_entropy_params_mlic_set_fused", "rgbd_channel_context_create", "rgbd_channel_context_forward", "rgbd_lrp_create",
            "rgbd_lrp_forward", "rgbd_pixel_mlp4_pack", "rgbd_pixel_mlp4", "rgbd_elic_create_mlic", "rgbd_mlic_lrp_apply",
-           "rgbd_mlic_slot_clear", "rgbd_pw_half_tanh"]
+           "rgbd_mlic_slot_clear", "rgbd_pw_half_tanh", "rgbd_master_latent_create", "rgbd_master_latent_forward",
+           "rgbd_master_latent_decompress"]
 
 
 _BS_HOLDERS = 0

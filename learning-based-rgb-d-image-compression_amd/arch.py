@@ -703,6 +703,46 @@ def feature_decoder_entries(in_ch: int = 64, out_ch: int = 3) -> "OrderedDict[st
     return b.entries
 
 
+MASTER_OUTER_PREFIXES = ("aux_encoder.", "master_encoder.", "master_decoder.", "channel_aligner.")  # models/elic_master.py:104-107
+
+
+def elic_master_entries(config=None, channel: int = 3) -> "OrderedDict[str, Entry]":
+    """Every state_dict entry of ELIC_master (reference: models/elic_master.py:56-107), in the reference's order: the entropy
+    bottleneck (CompressionModel registers it first), g_a = AnalysisTransformEX(N, M, ch = 128), g_s = SynthesisTransformPlus(N,
+    M, ch = N), ELIC's h_a / h_s, local and channel contexts, the EntropyParametersEX nets (widths 2M + 2c / 2M + 4c, without
+    the channel context for slice 0), the Gaussian conditional, and the four outer blocks: aux_encoder (1 channel for a
+    3-channel master image and the other way round), master_encoder, master_decoder (N + 64 -> channel) and channel_aligner."""
+    if channel not in (1, 3):
+        raise ValueError(f"channel must be 3 or 1 (models/elic_master.py:100-103), got {channel}")
+    cfg = model_config() if config is None else config
+    N, M = int(cfg["N"]), int(cfg["M"])
+    slice_ch = list(cfg["slice_ch"])
+    elic = elic_entries(cfg, channel=2 * FEATURE_CH)  # (cat([fv, fv_bar]), :67, 113)
+    b = _Builder()
+    b.entropy_bottleneck("entropy_bottleneck", N)
+    p = "g_a.analysis_transform."
+    rows = [(name, e) for name, e in elic.items() if name.startswith(p)]
+    rows.sort(key=lambda r: int(r[0][len(p):].split(".")[0]))  # (stable: stage by stage, each stage in its own order)
+    b.entries.update(rows)
+    _prefixed(b, "g_s.", synthesis_plus_entries(N, M, ch=N))
+    b.entries.update((name, e) for name, e in elic.items() if name.startswith(("h_a.", "h_s.", "local_context.", "channel_context.")))
+    for fam, extra in (("entropy_parameters_anchor", 0), ("entropy_parameters_nonanchor", 2)):
+        for i, c in enumerate(slice_ch):
+            b.entropy_params(f"{fam}.{i}", 2 * M + (extra + (2 if i else 0)) * c, 2 * c)
+    b.gaussian_conditional("gaussian_conditional")
+    _prefixed(b, "aux_encoder.", feature_encoder_entries(1 if channel == 3 else 3))
+    _prefixed(b, "master_encoder.", feature_encoder_entries(channel))
+    _prefixed(b, "master_decoder.", feature_decoder_entries(N + FEATURE_CH, channel))
+    _prefixed(b, "channel_aligner.", channel_aligner_entries())
+    return b.entries
+
+
+def elic_master_latent_entries(config=None) -> "OrderedDict[str, Entry]":
+    """elic_master_entries without the outer blocks: what rgbd_amd.MasterLatentCodec holds (the image's channel count only
+    shapes the outer blocks)."""
+    return OrderedDict((name, e) for name, e in elic_master_entries(config, 3).items() if not name.startswith(MASTER_OUTER_PREFIXES))
+
+
 def ckbd_config(N: int = 192) -> Config:
     """Cheng2020 anchor model with the checkerboard context (models/Cheng2020withCKBD.py:46-50): M = N, one slice."""
     cfg = model_config()

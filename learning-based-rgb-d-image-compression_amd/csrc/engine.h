@@ -250,7 +250,7 @@ int small_conv_set_kblocks(SmallConvArgs* a, const int* lens, int n, int Kt);
 }  // namespace rgbd_rt
 using namespace rgbd_rt;
 
-// What an engine handle is: a codec (0-5, 19) or one module alone (6-9, 13, 15-17: no codec calls, no tables, its own forward
+// What an engine handle is: a codec (0-5, 19, 20) or one module alone (6-9, 13, 15-17: no codec calls, no tables, its own forward
 // entry point).  DESIGN.md and the history name the families by these numbers, so the numbers stay; 10-12 are reserved for the
 // held-back modules of ELIC_master and refused everywhere, and so are 14 and 18, which nothing has claimed
 // (tests/test_synplus_kinds_cpu.py and tests/test_mlic_slice_kinds_cpu.py hold them refused): the table has holes, not a
@@ -271,8 +271,10 @@ enum class Family : int {
     ChannelContext = 16,           // modules/transform/context.py:140-160, rgbd_channel_context_forward /
     LatentResidualPrediction = 17, // modules/transform/LRP.py:9-26, rgbd_lrp_forward only
     MLIC = 19,                     // MLIC++ (models/mlicpp.py): the codec over families 7-9 and 15-17
+    ELIC_master_latent = 20,       // the latent codec of ELIC_master (models/elic_master.py:115-216, 228-304, 319-378): g_a on 128
+                                   // channels, h_a, h_s, the checkerboard slice loop with EntropyParametersEX, the guided g_s
 };
-constexpr int kFamilies = 20;
+constexpr int kFamilies = 21;
 
 struct FamilyRow {
     const char* name;
@@ -309,6 +311,7 @@ constexpr FamilyRow kFamilyTable[kFamilies] = {
     {"LatentResidualPrediction",    0, false, false, 0, false, false},
     {nullptr,                       0, false, false, 0, false, false},  // 18: a hole
     {"MLIC",                        1, true,  false, 0, true,  true},   // (mlicpp.py:406-413: x_hat is not clamped)
+    {"ELIC_master_latent",          1, true,  false, 0, true,  false},  // (elic_master.py:378: g_s's output goes on to master_decoder)
 };
 constexpr bool family_ok(int f) { return f >= 0 && f < kFamilies && kFamilyTable[f].name; }
 constexpr const FamilyRow& family_row(Family f) { return kFamilyTable[(int)f]; }
@@ -320,8 +323,8 @@ struct rgbd_elic {
     const FamilyRow& row() const { return family_row(family); }
     bool single() const { return row().nm == 1; }
     int in_ch = 3;    // image channels of the single-modal codecs (Spatial_aligner: channels of x and guided; contexts: dim;
-                      // SynthesisTransformPlus: M; the per-slice networks of MLIC++: in_dim)
-    int out_ch = 0;   // module handles: output channels
+                      // SynthesisTransformPlus: M; the per-slice networks of MLIC++: in_dim; ELIC_master_latent: channels of f)
+    int out_ch = 0;   // module handles: output channels; ELIC_master_latent: channels of f_hat (a codec with out_ch 0 returns in_ch)
     int ctx_heads = 0;  // contexts: num_heads
     // what the call paths (engine.hip) need to know about one versus two modalities; arrays are read at [0, nm)
     struct Modes {
@@ -329,14 +332,16 @@ struct rgbd_elic {
         const char* sfx[2];  // suffix of the debug-tensor names: "y" / "y_r", "y_d"
         const char* eb[2];   // prefix of the entropy bottleneck's tensors
         int img_ch[2];       // image channels
+        int out_ch[2];       // channels of x_hat (img_ch, but for ELIC_master_latent: f has 128 channels, f_hat N)
         int clamp;           // FamilyRow::clamp
         bool forward_names_z;  // FamilyRow::forward_names_z
     };
     Modes modes() const
     {
         const FamilyRow& f = row();
-        if (single()) return {1, {"", ""}, {"", ""}, {in_ch, in_ch}, f.clamp, f.forward_names_z};
-        return {2, {"_r", "_d"}, {"rgb_", "depth_"}, {3, 1}, f.clamp, f.forward_names_z};
+        const int oc = out_ch ? out_ch : in_ch;
+        if (single()) return {1, {"", ""}, {"", ""}, {in_ch, in_ch}, {oc, oc}, f.clamp, f.forward_names_z};
+        return {2, {"_r", "_d"}, {"rgb_", "depth_"}, {3, 1}, {3, 1}, f.clamp, f.forward_names_z};
     }
     std::vector<int> slice_ch;
     std::map<std::string, HostTensor> raw;
@@ -763,9 +768,17 @@ struct rgbd_elic {
     static constexpr SliceLoop kLoopSingle = {{{kLocR, kChR, kHypR, kSegEnd}, {kSegEnd}},
                                               {{{0, kChR, false}, {}}, {{0, kLocR, false}, {}}},
                                               {0, 0, 0}, {"", ""}, false, true, false, false, false};
+    // ELIC_master's latent codec (elic_master.py:148,172,188): kLoopSingle's layout with EntropyParametersEX nets (SE rescale,
+    // 1x1 / 3x3 / 5x5: entropy.py:56-78), whose 3x3 and 5x5 layers mix positions: only the last layer takes the checkerboard half
+    static constexpr SliceLoop kLoopMaster = {{{kLocR, kChR, kHypR, kSegEnd}, {kSegEnd}},
+                                              {{{0, kChR, false}, {}}, {{0, kLocR, false}, {}}},
+                                              {0, 0, 0}, {"", ""}, true, false, false, false, false};
     const SliceLoop& slice_loop_family() const
     {
-        return family == Family::ELIC ? kLoopSingle : family == Family::ELIC_united_R2D ? kLoopR2D : kLoopUnited;
+        return family == Family::ELIC                 ? kLoopSingle
+               : family == Family::ELIC_master_latent ? kLoopMaster
+               : family == Family::ELIC_united_R2D    ? kLoopR2D
+                                                      : kLoopUnited;
     }
 
     // The parameter net of one part: [SE rescale,] three convs (1x1 / 3x3 / 5x5 or 1x1 x 3; padding k / 2) with ReLU between.
@@ -871,6 +884,11 @@ struct rgbd_elic {
     Act g_a1(const Act& x);
     Act g_s1(const Act& yhat);
     const Act* mid_dst = nullptr;  // set around g_s_family by a return_mid call (run_forward / run_decompress)
+    // ELIC_master_latent (family 20): g_a = AnalysisTransformEX(N, M, ch = 128), the kAna15 walk on a 128-channel input, and
+    // g_s = SynthesisTransformPlus(N, M, ch = N) under "g_s.", family 13's guided walk (elic_master.py:67-68)
+    Act g_s_master(const Act& yhat);
+    const Act* guide_src = nullptr;  // up1..up3 of the call in progress (NHWC, converted in the prologue): set by guides_begin
+    int guides_begin(const float* const up_dev[3], int B, int H, int W, Act up[3]);
     // analysis.py:207-216
     Act h_a1(const Act& y);
     // synthesis.py:276-285
@@ -1030,10 +1048,14 @@ struct rgbd_elic {
     int run_compress(int nm, In2 x_dev, int B, int H, int W, int per_image, const Latents* lat = nullptr);
     // up: NULL, or (single-modal ELIC only) the three NCHW tensors of return_mid: [B,N,H/8,W/8], [B,N,H/4,W/4], [B,N,H/2,W/2]
     using Mid3 = std::array<float*, 3>;
-    int run_forward(int nm, In2 x_dev, int B, int H, int W, Out2 xhat_dev, Out2 ly, Out2 lz, const Mid3* up = nullptr);
+    // guides: NULL, or (ELIC_master_latent only, where they are required for every call that runs g_s) the three NCHW tensors
+    // up1..up3 of the aux decoder, shaped like Mid3
+    using Guide3 = std::array<const float*, 3>;
+    int run_forward(int nm, In2 x_dev, int B, int H, int W, Out2 xhat_dev, Out2 ly, Out2 lz, const Mid3* up = nullptr,
+                    const Guide3* guides = nullptr);
     int run_decompress(int nm, const uint8_t* const* ys[2], const int64_t* ylen[2], int n_y, const uint8_t* const* zs[2],
                        const int64_t* zlen[2], int B, int h, int w, Out2 xhat_dev, const Latents* lat = nullptr,
-                       const Mid3* up = nullptr);
+                       const Mid3* up = nullptr, const Guide3* guides = nullptr);
     void mids_begin(int B, int H, int W, Act mid[3]);  // workspace of up1..up3; g_s1 fills it while mid_dst points at it
     int mids_out(const Act mid[3], int B, int H, int W, const Mid3& up);
     int run_aligner(const float* x_dev, const float* guided_dev, int B, int H, int W, float* out_dev);

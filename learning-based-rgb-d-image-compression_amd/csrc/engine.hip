@@ -337,11 +337,13 @@ void rgbd_elic::y_encode(int nm, int B, const EncBufs& e)
 
 // ---- the family hooks: ELIC_united (family 0, models/elic_united.py), ELIC (1, models/elic.py), STF_united (2,
 // models/stf_united.py), ELIC_united_R2D (3, models/elic_united_R2D.py), STF (4, models/stf.py) and the checkerboard Cheng2020
-// (5, models/Cheng2020withCKBD.py) and MLIC++ (14, models/mlicpp.py) share one call path per direction; a family enters through the four hooks below ----------
+// (5, models/Cheng2020withCKBD.py), MLIC++ (19, models/mlicpp.py) and the latent codec of ELIC_master (20, models/elic_master.py)
+// share one call path per direction; a family enters through the four hooks below ----------
 void rgbd_elic::g_a_family(const Act x[2], Act y[2])
 {
     switch (family) {
-    case Family::ELIC: y[0] = g_a1(x[0]); break;
+    case Family::ELIC:
+    case Family::ELIC_master_latent: y[0] = g_a1(x[0]); break;  // (AnalysisTransformEX with ch = 3 / 1 or 128: the same names)
     case Family::STF_united: g_a_stf(x[0], x[1], &y[0], &y[1]); break;
     case Family::ELIC_united_R2D: g_a_r2d(x, y); break;
     case Family::STF: y[0] = g_a_stf1(x[0]); break;
@@ -354,7 +356,8 @@ void rgbd_elic::g_a_family(const Act x[2], Act y[2])
 void rgbd_elic::h_a_family(const Act y[2], Act z[2])
 {
     switch (family) {
-    case Family::ELIC: z[0] = h_a1(y[0]); break;
+    case Family::ELIC:
+    case Family::ELIC_master_latent: z[0] = h_a1(y[0]); break;
     case Family::STF: z[0] = h_a_stf1(y[0]); break;
     case Family::Cheng2020_ckbd: z[0] = h_a_ckbd(y[0]); break;
     case Family::MLIC: z[0] = h_a_mlic(y[0]); break;
@@ -371,6 +374,7 @@ void rgbd_elic::g_s_family(const Act yhat[2], Act xhat[2])
     case Family::STF: xhat[0] = g_s_stf1(yhat[0]); break;
     case Family::Cheng2020_ckbd: xhat[0] = g_s_ckbd(yhat[0]); break;
     case Family::MLIC: xhat[0] = g_s_mlic(yhat[0]); break;
+    case Family::ELIC_master_latent: xhat[0] = g_s_master(yhat[0]); break;
     default: g_s(yhat, xhat);
     }
 }
@@ -379,6 +383,7 @@ void rgbd_elic::g_s_family(const Act yhat[2], Act xhat[2])
 // coding loop (symbols when cd.encode, from the streams when not, likelihoods into cd.lik[m] when cd.estimate).  y: the
 // latents (null when decoding); hyp: the hyper tensors when the caller has them already (the Latents path; zhat is null then).
 //   ELIC: y_hat = round(y - mean) + mean slice by slice through the checkerboard slice loop (elic.py:180-251 / 268-316).
+//   ELIC_master_latent: the same buffers and loop under kLoopMaster (elic_master.py:128-208 / 248-300 / 329-371).
 //   STF: the y stream is ONE stream for all slices of all images of the call (per-image streams: one per image), coded after
 //     the last slice; the decoder resumes its rANS state slice by slice.  A batch decompresses as the inverse of compress()
 //     (the reference's decompress handles one image only, stf.py:799).
@@ -391,7 +396,8 @@ void rgbd_elic::latent_family(Coding& cd, int B, int h, int w, const Act* y, con
 {
     const Modes mo = modes();
     switch (family) {
-    case Family::ELIC: {
+    case Family::ELIC:
+    case Family::ELIC_master_latent: {
         Act hyper = h_s1(zhat[0]);
         named["hyper"] = hyper;
         yhat[0] = alloc(B, h, w, M);
@@ -582,11 +588,12 @@ int rgbd_elic::run_compress(int nm, In2 x_dev, int B, int H, int W, int per_imag
 // eval-mode forward(): elic_united.py:234-263 with quant == "ste" (round in eval), elic.py:60-161, stf.py:618-678,
 // Cheng2020withCKBD.py:52-71; likelihoods as in entropy_models.py:391-428 (factorised prior) and :534-558 (Gaussian
 // conditional) instead of symbols
-int rgbd_elic::run_forward(int nm, In2 x_dev, int B, int H, int W, Out2 xhat_dev, Out2 ly, Out2 lz, const Mid3* up)
+int rgbd_elic::run_forward(int nm, In2 x_dev, int B, int H, int W, Out2 xhat_dev, Out2 ly, Out2 lz, const Mid3* up, const Guide3* guides)
 {
     const Modes mo = modes();
     if (nm != mo.nm) return RGBD_ESTATE;
     if (up && family != Family::ELIC) return RGBD_EINVAL;
+    if ((guides != nullptr) != (family == Family::ELIC_master_latent)) return RGBD_EINVAL;
     const int h = H / 16, w = W / 16, zh = H / 64, zw = W / 64;
     begin_call(B, true);  // forward() is one reference call on the whole batch
     Act x[2];
@@ -596,6 +603,9 @@ int rgbd_elic::run_forward(int nm, In2 x_dev, int B, int H, int W, Out2 xhat_dev
         for (int m = 0; m < nm && !r; ++m) r = launch_nchw_to_nhwc16(x_dev[m], B, mo.img_ch[m], H, W, x[m].p, x[m].cs, s);
         if (r) return r;
     }
+    Act guide[3];
+    if (guides)
+        if (const int r = guides_begin(guides->data(), B, H, W, guide)) return r;
     // ==== body: captured into / replayed from a HIP graph per call shape (the prologue above reads the caller's pointers,
     // the epilogue below writes them) ====
     Act out[3][2];  // x_hat, likelihoods of y, likelihoods of z: cur_ge->out[2 * k + m]
@@ -619,6 +629,7 @@ int rgbd_elic::run_forward(int nm, In2 x_dev, int B, int H, int W, Out2 xhat_dev
         if (up) mids_begin(B, H, W, mid);
         g_s_family(yhat, out[0]);
         mid_dst = nullptr;
+        guide_src = nullptr;
         for (int m = 0; m < nm; ++m) out[1][m] = cd.lik[m];
         if (cur_ge && !dry()) {
             for (int k = 0; k < 3; ++k)
@@ -630,11 +641,12 @@ int rgbd_elic::run_forward(int nm, In2 x_dev, int B, int H, int W, Out2 xhat_dev
             for (int m = 0; m < nm; ++m) out[k][m] = cur_ge->out[2 * k + m];
         for (int k = 0; k < 3 && up; ++k) mid[k] = cur_ge->out[2 * k + 1];
     }
+    guide_src = nullptr;  // (a replayed body never reads it)
     if (const int r = finish_body()) return r;
     if (dry()) return RGBD_OK;
     int r = 0;  // (not clamped: stf.py:677)
     for (int m = 0; m < nm && !r; ++m)
-        r = launch_nhwc_to_nchw_clamp(out[0][m].p, B, mo.img_ch[m], H, W, out[0][m].cs, xhat_dev[m], 0, s);
+        r = launch_nhwc_to_nchw_clamp(out[0][m].p, B, mo.out_ch[m], H, W, out[0][m].cs, xhat_dev[m], 0, s);
     for (int m = 0; m < nm && !r; ++m) r = launch_nhwc_to_nchw_clamp(out[1][m].p, B, M, h, w, out[1][m].cs, ly[m], 0, s, perm());
     for (int m = 0; m < nm && !r; ++m) r = launch_nhwc_to_nchw_clamp(out[2][m].p, B, N, zh, zw, out[2][m].cs, lz[m], 0, s, perm());
     if (!r && up) r = mids_out(mid, B, H, W, *up);
@@ -646,6 +658,18 @@ int rgbd_elic::run_forward(int nm, In2 x_dev, int B, int H, int W, Out2 xhat_dev
 // copies them into workspace of the call that lives until its end (the addresses a captured graph replays); like x_hat they go
 // to the caller's NCHW tensors in the epilogue, which is never captured: a replay must not write to the tensors of the call
 // that was captured.
+// The guides of ELIC_master_latent (elic_master.py:213-216, 375-378): up1..up3 [B,N,H/8,W/8], [B,N,H/4,W/4], [B,N,H/2,W/2] of the aux
+// decoder, converted to NHWC workspace of the call in the prologue, as run_synthesis_plus takes them: the body reads workspace
+// addresses only, so a replayed graph sees the tensors of its own call.
+int rgbd_elic::guides_begin(const float* const up_dev[3], int B, int H, int W, Act up[3])
+{
+    for (int k = 0; k < 3; ++k) up[k] = alloc(B, H >> (3 - k), W >> (3 - k), N);
+    for (int k = 0; k < 3 && !dry(); ++k)
+        if (const int r = launch_nchw_to_nhwc16(up_dev[k], B, N, up[k].h, up[k].w, up[k].p, up[k].cs, s)) return r;
+    guide_src = up;
+    return RGBD_OK;
+}
+
 void rgbd_elic::mids_begin(int B, int H, int W, Act mid[3])
 {
     for (int k = 0; k < 3; ++k) mid[k] = alloc(B, H >> (3 - k), W >> (3 - k), N);
@@ -786,11 +810,13 @@ int rgbd_elic::run_slice_net(const float* const* seg_dev, const int* seg_c, int 
 
 // decompress: elic_united.py:462-578, elic.py:255-325, stf.py:766-816, Cheng2020withCKBD.py:138-174; h x w: the latent grid
 int rgbd_elic::run_decompress(int nm, const uint8_t* const* ys[2], const int64_t* ylen[2], int n_y, const uint8_t* const* zs[2],
-                              const int64_t* zlen[2], int B, int h, int w, Out2 xhat_dev, const Latents* lat, const Mid3* up)
+                              const int64_t* zlen[2], int B, int h, int w, Out2 xhat_dev, const Latents* lat, const Mid3* up,
+                              const Guide3* guides)
 {
     const Modes mo = modes();
     if (nm != mo.nm) return RGBD_ESTATE;
     if (up && (family != Family::ELIC || lat)) return RGBD_EINVAL;
+    if ((guides != nullptr) != (family == Family::ELIC_master_latent) || (guides && lat)) return RGBD_EINVAL;
     const int zh = lat ? 1 : h / 4, zw = lat ? 1 : w / 4, H = h * 16, W = w * 16;
     const int64_t T = (int64_t)M * h * w, Tz = (int64_t)N * zh * zw;
     const int per_image = (n_y == B && !(B == 1)) ? 1 : (n_y == 1 ? (B == 1 ? 1 : 0) : -1);
@@ -810,6 +836,9 @@ int rgbd_elic::run_decompress(int nm, const uint8_t* const* ys[2], const int64_t
             r = launch_nchw_to_nhwc16(lat->hyp[m], B, 2 * M, h, w, hyp[m].p, hyp[m].cs, s, perm());
         if (r) return r;
     }
+    Act guide[3];
+    if (guides)
+        if (const int r = guides_begin(guides->data(), B, H, W, guide)) return r;
 
     // ==== body: captured into / replayed from a HIP graph per call shape ================================================
     Act out[2];  // what the epilogue hands back: x_hat (or y_hat for decompress_united) per modality: cur_ge->out[m]
@@ -834,6 +863,7 @@ int rgbd_elic::run_decompress(int nm, const uint8_t* const* ys[2], const int64_t
             g_s_family(yhat, out);
             mid_dst = nullptr;
         }
+        guide_src = nullptr;
         if (cur_ge && !dry()) {
             for (int m = 0; m < nm; ++m) cur_ge->out[m] = out[m];
             for (int k = 0; k < 3 && up; ++k) cur_ge->out[2 * k + 1] = mid[k];
@@ -842,6 +872,7 @@ int rgbd_elic::run_decompress(int nm, const uint8_t* const* ys[2], const int64_t
         for (int m = 0; m < nm; ++m) out[m] = cur_ge->out[m];
         for (int k = 0; k < 3 && up; ++k) mid[k] = cur_ge->out[2 * k + 1];
     }
+    guide_src = nullptr;  // (a replayed body never reads it)
     if (const int r = finish_body()) return r;
     if (dry()) return RGBD_OK;
 
@@ -849,7 +880,7 @@ int rgbd_elic::run_decompress(int nm, const uint8_t* const* ys[2], const int64_t
     int r = 0;
     for (int m = 0; m < nm && !r; ++m)
         r = lat ? launch_nhwc_to_nchw_clamp(out[m].p, B, M, h, w, out[m].cs, lat->yhat[m], 0, s, perm())
-                : launch_nhwc_to_nchw_clamp(out[m].p, B, mo.img_ch[m], H, W, out[m].cs, xhat_dev[m], mo.clamp, s);
+                : launch_nhwc_to_nchw_clamp(out[m].p, B, mo.out_ch[m], H, W, out[m].cs, xhat_dev[m], mo.clamp, s);
     if (!r && up) r = mids_out(mid, B, H, W, *up);
     if (!r && d.err) {  // the caller's wait (run_call) reads the flag: a damaged wide stream fails the call
         if (!res_pin) HIP_TRY(hipHostMalloc((void**)&res_pin, kResPinBytes, hipHostMallocDefault));

@@ -136,6 +136,12 @@ inline bool one_or_b(int32_t n_y, int32_t B) { return n_y == 1 || n_y == B; }
 // MLIC++ runs 3x3 layers on the z grid (h_a, h_s): a z map of one row or one column is refused before any launch, as the 3x3
 // modules refuse H < 2 or W < 2 -- image sides of at least 128
 inline bool z_grid_ok(const rgbd_elic* m, int32_t zh, int32_t zw) { return m->family != Family::MLIC || (zh >= 2 && zw >= 2); }
+// ELIC_master_latent: f [B,128,H,W] and f_hat [B,N,H,W] are full-resolution tensors of many channels; the layout kernels index
+// them with 32 bits
+inline bool master_ok(const rgbd_elic* m, int32_t B, int64_t H, int64_t W)
+{
+    return m->family == Family::ELIC_master_latent && (int64_t)B * std::max(m->in_ch, m->out_ch) * H * W <= 0x7fffffff;
+}
 
 // ---- finalize, first half: what a tensor of the state dict is ---------------------------------------------------------
 bool ends_with(const std::string& s, const char* suf)
@@ -152,6 +158,11 @@ int tensor_kind(Family f, const std::string& name, const int64_t* shape, int ndi
     // MLIC++ holds ten of each context and per-slice network under these prefixes (mlicpp.py:40-75); behind the prefix the names
     // are the module handles' and so are the kinds
     const bool mlic = f == Family::MLIC;
+    // ELIC_master_latent reads none of ELIC_master's outer blocks (elic_master.py:104-107): a checkpoint's entries under these
+    // prefixes are not this family's
+    if (f == Family::ELIC_master_latent)
+        for (const char* outer : {"aux_encoder.", "master_encoder.", "master_decoder.", "channel_aligner."})
+            if (name.rfind(outer, 0) == 0) return RGBD_KIND_IGNORED;
     const bool mlic_local = mlic && name.rfind("local_context.", 0) == 0;
     const bool mlic_ctx = mlic_local || (mlic && (name.rfind("global_inter_context.", 0) == 0 || name.rfind("global_intra_context.", 0) == 0));
     if (ends_with(name, "recovery.weight") && ndim == 4 && shape[2] == 2 && shape[3] == 2) return RGBD_KIND_RECOVERY_DECONV;
@@ -168,7 +179,7 @@ int tensor_kind(Family f, const std::string& name, const int64_t* shape, int ndi
     if (weight && ndim == 4) {
         // ConvTranspose2d layers: g_s stages 1/6/12/17 and the h_s deconvs (single-modal ELIC: g_s stages 1/5/10/14 and
         // h_s.increase.*; stage numbers that are not a bare "<stage>.weight" in the other model belong to blocks with
-        // sub-names, so the union is unambiguous)
+        // sub-names, so the union is unambiguous; ELIC_master_latent: "g_s.synthesis_transform.{1,5,10,14}.weight", the same rule)
         bool transposed = name.find(".deconv.") != std::string::npos || (!mlic && name.rfind("h_s.increase.", 0) == 0);
         if (!mlic && name.rfind("g_s.", 0) == 0)  // (MLIC++'s transforms hold no transposed convolution: sub-pixel convs throughout)
             for (const char* suf : {"_transform.1.weight", "_transform.6.weight", "_transform.12.weight", "_transform.17.weight",
@@ -475,6 +486,14 @@ int rgbd_elic_create_mlic(int32_t N, int32_t M, int32_t slice_num, int32_t in_ch
     return engine_new(Family::MLIC, N, M, slices, slice_num, in_ch, 0, 0, out);
 }
 
+// The latent codec of ELIC_master (models/elic_master.py:67-98): g_a takes cat(fv, fv_bar) = 2 * 64 channels (:67, 113), g_s returns N
+// (:68).  sp1..sp3 are Spatial_aligner() with the default 192 channels (synthesis.py:94-96), so N is 192, as for family 13.
+int rgbd_master_latent_create(int32_t N, int32_t M, const int32_t* slice_ch, int32_t n_slices, rgbd_elic** out)
+{
+    if (!out || N != 192 || M < 16 || M > 1024) return RGBD_EINVAL;
+    return engine_new(Family::ELIC_master_latent, N, M, slice_ch, n_slices, 128, N, 0, out);
+}
+
 // Spatial_aligner alone (modules/transform/spatialAligner.py:341-390): embed_dim 96, 3 heads, 4x4 windows
 int rgbd_aligner_create(int32_t in_ch, int32_t out_ch, rgbd_elic** out)
 {
@@ -564,6 +583,7 @@ int rgbd_elic_compress_single(rgbd_elic* m, const float* x_dev, int32_t B, int32
 {
     if (const int r = check_ready(m)) return r;
     if (!m->single() || !x_dev || !hw64(B, H, W) || !z_grid_ok(m, H / 64, W / 64)) return RGBD_EINVAL;
+    if (m->family == Family::ELIC_master_latent && !master_ok(m, B, H, W)) return RGBD_EINVAL;
     const int per_image = (per_image_streams || B == 1) ? 1 : 0;
     return run_call(m, stream, call_key("c1|%d|%d|%d|%d", B, H, W, per_image), kCompressTail,
                     [&]() { return m->run_compress(1, {x_dev}, B, H, W, per_image); });
@@ -574,6 +594,7 @@ int rgbd_elic_forward_single(rgbd_elic* m, const float* x_dev, int32_t B, int32_
 {
     if (const int r = check_ready(m)) return r;
     if (!m->single() || !x_dev || !xhat_dev || !lik_y || !lik_z || !hw64(B, H, W) || !z_grid_ok(m, H / 64, W / 64)) return RGBD_EINVAL;
+    if (m->family == Family::ELIC_master_latent) return RGBD_EINVAL;  // (its g_s needs guides: rgbd_master_latent_forward)
     return run_call(m, stream, call_key("f1|%d|%d|%d", B, H, W), kForwardTail,
                     [&]() { return m->run_forward(1, {x_dev}, B, H, W, {xhat_dev}, {lik_y}, {lik_z}); });
 }
@@ -585,6 +606,7 @@ int rgbd_elic_decompress_single(rgbd_elic* m, const uint8_t* const* y, const int
     if (const int r = check_ready(m)) return r;
     if (!m->single() || !y || !y_len || !z || !z_len || !x_dev || B <= 0 || zh <= 0 || zw <= 0 || !one_or_b(n_y, B) || !z_grid_ok(m, zh, zw))
         return RGBD_EINVAL;
+    if (m->family == Family::ELIC_master_latent) return RGBD_EINVAL;  // (its g_s needs guides: rgbd_master_latent_decompress)
     return run_call(m, stream, call_key("d1|%d|%d|%d|%d", B, zh, zw, n_y), kDecompressTail,
                     [&]() { return m->run_decompress(1, &y, &y_len, n_y, &z, &z_len, B, zh * 4, zw * 4, {x_dev}); });
 }
@@ -612,6 +634,33 @@ int rgbd_elic_decompress_single_mid(rgbd_elic* m, const uint8_t* const* y, const
     const rgbd_elic::Mid3 up = {up1, up2, up3};
     return run_call(m, stream, call_key("d1m|%d|%d|%d|%d", B, zh, zw, n_y), kDecompressTail, [&]() {
         return m->run_decompress(1, &y, &y_len, n_y, &z, &z_len, B, zh * 4, zw * 4, {x_dev}, nullptr, &up);
+    });
+}
+
+// The latent codec of ELIC_master: the two calls that run the guided g_s (compress is rgbd_elic_compress_single).  Call shapes of
+// their own in the graph cache.
+int rgbd_master_latent_forward(rgbd_elic* m, const float* f_dev, const float* up1_dev, const float* up2_dev, const float* up3_dev,
+                               int32_t B, int32_t H, int32_t W, float* fhat_dev, float* lik_y, float* lik_z, void* stream)
+{
+    if (const int r = check_ready(m)) return r;
+    if (!f_dev || !up1_dev || !up2_dev || !up3_dev || !fhat_dev || !lik_y || !lik_z || !hw64(B, H, W) || !master_ok(m, B, H, W))
+        return RGBD_EINVAL;
+    const rgbd_elic::Guide3 g = {up1_dev, up2_dev, up3_dev};
+    return run_call(m, stream, call_key("fm|%d|%d|%d", B, H, W), kForwardTail,
+                    [&]() { return m->run_forward(1, {f_dev}, B, H, W, {fhat_dev}, {lik_y}, {lik_z}, nullptr, &g); });
+}
+
+int rgbd_master_latent_decompress(rgbd_elic* m, const uint8_t* const* y, const int64_t* y_len, int32_t n_y, const uint8_t* const* z,
+                                  const int64_t* z_len, int32_t B, int32_t zh, int32_t zw, const float* up1_dev, const float* up2_dev,
+                                  const float* up3_dev, float* fhat_dev, void* stream)
+{
+    if (const int r = check_ready(m)) return r;
+    if (!y || !y_len || !z || !z_len || !up1_dev || !up2_dev || !up3_dev || !fhat_dev || B <= 0 || zh <= 0 || zw <= 0 ||
+        !one_or_b(n_y, B) || !master_ok(m, B, (int64_t)zh * 64, (int64_t)zw * 64))
+        return RGBD_EINVAL;
+    const rgbd_elic::Guide3 g = {up1_dev, up2_dev, up3_dev};
+    return run_call(m, stream, call_key("dm|%d|%d|%d|%d", B, zh, zw, n_y), kDecompressTail, [&]() {
+        return m->run_decompress(1, &y, &y_len, n_y, &z, &z_len, B, zh * 4, zw * 4, {fhat_dev}, nullptr, nullptr, &g);
     });
 }
 
@@ -1077,8 +1126,9 @@ int rgbd_elic_set_forced_symbols(rgbd_elic* m, int32_t modality, const int32_t* 
 {
     std::unique_lock<std::shared_mutex> cap_lk(g_capture_mu);
     if (!m || modality < 0 || modality > 1 || n_y < 0 || n_z < 0 || (n_y && !y_sym) || (n_z && !z_sym)) return RGBD_EINVAL;
-    // (the two-modality codecs, and modality 0 of the checkerboard Cheng2020 model and of MLIC++)
-    if (m->single() && ((m->family != Family::Cheng2020_ckbd && m->family != Family::MLIC) || modality != 0)) return RGBD_EINVAL;
+    // (the two-modality codecs, and modality 0 of the checkerboard Cheng2020 model, of MLIC++ and of ELIC_master_latent)
+    if (m->single() && ((m->family != Family::Cheng2020_ckbd && m->family != Family::MLIC && m->family != Family::ELIC_master_latent) || modality != 0))
+        return RGBD_EINVAL;
     m->graphs_invalidate();  // the workspace layout and the launch list change
     m->force_y[modality].assign(y_sym, y_sym + n_y);
     m->force_z[modality].assign(z_sym, z_sym + n_z);

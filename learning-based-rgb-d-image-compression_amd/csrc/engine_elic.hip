@@ -672,6 +672,17 @@ Act rgbd_elic::g_s1(const Act& yhat)
     return xhat[0];
 }
 
+Act rgbd_elic::g_s_master(const Act& yhat)
+{
+    if (!guide_src) {  // (the entry points refuse a call without guides before anything runs)
+        fail(RGBD_ESTATE);
+        return Act();
+    }
+    Act xhat[2];
+    stages({kSyn15, 15, 1, {"g_s.synthesis_transform.", ""}, kNoFusion, false, false, false, nullptr, guide_src, "g_s."}, &yhat, xhat);
+    return xhat[0];
+}
+
 Act rgbd_elic::h_a1(const Act& y)
 {
     Epi relu;

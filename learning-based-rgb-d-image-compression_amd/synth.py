@@ -15,7 +15,8 @@ import numpy as np
 
 from .arch import (STF_SLICES, Entry, channel_aligner_entries, channel_context_entries, entropy_params_mlic_entries, lrp_entries, feature_decoder_entries, feature_encoder_entries, linear_global_inter_entries, linear_global_intra_entries, local_context_entries,
                    spatial_aligner_entries, synthesis_plus_entries, ckbd_config, ckbd_entries, elic_entries, elic_united_entries, elic_united_r2d_entries, model_config, stf_config,
-                   stf_entries, stf_single_config, stf_united_entries, MLIC_SLICE_CH, mlic_config, mlic_entries)
+                   stf_entries, stf_single_config, stf_united_entries, MLIC_SLICE_CH, mlic_config, mlic_entries, elic_master_entries,
+                   elic_master_latent_entries)
 
 _IH_STD = math.sqrt(4.0 * (65536.0**2 - 1.0) / 12.0)  # std of the sum of four uniform 16-bit ints
 _IH_MEAN = 2.0 * 65535.0
@@ -138,7 +139,9 @@ def synthetic_state_dict(seed: int = 0, config=None, stress: bool = True, as_tor
     always with _apply_stress_feature.  model="SynthesisTransformPlus" (N, M, channel = its `ch`): the guided synthesis transform
     alone, always with _apply_stress_synplus.  model="EntropyParametersMLIC", "ChannelContext" or "LatentResidualPrediction"
     (in_dim, out_dim): a per-slice network of MLIC++ alone, always with _apply_stress_mlic_slice.  model="MLIC" (N, M with
-    M / 32 slices, channel): the MLIC++ codec, recipes "stress" (_apply_stress_mlic) and "plain"."""
+    M / 32 slices, channel): the MLIC++ codec, recipes "stress" (_apply_stress_mlic) and "plain".  model="ELIC_master_latent"
+    (config): the latent codec of ELIC_master, recipes "stress" (_apply_stress_master) and "plain"; model="ELIC_master" (config,
+    channel): the same values with the four outer blocks of the full model added (_apply_stress_feature, _apply_stress_chalign)."""
     if model in ("EntropyParametersMLIC", "ChannelContext", "LatentResidualPrediction"):
         entries = {"EntropyParametersMLIC": entropy_params_mlic_entries, "ChannelContext": channel_context_entries,
                    "LatentResidualPrediction": lrp_entries}[model](in_dim, out_dim)
@@ -211,6 +214,9 @@ def synthetic_state_dict(seed: int = 0, config=None, stress: bool = True, as_tor
     elif model == "MLIC":
         cfg = mlic_config(N, M, M // MLIC_SLICE_CH)
         entries = mlic_entries(N, M, M // MLIC_SLICE_CH, channel)
+    elif model in ("ELIC_master", "ELIC_master_latent"):
+        cfg = model_config() if config is None else config
+        entries = elic_master_entries(cfg, channel) if model == "ELIC_master" else elic_master_latent_entries(cfg)
     else:
         cfg = model_config() if config is None else config
         entries = {"ELIC_united": elic_united_entries, "ELIC_united_R2D": elic_united_r2d_entries}.get(model)
@@ -230,6 +236,8 @@ def synthetic_state_dict(seed: int = 0, config=None, stress: bool = True, as_tor
         _apply_stress_ckbd(sd, seed, N)
     elif stress and model == "MLIC":
         _apply_stress_mlic(sd, seed, M // MLIC_SLICE_CH)
+    elif stress and model in ("ELIC_master", "ELIC_master_latent"):
+        _apply_stress_master(sd, cfg, seed, outer=model == "ELIC_master")
     elif stress:
         _apply_stress_single(sd, cfg)
     if recipe == "trained_like":
@@ -274,8 +282,8 @@ SYNPLUS_DECONV_GAIN = math.sqrt(12.0)
 SYNPLUS_RECOVERY_GAIN = 8.0
 
 
-def _apply_stress_synplus(sd, seed):
-    """SynthesisTransformPlus: the single-modal g_s recipe (which leaves g_s at its default initialisation) plus
+def _apply_stress_synplus(sd, seed, prefix=""):
+    """SynthesisTransformPlus (prefix: "" or the module's name inside a model with its dot, "g_s."): the single-modal g_s recipe (which leaves g_s at its default initialisation) plus
     _apply_stress_aligner on sp1, sp2 and sp3, and two gains that keep the signal alive through three replacements.  A 5x5
     stride-2 transposed convolution at the default initialisation (variance 1 / (3 * 25 cout), 25 / 4 taps of cin channels per
     output) shrinks a map by sqrt(12): its weights are scaled back by that.  A Spatial_aligner returns about a tenth of its
@@ -283,10 +291,10 @@ def _apply_stress_synplus(sd, seed):
     embeddings would outweigh x and an aligner in the wrong place, or fed the wrong x, would barely move the output: the
     recovery weights are scaled by 8."""
     for i in (1, 5, 10, 14):
-        sd[f"synthesis_transform.{i}.weight"] = sd[f"synthesis_transform.{i}.weight"] * np.float32(SYNPLUS_DECONV_GAIN)
+        sd[f"{prefix}synthesis_transform.{i}.weight"] = sd[f"{prefix}synthesis_transform.{i}.weight"] * np.float32(SYNPLUS_DECONV_GAIN)
     for k in (1, 2, 3):
-        _apply_stress_aligner(sd, seed, prefix=f"sp{k}.")
-        sd[f"sp{k}.recovery.weight"] = sd[f"sp{k}.recovery.weight"] * np.float32(SYNPLUS_RECOVERY_GAIN)
+        _apply_stress_aligner(sd, seed, prefix=f"{prefix}sp{k}.")
+        sd[f"{prefix}sp{k}.recovery.weight"] = sd[f"{prefix}sp{k}.recovery.weight"] * np.float32(SYNPLUS_RECOVERY_GAIN)
 
 
 LOCAL_QK_GAIN = 3.5
@@ -435,6 +443,30 @@ def _apply_stress_single(sd, cfg):
         for i, c in enumerate(slice_ch):
             sd[f"{fam}.{i}.fusion.4.weight"] *= np.float32(6.0)
             sd[f"{fam}.{i}.fusion.4.bias"][:c] = np.float32(1.0)  # scale half
+
+
+MASTER_Y_GAIN = 24.0
+
+
+def _apply_stress_master(sd, cfg, seed, outer=False):
+    """ELIC_master and its latent codec, composed from the recipes of their parts: the single-modal recipe for the transforms, the
+    hyper path and the heads of the parameter nets (_apply_stress_single: the EX nets end in the same `fusion.4` the united
+    model's recipe scales, with the same gains), _apply_stress_synplus under `g_s.`, and for the full model
+    _apply_stress_feature / _apply_stress_chalign on the outer blocks.  g_a's last convolution takes MASTER_Y_GAIN in place of the
+    single-modal 48 so that the value can follow the 128-channel input of unit variance (tests/master_latent_cases.py) on its
+    own."""
+    _apply_stress_single(sd, cfg)
+    sd["g_a.analysis_transform.13.weight"] *= np.float32(MASTER_Y_GAIN / 48.0)
+    _apply_stress_synplus(sd, seed, prefix="g_s.")
+    if not outer:
+        return
+    for p in ("aux_encoder.", "master_encoder.", "master_decoder."):
+        sub = OrderedDict((k[len(p):], v) for k, v in sd.items() if k.startswith(p))
+        _apply_stress_feature(sub)
+        sd.update((p + k, v) for k, v in sub.items())
+    sub = OrderedDict((k[len("channel_aligner."):], v) for k, v in sd.items() if k.startswith("channel_aligner."))
+    _apply_stress_chalign(sub)
+    sd.update(("channel_aligner." + k, v) for k, v in sub.items())
 
 
 # single-modal STF: y, z, hyper means / scales, scale head (weight, bias), mean head, LRP head
